@@ -16,6 +16,11 @@ previous-value responses (nr/examples/hashmap.rs:46-50) is measured beside it.
 Inputs are generated on device before the timed region (a pool of distinct batches, cycled).
 For N > 1 every rank adds 1M ops per round (weak scaling); the value counts all ranks' ops.
 
+A plain run sets up, warms up, times --steps rounds, writes the last round's responses if
+--dump-outputs is given, and prints the result line. Everything else the benchmark measures --
+the roofline region (kernel durations, algorithmic bytes per round), the previous-value
+variant, the CPU baselines -- runs only with --full.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -304,6 +309,48 @@ class Env:
             self.dist.destroy_process_group()
 
 
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all
+
+
+def _dump_index(n, bytes_per_elem):
+    """Every element when they fit DUMP_BYTES, else a fixed seeded sample (sorted indices)."""
+    import numpy as np
+
+    limit = DUMP_BYTES // bytes_per_elem
+    if n <= limit:
+        return None
+    return np.sort(np.random.default_rng(0x44554D50).choice(n, size=limit, replace=False))
+
+
+def dump_outputs(args, env, n, vals, flags, prefix, bits):
+    """--dump-outputs DIR: the responses of the timed region's last round, as its caller receives
+    them, written by rank 0 as DIR/<name>.npy. `flags` (found / Some, one byte per op) goes out
+    as float32. `vals` goes out as float64, exactly: a 32-bit response as it is, a 64-bit one as
+    two arrays, <prefix>_vals_lo and <prefix>_vals_hi (its low and high 32 bits). The value of
+    an op whose flag is 0 (None) is written as 0: the caller may not read it."""
+    if env.rank != 0:
+        return
+    import numpy as np
+
+    f = flags[:n].cpu().numpy()
+    v = vals[:n].cpu().numpy()
+    v = v.view(np.uint64 if bits == 64 else np.uint32) * (f != 0)
+    idx = _dump_index(n, 4 + (16 if bits == 64 else 8))
+    if idx is not None:
+        f, v = f[idx], v[idx]
+    out = {prefix + "_flags": f.astype(np.float32)}
+    if bits == 64:
+        out[prefix + "_vals_lo"] = (v & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        out[prefix + "_vals_hi"] = (v >> np.uint64(32)).astype(np.float64)
+    else:
+        out[prefix + "_vals"] = v.astype(np.float64)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+    log("dumped %s (%d of %d responses of round %d) to %s" % (
+        ", ".join(sorted(out)), len(f), n, args.steps - 1, args.dump_outputs))
+
+
 def apply_knobs(rep, args):
     for kv in args.knob:
         name, _, v = kv.partition("=")
@@ -345,7 +392,7 @@ def roofline_region(args, rep, run, names):
       longer than unbracketed ones (stack: ~17 % over rocprof's duration,
       profiles/r02_s8_event_bracketing.txt), so this is reported beside the window only.
     Returns ({name: (launches, total_ms)}, (window rounds, window ms))."""
-    if args.no_kernel_timing:
+    if args.no_kernel_timing or not args.full:
         return {n: (0, 0.0) for n in names}, (0, 0.0)
     torch = sys.modules["torch"]
     nwin = max(args.steps, ROOF_ROUNDS)
@@ -436,16 +483,18 @@ def run_hashmap(args, env):
     pfound = torch.empty(max(W, 1), dtype=torch.uint8, device=dev_t)
     torch.cuda.synchronize()
 
-    # distinct keys per batch (for the algorithmic byte count), outside the timed region
-    nb = min(P, 8)
-    u_r = sum(int(torch.unique(gkeys[p, :R]).numel()) for p in range(nb)) / nb if R else 0
-    u_w_local = sum(int(torch.unique(puts[p, :W, 0]).numel()) for p in range(nb)) / nb if W else 0
-    if world > 1:  # distinct keys of the whole round's log (all ranks' segments)
-        x = torch.tensor([u_w_local], dtype=torch.float64, device=dev_t if args.backend == "nccl" else "cpu")
-        env.dist.all_reduce(x)
-        u_w = float(x.item())
-    else:
-        u_w = u_w_local
+    # distinct keys per batch (for the algorithmic byte count of --full), outside the timed region
+    u_r = u_w = 0
+    if args.full:
+        nb = min(P, 8)
+        u_r = sum(int(torch.unique(gkeys[p, :R]).numel()) for p in range(nb)) / nb if R else 0
+        u_w_local = sum(int(torch.unique(puts[p, :W, 0]).numel()) for p in range(nb)) / nb if W else 0
+        if world > 1:  # distinct keys of the whole round's log (all ranks' segments)
+            x = torch.tensor([u_w_local], dtype=torch.float64, device=dev_t if args.backend == "nccl" else "cpu")
+            env.dist.all_reduce(x)
+            u_w = float(x.item())
+        else:
+            u_w = u_w_local
 
     group = cgroup = pgroup = None
     if args.partitioned:
@@ -528,6 +577,8 @@ def run_hashmap(args, env):
     host_s = [0.0]
     WATCH.phase = "timed region"
     elapsed = run(args.steps, host_s=host_s)  # no events in the timed region
+    if args.dump_outputs and R:  # the last round's Get responses, before any later region overwrites them
+        dump_outputs(args, env, R, gvals, gfound, "get", 64)
     kt, win = roofline_region(args, rep, run, ["hm_round", "hm_papply"])
     (k_n, k_ms), (a_n, a_ms) = kt["hm_round"], kt["hm_papply"]
     if a_n and k_n:  # partition rounds: hm_round (partition + reads) + hm_papply (the table pass)
@@ -536,7 +587,7 @@ def run_hashmap(args, env):
     value = world * args.ops_per_gpu * args.steps / elapsed / 1e6
 
     prev_value = None
-    if not args.no_prev_variant:
+    if args.full and not args.no_prev_variant:
         n2 = max(args.steps // 4, 10)
         e2 = run(n2, prev=True)
         prev_value = world * args.ops_per_gpu * n2 / e2 / 1e6
@@ -575,18 +626,19 @@ def run_hashmap(args, env):
         "put_responses": "Ok(None) as benches/hashmap.rs:114-119",
         "parallelism": "replicas%d" % world,
     })
-    res["roofline"] = roofline("hm_round+hm_papply" if a_n else "hm_round",
-                               round_bytes, k_n, k_ms, args,
-                               measured_traffic(args), win)
-    res["round"] = {
-        "algorithmic_bytes": int(round_bytes),
-        "achieved_GBps": round(round_bytes / (elapsed / args.steps) / 1e9, 1),
-        "host_enqueue_us": round(host_s[0] * 1e6 / args.steps, 2),
-        "host_first_steps_us": host_s[1:],
-        "host_first_step_by_region_us": Env.first_calls,
-        "distinct_get_keys": int(u_r),
-        "distinct_put_keys": int(u_w),
-    }
+    if args.full:
+        res["roofline"] = roofline("hm_round+hm_papply" if a_n else "hm_round",
+                                   round_bytes, k_n, k_ms, args,
+                                   measured_traffic(args), win)
+        res["round"] = {
+            "algorithmic_bytes": int(round_bytes),
+            "achieved_GBps": round(round_bytes / (elapsed / args.steps) / 1e9, 1),
+            "host_enqueue_us": round(host_s[0] * 1e6 / args.steps, 2),
+            "host_first_steps_us": host_s[1:],
+            "host_first_step_by_region_us": Env.first_calls,
+            "distinct_get_keys": int(u_r),
+            "distinct_put_keys": int(u_w),
+        }
     if not args.partitioned:
         s = amdahl_speedup(world, args.write_ratio)
         res["amdahl"] = {"predicted_speedup_vs_1gpu": round(s, 3), "write_pct": args.write_ratio,
@@ -595,7 +647,7 @@ def run_hashmap(args, env):
                                   "all-gather time ignored; every replica replays every Put"}
     if prev_value is not None:
         res["variants"] = {"prev_value_responses_Mops": round(prev_value, 3)}
-    if not args.no_cpu_baseline and world == 1 and args.dist == "uniform" and not args.partitioned:
+    if args.full and not args.no_cpu_baseline and world == 1 and args.dist == "uniform" and not args.partitioned:
         log(f"cpu baseline: {args.cpu_seconds}s ...")
         try:
             res["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.write_ratio, args.key_space, args.prefill)
@@ -763,6 +815,9 @@ def run_synthetic(args, env):
 
     WATCH.phase = "timed region"
     elapsed = run(args.steps)  # no events in the timed region
+    if args.dump_outputs:  # the last round's sums, before any later region overwrites them
+        last = (args.steps - 1) & 1
+        dump_outputs(args, env, N, resps[last], somes[last], "resp", 64)
     kt, win = roofline_region(args, rep, run, ["sy_replay"])
     k_n, k_ms = kt["sy_replay"]
     rep.sync()
@@ -782,10 +837,11 @@ def run_synthetic(args, env):
                             "ops_per_gpu_per_round": N,
                             "parallelism": "replicas%d" % world,
                         })
-    res["roofline"] = roofline("sy_replay", round_bytes, k_n, k_ms, args, measured_traffic(args), win)
-    res["round"] = {"algorithmic_bytes": int(round_bytes),
-                    "touches_per_s": round(6 * Ng * args.steps / elapsed, 1)}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        res["roofline"] = roofline("sy_replay", round_bytes, k_n, k_ms, args, measured_traffic(args), win)
+        res["round"] = {"algorithmic_bytes": int(round_bytes),
+                        "touches_per_s": round(6 * Ng * args.steps / elapsed, 1)}
+    if args.full and not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = synth_cpu_baseline(min(args.cpu_seconds, 10.0), min(N, 1 << 20))
     return res
 
@@ -818,7 +874,7 @@ def run_stack(args, env):
     # distinct slots written per round (S of SURVEY.md §8d): pushes at distinct depths; the
     # depth walk is shift-invariant while it stays above 0 (it starts at 50k)
     S = 0
-    for p in range(min(P, 4)):
+    for p in range(min(P, 4) if args.full else 0):
         o = ops[p]
         push = (o >> 32) & 1
         step_d = push * 2 - 1
@@ -871,6 +927,9 @@ def run_stack(args, env):
 
     WATCH.phase = "timed region"
     elapsed = run(args.steps)  # no events in the timed region
+    if args.dump_outputs:  # the last round's Pop responses, before any later region overwrites them
+        last = (args.steps - 1) & 1
+        dump_outputs(args, env, N, resps[last], somes[last], "resp", 32)
     kt, win = roofline_region(args, rep, run, ["st_replay"])
     k_n, k_ms = kt["st_replay"]
     rep.sync()
@@ -889,9 +948,10 @@ def run_stack(args, env):
                             "ops_per_gpu_per_round": N,
                             "parallelism": "replicas%d" % world,
                         })
-    res["roofline"] = roofline("st_replay", round_bytes, k_n, k_ms, args, measured_traffic(args), win)
-    res["round"] = {"algorithmic_bytes": int(round_bytes), "distinct_slots_written": int(S)}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        res["roofline"] = roofline("st_replay", round_bytes, k_n, k_ms, args, measured_traffic(args), win)
+        res["round"] = {"algorithmic_bytes": int(round_bytes), "distinct_slots_written": int(S)}
+    if args.full and not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = stack_cpu_baseline(min(args.cpu_seconds, 10.0), N, args.stack_init)
     return res
 
@@ -1012,6 +1072,12 @@ def main():
     ap.add_argument("--partitioned", action="store_true",
                     help="hashmap: cnr-style key-partitioned rounds (SURVEY.md 8 f4) instead of full replication")
     ap.add_argument("--pool", type=int, default=64, help="distinct pre-generated input batches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline region (kernel "
+                         "durations, bytes per round), the previous-value variant and the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the responses of the last timed round as DIR/<name>.npy (float32/float64, at most "
+                         "64 MB: a fixed seeded sample of a larger output)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prev-variant", action="store_true")
@@ -1040,6 +1106,8 @@ def main():
     args.timing_every = max(1, args.timing_every)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     ws = os.environ.get("WORLD_SIZE")
     if ws is None and args.gpus > 1:
         # no launcher around us: start the N ranks ourselves (this process never touches the GPU)

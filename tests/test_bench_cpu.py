@@ -147,3 +147,46 @@ def test_roofline_prefers_the_window(bench):
     # without a window (--no-kernel-timing has neither), the bracketed average stands in
     r2 = bench.roofline("st_replay", 12_000_000, 100, 100 * 0.0175, args, None)
     assert r2["avg_launch_us"] == pytest.approx(17.5)
+
+
+def test_dump_outputs_files(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 flags, 64-bit responses exact as two float64 halves, the value of a
+    None response written as 0, only rank 0 writes, and an output over the size limit is cut to
+    a fixed seeded sample."""
+    import argparse
+
+    import numpy as np
+    import torch
+
+    n = 1000
+    raw = np.random.default_rng(7).integers(0, 1 << 64, size=n + 5, dtype=np.uint64)
+    flags = (np.arange(n + 5) % 3 != 0).astype(np.uint8)
+    vals_t, flags_t = torch.from_numpy(raw.view(np.int64)), torch.from_numpy(flags)
+    args = argparse.Namespace(dump_outputs=str(tmp_path / "a"), steps=3)
+    bench.dump_outputs(args, argparse.Namespace(rank=1), n, vals_t, flags_t, "get", 64)
+    assert not os.path.exists(args.dump_outputs)
+    bench.dump_outputs(args, argparse.Namespace(rank=0), n, vals_t, flags_t, "get", 64)
+    f, lo, hi = (np.load(os.path.join(args.dump_outputs, "get_%s.npy" % s)) for s in ("flags", "vals_lo", "vals_hi"))
+    assert f.dtype == np.float32 and lo.dtype == hi.dtype == np.float64 and len(f) == len(lo) == len(hi) == n
+    np.testing.assert_array_equal(f, flags[:n])
+    back = (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+    np.testing.assert_array_equal(back, np.where(flags[:n] != 0, raw[:n], 0))
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 20 * 100)  # room for 100 of the 1000 responses
+    outs = []
+    for d in ("b", "c"):
+        args = argparse.Namespace(dump_outputs=str(tmp_path / d), steps=3)
+        bench.dump_outputs(args, argparse.Namespace(rank=0), n, vals_t, flags_t, "get", 64)
+        outs.append([np.load(os.path.join(args.dump_outputs, "get_%s.npy" % s)) for s in ("flags", "vals_lo", "vals_hi")])
+    assert [len(a) for a in outs[0]] == [100, 100, 100]
+    assert sum(a.nbytes for a in outs[0]) <= 20 * 100
+    for a, b in zip(*outs):
+        np.testing.assert_array_equal(a, b)
+    idx = bench._dump_index(n, 20)
+    assert len(np.unique(idx)) == 100 and idx.max() < n
+    np.testing.assert_array_equal(outs[0][1], np.where(flags[idx] != 0, raw[idx] & np.uint64(0xFFFFFFFF), 0))
+
+    st = torch.from_numpy(np.array([5, 0xFFFFFFFF, 9], np.uint32).view(np.int32))
+    args = argparse.Namespace(dump_outputs=str(tmp_path / "s"), steps=1)
+    bench.dump_outputs(args, argparse.Namespace(rank=0), 3, st, torch.tensor([1, 1, 0], dtype=torch.uint8), "resp", 32)
+    np.testing.assert_array_equal(np.load(tmp_path / "s" / "resp_vals.npy"), [5.0, 4294967295.0, 0.0])

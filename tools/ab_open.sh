@@ -4,7 +4,7 @@
 set -o pipefail
 TAG=${1:-abopen}; N=${2:-5}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-B="python3 bench.py --no-cpu-baseline --no-prev-variant --steps 20 --warmup 5"
+B="python3 bench.py --full --no-cpu-baseline --no-prev-variant --steps 20 --warmup 5"
 for i in $(seq 1 $N); do
   for m in sync spin; do
     timeout -k 10 120 $B --opening $m > $OUT/${m}_$i.json 2> $OUT/${m}_$i.err || exit $?

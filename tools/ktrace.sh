@@ -9,7 +9,7 @@ OUT=gpurun_out/kt_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o run -- \
-    python3 bench.py --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err
+    python3 bench.py --full --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err
 rc=$?
 if [ $rc -ne 0 ]; then echo "[ktrace $TAG] rc=$rc"; tail -5 $OUT/bench.err; exit $rc; fi
 S=$(find $OUT -name '*kernel_stats.csv' | head -1)

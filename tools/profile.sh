@@ -13,13 +13,13 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- \
-    python3 bench.py --no-cpu-baseline $ARGS > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+    python3 bench.py --full --no-cpu-baseline $ARGS > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -f csv -d $OUT/fetch -o run -- \
-    python3 bench.py --no-cpu-baseline --no-prev-variant $ARGS > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
+    python3 bench.py --full --no-cpu-baseline --no-prev-variant $ARGS > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -f csv -d $OUT/write -o run -- \
-    python3 bench.py --no-cpu-baseline --no-prev-variant $ARGS > $OUT/bench_write.json 2> $OUT/bench_write.err
+    python3 bench.py --full --no-cpu-baseline --no-prev-variant $ARGS > $OUT/bench_write.json 2> $OUT/bench_write.err
 if [ "${ATOMIC:-0}" = 1 ]; then
   timeout -s KILL 120 rocprofv3 --pmc TCC_ATOMIC_sum TCC_EA0_ATOMIC_sum TCC_EA0_RDREQ_sum -f csv -d $OUT/atomic -o run -- \
-      python3 bench.py --no-cpu-baseline --no-prev-variant $ARGS > $OUT/bench_atomic.json 2> $OUT/bench_atomic.err
+      python3 bench.py --full --no-cpu-baseline --no-prev-variant $ARGS > $OUT/bench_atomic.json 2> $OUT/bench_atomic.err
 fi
 echo "profile $TAG done"

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
-    base = ["--no-cpu-baseline", "--no-prev-variant", "--steps", "200"]
+    base = ["--full", "--no-cpu-baseline", "--no-prev-variant", "--steps", "200"]
     for spec in sys.argv[1:]:
         name, envs, args = (spec.split("|") + ["", ""])[:3]
         env = dict(os.environ)

@@ -8,7 +8,7 @@ TAG=${1:-t20}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python3 bench.py --no-cpu-baseline --no-prev-variant"
+B="python3 bench.py --full --no-cpu-baseline --no-prev-variant"
 timeout -k 10 120 $B --steps 20 --warmup 5 > $OUT/s20.json 2> $OUT/s20.err &&
 timeout -k 10 120 $B --steps 20 --warmup 5 --no-kernel-timing > $OUT/s20_nt.json 2> $OUT/s20_nt.err &&
 timeout -k 10 120 $B --steps 400 --warmup 40 --no-kernel-timing > $OUT/s400_nt.json 2> $OUT/s400_nt.err &&
