@@ -2,7 +2,7 @@
  * nrgpu.h — C ABI of the MI355X-native node-replication (NR) log-replay path.
  *
  * One `nrg_ctx` is one NR *replica* living on one GPU: it owns the replicated data
- * structure in HBM (NrHashMap / Stack / AbstractDataStructure), its copy of the shared
+ * structure in HBM (NrHashMap / Stack / AbstractDataStructure / FIFO queue), its copy of the shared
  * operation log (an HBM ring of fixed-width records tagged by logical log index), the
  * per-replica replay epoch (`ltail`), scratch for the replay kernels, and a HIP stream.
  *
@@ -20,6 +20,7 @@
  *   nrg_hashmap_dump / digest     Replica::verify(closure)           nr/src/replica.rs:443-467
  *   nrg_stack_*                   Stack Dispatch                     benches/stack.rs:36-84, nr/tests/stack.rs:31-96
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
+ *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -67,6 +68,7 @@ extern "C" {
 #define NRG_DS_HASHMAP 1u   /* NrHashMap: u64 -> u64, Put/Get                       */
 #define NRG_DS_STACK 2u     /* Stack: Vec<u32>, Push/Pop, Peek                      */
 #define NRG_DS_SYNTHETIC 3u /* AbstractDataStructure(n, 20, 5, 2, 1)                */
+#define NRG_DS_QUEUE 4u     /* FIFO queue of u64: Push/Pop, Len   benches/lockfree.rs:43-52 */
 
 /* ---- log record layouts (one WriteOperation each) --------------------------------- */
 /* NrHashMap WriteOperation::Put(key, val)               benches/hashmap.rs:52-56       */
@@ -93,6 +95,15 @@ typedef struct {
     uint64_t op;
 } nrg_synth_op;
 
+/* Queue WriteOperation (QueueWr): op = NRG_QUEUE_PUSH (val used) or NRG_QUEUE_POP
+ * benches/lockfree.rs:43-47; the one read, QueueRd::Len (:49-52), carries no record */
+#define NRG_QUEUE_POP 0u
+#define NRG_QUEUE_PUSH 1u
+typedef struct {
+    uint64_t val;
+    uint64_t op;
+} nrg_queue_op;
+
 /* Synthetic ReadOperation::ReadOnly(tid, rnd1, rnd2)     benches/synthetic.rs:28-31       */
 typedef struct {
     uint64_t tid;
@@ -109,7 +120,7 @@ typedef struct {
                                  reference (min 2*GC_FROM_HEAD, power of two). 0 = 32 MiB   */
     uint64_t max_batch;       /* largest number of log records replayed per kernel pass;
                                  larger exec ranges are replayed in order, in chunks
-                                 (< 2^30; stack: <= 2^24)                                   */
+                                 (< 2^30; stack, queue: <= 2^24)                            */
     uint64_t max_reads;       /* largest read batch per call                               */
     uint64_t stack_capacity;  /* stack: maximum number of elements                          */
     uint64_t synth_n;         /* synthetic: number of words (default 200000)               */
@@ -121,12 +132,17 @@ typedef struct {
                                  ordered on the context's stream. 1: the tail of a replay round
                                  rides in the next round's launch -- hashmap: the apply + reads;
                                  stack: the Pops answered from earlier tiles and the commit;
-                                 synthetic: the per-op sums and the hot-word fold. Those outputs
+                                 synthetic: the per-op sums and the hot-word fold; queue: accepted,
+                                 but nothing is deferred: a queue's outputs are always complete
+                                 in stream order. Those outputs
                                  (and the buffers they read) are complete only after nrg_join(),
                                  the next round call on this context (an empty one included), or
                                  nrg_sync(); give back-to-back rounds distinct response buffers.
                                  Synchronous calls are unaffected (their outputs are complete on
                                  return). */
+    uint64_t queue_capacity;  /* queue: maximum number of elements (default 2^24; 1 .. 2^32,
+                                 else nrg_open returns NRG_E_INVAL; the queue's ring holds a
+                                 power of two >= queue_capacity + max_batch u64) */
 } nrg_config;
 
 /* Fill `cfg` with the defaults of the reference benches for `ds_kind`. */
@@ -193,6 +209,8 @@ int nrg_log_append_segments_async(nrg_ctx* ctx, const void* d_base, uint32_t nse
  *              (HashMap::insert's return, nr/examples/hashmap.rs:46-50)
  *   stack    : resp[u32] = popped (or pushed, if stack_push_resp) value, some[u8]
  *   synthetic: resp[u64] = ReadWrite sum (WriteOnly -> 0), some = 1
+ *   queue    : resp[u64] = pushed (Push -> Some(v)) or popped value, some[u8] = 0 for a Pop on
+ *              an empty queue (benches/lockfree_comparisons.rs:94-98)
  * `resp`/`some` may be NULL (no responses wanted, as benches/hashmap.rs:114-119 returns
  * Ok(None)); the hashmap then skips the previous-value pipeline entirely. */
 int nrg_log_exec(nrg_ctx* ctx, uint64_t resp_lo, uint64_t resp_hi, void* resp, uint8_t* some);
@@ -245,7 +263,7 @@ int nrg_hashmap_digest(nrg_ctx* ctx, uint64_t out[3]);
 
 /* ---- Flat combining on the host ---------------------------------------------------------- */
 /* Replica's flat combiner for many client threads (nr/src/context.rs:88-194,
- * nr/src/replica.rs:345-356, 404-433, 483-497, 508-595), for any of the three data structures:
+ * nr/src/replica.rs:345-356, 404-433, 483-497, 508-595), for any of the four data structures:
  * each registered thread posts up to 32 ops (MAX_PENDING_OPS) per call into the open batch and
  * parks; the combiner's own thread seals the batch into ONE GPU round of `ctx` (its writes
  * appended and replayed in batch order, then its reads answered against the post-round state)
@@ -262,12 +280,13 @@ int nrg_combiner_close(nrg_combiner* comb);
 /* Replica::register: a token 0..max_threads-1, or NRG_E_CAPACITY. */
 int nrg_combiner_register(nrg_combiner* comb, uint32_t* token);
 /* Replica::execute_mut for n <= 32 log records of the replica's kind (nrg_put / nrg_stack_op /
- * nrg_synth_op): resp[i] / some[i] as nrg_log_exec gives them (u64 previous value, u32 popped
- * value, u64 sum). */
+ * nrg_synth_op / nrg_queue_op): resp[i] / some[i] as nrg_log_exec gives them (u64 previous value,
+ * u32 popped value, u64 sum, u64 pushed or popped value). */
 int nrg_combiner_execute_mut(nrg_combiner* comb, uint32_t token, const void* recs, uint32_t n, void* resp,
                              uint8_t* some);
 /* Replica::execute for n <= 32 reads: hashmap Get (u64 keys -> u64 value, found), stack Peek
- * (`reads` unused -> u32 top, some), synthetic ReadOnly (nrg_synth_rd -> u64 sum, some = 1). */
+ * (`reads` unused -> u32 top, some), synthetic ReadOnly (nrg_synth_rd -> u64 sum, some = 1), queue
+ * Len (`reads` unused -> u64 length after the round, some = 1). */
 int nrg_combiner_execute(nrg_combiner* comb, uint32_t token, const void* reads, uint32_t n, void* resp,
                          uint8_t* some);
 /* NrHashMap conveniences: Put(keys[i], vals[i]) -> prev[i]/some[i] = HashMap::insert's previous
@@ -303,6 +322,28 @@ int nrg_synth_round_async(nrg_ctx* ctx, const nrg_synth_op* d_ops, uint64_t n, u
 int nrg_synth_read(nrg_ctx* ctx, const nrg_synth_rd* ops, uint64_t n, uint64_t* sums);
 int nrg_synth_read_async(nrg_ctx* ctx, const nrg_synth_rd* d_ops, uint64_t n, uint64_t* d_sums);
 int nrg_synth_dump(nrg_ctx* ctx, uint64_t* words, uint64_t cap, uint64_t* n);
+
+/* ---- FIFO queue (SegQueueWrapper) ------------------------------------------------------- */
+/* The queue holds at most config.queue_capacity elements. A replay during which the length
+ * exceeds it latches NRG_E_CAPACITY once (reported by the next nrg_sync / synchronous call), as
+ * the stack does; afterwards nrg_queue_len and nrg_queue_dump never report or copy more than
+ * queue_capacity elements. */
+/* SegQueueWrapper::default with caller values: the queue holds vals[0..n) (front first). */
+int nrg_queue_init(nrg_ctx* ctx, const uint64_t* vals, uint64_t n);
+/* SegQueueWrapper::default (benches/lockfree_comparisons.rs:80-88): values 0..n-1 pushed in
+ * order, generated on the device. */
+int nrg_queue_init_range(nrg_ctx* ctx, uint64_t n);
+/* Dispatch::dispatch(QueueRd::Len) (benches/lockfree_comparisons.rs:99): the length. */
+int nrg_queue_len(nrg_ctx* ctx, uint64_t* n);
+/* Copy out the elements, front first. `*n` receives their number; if it exceeds `cap`, nothing
+ * is copied and NRG_E_CAPACITY is returned (as nrg_stack_dump). */
+int nrg_queue_dump(nrg_ctx* ctx, uint64_t* vals, uint64_t cap, uint64_t* n);
+/* Replica::combine for one queue batch (nr/src/replica.rs:544-595): Log::append of the n ops in
+ * d_ops (device) with `origin`, then Log::exec, with the log copy written by the replay's first
+ * pass. Responses for these ops (d_resp[i] u64, d_some[i]; nullable) as nrg_log_exec_async gives
+ * them. Same result as nrg_log_append_async + nrg_log_exec_async. */
+int nrg_queue_round_async(nrg_ctx* ctx, const nrg_queue_op* d_ops, uint64_t n, uint32_t origin,
+                          uint64_t* d_resp, uint8_t* d_some);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's

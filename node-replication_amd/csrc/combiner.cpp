@@ -26,8 +26,8 @@
 // Reads ride in the round that collects them, after its writes: they see every write completed
 // before they were posted (sync-to-tail) and never wait behind a later write round.
 //
-// Generic over the three data structures (nr's Replica<D> is generic over Dispatch,
-// nr/src/replica.rs:72-115): hashmap Put/Get, stack Push-Pop/Peek, synthetic writes/ReadOnly.
+// Generic over the four data structures (nr's Replica<D> is generic over Dispatch,
+// nr/src/replica.rs:72-115): hashmap Put/Get, stack Push-Pop/Peek, synthetic writes/ReadOnly, queue Push-Pop/Len.
 #include <hip/hip_runtime.h>
 #include <immintrin.h>
 #include <linux/futex.h>
@@ -367,13 +367,18 @@ int launch(nrg_combiner* m, Batch& x, uint64_t k, uint32_t W, uint32_t R) {
                 if (hipGetLastError() != hipSuccess) rc = NRG_E_HIP;
             }
             break;
-        default:  // synthetic: ReadWrite/WriteOnly sums, then ReadOnly sums
+        case NRG_DS_QUEUE:  // Push / Pop, then Len against the post-round length
+            if (W) rc = nrg_queue_round_async(c, (const nrg_queue_op*)x.recs, W, origin, (uint64_t*)x.wresp, x.wsome);
+            if (!rc && R && nrg::qu_len_answers(c, R, (uint64_t*)x.rresp, x.rsome) != hipSuccess) rc = NRG_E_HIP;
+            break;
+        case NRG_DS_SYNTHETIC:  // ReadWrite/WriteOnly sums, then ReadOnly sums
             if (W) rc = nrg_synth_round_async(c, (const nrg_synth_op*)x.recs, W, origin, (uint64_t*)x.wresp, x.wsome);
             if (!rc && R) {
                 std::memset(x.rsome, 1, R);
                 rc = nrg_synth_read_async(c, (const nrg_synth_rd*)x.reads, R, (uint64_t*)x.rresp);
             }
             break;
+        default: rc = NRG_E_INVAL; break;
     }
     if (!rc && nrg_join(c)) rc = NRG_E_HIP;  // a deferred round tail would write responses later
     if (!rc && (!small || c->err_out)) {
@@ -469,8 +474,9 @@ void combiner_main(nrg_combiner* m) {
 // Post n ops of one thread, then combine or wait until their round is done (nr/src/replica.rs:414-433).
 int post_and_wait(nrg_combiner* m, uint32_t token, bool write, const void* ops, uint32_t n, void* out,
                   uint8_t* some) {
-    if (!m || token >= m->max_threads || (n && (!out || !some || (!ops && (write || m->kind != NRG_DS_STACK)))))
-        return NRG_E_INVAL;
+    // reads that carry no record: the stack's Peek and the queue's Len
+    const bool bare_read = m && !write && (m->kind == NRG_DS_STACK || m->kind == NRG_DS_QUEUE);
+    if (!m || token >= m->max_threads || (n && (!out || !some || (!ops && !bare_read)))) return NRG_E_INVAL;
     if (n > MAX_PENDING) return NRG_E_CAPACITY;
     if (!n) return NRG_OK;
     if (m->tok[token].busy.exchange(1, std::memory_order_acquire)) return NRG_E_INVAL;  // token in use
@@ -543,7 +549,8 @@ int post_and_wait(nrg_combiner* m, uint32_t token, bool write, const void* ops, 
 extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combiner** out) {
     if (!ctx || !out || !max_threads || max_threads > 4096) return NRG_E_INVAL;
     const uint32_t kind = ctx->cfg.ds_kind;
-    if (kind != NRG_DS_HASHMAP && kind != NRG_DS_STACK && kind != NRG_DS_SYNTHETIC) return NRG_E_INVAL;
+    if (kind != NRG_DS_HASHMAP && kind != NRG_DS_STACK && kind != NRG_DS_SYNTHETIC && kind != NRG_DS_QUEUE)
+        return NRG_E_INVAL;
     const uint64_t cap = (uint64_t)max_threads * MAX_PENDING;
     if (cap > ctx->cfg.max_batch || (kind == NRG_DS_HASHMAP && cap > ctx->cfg.max_reads)) return NRG_E_CAPACITY;
     int r = nrg::ctx_use_device(ctx);
@@ -561,7 +568,9 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
     switch (kind) {
         case NRG_DS_HASHMAP: m->rd_b = 8, m->wr_b = 8, m->rr_b = 8; break;            // key; previous value; value
         case NRG_DS_STACK: m->rd_b = 0, m->wr_b = 4, m->rr_b = 4; break;              // Peek; popped; top
-        default: m->rd_b = sizeof(nrg_synth_rd), m->wr_b = 8, m->rr_b = 8; break;  // sums
+        case NRG_DS_QUEUE: m->rd_b = 0, m->wr_b = 8, m->rr_b = 8; break;              // Len; pushed or popped; length
+        case NRG_DS_SYNTHETIC: m->rd_b = sizeof(nrg_synth_rd), m->wr_b = 8, m->rr_b = 8; break;  // sums
+        default: comb_free(m); return NRG_E_INVAL;  // (the kind check above admits no other)
     }
     bool ok = true;
     ok = ok && (m->tok = new (std::nothrow) nrg_combiner::Tok[max_threads]());

@@ -87,6 +87,14 @@ struct SyDeferred {
     uint8_t* some = nullptr;
 };
 
+// The queue's device state, an allocation of its own (queue.hip): the ring position of the front
+// as a monotonic count of elements ever popped, the length, and the same two at the start of the
+// chunk being replayed with that chunk's successful Pops.
+struct QuState {
+    u64 head, len;
+    u64 ck_head, ck_len, ck_pops;
+};
+
 struct HostRun {  // origin tags of appended log ranges (the Entry::replica field)
     u64 first, count;
     u32 origin;
@@ -174,6 +182,12 @@ struct nrg_ctx {
     uint64_t* d_sort_aux = nullptr;  // per-touch max-scan output
     uint32_t synth_key_bits = 0;
     void* d_sy_aux = nullptr;  // bucket replay scratch (synthetic.hip); nullptr: sort path
+
+    // ---- Queue ----
+    uint64_t* d_queue = nullptr;          // ring of qu_size (power of two >= capacity + max_batch) values
+    uint64_t qu_size = 0;
+    nrg::QuState* d_qu_state = nullptr;
+    void* d_qu_aux = nullptr;             // per-tile aggregates and scanned starts (queue.hip)
 
     // ---- shared scratch ----
     nrg::SortScratch sort;
@@ -285,6 +299,13 @@ hipError_t st_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, 
                            uint8_t* d_some, const nrg_stack_op* src = nullptr);
 u64 st_aux_bytes(u64 max_batch);   // size of nrg_ctx::d_st_aux
 u64 st_desc_words(u64 max_batch);  // u32 words of look-back descriptors the stack needs
+
+// queue.hip
+hipError_t qu_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, u64* d_resp, uint8_t* d_some,
+                           const nrg_queue_op* src = nullptr);
+hipError_t qu_init_range(nrg_ctx* c, u64 n);  // values 0..n-1, front first
+hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads
+u64 qu_aux_bytes(u64 max_batch);  // size of nrg_ctx::d_qu_aux
 
 // synthetic.hip
 hipError_t sy_init(nrg_ctx* c);

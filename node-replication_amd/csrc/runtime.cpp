@@ -54,6 +54,7 @@ uint32_t rec_bytes_for(uint32_t kind) {
         case NRG_DS_HASHMAP: return sizeof(nrg_put);
         case NRG_DS_STACK: return sizeof(nrg_stack_op);
         case NRG_DS_SYNTHETIC: return sizeof(nrg_synth_op);
+        case NRG_DS_QUEUE: return sizeof(nrg_queue_op);
         default: return 0;
     }
 }
@@ -74,6 +75,7 @@ int use_device(nrg_ctx* c) {
 hipError_t hm_flush_if(nrg_ctx* c) {
     if (c->cfg.ds_kind == NRG_DS_HASHMAP) return hm_flush(c);
     if (c->cfg.ds_kind == NRG_DS_STACK) return st_flush(c);
+    if (c->cfg.ds_kind == NRG_DS_QUEUE) return hipSuccess;  // a queue chunk defers nothing (queue.hip)
     return sy_flush(c);
 }
 
@@ -125,6 +127,9 @@ int exec_range(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_resp, uin
                 break;
             case NRG_DS_SYNTHETIC:
                 e = sy_replay_chunk(c, lo, n, resp_lo, resp_hi, (u64*)d_resp, d_some);
+                break;
+            case NRG_DS_QUEUE:
+                e = qu_replay_chunk(c, lo, n, resp_lo, resp_hi, (u64*)d_resp, d_some);
                 break;
             default: return NRG_E_INVAL;
         }
@@ -283,6 +288,7 @@ void nrg_config_default(nrg_config* cfg, uint32_t ds_kind) {
     cfg->stack_push_resp = 0;
     cfg->replica_id = 1;
     cfg->pipeline = 0;  // opt-in: see nrg_config.pipeline
+    cfg->queue_capacity = 1u << 24;
 }
 
 const char* nrg_strerror(int code) {
@@ -384,6 +390,20 @@ int nrg_open(int dev, const nrg_config* cfg_in, nrg_ctx** out) {
         OPEN_CHK(hipMemsetAsync(c->d_scan_desc, 0, c->scan_desc_words * 4, c->stream));
         OPEN_CHK(hipMalloc(&c->d_st_aux, st_aux_bytes(mb)));
         c->pipeline = cf.pipeline != 0;
+    } else if (cf.ds_kind == NRG_DS_QUEUE) {
+        // max_batch <= 2^24: one workgroup scans the tile aggregates (queue.hip); the capacity
+        // bounds the ring of u64 values
+        if (!cf.queue_capacity || cf.queue_capacity > (1ull << 32) || mb > (1ull << 24)) {
+            nrg_close(c);
+            return NRG_E_INVAL;
+        }
+        // capacity + max_batch slots: the positions one chunk touches never alias (queue.hip)
+        c->qu_size = pow2_at_least(cf.queue_capacity + mb);
+        OPEN_CHK(hipMalloc(&c->d_queue, c->qu_size * sizeof(uint64_t)));
+        OPEN_CHK(hipMalloc(&c->d_qu_state, sizeof(QuState)));
+        OPEN_CHK(hipMemsetAsync(c->d_qu_state, 0, sizeof(QuState), c->stream));
+        OPEN_CHK(hipMalloc(&c->d_qu_aux, qu_aux_bytes(mb)));
+        c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
     } else {
         const uint64_t T = cf.synth_hot_writes + cf.synth_cold_writes;
         if (!cf.synth_n || cf.synth_hot_reads == 0 || cf.synth_n <= cf.synth_hot_reads || T == 0 || T > 64 ||
@@ -422,7 +442,8 @@ int nrg_close(nrg_ctx* c) {
     if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->d_ring,    c->d_ctl,      c->d_table,    c->d_stack,  c->d_words,
                     c->d_sort_aux, c->d_tmp_u64, c->d_scan_desc, c->d_created, c->d_st_aux,
-                    c->d_sy_aux,  c->d_bk_ent,   c->d_bk_idx,   c->d_bk_cnt, c->d_dbg,     c->d_pt};
+                    c->d_sy_aux,  c->d_bk_ent,   c->d_bk_idx,   c->d_bk_cnt, c->d_dbg,     c->d_pt,
+                    c->d_queue,   c->d_qu_state, c->d_qu_aux};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     sort_free(c->sort);
@@ -541,7 +562,11 @@ int nrg_log_exec_async(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_r
 }
 
 static uint64_t resp_elem_bytes(const nrg_ctx* c) {
-    return c->cfg.ds_kind == NRG_DS_STACK ? 4 : 8;
+    switch (c->cfg.ds_kind) {
+        case NRG_DS_STACK: return 4;  // u32 popped value
+        case NRG_DS_QUEUE: return 8;  // u64 pushed or popped value
+        default: return 8;            // hashmap previous value, synthetic sum
+    }
 }
 
 int nrg_log_exec(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* resp, uint8_t* some) {
@@ -896,6 +921,91 @@ int nrg_stack_dump(nrg_ctx* c, uint32_t* vals, uint64_t cap, uint64_t* n) {
     if (*n > cap) return NRG_E_CAPACITY;
     if (*n) {
         HIPCHK(hipMemcpyAsync(vals, c->d_stack, *n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    return NRG_OK;
+}
+
+// ---- FIFO queue ----------------------------------------------------------------------------
+int nrg_queue_round_async(nrg_ctx* c, const nrg_queue_op* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                          uint8_t* d_some) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
+    if (n && !d_ops) return NRG_E_INVAL;
+    if (!d_resp || !d_some) d_resp = nullptr, d_some = nullptr;
+    // catch up on anything appended by others first (Replica::combine execs the whole log)
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    if ((r = reserve(c, n))) return r;
+    const uint64_t lo = c->tail;
+    // the replay's first pass also writes the log copy (Log::append + Log::exec of this batch)
+    HIPCHK(qu_replay_chunk(c, lo, n, lo, lo + n, d_resp, d_some, d_ops));
+    if (n) note_origin(c, lo, n, origin);
+    c->tail = lo + n;
+    c->ltail = c->tail;
+    if (c->ctail < c->tail) c->ctail = c->tail;
+    return NRG_OK;
+}
+
+static int qu_set_state(nrg_ctx* c, uint64_t n) {
+    QuState s{};
+    s.len = n;
+    HIPCHK(hipMemcpyAsync(c->d_qu_state, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_queue_init(nrg_ctx* c, const uint64_t* vals, uint64_t n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (n > c->cfg.queue_capacity) return NRG_E_CAPACITY;
+    if (n && !vals) return NRG_E_INVAL;
+    // head = 0: the n values sit at the start of the ring (capacity <= its size)
+    if (n) HIPCHK(hipMemcpyAsync(c->d_queue, vals, n * 8, hipMemcpyHostToDevice, c->stream));
+    return qu_set_state(c, n);
+}
+
+int nrg_queue_init_range(nrg_ctx* c, uint64_t n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (n > c->cfg.queue_capacity) return NRG_E_CAPACITY;
+    HIPCHK(qu_init_range(c, n));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+// the front's monotonic position and the length, never more than the capacity
+static int qu_get_state(nrg_ctx* c, uint64_t* head, uint64_t* len) {
+    QuState s{};
+    HIPCHK(hipMemcpyAsync(&s, c->d_qu_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    *head = s.head;
+    *len = s.len > c->cfg.queue_capacity ? c->cfg.queue_capacity : s.len;
+    return check_err(c);
+}
+
+int nrg_queue_len(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    uint64_t head = 0;
+    return qu_get_state(c, &head, n);
+}
+
+int nrg_queue_dump(nrg_ctx* c, uint64_t* vals, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    uint64_t head = 0;
+    if ((r = qu_get_state(c, &head, n))) return r;
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n) {
+        if (!vals) return NRG_E_INVAL;
+        const uint64_t phys = head & (c->qu_size - 1);
+        const uint64_t first = *n < c->qu_size - phys ? *n : c->qu_size - phys;
+        HIPCHK(hipMemcpyAsync(vals, c->d_queue + phys, first * 8, hipMemcpyDeviceToHost, c->stream));
+        if (first < *n)
+            HIPCHK(hipMemcpyAsync(vals + first, c->d_queue, (*n - first) * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(sync_all(c));
     }
     return NRG_OK;

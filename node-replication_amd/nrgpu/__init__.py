@@ -8,18 +8,21 @@ from ._lib import NrgError, load
 from .combiner import Combiner
 from .replica import (
     PUT_DTYPE,
+    QUEUE_OP_DTYPE,
     STACK_OP_DTYPE,
     SYNTH_OP_DTYPE,
     SYNTH_RD_DTYPE,
     AbstractDataStructure,
     DeviceReplica,
     Get,
+    Len,
     Log,
     NrHashMap,
     Peek,
     Pop,
     Push,
     Put,
+    Queue,
     ReadOnly,
     ReadWrite,
     Replica,
@@ -29,8 +32,8 @@ from .replica import (
 )
 
 __all__ = [
-    "_lib", "NrgError", "load", "Combiner", "PUT_DTYPE", "STACK_OP_DTYPE", "SYNTH_OP_DTYPE", "SYNTH_RD_DTYPE",
-    "AbstractDataStructure", "DeviceReplica", "Get", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put",
+    "_lib", "NrgError", "load", "Combiner", "PUT_DTYPE", "QUEUE_OP_DTYPE", "STACK_OP_DTYPE", "SYNTH_OP_DTYPE", "SYNTH_RD_DTYPE",
+    "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
 ]
 

@@ -37,9 +37,12 @@ NRG_MAX_PARTS = 64
 NRG_DS_HASHMAP = 1
 NRG_DS_STACK = 2
 NRG_DS_SYNTHETIC = 3
+NRG_DS_QUEUE = 4
 
 NRG_STACK_POP = 0
 NRG_STACK_PUSH = 1
+NRG_QUEUE_POP = 0
+NRG_QUEUE_PUSH = 1
 NRG_SYNTH_WRITE_ONLY = 0
 NRG_SYNTH_READ_WRITE = 1
 
@@ -67,6 +70,7 @@ class Config(C.Structure):
         ("stack_push_resp", C.c_uint32),
         ("replica_id", C.c_uint32),
         ("pipeline", C.c_uint32),
+        ("queue_capacity", C.c_uint64),
     ]
 
 
@@ -138,6 +142,11 @@ SIGNATURES = {
     "nrg_stack_peek": (C.c_int, [vp, C.POINTER(u32), C.POINTER(C.c_uint8)]),
     "nrg_stack_len": (C.c_int, [vp, u64p]),
     "nrg_stack_dump": (C.c_int, [vp, vp, u64, u64p]),
+    "nrg_queue_init": (C.c_int, [vp, vp, u64]),
+    "nrg_queue_init_range": (C.c_int, [vp, u64]),
+    "nrg_queue_len": (C.c_int, [vp, u64p]),
+    "nrg_queue_dump": (C.c_int, [vp, vp, u64, u64p]),
+    "nrg_queue_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

@@ -4,7 +4,7 @@ Mirrors the reference's per-thread registration and synchronous execute / execut
 (nr/src/replica.rs:345-356, 404-433, 508-595; nr/src/context.rs:88-194): every call posts up to
 32 ops of one thread into the open batch, and the combiner's own thread turns the batch into one
 GPU round of the replica (writes, then reads) without waiting for the GPU. One call at a time per
-token: a call on a token whose previous call is still waiting is refused (NRG_E_INVAL). Works for the three data structures (NrHashMap, Stack, AbstractDataStructure). ctypes
+token: a call on a token whose previous call is still waiting is refused (NRG_E_INVAL). Works for the four data structures (NrHashMap, Stack, AbstractDataStructure, Queue). ctypes
 releases the GIL for the call, so Python threads combine for real.
 """
 import ctypes as C
@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .replica import PUT_DTYPE, STACK_OP_DTYPE, SYNTH_OP_DTYPE, SYNTH_RD_DTYPE
+from .replica import PUT_DTYPE, QUEUE_OP_DTYPE, STACK_OP_DTYPE, SYNTH_OP_DTYPE, SYNTH_RD_DTYPE
 
 MAX_PENDING_OPS = 32  # nr/src/context.rs:12
 
@@ -21,6 +21,7 @@ _KINDS = {
     L.NRG_DS_HASHMAP: (PUT_DTYPE, np.uint64, np.uint64, np.uint64),
     L.NRG_DS_STACK: (STACK_OP_DTYPE, np.uint32, None, np.uint32),
     L.NRG_DS_SYNTHETIC: (SYNTH_OP_DTYPE, np.uint64, SYNTH_RD_DTYPE, np.uint64),
+    L.NRG_DS_QUEUE: (QUEUE_OP_DTYPE, np.uint64, None, np.uint64),
 }
 
 
@@ -60,7 +61,7 @@ class Combiner:
 
     def execute(self, token: int, reads=None, n: int = None):
         """Replica::execute for up to 32 reads (hashmap keys, synthetic nrg_synth_rd records, or
-        n stack Peeks): (responses, Some flags)."""
+        n stack Peeks or queue Lens): (responses, Some flags)."""
         _, _, qdt, adt = _KINDS[self.kind]
         if qdt is None:
             q, cnt, ptr = None, int(n if n is not None else len(reads)), None

@@ -7,8 +7,9 @@
                                    sync / verify, with flat combining of the registered
                                    threads' pending ops into one log append + one replay
   ReplicaToken    nr::ReplicaToken
-  NrHashMap, Stack, AbstractDataStructure — the Dispatch plug-ins of the reference
-                                   (benches/hashmap.rs, benches/stack.rs, benches/synthetic.rs)
+  NrHashMap, Stack, AbstractDataStructure, Queue — the Dispatch plug-ins of the reference
+                                   (benches/hashmap.rs, benches/stack.rs, benches/synthetic.rs,
+                                   benches/lockfree_comparisons.rs)
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ from . import _lib as L
 
 PUT_DTYPE = np.dtype([("key", "<u8"), ("val", "<u8")])
 STACK_OP_DTYPE = np.dtype([("val", "<u4"), ("op", "<u4")])
+QUEUE_OP_DTYPE = np.dtype([("val", "<u8"), ("op", "<u8")])
 SYNTH_OP_DTYPE = np.dtype([("tid", "<u8"), ("r1", "<u8"), ("r2", "<u8"), ("op", "<u8")])
 SYNTH_RD_DTYPE = np.dtype([("tid", "<u8"), ("r1", "<u8"), ("r2", "<u8")])
 
@@ -195,7 +197,10 @@ class DeviceReplica:
         return list(fa)
 
     def _resp_dtype(self):
-        return np.uint32 if self.kind == L.NRG_DS_STACK else np.uint64
+        if self.kind == L.NRG_DS_STACK:
+            return np.uint32
+        # hashmap previous values, synthetic sums, queue pushed / popped values
+        return np.uint64
 
     def log_exec(self, resp_lo: int = 0, resp_hi: int = 0):
         n = resp_hi - resp_lo
@@ -226,6 +231,15 @@ class DeviceReplica:
         Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
         L.check(self._lib.nrg_synth_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
                 "synth_round")
+
+    @_stream_ordered
+    def qu_round_device(self, d_ops, n: int, origin: int, d_resp=None, d_some=None):
+        """Replica::combine for one queue batch on device buffers: append + exec, the log copy
+        written by the replay (nrg_queue_round_async); responses (u64 pushed or popped value)
+        for these ops into d_resp / d_some.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_queue_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
+                "queue_round")
 
     def log_reset(self):
         L.check(self._lib.nrg_log_reset(self._h))
@@ -355,6 +369,29 @@ class DeviceReplica:
         L.check(self._lib.nrg_stack_dump(self._h, _ptr(out), n, C.byref(m)), "stack_dump")
         return out[: m.value]
 
+    # -- queue ---------------------------------------------------------------------
+    def qu_init(self, vals):
+        """The queue holds `vals`, front first."""
+        vals = np.ascontiguousarray(np.asarray(vals, np.uint64))
+        L.check(self._lib.nrg_queue_init(self._h, _ptr(vals), len(vals)), "queue_init")
+
+    def qu_init_range(self, n: int):
+        """SegQueueWrapper::default: values 0..n-1 pushed in order."""
+        L.check(self._lib.nrg_queue_init_range(self._h, n), "queue_init_range")
+
+    def qu_len(self) -> int:
+        n = C.c_uint64()
+        L.check(self._lib.nrg_queue_len(self._h, C.byref(n)), "queue_len")
+        return n.value
+
+    def qu_dump(self) -> np.ndarray:
+        """The elements, front first."""
+        n = self.qu_len()
+        out = np.zeros(max(n, 1), np.uint64)
+        m = C.c_uint64()
+        L.check(self._lib.nrg_queue_dump(self._h, _ptr(out), n, C.byref(m)), "queue_dump")
+        return out[: m.value]
+
     # -- synthetic -----------------------------------------------------------------
     def sy_read(self, ops: np.ndarray) -> np.ndarray:
         ops = np.ascontiguousarray(ops, SYNTH_RD_DTYPE)
@@ -437,6 +474,11 @@ class Peek:  # nr/tests/stack.rs:26-29
 
 
 @dataclass(frozen=True)
+class Len:  # benches/lockfree.rs:49-52 (QueueRd::Len)
+    pass
+
+
+@dataclass(frozen=True)
 class WriteOnly:  # benches/synthetic.rs:33-39
     tid: int
     r1: int
@@ -510,6 +552,34 @@ class Stack:
     @staticmethod
     def snapshot(dev: DeviceReplica):
         return dev.st_dump().tolist()
+
+
+class Queue:
+    """SegQueueWrapper (benches/lockfree_comparisons.rs:75-101): a FIFO of u64; Push -> Some(v),
+    Pop -> Option<u64>, Len -> the length."""
+
+    kind = L.NRG_DS_QUEUE
+    rec_dtype = QUEUE_OP_DTYPE
+
+    @staticmethod
+    def encode(ops) -> np.ndarray:
+        r = np.zeros(len(ops), QUEUE_OP_DTYPE)
+        r["val"] = [o.val if isinstance(o, Push) else 0 for o in ops]
+        r["op"] = [L.NRG_QUEUE_PUSH if isinstance(o, Push) else L.NRG_QUEUE_POP for o in ops]
+        return r
+
+    @staticmethod
+    def decode(resp, some) -> list:
+        return [int(v) if s else None for v, s in zip(resp, some)]
+
+    @staticmethod
+    def read_batch(dev: DeviceReplica, ops) -> list:
+        n = dev.qu_len()
+        return [n for _ in ops]
+
+    @staticmethod
+    def snapshot(dev: DeviceReplica):
+        return dev.qu_dump().tolist()
 
 
 class AbstractDataStructure:
