@@ -57,7 +57,8 @@ extern "C" {
 #define NRG_OK 0
 #define NRG_E_INVAL (-1)        /* bad argument / wrong data-structure kind              */
 #define NRG_E_HIP (-2)          /* a HIP runtime call failed                             */
-#define NRG_E_TABLE_FULL (-3)   /* hash table probe exhausted (reference would grow)     */
+#define NRG_E_TABLE_FULL (-3)   /* hash table probe exhausted: a fixed table, or one grown
+                                   to config.hashmap_max_log2_slots, is full             */
 #define NRG_E_RING_FULL (-4)    /* log ring cannot hold the append even after GC         */
 #define NRG_E_NOMEM (-5)        /* device allocation failed                              */
 #define NRG_E_NOT_SYNCED (-6)   /* read requested while ltail < tail (sync first)        */
@@ -140,6 +141,19 @@ typedef struct {
                                  nrg_sync(); give back-to-back rounds distinct response buffers.
                                  Synchronous calls are unaffected (their outputs are complete on
                                  return). */
+    uint32_t hashmap_max_log2_slots; /* hashmap: 0 (default) = a fixed table of 2^log2_slots slots
+                                 (NRG_E_TABLE_FULL when it fills). Otherwise the table grows by
+                                 itself, as HashMap<u64, u64> does (nr/examples/hashmap.rs starts
+                                 from an empty map; benches/hashmap.rs:91-100 only pre-sizes it),
+                                 up to 2^hashmap_max_log2_slots slots: before a replay chunk or a
+                                 prefill could take it past one key per two slots it is rehashed,
+                                 synchronously, into the smallest table that holds the keys.
+                                 log2_slots <= hashmap_max_log2_slots <= 30, else nrg_open returns
+                                 NRG_E_INVAL. Answers, nrg_hashmap_size / dump / digest do not
+                                 depend on the table's size; replicas replaying the same log with
+                                 the same config grow at the same record. (The field takes what
+                                 was padding in front of queue_capacity: no offset and not the
+                                 struct's size changed, and nrg_config_default always zeroed it.) */
     uint64_t queue_capacity;  /* queue: maximum number of elements (default 2^24; 1 .. 2^32,
                                  else nrg_open returns NRG_E_INVAL; the queue's ring holds a
                                  power of two >= queue_capacity + max_batch u64) */
@@ -255,6 +269,18 @@ int nrg_hashmap_prefill(nrg_ctx* ctx, const uint64_t* keys, const uint64_t* vals
  * n = INITIAL_CAPACITY, val_offset = 1). */
 int nrg_hashmap_prefill_range(nrg_ctx* ctx, uint64_t n, uint64_t val_offset);
 int nrg_hashmap_size(nrg_ctx* ctx, uint64_t* n);
+/* HashMap::reserve / with_capacity (benches/hashmap.rs:91-100 pre-sizes the map;
+ * nr/examples/hashmap.rs lets it grow): make the table large enough for `n_keys` keys in all at
+ * one key per two slots, with automatic growth (config.hashmap_max_log2_slots) on or off. It never
+ * shrinks: a request the table already satisfies returns NRG_OK and does nothing. Automatic
+ * growth stays bounded by the config; a table reserved beyond that bound is a fixed one.
+ * NRG_E_INVAL: not a hashmap, or more keys than nrg_open's largest table (2^30 slots) holds.
+ * NRG_E_NOMEM: the new table could not be allocated; the old one is intact and the replica
+ * usable. Synchronous (one rehash of the whole table); like every direct call, not allowed while
+ * a combiner is open on the context. */
+int nrg_hashmap_reserve(nrg_ctx* ctx, uint64_t n_keys);
+/* The current table size: *log2_slots. */
+int nrg_hashmap_capacity(nrg_ctx* ctx, uint32_t* log2_slots);
 /* Copy out every (key, value) pair (unordered). `*n` receives the number of pairs; if it
  * exceeds `cap`, nothing is copied and NRG_E_CAPACITY is returned. */
 int nrg_hashmap_dump(nrg_ctx* ctx, uint64_t* keys, uint64_t* vals, uint64_t cap, uint64_t* n);
@@ -499,7 +525,8 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
 /* enable = 0: off; 1: every launch; n > 1: every n-th launch (sampling keeps the timed stream
  * unperturbed). The main replay kernel ("hm_round") is timed with start/stop events stamped
  * from its own dispatch (hipExtLaunchKernelGGL); multi-kernel pipelines ("hm_prev",
- * "st_replay", "sy_replay") with event records around them. nrg_kernel_time reads (timed
+ * "st_replay", "sy_replay") with event records around them; a table growth's two passes are
+ * "hm_grow_init" and "hm_rehash". nrg_kernel_time reads (timed
  * launches, their total milliseconds) after synchronising. */
 int nrg_kernel_timing(nrg_ctx* ctx, int enable);
 /* Restrict timing to one kernel name (NULL or "" = all). */

@@ -344,7 +344,14 @@ int launch(nrg_combiner* m, Batch& x, uint64_t k, uint32_t W, uint32_t R) {
             x.served = true;
             return NRG_OK;
         }
-        rc = NRG_OK;  // not a small round of a caught-up replica: launched below
+        // Not a small round of a caught-up replica, or (table growth) a round before which the keys
+        // must be counted or the table rehashed: hm_small_job accounts a served round's Puts
+        // through hm_room, as hm_replay_chunk does for a launched one, and refuses the round when
+        // that needs the stream. Launched below: the server, which holds the old table's address,
+        // shift and mask as kernel arguments, is stopped first (it drains the posted rounds), the
+        // launched round counts and grows in hm_replay_chunk, and the next small round starts a
+        // server with the new table.
+        rc = NRG_OK;
     }
     if (m->srv_running && (rc = serve_stop(m)) != NRG_OK) return rc;  // launches queue behind the server
     // hashmap rounds of <= 2048 Puts (>= 1) and <= 8192 Gets run as ONE small-round workgroup

@@ -29,6 +29,12 @@ constexpr u32 HM_BK_MAX = 1024;
 // Largest hashmap replay chunk: keeps the partition apply's per-tile LDS prefix (one u32 + one
 // u16 per tile of 2048 Puts) and 16-bit tile offsets within bounds.
 constexpr u64 HM_MAX_BATCH = 1ull << 23;
+// Table growth (nrg_config.hashmap_max_log2_slots, nrg_hashmap_reserve): a table of S slots that
+// growth manages holds at most S / HM_GROW_SLOTS_PER_KEY keys, a load of 0.5. A miss under linear
+// probing costs about (1 + 1/(1-a)^2) / 2 probes: 2.5 at a = 0.5, 8.5 at a = 0.75. Every probe
+// past the home slot's 128-B line (4 slots) is another random line, and random lines are what the
+// read role's time is made of: at 0.5 most chains end inside the first line, at 0.75 few do.
+constexpr u64 HM_GROW_SLOTS_PER_KEY = 2;
 
 // splitmix64 finaliser — identical constants to oracle/nr_oracle.c (orc_mix64) so that
 // device-generated workloads are reproducible by the CPU oracle.

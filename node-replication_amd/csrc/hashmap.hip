@@ -1484,14 +1484,106 @@ hipError_t hm_serve_launch(nrg_ctx* c, ServeCtl* sc, const SmallJobBlob* hdr, u3
     return hipGetLastError();
 }
 
+// NT (hm_grow's A/B, NRG_KNOB_EXP bit 7): streamed stores
+template <bool NT = false>
 __global__ __launch_bounds__(TPB) void hm_init_table_kernel(Slot* table, u64 slots) {
     for (u64 s = blockIdx.x * (u64)TPB + threadIdx.x; s < slots; s += (u64)gridDim.x * TPB) {
         u64x2 z;
         z.x = EMPTY_KEY;
         z.y = 0;
-        *(u64x2*)&table[s] = z;
+        st_pol<NT>((u64x2*)&table[s], z);
         z.x = z.y = 0;
-        *(u64x2*)&table[s].st[0] = z;
+        st_pol<NT>((u64x2*)&table[s].st[0], z);
+    }
+}
+
+// ---- hm_rehash_kernel: table growth (hm_grow) ------------------------------------------------------
+// Every key of the old table moves to the new, larger one: claimed from its new home, its value
+// copied, both stamps "present since before the replay rounds" (the epochs restart, as after
+// hm_renorm_kernel). Nothing else runs on the replica (hm_grow flushed the deferred half), so every
+// non-empty old slot holds a present key and the old stamps are not needed: a lane loads the 16 B
+// {key, value} of its slot, a wave 64 consecutive slots (the memory side moves their 16 lines whole
+// either way).
+// The home slot is the TOP bits of mix64(key) (table_home), so growing by 2^d sends old home h to
+// (h << d) | the next d bits: the map is monotone, and a key found at old slot s lands near s << d
+// (it sat s - h >= 0 slots past its old home, h itself near s). So each workgroup takes a
+// CONTIGUOUS run of RH_RUN old slots (128 KiB), not a grid-stride interleave: its claims, stamps and
+// values fall into one contiguous region of the new table (RH_RUN << d slots), the lines it
+// dirties are dirtied while they sit in its XCD's L2, and the pass streams through both tables
+// instead of writing a random line per key. Probe chains cross the regions' edges and wrap at the
+// table's end; the 64-bit CAS of the claim makes that safe without any order between workgroups.
+// A thread takes RH_Q slots at a time, RH_TPB apart: their loads are in flight together, then their
+// claims. A claim is the CAS alone, from the home slot on, with no first probe of the slot as
+// claim_slot / pa_resolve make it: the new table holds none of the keys being moved and, when the load limit
+// manages it, at most one key per four slots, so the probe would nearly always read "empty" and only add a memory round
+// trip and a request per key (configs[1], 2^26 -> 2^27 slots, 10M keys: 1222 us with pa_resolve,
+// 898-950 us with the CAS alone).
+constexpr int RH_TPB = 256, RH_Q = 8;
+constexpr u64 RH_RUN = 4096;  // old slots per workgroup
+static_assert(RH_RUN % ((u64)RH_TPB * RH_Q) == 0, "a run is whole batches");
+__global__ __launch_bounds__(RH_TPB) void hm_rehash_kernel(const Slot* __restrict__ old, u64 old_slots, Slot* table,
+                                                           u32 shift, u64 tmask, DevCtl* ctl) {
+    __shared__ u32 s_moved;
+    if (threadIdx.x == 0) s_moved = 0;
+    __syncthreads();
+    const u64 run0 = (u64)blockIdx.x * RH_RUN;
+    u32 moved = 0;
+    for (u64 b0 = run0; b0 < run0 + RH_RUN && b0 < old_slots; b0 += (u64)RH_TPB * RH_Q) {
+        u64 k[RH_Q], v[RH_Q];
+        bool on[RH_Q];
+#pragma unroll
+        for (int q = 0; q < RH_Q; q++) {
+            const u64 s = b0 + (u64)q * RH_TPB + threadIdx.x;
+            u64x2 e;
+            e.x = EMPTY_KEY;
+            e.y = 0;
+            if (s < old_slots) e = *(const u64x2*)&old[s];
+            k[q] = e.x;
+            v[q] = e.y;
+            on[q] = e.x != EMPTY_KEY;
+        }
+        u64 s[RH_Q];
+        bool any = false;
+#pragma unroll
+        for (int q = 0; q < RH_Q; q++) {
+            s[q] = table_home(k[q], shift);
+            any = any || on[q];
+        }
+        for (u64 pr = 0; any && pr <= tmask; pr++) {
+            u64 was[RH_Q];
+#pragma unroll
+            for (int q = 0; q < RH_Q; q++)
+                if (on[q])
+                    was[q] = atomicCAS((unsigned long long*)&table[s[q]].key, (unsigned long long)EMPTY_KEY,
+                                       (unsigned long long)k[q]);
+            any = false;
+#pragma unroll
+            for (int q = 0; q < RH_Q; q++) {
+                if (!on[q]) continue;
+                if (was[q] == EMPTY_KEY || was[q] == k[q]) {
+                    u64x2 z;
+                    z.x = z.y = STAMP_PRESENT;
+                    *(u64x2*)&table[s[q]].st[0] = z;
+                    table[s[q]].val = v[q];
+                    moved++;
+                    on[q] = false;
+                } else {
+                    s[q] = (s[q] + 1) & tmask;
+                    any = true;
+                }
+            }
+        }
+        if (any) atomicOr(&ctl->err, ERR_TABLE_FULL);  // (cannot happen: the new table is the larger one)
+    }
+    if (moved) atomicAdd(&s_moved, moved);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 m = s_moved;
+        if (blockIdx.x == 0 && ctl->sp_claim) {  // the side slot lives in DevCtl and does not move
+            ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
+            m++;
+        }
+        if (m) atomicAdd((unsigned long long*)&ctl->nkeys, (unsigned long long)m);  // (hm_grow zeroed it)
     }
 }
 
@@ -1837,8 +1929,100 @@ static hipError_t skew_sample(nrg_ctx* c) {
 }
 
 hipError_t hm_init(nrg_ctx* c) {
-    hm_init_table_kernel<<<grid_for(c->slots, 16384), TPB, 0, c->stream>>>(c->d_table, c->slots);
+    hm_init_table_kernel<false><<<grid_for(c->slots, 16384), TPB, 0, c->stream>>>(c->d_table, c->slots);
     return hipGetLastError();
+}
+
+// ---- table growth ---------------------------------------------------------------------------------
+// HashMap<u64, u64> grows as it fills (nr/examples/hashmap.rs starts from an empty map;
+// benches/hashmap.rs:91-100 only pre-sizes it). Here: a synchronous rehash into a larger table,
+// rare, decided on the host from an upper bound of the key count (hm_room).
+u32 hm_slots_for(u64 keys) {
+    u32 l = 4;  // the smallest table nrg_open accepts
+    while (l < 63 && (1ull << l) / HM_GROW_SLOTS_PER_KEY < keys) l++;
+    return l;
+}
+
+// Steps, in stream order: the deferred half of the last round runs against the old table (after
+// it no claim is in flight: what hm_renorm_kernel relies on too); the new table is initialised;
+// the rehash; the epochs restart as in next_epoch's renormalisation (every stamp is "present",
+// the put_slot / win / over tags hold slot ids and epochs of the old table); the key count is
+// folded into DevCtl::nkeys (exact) and the created-key counters cleared. Then the stream is
+// synchronised, the old table freed and the new one installed. If the allocation fails nothing
+// has been launched but the flush: the old table stays installed and the replica is as it was.
+hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
+    if (new_log2 > 30 || (1ull << new_log2) <= c->slots) return hipErrorInvalidValue;
+    hipError_t e = hm_flush(c);
+    if (e != hipSuccess) return e;
+    const u64 nslots = 1ull << new_log2;
+    Slot* nt = nullptr;
+    if ((e = hipMalloc(&nt, nslots * sizeof(Slot))) != hipSuccess) {
+        (void)hipGetLastError();  // (the failure is reported by the return value alone)
+        return hipErrorOutOfMemory;
+    }
+    const bool nt_init = (c->exp >> 7) & 1;  // (A/B: streamed init stores; measured 2.6x slower)
+    if (nt_init) NRG_LAUNCH(c, "hm_grow_init", hm_init_table_kernel<true>, grid_for(nslots, 16384), TPB, 0, c->stream, nt, nslots);
+    else NRG_LAUNCH(c, "hm_grow_init", hm_init_table_kernel<false>, grid_for(nslots, 16384), TPB, 0, c->stream, nt, nslots);
+    if ((e = hipGetLastError()) == hipSuccess) e = hipMemsetAsync(&c->d_ctl->nkeys, 0, sizeof(u64), c->stream);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)((c->slots + RH_RUN - 1) / RH_RUN);
+        NRG_LAUNCH(c, "hm_rehash", hm_rehash_kernel, grid, RH_TPB, 0, c->stream, c->d_table, c->slots, nt,
+                   64 - new_log2, nslots - 1, c->d_ctl);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream);
+    for (int i = 0; i < 2 && c->d_put_slot[i] && e == hipSuccess; i++)
+        e = hipMemsetAsync(c->d_put_slot[i], 0, 3 * c->stamp_alloc * sizeof(u32), c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        // a launch or the stream failed: the old table is still the replica's
+        (void)hipFree(nt);
+        return e;
+    }
+    (void)hipFree(c->d_table);
+    c->d_table = nt;
+    c->slots = nslots;
+    c->slot_shift = 64 - new_log2;
+    c->epoch = 1;
+    return hipSuccess;
+}
+
+// The growth policy. With growth enabled a table of S slots is kept to S / HM_GROW_SLOTS_PER_KEY
+// keys. The n Puts about to be replayed (or keys about to be prefilled) are added to the upper
+// bound keys_ub; only when the bound passes the limit is the exact count taken (hm_count sums 8192
+// counters and does not scan the table; an 8-B copy and a stream synchronise), and only if
+// exact + n still passes the limit does the table grow, straight to the smallest size that holds
+// exact + n keys or to the configured maximum. At the maximum the table is a fixed one: nothing
+// is counted, and a table that really fills latches ERR_TABLE_FULL as a fixed table does. The
+// decision (exact + n against the size) depends on the log prefix and the configuration alone, so
+// the replicas of a group, which replay the same log in the same chunks, grow at the same round.
+hipError_t hm_room(nrg_ctx* c, u64 n, bool* due) {
+    if (due) *due = false;
+    const u32 log2_slots = 64 - c->slot_shift;
+    if (!n || c->grow_max_log2 <= log2_slots) return hipSuccess;
+    if (n > (1ull << 31)) n = 1ull << 31;  // (more than any table holds; keeps the sums below from wrapping)
+    const u64 limit = c->slots / HM_GROW_SLOTS_PER_KEY;
+    if (c->keys_ub + n <= limit) {
+        c->keys_ub += n;
+        return hipSuccess;
+    }
+    if (due) {
+        *due = true;
+        return hipSuccess;
+    }
+    hipError_t e = hm_count(c);  // (flushes the deferred half first)
+    if (e != hipSuccess) return e;
+    u64 exact = 0;
+    if ((e = hipMemcpyAsync(&exact, &c->d_ctl->nkeys_total, sizeof(u64), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+    if (exact + n > limit) {
+        u32 want = hm_slots_for(exact + n);
+        if (want > c->grow_max_log2) want = c->grow_max_log2;
+        if ((e = hm_grow(c, want)) != hipSuccess) return e;
+    }
+    c->keys_ub = exact + n;
+    return hipSuccess;
 }
 
 // The next round's epoch; before the 32-bit epoch wraps, every stamp is renormalised to epoch 1.
@@ -1867,6 +2051,8 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
     if (n > HM_MAX_BATCH) return hipErrorInvalidValue;
     const nrg_put* src = (const nrg_put*)src_recs;
     const bool want_prev = d_prev && resp_lo < lo + n && resp_hi > lo;
+    hipError_t eg = hm_room(c, n);  // every round kind below: the table grows first if it has to
+    if (eg != hipSuccess) return eg;
     if (c->small_max && n <= c->small_max && n <= SM_W && R <= SM_R) {  // one launch, nothing deferred
         hipError_t e = small_round(c, src, lo, n, write_ring, d_get_keys, R, d_get_vals, d_get_found, resp_lo, resp_hi,
                                    want_prev ? d_prev : nullptr, d_prev_found);
@@ -2003,6 +2189,13 @@ hipError_t hm_get_only(nrg_ctx* c, const u64* d_keys, u64 n, u64* d_vals, uint8_
 hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part, u32 parts) {
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
+    // room for the keys first (growth enabled): all n, or a key partition's exact share of them
+    u64 mine = n;
+    if (parts > 1 && c->grow_max_log2 > 64 - c->slot_shift) {
+        mine = 0;
+        for (u64 k = 0; k < n; k++) mine += key_owner(k, parts) == part;
+    }
+    if ((e = hm_room(c, mine)) != hipSuccess) return e;
     hm_prefill_range_kernel<<<grid_for(n, 8192), TPB, 0, c->stream>>>(c->d_table, n, off, c->slot_shift,
                                                                       c->slots - 1, c->d_ctl, part, parts);
     return hipGetLastError();

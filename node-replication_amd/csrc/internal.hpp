@@ -121,7 +121,12 @@ struct nrg_ctx {
     uint32_t slot_shift = 0;  // 64 - log2_slots
     uint64_t slots = 0;
     nrg::Slot* d_table = nullptr;
-    uint64_t rounds = 0;             // replay rounds launched (statistics)
+    // Table growth (hashmap.hip hm_room / hm_grow): the table may grow to 2^grow_max_log2 slots
+    // (0: fixed); keys_ub bounds the key count from above: the exact count when it was last taken
+    // plus every Put replayed and every key prefilled since.
+    uint32_t grow_max_log2 = 0;
+    uint64_t keys_ub = 0;
+    uint64_t rounds = 0;            // replay rounds launched (statistics)
     // tuning and diagnostic knobs: set only through nrg_test_set_knob (include/nrgpu_testing.h)
     uint32_t k1_items = 0;           // Puts per index thread (0: by round size; NRG_KNOB_K1)
     uint32_t exp = 0;                // diagnostic bits (NRG_KNOB_EXP; see hashmap.hip StampJob)
@@ -241,6 +246,16 @@ hipError_t hm_init(nrg_ctx* c);
 hipError_t hm_alloc(nrg_ctx* c, u64 max_batch);  // per-round scratch (entries, counts, overlays)
 void hm_free(nrg_ctx* c);
 hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part = 0, u32 parts = 1);
+// Table growth. hm_room: every path calls it before it replays n Puts (or prefills n keys): it adds
+// them to keys_ub and, when the load limit could be passed, counts the keys and grows the table
+// (synchronously). With `due` given it launches nothing: when a count or a grow would be needed it
+// sets *due, accounts nothing and returns (the combiner's round server must stop first).
+// hm_grow: rehash into a table of 2^new_log2_slots slots (larger than the current one);
+// hipErrorOutOfMemory leaves the old table installed and the replica as it was.
+// hm_slots_for: log2 of the smallest table that holds `keys` keys at the load limit.
+hipError_t hm_room(nrg_ctx* c, u64 n, bool* due = nullptr);
+hipError_t hm_grow(nrg_ctx* c, u32 new_log2_slots);
+u32 hm_slots_for(u64 keys);
 // partition.hip: stable partition of records (key in word 0) by key owner; answers routed back
 hipError_t pt_partition(nrg_ctx* c, const u64* in, u64 n, u32 words, u32 parts, u64* out, u32* pos, u64* total);
 hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, const u32* pos, u64 n, u64* dst, uint8_t* dst8);

@@ -208,6 +208,11 @@ int hm_small_job(nrg_ctx* c, const nrg_put* recs, u64 W, u32 origin, const u64* 
     if (r) return r;
     const uint64_t lo = c->tail;
     if (!hm_small_fill(c, recs, lo, W, keys, R, vals, found, prev, prevf, e_out, blob)) return NRG_E_INVAL;
+    // the round's Puts against the table's load limit (hm_room): a round before which the keys have
+    // to be counted or the table has to grow is not served but launched -- the combiner stops the
+    // server before any launch, and the launched round counts and grows in hm_replay_chunk
+    bool due = false;
+    if (hm_room(c, W, &due) != hipSuccess || due) return NRG_E_INVAL;
     if (lo_out) *lo_out = lo;
     c->rounds++;
     if (W) note_origin(c, lo, W, origin);
@@ -323,6 +328,10 @@ int nrg_open(int dev, const nrg_config* cfg_in, nrg_ctx** out) {
     *out = nullptr;
     const uint32_t rb = rec_bytes_for(cfg_in->ds_kind);
     if (!rb) return NRG_E_INVAL;
+    // table growth (0: a fixed table): up to a size nrg_open accepts for log2_slots, never below it
+    if (cfg_in->ds_kind == NRG_DS_HASHMAP && cfg_in->hashmap_max_log2_slots &&
+        (cfg_in->hashmap_max_log2_slots < cfg_in->log2_slots || cfg_in->hashmap_max_log2_slots > 30))
+        return NRG_E_INVAL;
     int ndev = nrg_device_count();
     if (dev < 0 || dev >= ndev) return NRG_E_NODEV;
     nrg_ctx* c = new (std::nothrow) nrg_ctx();
@@ -363,6 +372,7 @@ int nrg_open(int dev, const nrg_config* cfg_in, nrg_ctx** out) {
         // slot ids are < 2^30 (entry ids carry two flag values above them, hashmap.hip);
         // replay chunks are bounded by the partition rounds' 16-bit tile offsets (HM_MAX_BATCH)
         if (cf.log2_slots < 4 || cf.log2_slots > 30 || mb > HM_MAX_BATCH) { nrg_close(c); return NRG_E_INVAL; }
+        c->grow_max_log2 = cf.hashmap_max_log2_slots;  // (checked above; 0: a fixed table)
         c->slots = 1ull << cf.log2_slots;
         c->slot_shift = 64 - cf.log2_slots;
         OPEN_CHK(hipMalloc(&c->d_table, c->slots * sizeof(Slot)));
@@ -760,6 +770,24 @@ int nrg_hashmap_prefill_range(nrg_ctx* c, uint64_t n, uint64_t off) {
     HIPCHK(hm_prefill_range(c, n, off));
     HIPCHK(sync_all(c));
     return check_err(c);
+}
+
+// HashMap::reserve / with_capacity (benches/hashmap.rs:91-100 pre-sizes the map; nr/examples/hashmap.rs
+// lets it grow): a table that holds n_keys keys in all at the load limit. Never shrinks.
+int nrg_hashmap_reserve(nrg_ctx* c, uint64_t n_keys) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (n_keys > (1ull << 30) / HM_GROW_SLOTS_PER_KEY) return NRG_E_INVAL;  // beyond nrg_open's largest table
+    const uint32_t want = hm_slots_for(n_keys);
+    if ((1ull << want) <= c->slots) return NRG_OK;
+    HIPCHK(hm_grow(c, want));
+    return NRG_OK;
+}
+
+int nrg_hashmap_capacity(nrg_ctx* c, uint32_t* log2_slots) {
+    if (!c || !log2_slots || c->cfg.ds_kind != NRG_DS_HASHMAP) return NRG_E_INVAL;
+    *log2_slots = 64 - c->slot_shift;
+    return NRG_OK;
 }
 
 // ---- cnr-style key partitioning (partition.hip) ----------------------------

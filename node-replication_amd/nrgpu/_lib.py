@@ -70,6 +70,7 @@ class Config(C.Structure):
         ("stack_push_resp", C.c_uint32),
         ("replica_id", C.c_uint32),
         ("pipeline", C.c_uint32),
+        ("hashmap_max_log2_slots", C.c_uint32),
         ("queue_capacity", C.c_uint64),
     ]
 
@@ -136,6 +137,8 @@ SIGNATURES = {
     "nrg_hashmap_prefill": (C.c_int, [vp, vp, vp, u64]),
     "nrg_hashmap_prefill_range": (C.c_int, [vp, u64, u64]),
     "nrg_hashmap_size": (C.c_int, [vp, u64p]),
+    "nrg_hashmap_reserve": (C.c_int, [vp, u64]),
+    "nrg_hashmap_capacity": (C.c_int, [vp, C.POINTER(u32)]),
     "nrg_hashmap_dump": (C.c_int, [vp, vp, vp, u64, u64p]),
     "nrg_hashmap_digest": (C.c_int, [vp, vp]),
     "nrg_stack_init": (C.c_int, [vp, vp, u64]),

@@ -330,6 +330,24 @@ class DeviceReplica:
         L.check(self._lib.nrg_hashmap_size(self._h, C.byref(n)))
         return n.value
 
+    def hm_reserve(self, n_keys: int):
+        """HashMap::reserve: a table large enough for `n_keys` keys in all (one key per two slots);
+        never shrinks (nrg_hashmap_reserve). Synchronous."""
+        if self.kind != L.NRG_DS_HASHMAP:
+            raise TypeError("hm_reserve needs a hashmap replica")
+        n_keys = int(n_keys)
+        if n_keys < 0 or n_keys >= 2**64:
+            raise ValueError("n_keys must be a u64")
+        L.check(self._lib.nrg_hashmap_reserve(self._h, n_keys), "reserve")
+
+    def hm_log2_slots(self) -> int:
+        """log2 of the table's current number of slots (nrg_hashmap_capacity)."""
+        if self.kind != L.NRG_DS_HASHMAP:
+            raise TypeError("hm_log2_slots needs a hashmap replica")
+        n = C.c_uint32()
+        L.check(self._lib.nrg_hashmap_capacity(self._h, C.byref(n)), "capacity")
+        return n.value
+
     def hm_dump(self):
         """(keys, vals) sorted by key"""
         n = self.hm_size()
