@@ -556,8 +556,7 @@ int post_and_wait(nrg_combiner* m, uint32_t token, bool write, const void* ops, 
 extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combiner** out) {
     if (!ctx || !out || !max_threads || max_threads > 4096) return NRG_E_INVAL;
     const uint32_t kind = ctx->cfg.ds_kind;
-    if (kind != NRG_DS_HASHMAP && kind != NRG_DS_STACK && kind != NRG_DS_SYNTHETIC && kind != NRG_DS_QUEUE)
-        return NRG_E_INVAL;
+    if (!nrg::ds_ops(kind)) return NRG_E_INVAL;
     const uint64_t cap = (uint64_t)max_threads * MAX_PENDING;
     if (cap > ctx->cfg.max_batch || (kind == NRG_DS_HASHMAP && cap > ctx->cfg.max_reads)) return NRG_E_CAPACITY;
     int r = nrg::ctx_use_device(ctx);
@@ -572,12 +571,13 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
     m->max_threads = max_threads;
     m->cap = cap;
     m->rec_b = ctx->rec_bytes;
-    switch (kind) {
-        case NRG_DS_HASHMAP: m->rd_b = 8, m->wr_b = 8, m->rr_b = 8; break;            // key; previous value; value
-        case NRG_DS_STACK: m->rd_b = 0, m->wr_b = 4, m->rr_b = 4; break;              // Peek; popped; top
-        case NRG_DS_QUEUE: m->rd_b = 0, m->wr_b = 8, m->rr_b = 8; break;              // Len; pushed or popped; length
-        case NRG_DS_SYNTHETIC: m->rd_b = sizeof(nrg_synth_rd), m->wr_b = 8, m->rr_b = 8; break;  // sums
-        default: comb_free(m); return NRG_E_INVAL;  // (the kind check above admits no other)
+    m->wr_b = ctx->ops->resp_bytes;
+    switch (kind) {  // a read and its answer
+        case NRG_DS_HASHMAP: m->rd_b = 8, m->rr_b = 8; break;                     // key; value
+        case NRG_DS_STACK: m->rd_b = 0, m->rr_b = 4; break;                       // Peek; top
+        case NRG_DS_QUEUE: m->rd_b = 0, m->rr_b = 8; break;                       // Len; length
+        case NRG_DS_SYNTHETIC: m->rd_b = sizeof(nrg_synth_rd), m->rr_b = 8; break;  // ReadOnly; sum
+        default: comb_free(m); return NRG_E_INVAL;  // (a kind whose reads the combiner does not know)
     }
     bool ok = true;
     ok = ok && (m->tok = new (std::nothrow) nrg_combiner::Tok[max_threads]());

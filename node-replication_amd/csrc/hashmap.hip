@@ -1423,6 +1423,7 @@ __global__ __launch_bounds__(SM_TPB) void hm_serve_kernel(ServeCtl* sc, const Sm
 }
 
 static RecSrc ring_src(nrg_ctx* c, const nrg_put* src, u64 lo);
+static hipError_t hm_flush(nrg_ctx* c);
 
 // A round through hm_small_round_kernel (hm_replay_chunk decides; n <= SM_W, R <= SM_R).
 static hipError_t small_round(nrg_ctx* c, const nrg_put* src, u64 lo, u64 n, bool write_ring, const u64* keys, u64 R,
@@ -1845,7 +1846,8 @@ static hipError_t launch(nrg_ctx* c, Launch& L) {
     return hipGetLastError();
 }
 
-hipError_t hm_flush(nrg_ctx* c) {
+// The deferred half of the last replayed round (its reads and, for a stamp round, its apply), if any.
+static hipError_t hm_flush(nrg_ctx* c) {
     if (!c->pend.valid) return hipSuccess;
     Launch L;
     attach_deferred(c, L);
@@ -1873,7 +1875,8 @@ static hipError_t hm_reads(nrg_ctx* c, const u64* keys, u64 R, u64* vals, uint8_
     return launch(c, L);
 }
 
-hipError_t hm_alloc(nrg_ctx* c, u64 mb) {
+// per-round scratch (entries, counts, overlays)
+static hipError_t hm_alloc(nrg_ctx* c, u64 mb) {
     const u64 tiles = (mb + TPB - 1) / TPB;  // index tiles of >= TPB Puts
     const u64 ents = tiles * TPB;
     hipError_t e;
@@ -1901,15 +1904,11 @@ hipError_t hm_alloc(nrg_ctx* c, u64 mb) {
     return hipSuccess;
 }
 
-void hm_free(nrg_ctx* c) {
-    for (int i = 0; i < 2; i++) {
-        if (c->d_put_slot[i]) (void)hipFree(c->d_put_slot[i]);
-        c->d_put_slot[i] = nullptr;
-    }
-    if (c->d_dup) (void)hipFree(c->d_dup);
+static void hm_close(nrg_ctx* c) {
+    void* ptrs[] = {c->d_table, c->d_created, c->d_bk_ent, c->d_bk_idx, c->d_bk_cnt, c->d_put_slot[0],
+                    c->d_put_slot[1], c->d_dup};
+    for (void* p : ptrs) (void)hipFree(p);
     if (c->h_dup) (void)hipHostFree((void*)c->h_dup);
-    c->d_dup = nullptr;
-    c->h_dup = nullptr;
 }
 
 // Every dup_every rounds: read the previous sample (if it has landed) and decide whether the
@@ -1928,9 +1927,27 @@ static hipError_t skew_sample(nrg_ctx* c) {
     return hipSuccess;
 }
 
-hipError_t hm_init(nrg_ctx* c) {
+static int hm_open(nrg_ctx* c) {
+    const nrg_config& cf = c->cfg;
+    // slot ids are < 2^30 (entry ids carry two flag values above them); replay chunks are
+    // bounded by the partition rounds' 16-bit tile offsets (HM_MAX_BATCH)
+    if (cf.log2_slots < 4 || cf.log2_slots > 30 || cf.max_batch > HM_MAX_BATCH) return NRG_E_INVAL;
+    c->grow_max_log2 = cf.hashmap_max_log2_slots;  // (checked by nrg_open; 0: a fixed table)
+    c->slots = 1ull << cf.log2_slots;
+    c->slot_shift = 64 - cf.log2_slots;
+    HIPCHK(hipMalloc(&c->d_table, c->slots * sizeof(Slot)));
     hm_init_table_kernel<false><<<grid_for(c->slots, 16384), TPB, 0, c->stream>>>(c->d_table, c->slots);
-    return hipGetLastError();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMalloc(&c->d_created, HM_CREATED_SLOTS * sizeof(u64)));
+    HIPCHK(hipMemsetAsync(c->d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
+    // rounds without previous values replay in one launch (stamp rounds) unless the key
+    // stream is skewed (skew_sample) or the round is large (PART_MIN); skewed, large and
+    // previous-value rounds take partition rounds
+    c->stamp_max = HM_MAX_BATCH;       // (NRG_KNOB_STAMP_MAX lowers it for tests)
+    HIPCHK(hm_alloc(c, cf.max_batch));  // clamps stamp_max to max_batch (the put_slot arrays' size)
+    c->stamp_alloc = c->stamp_max;
+    c->pipeline = cf.pipeline != 0;
+    return NRG_OK;
 }
 
 // ---- table growth ---------------------------------------------------------------------------------
@@ -2184,6 +2201,18 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
 
 hipError_t hm_get_only(nrg_ctx* c, const u64* d_keys, u64 n, u64* d_vals, uint8_t* d_found) {
     return hm_reads(c, d_keys, n, d_vals, d_found);
+}
+
+// a chunk without reads; responses are the Puts' previous values
+static hipError_t hm_replay(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                            uint8_t* d_some) {
+    return hm_replay_chunk(c, src, lo, n, src != nullptr, nullptr, 0, nullptr, nullptr, resp_lo, resp_hi,
+                           (u64*)d_resp, d_some);
+}
+
+const DsOps* hm_ops() {
+    static const DsOps ops = {sizeof(nrg_put), sizeof(u64), hm_open, hm_close, hm_flush, hm_replay};
+    return &ops;
 }
 
 hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part, u32 parts) {

@@ -100,11 +100,33 @@ struct HostRun {  // origin tags of appended log ranges (the Entry::replica fiel
     u32 origin;
 };
 
+// What the runtime knows about a data structure: one table per kind, defined beside the
+// structure's launchers (hashmap.hip, stack.hip, synthetic.hip, queue.hip).
+struct DsOps {
+    uint32_t rec_bytes;   // one log record
+    uint32_t resp_bytes;  // one write response
+    // validate c->cfg, allocate and initialise the structure; an NRG_* code (nrg_open closes the
+    // context on failure, so nothing is released here)
+    int (*open)(nrg_ctx* c);
+    // free what open, and growth since, allocated
+    void (*close)(nrg_ctx* c);
+    // launch the work the last replayed chunk deferred, if any
+    hipError_t (*flush)(nrg_ctx* c);
+    // replay the n records at log positions [lo, lo + n) (n <= max_batch): from the ring, or from
+    // `src` if given, and then the ring copy is written too; write responses of [resp_lo, resp_hi)
+    // into d_resp / d_some (nullptr: none wanted)
+    hipError_t (*replay)(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                         uint8_t* d_some);
+};
+const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops();
+const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
+
 }  // namespace nrg
 
 struct nrg_ctx {
     int device = 0;
     nrg_config cfg{};
+    const nrg::DsOps* ops = nullptr;  // of cfg.ds_kind
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
 
@@ -232,19 +254,29 @@ bool timer_events(nrg_ctx* c, const char* name, hipEvent_t* start, hipEvent_t* s
     } while (0)
 // make the context's device current for this thread (runtime.cpp; cached per thread)
 int ctx_use_device(nrg_ctx* c);
-// launch the deferred reads of the last hashmap round, if any (hashmap.hip)
-hipError_t hm_flush(nrg_ctx* c);
-hipError_t st_flush(nrg_ctx* c);
-hipError_t sy_flush(nrg_ctx* c);
+
+inline int hip_fail(hipError_t e) {
+    if (e == hipSuccess) return NRG_OK;
+    if (e == hipErrorOutOfMemory) return NRG_E_NOMEM;
+    return NRG_E_HIP;
+}
+#define HIPCHK(x)                                  \
+    do {                                           \
+        hipError_t _e = (x);                       \
+        if (_e != hipSuccess) return hip_fail(_e); \
+    } while (0)
+
+inline uint64_t pow2_at_least(uint64_t x) {
+    uint64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
 
 // hashmap.hip
 hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool write_ring,
                            const u64* d_get_keys, u64 R, u64* d_get_vals, uint8_t* d_get_found,
                            u64 resp_lo, u64 resp_hi, u64* d_prev, uint8_t* d_prev_found);
 hipError_t hm_get_only(nrg_ctx* c, const u64* d_keys, u64 n, u64* d_vals, uint8_t* d_found);
-hipError_t hm_init(nrg_ctx* c);
-hipError_t hm_alloc(nrg_ctx* c, u64 max_batch);  // per-round scratch (entries, counts, overlays)
-void hm_free(nrg_ctx* c);
 hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part = 0, u32 parts = 1);
 // Table growth. hm_room: every path calls it before it replays n Puts (or prefills n keys): it adds
 // them to keys_ub and, when the load limit could be passed, counts the keys and grows the table
@@ -309,23 +341,11 @@ hipError_t gen_zipf(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 N, double theta, in
 hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_stride, const u64* lens,
                          u64 dst_lo);
 
-// stack.hip
-hipError_t st_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, uint32_t* d_resp,
-                           uint8_t* d_some, const nrg_stack_op* src = nullptr);
-u64 st_aux_bytes(u64 max_batch);   // size of nrg_ctx::d_st_aux
-u64 st_desc_words(u64 max_batch);  // u32 words of look-back descriptors the stack needs
-
 // queue.hip
-hipError_t qu_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, u64* d_resp, uint8_t* d_some,
-                           const nrg_queue_op* src = nullptr);
 hipError_t qu_init_range(nrg_ctx* c, u64 n);  // values 0..n-1, front first
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads
-u64 qu_aux_bytes(u64 max_batch);  // size of nrg_ctx::d_qu_aux
 
 // synthetic.hip
-hipError_t sy_init(nrg_ctx* c);
-hipError_t sy_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, u64* d_resp,
-                           uint8_t* d_some, const nrg_synth_op* src = nullptr);
 hipError_t sy_read(nrg_ctx* c, const nrg_synth_rd* d_ops, u64 n, u64* d_sums);
 bool sy_bucket_eligible(const nrg_config& cf);  // configs the sort-free bucket replay handles
 u64 sy_bucket_aux_bytes(const nrg_config& cf);  // size of nrg_ctx::d_sy_aux

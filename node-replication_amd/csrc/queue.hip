@@ -347,15 +347,15 @@ __global__ void qu_len_kernel(const QuState* st, u32 n, u64* out, uint8_t* some)
 
 static u64 qu_max_tiles(u64 max_batch) { return (max_batch + QU_TILE - 1) / QU_TILE; }
 
-u64 qu_aux_bytes(u64 max_batch) { return qu_max_tiles(max_batch) * (sizeof(QuAgg) + sizeof(QuStart)); }
+static u64 qu_aux_bytes(u64 max_batch) { return qu_max_tiles(max_batch) * (sizeof(QuAgg) + sizeof(QuStart)); }
 
 // One chunk of at most max_batch records: log indices [lo, lo + n), read from the ring or, for a
 // fused round, from `src` (the log copy is then written by the aggregate pass).
-hipError_t qu_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, u64* d_resp, uint8_t* d_some,
-                           const nrg_queue_op* src) {
+static hipError_t qu_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                                  uint8_t* d_some) {
     if (n == 0) return hipSuccess;
     QuJob j{};
-    j.src = src;
+    j.src = (const nrg_queue_op*)src;
     j.ring = (nrg_queue_op*)c->d_ring;
     j.ring_mask = c->log_size - 1;
     j.lo = lo;
@@ -364,7 +364,7 @@ hipError_t qu_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, 
     const bool want = d_resp != nullptr && d_some != nullptr && resp_lo < resp_hi && resp_lo < lo + n && resp_hi > lo;
     j.rlo = want ? resp_lo : 0;
     j.rhi = want ? resp_hi : 0;
-    j.resp = want ? d_resp : nullptr;
+    j.resp = want ? (u64*)d_resp : nullptr;
     j.some = want ? d_some : nullptr;
     j.q = c->d_queue;
     j.qmask = c->qu_size - 1;
@@ -395,6 +395,35 @@ hipError_t qu_init_range(nrg_ctx* c, u64 n) {
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some) {
     qu_len_kernel<<<1, 256, 0, c->stream>>>(c->d_qu_state, n, d_out, d_some);
     return hipGetLastError();
+}
+
+static int qu_open(nrg_ctx* c) {
+    const nrg_config& cf = c->cfg;
+    const u64 mb = cf.max_batch;
+    // max_batch <= 2^24: one workgroup scans the tile aggregates; the capacity bounds the ring of
+    // u64 values
+    if (!cf.queue_capacity || cf.queue_capacity > (1ull << 32) || mb > (1ull << 24)) return NRG_E_INVAL;
+    // capacity + max_batch slots: the positions one chunk touches never alias
+    c->qu_size = pow2_at_least(cf.queue_capacity + mb);
+    HIPCHK(hipMalloc(&c->d_queue, c->qu_size * sizeof(u64)));
+    HIPCHK(hipMalloc(&c->d_qu_state, sizeof(QuState)));
+    HIPCHK(hipMemsetAsync(c->d_qu_state, 0, sizeof(QuState), c->stream));
+    HIPCHK(hipMalloc(&c->d_qu_aux, qu_aux_bytes(mb)));
+    c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
+    return NRG_OK;
+}
+
+static void qu_close(nrg_ctx* c) {
+    (void)hipFree(c->d_queue);
+    (void)hipFree(c->d_qu_state);
+    (void)hipFree(c->d_qu_aux);
+}
+
+static hipError_t qu_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
+
+const DsOps* qu_ops() {
+    static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk};
+    return &ops;
 }
 
 }  // namespace nrg

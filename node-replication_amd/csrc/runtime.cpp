@@ -1,6 +1,7 @@
 // runtime.cpp — the nrgpu C ABI (include/nrgpu.h): replica lifetime, the per-replica HBM
 // log ring with the reference's head/tail/ctail/ltail bookkeeping, and dispatch of the
-// replay pipelines (hashmap.hip, stack.hip, synthetic.hip).
+// replay pipelines through each structure's ops table (hashmap.hip, stack.hip, synthetic.hip,
+// queue.hip).
 //
 // Log bookkeeping follows nr/src/log.rs: Log::new sizing (:179-242), append with GC when
 // fewer than GC_FROM_HEAD entries would remain (:343-427, :536-580), exec of
@@ -25,40 +26,6 @@ constexpr uint64_t GC_FROM_HEAD = 32 * 256;  // MAX_PENDING_OPS * MAX_THREADS_PE
 constexpr uint64_t ENTRY_BYTES = 64;         // size_of::<Entry<T>>() in the reference
 constexpr uint64_t DEFAULT_LOG_BYTES = 32ull << 20;
 
-uint64_t pow2_at_least(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-uint32_t bits_for(uint64_t maxval) {  // smallest b with (1<<b)-1 >= maxval
-    uint32_t b = 1;
-    while (((1ull << b) - 1) < maxval) b++;
-    return b;
-}
-
-int hip_fail(hipError_t e) {
-    if (e == hipSuccess) return NRG_OK;
-    if (e == hipErrorOutOfMemory) return NRG_E_NOMEM;
-    return NRG_E_HIP;
-}
-
-#define HIPCHK(x)                                \
-    do {                                         \
-        hipError_t _e = (x);                     \
-        if (_e != hipSuccess) return hip_fail(_e); \
-    } while (0)
-
-uint32_t rec_bytes_for(uint32_t kind) {
-    switch (kind) {
-        case NRG_DS_HASHMAP: return sizeof(nrg_put);
-        case NRG_DS_STACK: return sizeof(nrg_stack_op);
-        case NRG_DS_SYNTHETIC: return sizeof(nrg_synth_op);
-        case NRG_DS_QUEUE: return sizeof(nrg_queue_op);
-        default: return 0;
-    }
-}
-
 thread_local int g_dev_set = -1;
 
 int use_device(nrg_ctx* c) {
@@ -70,14 +37,9 @@ int use_device(nrg_ctx* c) {
 }
 
 // the deferred half of the last hashmap round (hashmap.hip), the deferred finish of the last
-// stack chunk (stack.hip) or the deferred sums of the last synthetic chunk (synthetic.hip),
+// stack chunk (stack.hip) or the deferred sums of the last synthetic chunks (synthetic.hip),
 // launched now if there is one
-hipError_t hm_flush_if(nrg_ctx* c) {
-    if (c->cfg.ds_kind == NRG_DS_HASHMAP) return hm_flush(c);
-    if (c->cfg.ds_kind == NRG_DS_STACK) return st_flush(c);
-    if (c->cfg.ds_kind == NRG_DS_QUEUE) return hipSuccess;  // a queue chunk defers nothing (queue.hip)
-    return sy_flush(c);
-}
+hipError_t flush_deferred(nrg_ctx* c) { return c->ops->flush(c); }
 
 // Log GC boundary: the slowest replica's tail (this replica's ltail), held back to the first
 // record of a deferred hashmap stamp round, whose apply and reads take values from the ring.
@@ -87,9 +49,9 @@ uint64_t gc_head(const nrg_ctx* c) {
     return c->ltail;
 }
 
-// wait for everything queued on this replica, including a deferred hashmap round
+// wait for everything queued on this replica, including what the last chunk deferred
 hipError_t sync_all(nrg_ctx* c) {
-    hipError_t e = hm_flush_if(c);
+    hipError_t e = flush_deferred(c);
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(c->stream);
 }
@@ -110,34 +72,37 @@ int check_err(nrg_ctx* c) {
     return NRG_OK;
 }
 
-// replay [ltail, tail) in order, in chunks of at most max_batch records
-int exec_range(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_resp, uint8_t* d_some) {
+struct HmGets {  // hashmap reads answered against the state after a replay
+    const uint64_t* keys;
+    uint64_t R;
+    uint64_t* vals;
+    uint8_t* found;
+};
+
+// replay [ltail, tail) in order, in chunks of at most max_batch records; `gets` (hashmap) are
+// fused into the last chunk
+int exec_range(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_resp, uint8_t* d_some,
+               const HmGets* gets = nullptr) {
     while (c->ltail < c->tail) {
         uint64_t n = c->tail - c->ltail;
         if (n > c->cfg.max_batch) n = c->cfg.max_batch;
         const uint64_t lo = c->ltail;
-        hipError_t e = hipSuccess;
-        switch (c->cfg.ds_kind) {
-            case NRG_DS_HASHMAP:
-                e = hm_replay_chunk(c, nullptr, lo, n, false, nullptr, 0, nullptr, nullptr, resp_lo, resp_hi,
-                                    (u64*)d_resp, d_some);
-                break;
-            case NRG_DS_STACK:
-                e = st_replay_chunk(c, lo, n, resp_lo, resp_hi, (uint32_t*)d_resp, d_some);
-                break;
-            case NRG_DS_SYNTHETIC:
-                e = sy_replay_chunk(c, lo, n, resp_lo, resp_hi, (u64*)d_resp, d_some);
-                break;
-            case NRG_DS_QUEUE:
-                e = qu_replay_chunk(c, lo, n, resp_lo, resp_hi, (u64*)d_resp, d_some);
-                break;
-            default: return NRG_E_INVAL;
-        }
-        if (e != hipSuccess) return hip_fail(e);
+        if (gets && lo + n == c->tail)
+            HIPCHK(hm_replay_chunk(c, nullptr, lo, n, false, gets->keys, gets->R, gets->vals, gets->found, resp_lo,
+                                   resp_hi, (u64*)d_resp, d_some));
+        else
+            HIPCHK(c->ops->replay(c, nullptr, lo, n, resp_lo, resp_hi, d_resp, d_some));
         c->ltail = lo + n;
     }
     if (c->ctail < c->ltail) c->ctail = c->ltail;
     return NRG_OK;
+}
+
+// a round appended and replayed in one go (Log::append + Log::exec of [lo, lo + n))
+void commit_round(nrg_ctx* c, uint64_t lo, uint64_t n) {
+    c->tail = lo + n;
+    c->ltail = c->tail;
+    if (c->ctail < c->tail) c->ctail = c->tail;
 }
 
 // Make room for n records (Log::append's GC path): advance head to the slowest replica's
@@ -149,7 +114,7 @@ int reserve(nrg_ctx* c, uint64_t n) {
         if (c->tail + n > c->head + c->log_size - GC_FROM_HEAD) {
             int r = exec_range(c, 0, 0, nullptr, nullptr);
             if (r != NRG_OK) return r;
-            HIPCHK(hm_flush_if(c));
+            HIPCHK(flush_deferred(c));
             c->head = gc_head(c);
         }
     }
@@ -182,7 +147,7 @@ int copy_into_ring(nrg_ctx* c, const void* src, uint64_t n, hipMemcpyKind kind) 
     return NRG_OK;
 }
 
-int staging(nrg_ctx* c, Staging& st, uint64_t bytes) {
+int staging(Staging& st, uint64_t bytes) {
     if (st.bytes >= bytes) return NRG_OK;
     if (st.p) (void)hipFree(st.p);
     st.p = nullptr;
@@ -190,7 +155,6 @@ int staging(nrg_ctx* c, Staging& st, uint64_t bytes) {
     uint64_t b = bytes < 4096 ? 4096 : bytes;
     HIPCHK(hipMalloc(&st.p, b));
     st.bytes = b;
-    (void)c;
     return NRG_OK;
 }
 
@@ -216,11 +180,20 @@ int hm_small_job(nrg_ctx* c, const nrg_put* recs, u64 W, u32 origin, const u64* 
     if (lo_out) *lo_out = lo;
     c->rounds++;
     if (W) note_origin(c, lo, W, origin);
-    c->tail = lo + W;
-    c->ltail = c->tail;
-    if (c->ctail < c->tail) c->ctail = c->tail;
+    commit_round(c, lo, W);
     return NRG_OK;
 }
+
+const DsOps* ds_ops(uint32_t kind) {
+    switch (kind) {
+        case NRG_DS_HASHMAP: return hm_ops();
+        case NRG_DS_STACK: return st_ops();
+        case NRG_DS_SYNTHETIC: return sy_ops();
+        case NRG_DS_QUEUE: return qu_ops();
+        default: return nullptr;
+    }
+}
+
 // c->timing_only: empty (time every kernel) or a comma-separated list of kernel names
 static bool timer_match(const nrg_ctx* c, const char* name) {
     if (c->timing_only.empty()) return true;
@@ -323,11 +296,28 @@ int nrg_device_count(void) {
 
 int nrg_close(nrg_ctx* c);
 
+// nrg_open's allocations: the stream, the log ring and DevCtl, then the structure's own
+static int open_buffers(nrg_ctx* c) {
+    HIPCHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    // Log::new(bytes): entries = bytes / 64, at least 2*GC_FROM_HEAD, power of two.
+    uint64_t num = (c->cfg.log_bytes ? c->cfg.log_bytes : DEFAULT_LOG_BYTES) / ENTRY_BYTES;
+    if (num < 2 * GC_FROM_HEAD) num = 2 * GC_FROM_HEAD;
+    c->log_size = pow2_at_least(num);
+    HIPCHK(hipMalloc(&c->d_ring, c->log_size * c->rec_bytes));
+    HIPCHK(hipMalloc(&c->d_ctl, sizeof(DevCtl)));
+    HIPCHK(hipMemsetAsync(c->d_ctl, 0, sizeof(DevCtl), c->stream));
+    int r = c->ops->open(c);
+    if (r != NRG_OK) return r;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return NRG_OK;
+}
+
 int nrg_open(int dev, const nrg_config* cfg_in, nrg_ctx** out) {
     if (!cfg_in || !out) return NRG_E_INVAL;
     *out = nullptr;
-    const uint32_t rb = rec_bytes_for(cfg_in->ds_kind);
-    if (!rb) return NRG_E_INVAL;
+    const DsOps* ops = ds_ops(cfg_in->ds_kind);
+    if (!ops) return NRG_E_INVAL;
     // table growth (0: a fixed table): up to a size nrg_open accepts for log2_slots, never below it
     if (cfg_in->ds_kind == NRG_DS_HASHMAP && cfg_in->hashmap_max_log2_slots &&
         (cfg_in->hashmap_max_log2_slots < cfg_in->log2_slots || cfg_in->hashmap_max_log2_slots > 30))
@@ -338,108 +328,21 @@ int nrg_open(int dev, const nrg_config* cfg_in, nrg_ctx** out) {
     if (!c) return NRG_E_NOMEM;
     c->device = dev;
     c->cfg = *cfg_in;
+    c->ops = ops;
     nrg_config& cf = c->cfg;
     if (!cf.max_batch) cf.max_batch = 1u << 20;
     if (!cf.max_reads) cf.max_reads = 1u << 20;
     if (!cf.replica_id) cf.replica_id = 1;
     if (cf.max_batch >= (1ull << 30)) { delete c; return NRG_E_INVAL; }
-    c->rec_bytes = rb;
+    c->rec_bytes = ops->rec_bytes;
     g_dev_set = -1;
     int rc = use_device(c);
     if (rc != NRG_OK) { delete c; return rc; }
-#define OPEN_CHK(x)                   \
-    do {                              \
-        hipError_t _e = (x);          \
-        if (_e != hipSuccess) {       \
-            nrg_close(c);             \
-            return hip_fail(_e);      \
-        }                             \
-    } while (0)
-    OPEN_CHK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-
-    // Log::new(bytes): entries = bytes / 64, at least 2*GC_FROM_HEAD, power of two.
-    uint64_t lb = cf.log_bytes ? cf.log_bytes : DEFAULT_LOG_BYTES;
-    uint64_t num = lb / ENTRY_BYTES;
-    if (num < 2 * GC_FROM_HEAD) num = 2 * GC_FROM_HEAD;
-    c->log_size = pow2_at_least(num);
-    OPEN_CHK(hipMalloc(&c->d_ring, c->log_size * rb));
-    OPEN_CHK(hipMalloc(&c->d_ctl, sizeof(DevCtl)));
-    OPEN_CHK(hipMemsetAsync(c->d_ctl, 0, sizeof(DevCtl), c->stream));
-
-    const uint64_t mb = cf.max_batch;
-    if (cf.ds_kind == NRG_DS_HASHMAP) {
-        // slot ids are < 2^30 (entry ids carry two flag values above them, hashmap.hip);
-        // replay chunks are bounded by the partition rounds' 16-bit tile offsets (HM_MAX_BATCH)
-        if (cf.log2_slots < 4 || cf.log2_slots > 30 || mb > HM_MAX_BATCH) { nrg_close(c); return NRG_E_INVAL; }
-        c->grow_max_log2 = cf.hashmap_max_log2_slots;  // (checked above; 0: a fixed table)
-        c->slots = 1ull << cf.log2_slots;
-        c->slot_shift = 64 - cf.log2_slots;
-        OPEN_CHK(hipMalloc(&c->d_table, c->slots * sizeof(Slot)));
-        OPEN_CHK(hm_init(c));
-        OPEN_CHK(hipMalloc(&c->d_created, HM_CREATED_SLOTS * sizeof(uint64_t)));
-        OPEN_CHK(hipMemsetAsync(c->d_created, 0, HM_CREATED_SLOTS * sizeof(uint64_t), c->stream));
-        // rounds without previous values replay in one launch (stamp rounds) unless the key
-        // stream is skewed (hashmap.hip skew_sample) or the round is large (PART_MIN); skewed,
-        // large and previous-value rounds take partition rounds
-        c->stamp_max = HM_MAX_BATCH;  // (NRG_KNOB_STAMP_MAX lowers it for tests)
-        OPEN_CHK(hm_alloc(c, mb));       // clamps stamp_max to max_batch (the put_slot arrays' size)
-        c->stamp_alloc = c->stamp_max;
-        c->pipeline = cf.pipeline != 0;
-    } else if (cf.ds_kind == NRG_DS_STACK) {
-        // max_batch <= 2^24: the finish stages one minimum per tile in LDS (stack.hip)
-        if (!cf.stack_capacity || cf.stack_capacity >= (1ull << 31) || mb > (1ull << 24)) {
-            nrg_close(c);
-            return NRG_E_INVAL;
-        }
-        OPEN_CHK(hipMalloc(&c->d_stack, cf.stack_capacity * sizeof(uint32_t)));
-        // look-back descriptors of both tile parities (stack.hip st_pass), and at least what
-        // nrg_test_maxscan's 2048-key tiles use
-        c->scan_desc_words = std::max<uint64_t>(st_desc_words(mb), 2 * (32 + (mb + 2047) / 2048));
-        OPEN_CHK(hipMalloc(&c->d_scan_desc, c->scan_desc_words * 4));
-        OPEN_CHK(hipMemsetAsync(c->d_scan_desc, 0, c->scan_desc_words * 4, c->stream));
-        OPEN_CHK(hipMalloc(&c->d_st_aux, st_aux_bytes(mb)));
-        c->pipeline = cf.pipeline != 0;
-    } else if (cf.ds_kind == NRG_DS_QUEUE) {
-        // max_batch <= 2^24: one workgroup scans the tile aggregates (queue.hip); the capacity
-        // bounds the ring of u64 values
-        if (!cf.queue_capacity || cf.queue_capacity > (1ull << 32) || mb > (1ull << 24)) {
-            nrg_close(c);
-            return NRG_E_INVAL;
-        }
-        // capacity + max_batch slots: the positions one chunk touches never alias (queue.hip)
-        c->qu_size = pow2_at_least(cf.queue_capacity + mb);
-        OPEN_CHK(hipMalloc(&c->d_queue, c->qu_size * sizeof(uint64_t)));
-        OPEN_CHK(hipMalloc(&c->d_qu_state, sizeof(QuState)));
-        OPEN_CHK(hipMemsetAsync(c->d_qu_state, 0, sizeof(QuState), c->stream));
-        OPEN_CHK(hipMalloc(&c->d_qu_aux, qu_aux_bytes(mb)));
-        c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
-    } else {
-        const uint64_t T = cf.synth_hot_writes + cf.synth_cold_writes;
-        if (!cf.synth_n || cf.synth_hot_reads == 0 || cf.synth_n <= cf.synth_hot_reads || T == 0 || T > 64 ||
-            mb * T >= (1ull << 31) || cf.synth_n >= (1ull << 31)) {
-            nrg_close(c);
-            return NRG_E_INVAL;
-        }
-        OPEN_CHK(hipMalloc(&c->d_words, cf.synth_n * sizeof(uint64_t)));
-        c->synth_key_bits = bits_for(cf.synth_n);
-        OPEN_CHK(hipMalloc(&c->d_tmp_u64, mb * T * sizeof(uint64_t)));
-        c->tmp_words = mb * T;
-        OPEN_CHK(hipMalloc(&c->d_sort_aux, mb * T * sizeof(uint32_t)));
-        c->scan_desc_words = 2 * (32 + (mb * T + 2047) / 2048);
-        OPEN_CHK(hipMalloc(&c->d_scan_desc, c->scan_desc_words * 4));
-        if (sort_alloc(c->sort, mb * T) != NRG_OK) { nrg_close(c); return NRG_E_NOMEM; }
-        // sort-free bucket replay where the config allows it (the sort path stays for the rest;
-        // nrg_test_set_knob(NRG_KNOB_SY_SORT) forces it for tests)
-        if (sy_bucket_eligible(cf)) {
-            OPEN_CHK(hipMalloc(&c->d_sy_aux, sy_bucket_aux_bytes(cf)));
-            OPEN_CHK(sy_aux_init(c));
-        }
-        c->pipeline = cf.pipeline != 0;
-        OPEN_CHK(sy_init(c));
+    rc = open_buffers(c);
+    if (rc != NRG_OK) {
+        nrg_close(c);
+        return rc;
     }
-    OPEN_CHK(hipStreamSynchronize(c->stream));
-#undef OPEN_CHK
     *out = c;
     return NRG_OK;
 }
@@ -450,14 +353,12 @@ int nrg_close(nrg_ctx* c) {
     g_dev_set = c->device;
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
-    void* ptrs[] = {c->d_ring,    c->d_ctl,      c->d_table,    c->d_stack,  c->d_words,
-                    c->d_sort_aux, c->d_tmp_u64, c->d_scan_desc, c->d_created, c->d_st_aux,
-                    c->d_sy_aux,  c->d_bk_ent,   c->d_bk_idx,   c->d_bk_cnt, c->d_dbg,     c->d_pt,
-                    c->d_queue,   c->d_qu_state, c->d_qu_aux};
+    // what every kind shares; each structure frees its own buffers
+    void* ptrs[] = {c->d_ring, c->d_ctl, c->d_scan_desc, c->d_tmp_u64, c->d_dbg, c->d_pt};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     sort_free(c->sort);
-    hm_free(c);
+    c->ops->close(c);
     Staging* s = stg(c);
     for (int i = 0; i < 4; i++)
         if (s[i].p) (void)hipFree(s[i].p);
@@ -472,8 +373,8 @@ int nrg_set_stream(nrg_ctx* c, void* s) {
     if (!c) return NRG_E_INVAL;
     int r = use_device(c);
     if (r) return r;
-    // deferred hashmap work belongs to the old stream: launch it there first
-    hipError_t e = hm_flush_if(c);
+    // deferred work belongs to the old stream: launch it there first
+    hipError_t e = flush_deferred(c);
     if (e != hipSuccess) return hip_fail(e);
     hipStream_t ns = (hipStream_t)s;  // NULL: the device's null stream, as in HIP
     if (ns != c->stream) {
@@ -506,7 +407,7 @@ int nrg_join(nrg_ctx* c) {
     if (!c) return NRG_E_INVAL;
     int r = use_device(c);
     if (r) return r;
-    HIPCHK(hm_flush_if(c));
+    HIPCHK(flush_deferred(c));
     return NRG_OK;
 }
 
@@ -571,14 +472,6 @@ int nrg_log_exec_async(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_r
     return exec_range(c, resp_lo, resp_hi, d_resp, d_some);
 }
 
-static uint64_t resp_elem_bytes(const nrg_ctx* c) {
-    switch (c->cfg.ds_kind) {
-        case NRG_DS_STACK: return 4;  // u32 popped value
-        case NRG_DS_QUEUE: return 8;  // u64 pushed or popped value
-        default: return 8;            // hashmap previous value, synthetic sum
-    }
-}
-
 int nrg_log_exec(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* resp, uint8_t* some) {
     if (!c || resp_hi < resp_lo) return NRG_E_INVAL;
     int r = use_device(c);
@@ -587,18 +480,18 @@ int nrg_log_exec(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* resp, uin
     void* dr = nullptr;
     uint8_t* ds = nullptr;
     Staging* s = stg(c);
+    const uint64_t eb = c->ops->resp_bytes;
     if (w) {
-        const uint64_t eb = resp_elem_bytes(c);
-        if ((r = staging(c, s[0], w * eb)) || (r = staging(c, s[1], w))) return r;
+        if ((r = staging(s[0], w * eb)) || (r = staging(s[1], w))) return r;
         dr = s[0].p;
         ds = (uint8_t*)s[1].p;
         HIPCHK(hipMemsetAsync(dr, 0, w * eb, c->stream));
         HIPCHK(hipMemsetAsync(ds, 0, w, c->stream));
     }
     if ((r = exec_range(c, resp_lo, resp_hi, dr, ds))) return r;
-    HIPCHK(hm_flush_if(c));  // deferred work writes responses too: complete them before the copy
+    HIPCHK(flush_deferred(c));  // deferred work writes responses too: complete them before the copy
     if (w) {
-        HIPCHK(hipMemcpyAsync(resp, dr, w * resp_elem_bytes(c), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(resp, dr, w * eb, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(some, ds, w, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(sync_all(c));
@@ -621,8 +514,8 @@ int nrg_log_reset(nrg_ctx* c) {
     if (!c) return NRG_E_INVAL;
     int r = use_device(c);
     if (r) return r;
-    // a deferred hashmap read batch belongs to the log positions being reset: answer it now
-    HIPCHK(hm_flush_if(c));
+    // deferred work (reads, a chunk's finish or sums) belongs to the log positions being reset: run it now
+    HIPCHK(flush_deferred(c));
     c->head = c->tail = c->ctail = c->ltail = 0;
     c->origins.clear();
     return NRG_OK;
@@ -633,6 +526,25 @@ static int need(nrg_ctx* c, uint32_t kind) {
     if (!c) return NRG_E_INVAL;
     if (c->cfg.ds_kind != kind) return NRG_E_INVAL;
     return use_device(c);
+}
+
+// Replica::combine for one batch of a stack, synthetic or queue replica: one replay pass that
+// also writes the log copy (Log::append + Log::exec of this batch)
+static int round_common(nrg_ctx* c, uint32_t kind, const void* d_ops, uint64_t n, uint32_t origin, void* d_resp,
+                        uint8_t* d_some) {
+    int r = need(c, kind);
+    if (r) return r;
+    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
+    if (n && !d_ops) return NRG_E_INVAL;
+    if (!d_resp || !d_some) d_resp = nullptr, d_some = nullptr;
+    // catch up on anything appended by others first (Replica::combine execs the whole log)
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    if ((r = reserve(c, n))) return r;
+    const uint64_t lo = c->tail;
+    HIPCHK(c->ops->replay(c, d_ops, lo, n, lo, lo + n, d_resp, d_some));
+    if (n) note_origin(c, lo, n, origin);
+    commit_round(c, lo, n);
+    return NRG_OK;
 }
 
 int nrg_hashmap_get_async(nrg_ctx* c, const uint64_t* d_keys, uint64_t n, uint64_t* d_vals, uint8_t* d_found) {
@@ -649,7 +561,7 @@ int nrg_hashmap_get(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint64_t* vals
     if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
     if (n == 0) return NRG_OK;
     Staging* s = stg(c);
-    if ((r = staging(c, s[0], n * 8)) || (r = staging(c, s[1], n * 8)) || (r = staging(c, s[2], n))) return r;
+    if ((r = staging(s[0], n * 8)) || (r = staging(s[1], n * 8)) || (r = staging(s[2], n))) return r;
     HIPCHK(hipMemcpyAsync(s[0].p, keys, n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hm_get_only(c, (u64*)s[0].p, n, (u64*)s[1].p, (uint8_t*)s[2].p));
     HIPCHK(hipMemcpyAsync(vals, s[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -673,27 +585,7 @@ int nrg_hashmap_round_async(nrg_ctx* c, const nrg_put* d_puts, uint64_t W, uint3
     HIPCHK(hm_replay_chunk(c, d_puts, lo, W, true, d_get_keys, R, d_get_vals, d_get_found, lo, lo + W, d_prev,
                            d_prev_found));
     if (W) note_origin(c, lo, W, origin);
-    c->tail = lo + W;
-    c->ltail = c->tail;
-    if (c->ctail < c->tail) c->ctail = c->tail;
-    return NRG_OK;
-}
-
-// replay [ltail, tail) and answer R reads against the final state, fused into the last chunk
-static int hm_exec_with_gets(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, uint64_t* d_prev, uint8_t* d_prevf,
-                             const uint64_t* d_get_keys, uint64_t R, uint64_t* d_get_vals, uint8_t* d_get_found) {
-    if (c->ltail == c->tail) return hip_fail(hm_get_only(c, d_get_keys, R, d_get_vals, d_get_found));
-    while (c->ltail < c->tail) {
-        uint64_t n = c->tail - c->ltail;
-        if (n > c->cfg.max_batch) n = c->cfg.max_batch;
-        const uint64_t lo = c->ltail;
-        const bool last = lo + n == c->tail;
-        HIPCHK(hm_replay_chunk(c, nullptr, lo, n, false, last ? d_get_keys : nullptr, last ? R : 0,
-                               last ? d_get_vals : nullptr, last ? d_get_found : nullptr, resp_lo, resp_hi, d_prev,
-                               d_prevf));
-        c->ltail = lo + n;
-    }
-    if (c->ctail < c->ltail) c->ctail = c->ltail;
+    commit_round(c, lo, W);
     return NRG_OK;
 }
 
@@ -726,9 +618,7 @@ int nrg_hashmap_round_segments_async(nrg_ctx* c, const nrg_put* d_base, uint32_t
                                d_prev_found));
         for (uint32_t s = 0, off = 0; s < nseg; off += (uint32_t)lens[s], s++)
             if (lens[s]) note_origin(c, lo + off, lens[s], origins ? origins[s] : s + 1);
-        c->tail = lo + total;
-        c->ltail = c->tail;
-        if (c->ctail < c->tail) c->ctail = c->tail;
+        commit_round(c, lo, total);
         return NRG_OK;
     }
     HIPCHK(copy_segments(c, d_base, nseg, seg_stride, lens, lo));
@@ -736,7 +626,10 @@ int nrg_hashmap_round_segments_async(nrg_ctx* c, const nrg_put* d_base, uint32_t
         if (lens[s]) note_origin(c, c->tail, lens[s], origins ? origins[s] : s + 1);
         c->tail += lens[s];
     }
-    return hm_exec_with_gets(c, rlo, rhi, d_prev, d_prev_found, d_get_keys, R, d_get_vals, d_get_found);
+    // replay them and answer the reads against the final state, fused into the last chunk
+    if (c->ltail == c->tail) return hip_fail(hm_get_only(c, d_get_keys, R, d_get_vals, d_get_found));
+    const HmGets gets{d_get_keys, R, d_get_vals, d_get_found};
+    return exec_range(c, rlo, rhi, d_prev, d_prev_found, &gets);
 }
 
 int nrg_hashmap_prefill(nrg_ctx* c, const uint64_t* keys, const uint64_t* vals, uint64_t n) {
@@ -745,7 +638,7 @@ int nrg_hashmap_prefill(nrg_ctx* c, const uint64_t* keys, const uint64_t* vals, 
     Staging* s = stg(c);
     uint64_t done = 0;
     const uint64_t chunk = c->cfg.max_batch;
-    if ((r = staging(c, s[0], (n < chunk ? n : chunk) * sizeof(nrg_put)))) return r;
+    if ((r = staging(s[0], (n < chunk ? n : chunk) * sizeof(nrg_put)))) return r;
     while (done < n) {
         const uint64_t m = n - done < chunk ? n - done : chunk;
         nrg_put* h = (nrg_put*)std::malloc(m * sizeof(nrg_put));
@@ -841,7 +734,7 @@ int nrg_hashmap_dump(nrg_ctx* c, uint64_t* keys, uint64_t* vals, uint64_t cap, u
     if (*n > cap) return NRG_E_CAPACITY;
     if (*n == 0) return NRG_OK;
     Staging* s = stg(c);
-    if ((r = staging(c, s[0], *n * 8)) || (r = staging(c, s[1], *n * 8))) return r;
+    if ((r = staging(s[0], *n * 8)) || (r = staging(s[1], *n * 8))) return r;
     HIPCHK(hm_dump(c, (u64*)s[0].p, (u64*)s[1].p));
     HIPCHK(hipMemcpyAsync(keys, s[0].p, *n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(vals, s[1].p, *n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -853,7 +746,7 @@ int nrg_hashmap_digest(nrg_ctx* c, uint64_t out[3]) {
     int r = need(c, NRG_DS_HASHMAP);
     if (r) return r;
     Staging* s = stg(c);
-    if ((r = staging(c, s[3], 64))) return r;
+    if ((r = staging(s[3], 64))) return r;
     HIPCHK(hm_digest(c, (u64*)s[3].p));
     HIPCHK(hipMemcpyAsync(out, s[3].p, 24, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
@@ -863,47 +756,19 @@ int nrg_hashmap_digest(nrg_ctx* c, uint64_t out[3]) {
 // ---- Stack ---------------------------------------------------------------------------------
 int nrg_stack_round_async(nrg_ctx* c, const nrg_stack_op* d_ops, uint64_t n, uint32_t origin, uint32_t* d_pop_vals,
                           uint8_t* d_some_bits) {
-    int r = need(c, NRG_DS_STACK);
-    if (r) return r;
-    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
-    if (n && !d_ops) return NRG_E_INVAL;
-    if (!d_pop_vals || !d_some_bits) d_pop_vals = nullptr, d_some_bits = nullptr;
-    // catch up on anything appended by others first (Replica::combine execs the whole log)
-    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
-    if ((r = reserve(c, n))) return r;
-    const uint64_t lo = c->tail;
-    // one replay pass that also writes the log copy (Log::append + Log::exec of this batch)
-    HIPCHK(st_replay_chunk(c, lo, n, lo, lo + n, d_pop_vals, d_some_bits, d_ops));
-    if (n) note_origin(c, lo, n, origin);
-    c->tail = lo + n;
-    c->ltail = c->tail;
-    if (c->ctail < c->tail) c->ctail = c->tail;
-    return NRG_OK;
+    return round_common(c, NRG_DS_STACK, d_ops, n, origin, d_pop_vals, d_some_bits);
 }
 
 int nrg_synth_round_async(nrg_ctx* c, const nrg_synth_op* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
                           uint8_t* d_some) {
-    int r = need(c, NRG_DS_SYNTHETIC);
-    if (r) return r;
-    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
-    if (n && !d_ops) return NRG_E_INVAL;
-    if (!d_resp || !d_some) d_resp = nullptr, d_some = nullptr;
-    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
-    if ((r = reserve(c, n))) return r;
-    const uint64_t lo = c->tail;
-    HIPCHK(sy_replay_chunk(c, lo, n, lo, lo + n, d_resp, d_some, d_ops));
-    if (n) note_origin(c, lo, n, origin);
-    c->tail = lo + n;
-    c->ltail = c->tail;
-    if (c->ctail < c->tail) c->ctail = c->tail;
-    return NRG_OK;
+    return round_common(c, NRG_DS_SYNTHETIC, d_ops, n, origin, d_resp, d_some);
 }
 
 int nrg_stack_init(nrg_ctx* c, const uint32_t* vals, uint64_t n) {
     int r = need(c, NRG_DS_STACK);
     if (r) return r;
     if (n > c->cfg.stack_capacity) return NRG_E_CAPACITY;
-    HIPCHK(hm_flush_if(c));  // a deferred chunk finish commits before the stack is replaced
+    HIPCHK(flush_deferred(c));  // a deferred chunk finish commits before the stack is replaced
     if (n) HIPCHK(hipMemcpyAsync(c->d_stack, vals, n * 4, hipMemcpyHostToDevice, c->stream));
     long long d = (long long)n;
     HIPCHK(hipMemcpyAsync(&c->d_ctl->depth, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
@@ -917,7 +782,7 @@ int nrg_stack_len(nrg_ctx* c, uint64_t* n) {
     int r = need(c, NRG_DS_STACK);
     if (r) return r;
     long long d = 0;
-    HIPCHK(hm_flush_if(c));  // a deferred chunk finish publishes the length
+    HIPCHK(flush_deferred(c));  // a deferred chunk finish publishes the length
     HIPCHK(hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
     // an overflowing chunk latches ERR_CAPACITY once but keeps counting: never report (or
@@ -957,22 +822,7 @@ int nrg_stack_dump(nrg_ctx* c, uint32_t* vals, uint64_t cap, uint64_t* n) {
 // ---- FIFO queue ----------------------------------------------------------------------------
 int nrg_queue_round_async(nrg_ctx* c, const nrg_queue_op* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
                           uint8_t* d_some) {
-    int r = need(c, NRG_DS_QUEUE);
-    if (r) return r;
-    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
-    if (n && !d_ops) return NRG_E_INVAL;
-    if (!d_resp || !d_some) d_resp = nullptr, d_some = nullptr;
-    // catch up on anything appended by others first (Replica::combine execs the whole log)
-    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
-    if ((r = reserve(c, n))) return r;
-    const uint64_t lo = c->tail;
-    // the replay's first pass also writes the log copy (Log::append + Log::exec of this batch)
-    HIPCHK(qu_replay_chunk(c, lo, n, lo, lo + n, d_resp, d_some, d_ops));
-    if (n) note_origin(c, lo, n, origin);
-    c->tail = lo + n;
-    c->ltail = c->tail;
-    if (c->ctail < c->tail) c->ctail = c->tail;
-    return NRG_OK;
+    return round_common(c, NRG_DS_QUEUE, d_ops, n, origin, d_resp, d_some);
 }
 
 static int qu_set_state(nrg_ctx* c, uint64_t n) {
@@ -1053,7 +903,7 @@ int nrg_synth_read(nrg_ctx* c, const nrg_synth_rd* ops, uint64_t n, uint64_t* su
     if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
     if (!n) return NRG_OK;
     Staging* s = stg(c);
-    if ((r = staging(c, s[0], n * sizeof(nrg_synth_rd))) || (r = staging(c, s[1], n * 8))) return r;
+    if ((r = staging(s[0], n * sizeof(nrg_synth_rd))) || (r = staging(s[1], n * 8))) return r;
     HIPCHK(hipMemcpyAsync(s[0].p, ops, n * sizeof(nrg_synth_rd), hipMemcpyHostToDevice, c->stream));
     HIPCHK(sy_read(c, (const nrg_synth_rd*)s[0].p, n, (u64*)s[1].p));
     HIPCHK(hipMemcpyAsync(sums, s[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1066,7 +916,7 @@ int nrg_synth_dump(nrg_ctx* c, uint64_t* words, uint64_t cap, uint64_t* n) {
     if (r) return r;
     *n = c->cfg.synth_n;
     if (*n > cap) return NRG_E_CAPACITY;
-    HIPCHK(hm_flush_if(c));  // deferred sums fold the hot words
+    HIPCHK(flush_deferred(c));  // deferred sums fold the hot words
     HIPCHK(hipMemcpyAsync(words, c->d_words, *n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
     return check_err(c);
@@ -1100,7 +950,7 @@ int nrg_memcpy_d2h(nrg_ctx* c, void* h, const void* d, uint64_t bytes) {
     if (!c) return NRG_E_INVAL;
     int r = use_device(c);
     if (r) return r;
-    HIPCHK(hm_flush_if(c));
+    HIPCHK(flush_deferred(c));
     HIPCHK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
     return NRG_OK;

@@ -927,7 +927,7 @@ static hipError_t st_launch(nrg_ctx* c, const StPass& A, const StPass& P) {
 }
 
 // The finish of the last replayed chunk (its cross-tile Pops and its commit), if still pending.
-hipError_t st_flush(nrg_ctx* c) {
+static hipError_t st_flush(nrg_ctx* c) {
     if (!c->st_pend.valid) return hipSuccess;
     StPass P = st_pass(c, c->st_pend.par);
     P.lo = c->st_pend.lo;
@@ -945,18 +945,18 @@ hipError_t st_flush(nrg_ctx* c) {
 // One chunk: its tile pass, fused with the previous chunk's finish in one launch. The chunk's
 // own finish runs in the next chunk's launch (config.pipeline = 1, until nrg_join or a sync)
 // or right away.
-hipError_t st_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, uint32_t* d_resp, uint8_t* d_some,
-                           const nrg_stack_op* src) {
+static hipError_t st_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                                  uint8_t* d_some) {
     if (n == 0) return st_flush(c);  // an empty round still completes the last round's deferred finish
     StPass A = st_pass(c, c->st_par);
-    A.src = src;
+    A.src = (const nrg_stack_op*)src;
     A.lo = lo;
     A.n = n;
     A.tiles = (u32)((n + ST_TILE - 1) / ST_TILE);
     const bool want = d_resp != nullptr && resp_lo < lo + n && resp_hi > lo;
     A.rlo = want ? resp_lo : 0;
     A.rhi = want ? resp_hi : 0;
-    A.resp = want ? d_resp : nullptr;
+    A.resp = want ? (uint32_t*)d_resp : nullptr;
     A.some = want ? d_some : nullptr;
     StPass P{};
     if (c->st_pend.valid) {
@@ -979,8 +979,35 @@ hipError_t st_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, 
 }
 
 // [32 u64 unused] [parity][max tiles] u64 (st_pass)
-u64 st_desc_words(u64 max_batch) { return 2 * (32 + 2 * ((max_batch + ST_TILE - 1) / ST_TILE)); }
+static u64 st_desc_words(u64 max_batch) { return 2 * (32 + 2 * ((max_batch + ST_TILE - 1) / ST_TILE)); }
 
-u64 st_aux_bytes(u64 max_batch) { return 2 * st_parity_bytes((max_batch + ST_TILE - 1) / ST_TILE); }
+// size of nrg_ctx::d_st_aux
+static u64 st_aux_bytes(u64 max_batch) { return 2 * st_parity_bytes((max_batch + ST_TILE - 1) / ST_TILE); }
+
+static int st_open(nrg_ctx* c) {
+    const nrg_config& cf = c->cfg;
+    const u64 mb = cf.max_batch;
+    // max_batch <= 2^24: the finish stages one minimum per tile in LDS
+    if (!cf.stack_capacity || cf.stack_capacity >= (1ull << 31) || mb > (1ull << 24)) return NRG_E_INVAL;
+    HIPCHK(hipMalloc(&c->d_stack, cf.stack_capacity * sizeof(uint32_t)));
+    // look-back descriptors of both tile parities (st_pass), and at least what
+    // nrg_test_maxscan's 2048-key tiles use
+    c->scan_desc_words = std::max<u64>(st_desc_words(mb), 2 * (32 + (mb + 2047) / 2048));
+    HIPCHK(hipMalloc(&c->d_scan_desc, c->scan_desc_words * 4));
+    HIPCHK(hipMemsetAsync(c->d_scan_desc, 0, c->scan_desc_words * 4, c->stream));
+    HIPCHK(hipMalloc(&c->d_st_aux, st_aux_bytes(mb)));
+    c->pipeline = cf.pipeline != 0;
+    return NRG_OK;
+}
+
+static void st_close(nrg_ctx* c) {
+    (void)hipFree(c->d_stack);
+    (void)hipFree(c->d_st_aux);
+}
+
+const DsOps* st_ops() {
+    static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk};
+    return &ops;
+}
 
 }  // namespace nrg

@@ -1351,7 +1351,7 @@ static hipError_t sy_launch_bucket(nrg_ctx* c, const SyDeferred& d) {
 
 // The deferred work of the last replayed chunks, if any: the sums (and hot-word fold) of the
 // last chunk; with one launch per round also the bucket pass of the last chunk, then its sums.
-hipError_t sy_flush(nrg_ctx* c) {
+static hipError_t sy_flush(nrg_ctx* c) {
     if (c->sy_fused) {
         while (c->sy_pend_b.valid || c->sy_pend.valid) {
             const SySumArgs S = sy_sum_args(c, c->sy_pend);
@@ -1451,14 +1451,10 @@ hipError_t sy_lds_add_order(nrg_ctx* c, u32 K, u32 trials, u32 blocks, u64* d_ou
     return hipGetLastError();
 }
 
-hipError_t sy_init(nrg_ctx* c) {
-    sy_init_kernel<<<1024, 256, 0, c->stream>>>(c->d_words, c->cfg.synth_n);
-    return hipGetLastError();
-}
-
-
-hipError_t sy_replay_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, u64* d_resp, uint8_t* d_some,
-                           const nrg_synth_op* src) {
+static hipError_t sy_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, u64 resp_lo, u64 resp_hi,
+                                  void* d_resp_v, uint8_t* d_some) {
+    const nrg_synth_op* src = (const nrg_synth_op*)src_recs;
+    u64* d_resp = (u64*)d_resp_v;
     if (n == 0) return sy_flush(c);  // an empty round still completes the last round's deferred sums
     if (c->d_sy_aux) return sy_bucket_chunk(c, lo, n, resp_lo, resp_hi, d_resp, d_some, src);
     if (src) {  // the sort path replays from the ring: append the ops first (wrapping)
@@ -1525,6 +1521,43 @@ hipError_t sy_read(nrg_ctx* c, const nrg_synth_rd* d_ops, u64 n, u64* d_sums) {
     sy_read_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(
         d_ops, n, c->d_words, cf.synth_n, cf.synth_hot_reads, cf.synth_hot_writes, cf.synth_cold_reads, d_sums);
     return hipGetLastError();
+}
+
+static int sy_open(nrg_ctx* c) {
+    const nrg_config& cf = c->cfg;
+    const u64 mb = cf.max_batch, T = cf.synth_hot_writes + cf.synth_cold_writes;
+    if (!cf.synth_n || cf.synth_hot_reads == 0 || cf.synth_n <= cf.synth_hot_reads || T == 0 || T > 64 ||
+        mb * T >= (1ull << 31) || cf.synth_n >= (1ull << 31))
+        return NRG_E_INVAL;
+    HIPCHK(hipMalloc(&c->d_words, cf.synth_n * sizeof(u64)));
+    c->synth_key_bits = 1;  // the smallest b with 2^b - 1 >= synth_n
+    while (((1ull << c->synth_key_bits) - 1) < cf.synth_n) c->synth_key_bits++;
+    HIPCHK(hipMalloc(&c->d_tmp_u64, mb * T * sizeof(u64)));
+    c->tmp_words = mb * T;
+    HIPCHK(hipMalloc(&c->d_sort_aux, mb * T * sizeof(u32)));
+    c->scan_desc_words = 2 * (32 + (mb * T + 2047) / 2048);
+    HIPCHK(hipMalloc(&c->d_scan_desc, c->scan_desc_words * 4));
+    if (sort_alloc(c->sort, mb * T) != NRG_OK) return NRG_E_NOMEM;
+    // sort-free bucket replay where the config allows it (the sort path stays for the rest;
+    // nrg_test_set_knob(NRG_KNOB_SY_SORT) forces it for tests)
+    if (sy_bucket_eligible(cf)) {
+        HIPCHK(hipMalloc(&c->d_sy_aux, sy_bucket_aux_bytes(cf)));
+        HIPCHK(sy_aux_init(c));
+    }
+    c->pipeline = cf.pipeline != 0;
+    sy_init_kernel<<<1024, 256, 0, c->stream>>>(c->d_words, cf.synth_n);
+    return hip_fail(hipGetLastError());
+}
+
+static void sy_close(nrg_ctx* c) {
+    (void)hipFree(c->d_words);
+    (void)hipFree(c->d_sort_aux);
+    (void)hipFree(c->d_sy_aux);
+}
+
+const DsOps* sy_ops() {
+    static const DsOps ops = {sizeof(nrg_synth_op), sizeof(u64), sy_open, sy_close, sy_flush, sy_replay_chunk};
+    return &ops;
 }
 
 }  // namespace nrg
