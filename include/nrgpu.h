@@ -2,7 +2,7 @@
  * nrgpu.h — C ABI of the MI355X-native node-replication (NR) log-replay path.
  *
  * One `nrg_ctx` is one NR *replica* living on one GPU: it owns the replicated data
- * structure in HBM (NrHashMap / Stack / AbstractDataStructure / FIFO queue), its copy of the shared
+ * structure in HBM (NrHashMap / Stack / AbstractDataStructure / FIFO queue / VSpace), its copy of the shared
  * operation log (an HBM ring of fixed-width records tagged by logical log index), the
  * per-replica replay epoch (`ltail`), scratch for the replay kernels, and a HIP stream.
  *
@@ -21,6 +21,7 @@
  *   nrg_stack_*                   Stack Dispatch                     benches/stack.rs:36-84, nr/tests/stack.rs:31-96
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
  *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
+ *   nrg_vspace_*                  VSpace Dispatch (x86-64 page table) benches/vspace.rs:177-381, :436-467, :499-526
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -70,6 +71,7 @@ extern "C" {
 #define NRG_DS_STACK 2u     /* Stack: Vec<u32>, Push/Pop, Peek                      */
 #define NRG_DS_SYNTHETIC 3u /* AbstractDataStructure(n, 20, 5, 2, 1)                */
 #define NRG_DS_QUEUE 4u     /* FIFO queue of u64: Push/Pop, Len   benches/lockfree.rs:43-52 */
+#define NRG_DS_VSPACE 5u    /* four-level page table: Map/MapDevice, Identify  benches/vspace.rs:483-526 */
 
 /* ---- log record layouts (one WriteOperation each) --------------------------------- */
 /* NrHashMap WriteOperation::Put(key, val)               benches/hashmap.rs:52-56       */
@@ -105,6 +107,37 @@ typedef struct {
     uint64_t op;
 } nrg_queue_op;
 
+/* VSpace WriteOperation (OpcodeWr, benches/vspace.rs:483-487): op = NRG_VSPACE_MAP
+ * (Map(vbase, len, rights, pbase)) or NRG_VSPACE_MAP_DEVICE (MapDevice(vbase, pbase, len), which
+ * maps ReadWriteUser and ignores `rights`). rights: 1..8 in MapAction order (:54-73: ReadUser,
+ * ReadKernel, ReadWriteUser, ReadWriteKernel, ReadExecuteUser, ReadExecuteKernel,
+ * ReadWriteExecuteUser, ReadWriteExecuteKernel). Domain: vbase, pbase and len multiples of 4096;
+ * vbase, pbase < 2^48; len < 2^30 (so 1 GiB pages never arise); vbase + len <= 2^48; for Map,
+ * rights in 1..8. The reference asserts on anything else; here such a record changes nothing,
+ * answers some = 0 with a = vbase, and latches NRG_E_INVAL once. The one read,
+ * OpcodeRd::Identify(vaddr) (:489-492), carries no record (nrg_vspace_resolve). */
+#define NRG_VSPACE_MAP 0u
+#define NRG_VSPACE_MAP_DEVICE 1u
+typedef struct {
+    uint64_t vbase;
+    uint64_t pbase;
+    uint64_t len;
+    uint32_t op;
+    uint32_t rights;
+} nrg_vspace_op;
+/* VSpace write response, Result<(u64, u64), VSpaceError> (:502): Ok -> some = 1 and (a, b) =
+ * (pbase, len) for Map, (0, 0) for MapDevice; Err(VSpaceError{at}) -> some = 0, a = at, b = 0 */
+typedef struct {
+    uint64_t a;
+    uint64_t b;
+} nrg_vspace_resp;
+/* One leaf entry of the page table (nrg_vspace_dump): the first virtual address it maps and the
+ * entry itself (paddr | flags; bit 7, PS, set for a 2 MiB page) */
+typedef struct {
+    uint64_t vaddr;
+    uint64_t entry;
+} nrg_vspace_leaf;
+
 /* Synthetic ReadOperation::ReadOnly(tid, rnd1, rnd2)     benches/synthetic.rs:28-31       */
 typedef struct {
     uint64_t tid;
@@ -116,12 +149,15 @@ typedef struct {
 typedef struct {
     uint32_t ds_kind;         /* NRG_DS_*                                                  */
     uint32_t log2_slots;      /* hashmap: table has 2^log2_slots 32-B slots {key, value, two
-                                 round stamps} (default 26: 2 GiB of HBM; < 2^30 slots)       */
+                                 round stamps} (default 26: 2 GiB of HBM; < 2^30 slots);
+                                 vspace (the field is reused): the pool holds 2^log2_slots page
+                                 tables of 4 KiB (default 18: 1 GiB; 2 .. 22, else nrg_open
+                                 returns NRG_E_INVAL)                                         */
     uint64_t log_bytes;       /* Log::new(bytes): ring entries = bytes/64 rounded as in the
                                  reference (min 2*GC_FROM_HEAD, power of two). 0 = 32 MiB   */
     uint64_t max_batch;       /* largest number of log records replayed per kernel pass;
                                  larger exec ranges are replayed in order, in chunks
-                                 (< 2^30; stack, queue: <= 2^24)                            */
+                                 (< 2^30; stack, queue: <= 2^24; vspace: <= 2^16, its default) */
     uint64_t max_reads;       /* largest read batch per call                               */
     uint64_t stack_capacity;  /* stack: maximum number of elements                          */
     uint64_t synth_n;         /* synthetic: number of words (default 200000)               */
@@ -135,7 +171,7 @@ typedef struct {
                                  stack: the Pops answered from earlier tiles and the commit;
                                  synthetic: the per-op sums and the hot-word fold; queue: accepted,
                                  but nothing is deferred: a queue's outputs are always complete
-                                 in stream order. Those outputs
+                                 in stream order; vspace: the same. Those outputs
                                  (and the buffers they read) are complete only after nrg_join(),
                                  the next round call on this context (an empty one included), or
                                  nrg_sync(); give back-to-back rounds distinct response buffers.
@@ -225,6 +261,7 @@ int nrg_log_append_segments_async(nrg_ctx* ctx, const void* d_base, uint32_t nse
  *   synthetic: resp[u64] = ReadWrite sum (WriteOnly -> 0), some = 1
  *   queue    : resp[u64] = pushed (Push -> Some(v)) or popped value, some[u8] = 0 for a Pop on
  *              an empty queue (benches/lockfree_comparisons.rs:94-98)
+ *   vspace   : resp[nrg_vspace_resp] (16 B), some[u8] = 1 for Ok, 0 for Err (a = at)
  * `resp`/`some` may be NULL (no responses wanted, as benches/hashmap.rs:114-119 returns
  * Ok(None)); the hashmap then skips the previous-value pipeline entirely. */
 int nrg_log_exec(nrg_ctx* ctx, uint64_t resp_lo, uint64_t resp_hi, void* resp, uint8_t* some);
@@ -289,7 +326,9 @@ int nrg_hashmap_digest(nrg_ctx* ctx, uint64_t out[3]);
 
 /* ---- Flat combining on the host ---------------------------------------------------------- */
 /* Replica's flat combiner for many client threads (nr/src/context.rs:88-194,
- * nr/src/replica.rs:345-356, 404-433, 483-497, 508-595), for any of the four data structures:
+ * nr/src/replica.rs:345-356, 404-433, 483-497, 508-595), for the hashmap, the stack, the synthetic
+ * structure and the queue (not the page table: nrg_combiner_open on a vspace context returns
+ * NRG_E_INVAL):
  * each registered thread posts up to 32 ops (MAX_PENDING_OPS) per call into the open batch and
  * parks; the combiner's own thread seals the batch into ONE GPU round of `ctx` (its writes
  * appended and replayed in batch order, then its reads answered against the post-round state)
@@ -370,6 +409,38 @@ int nrg_queue_dump(nrg_ctx* ctx, uint64_t* vals, uint64_t cap, uint64_t* n);
  * them. Same result as nrg_log_append_async + nrg_log_exec_async. */
 int nrg_queue_round_async(nrg_ctx* ctx, const nrg_queue_op* d_ops, uint64_t n, uint32_t origin,
                           uint64_t* d_resp, uint8_t* d_some);
+
+/* ---- VSpace: the replicated x86-64 page table (VSpaceDispatcher) ---------------------------- */
+/* The replica's tables live in a device pool of 2^config.log2_slots tables of 4 KiB, zeroed at
+ * open; table 0 is the PML4, and an inner entry holds table_index * 4096 | P|RW|US where the
+ * reference stores a heap pointer (nothing observable depends on it). A replay that needs more
+ * tables than the pool holds latches NRG_E_CAPACITY once (reported by the next nrg_sync /
+ * synchronous call): exactly the ops whose tables do not fit when their turn comes in log order
+ * change nothing and answer some = 0 with a = vbase, b = 0; the ops after them go on, and the
+ * replica keeps answering from what was written. The result is the same however the log is cut
+ * into chunks. Replica groups and the log calls
+ * take the kind as they take the others; there is no combiner and no partitioned mode for it. */
+/* Replica::combine for one batch (nr/src/replica.rs:544-595) of Map / MapDevice ops
+ * (benches/vspace.rs:513-525 dispatch_mut -> :469-481 map_new -> :177-381 map_generic):
+ * Log::append of the n ops in d_ops (device) with `origin`, then Log::exec, with the log copy
+ * written by the replay's first pass. Responses for these ops (d_resp[i], d_some[i]; nullable) as
+ * nrg_log_exec_async gives them. Same result as nrg_log_append_async + nrg_log_exec_async. */
+int nrg_vspace_round_async(nrg_ctx* ctx, const nrg_vspace_op* d_ops, uint64_t n, uint32_t origin,
+                           nrg_vspace_resp* d_resp, uint8_t* d_some);
+/* Dispatch::dispatch(Identify(vaddr)) for a batch (benches/vspace.rs:504-511 -> :436-467
+ * resolve_addr), after sync-to-tail (NRG_E_NOT_SYNCED while ltail < tail; n <= max_reads, else
+ * NRG_E_CAPACITY): paddrs[i] = the leaf's address plus the offset into its 4 KiB or 2 MiB page,
+ * or 0 where nothing is mapped (found[i] = 0). Bits 48..63 of a vaddr are ignored, as the
+ * reference's index functions ignore them. */
+int nrg_vspace_resolve(nrg_ctx* ctx, const uint64_t* vaddrs, uint64_t n, uint64_t* paddrs, uint8_t* found);
+int nrg_vspace_resolve_async(nrg_ctx* ctx, const uint64_t* d_vaddrs, uint64_t n, uint64_t* d_paddrs,
+                             uint8_t* d_found);
+/* Tables allocated so far, the PML4 included (VSpace::allocs.len() + 1, :384-404). */
+int nrg_vspace_tables(nrg_ctx* ctx, uint64_t* n);
+/* Replica::verify's view (nr/src/replica.rs:443-467): every leaf entry, one record each, in
+ * ascending vaddr, whatever order the tables were allocated in. `*n` receives their number; if it
+ * exceeds `cap`, nothing is copied and NRG_E_CAPACITY is returned (as nrg_queue_dump). */
+int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_t* n);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's

@@ -18,6 +18,7 @@ constexpr u64 EMPTY_KEY = ~0ull;
 // Device error bits latched in DevCtl::err and reported by nrg_sync.
 constexpr u32 ERR_TABLE_FULL = 1u;
 constexpr u32 ERR_CAPACITY = 4u;
+constexpr u32 ERR_INVAL = 16u;  // a log record outside its structure's domain (vspace.hip)
 constexpr u32 ERR_GROUP = 8u;  // a replica group's ranks disagreed on a round's segment lengths (group.cpp)
 
 // Counters of keys created by replay rounds (claiming blocks add to slot blk % HM_CREATED_SLOTS).

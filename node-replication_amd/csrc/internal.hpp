@@ -95,13 +95,18 @@ struct QuState {
     u64 ck_head, ck_len, ck_pops;
 };
 
+// The page table's device state (vspace.hip): tables allocated from the pool, the PML4 included.
+struct VsState {
+    u64 ntables;
+};
+
 struct HostRun {  // origin tags of appended log ranges (the Entry::replica field)
     u64 first, count;
     u32 origin;
 };
 
 // What the runtime knows about a data structure: one table per kind, defined beside the
-// structure's launchers (hashmap.hip, stack.hip, synthetic.hip, queue.hip).
+// structure's launchers (hashmap.hip, stack.hip, synthetic.hip, queue.hip, vspace.hip).
 struct DsOps {
     uint32_t rec_bytes;   // one log record
     uint32_t resp_bytes;  // one write response
@@ -118,7 +123,7 @@ struct DsOps {
     hipError_t (*replay)(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                          uint8_t* d_some);
 };
-const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops();
+const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
 
 }  // namespace nrg
@@ -215,6 +220,12 @@ struct nrg_ctx {
     uint64_t qu_size = 0;
     nrg::QuState* d_qu_state = nullptr;
     void* d_qu_aux = nullptr;             // per-tile aggregates and scanned starts (queue.hip)
+
+    // ---- VSpace ----
+    uint64_t* d_vs_pool = nullptr;        // vs_cap tables of 512 entries; table 0 is the PML4
+    uint64_t vs_cap = 0;
+    nrg::VsState* d_vs_state = nullptr;
+    void* d_vs_aux = nullptr;             // per-op scratch of one chunk (vspace.hip)
 
     // ---- shared scratch ----
     nrg::SortScratch sort;
@@ -344,6 +355,9 @@ hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_strid
 // queue.hip
 hipError_t qu_init_range(nrg_ctx* c, u64 n);  // values 0..n-1, front first
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads
+
+// vspace.hip
+hipError_t vs_resolve(nrg_ctx* c, const u64* d_va, u64 n, u64* d_pa, uint8_t* d_found);  // n Identify reads
 
 // synthetic.hip
 hipError_t sy_read(nrg_ctx* c, const nrg_synth_rd* d_ops, u64 n, u64* d_sums);

@@ -1,7 +1,7 @@
 // runtime.cpp — the nrgpu C ABI (include/nrgpu.h): replica lifetime, the per-replica HBM
 // log ring with the reference's head/tail/ctail/ltail bookkeeping, and dispatch of the
 // replay pipelines through each structure's ops table (hashmap.hip, stack.hip, synthetic.hip,
-// queue.hip).
+// queue.hip, vspace.hip).
 //
 // Log bookkeeping follows nr/src/log.rs: Log::new sizing (:179-242), append with GC when
 // fewer than GC_FROM_HEAD entries would remain (:343-427, :536-580), exec of
@@ -67,6 +67,7 @@ int check_err(nrg_ctx* c) {
         if (err & ERR_TABLE_FULL) return NRG_E_TABLE_FULL;
         if (err & ERR_CAPACITY) return NRG_E_CAPACITY;
         if (err & ERR_GROUP) return NRG_E_INVAL;
+        if (err & ERR_INVAL) return NRG_E_INVAL;
         return NRG_E_HIP;
     }
     return NRG_OK;
@@ -190,6 +191,7 @@ const DsOps* ds_ops(uint32_t kind) {
         case NRG_DS_STACK: return st_ops();
         case NRG_DS_SYNTHETIC: return sy_ops();
         case NRG_DS_QUEUE: return qu_ops();
+        case NRG_DS_VSPACE: return vs_ops();
         default: return nullptr;
     }
 }
@@ -267,6 +269,10 @@ void nrg_config_default(nrg_config* cfg, uint32_t ds_kind) {
     cfg->replica_id = 1;
     cfg->pipeline = 0;  // opt-in: see nrg_config.pipeline
     cfg->queue_capacity = 1u << 24;
+    if (ds_kind == NRG_DS_VSPACE) {
+        cfg->log2_slots = 18;       // the pool: 2^18 tables of 4 KiB, 1 GiB
+        cfg->max_batch = 1u << 16;  // the largest chunk a page table replays
+    }
 }
 
 const char* nrg_strerror(int code) {
@@ -330,7 +336,7 @@ int nrg_open(int dev, const nrg_config* cfg_in, nrg_ctx** out) {
     c->cfg = *cfg_in;
     c->ops = ops;
     nrg_config& cf = c->cfg;
-    if (!cf.max_batch) cf.max_batch = 1u << 20;
+    if (!cf.max_batch) cf.max_batch = cf.ds_kind == NRG_DS_VSPACE ? 1u << 16 : 1u << 20;  // as nrg_config_default
     if (!cf.max_reads) cf.max_reads = 1u << 20;
     if (!cf.replica_id) cf.replica_id = 1;
     if (cf.max_batch >= (1ull << 30)) { delete c; return NRG_E_INVAL; }
@@ -528,7 +534,7 @@ static int need(nrg_ctx* c, uint32_t kind) {
     return use_device(c);
 }
 
-// Replica::combine for one batch of a stack, synthetic or queue replica: one replay pass that
+// Replica::combine for one batch of a stack, synthetic, queue or page-table replica: one replay pass that
 // also writes the log copy (Log::append + Log::exec of this batch)
 static int round_common(nrg_ctx* c, uint32_t kind, const void* d_ops, uint64_t n, uint32_t origin, void* d_resp,
                         uint8_t* d_some) {
@@ -885,6 +891,99 @@ int nrg_queue_dump(nrg_ctx* c, uint64_t* vals, uint64_t cap, uint64_t* n) {
         if (first < *n)
             HIPCHK(hipMemcpyAsync(vals + first, c->d_queue, (*n - first) * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(sync_all(c));
+    }
+    return NRG_OK;
+}
+
+// ---- VSpace (replicated page table) --------------------------------------------------------
+int nrg_vspace_round_async(nrg_ctx* c, const nrg_vspace_op* d_ops, uint64_t n, uint32_t origin,
+                           nrg_vspace_resp* d_resp, uint8_t* d_some) {
+    return round_common(c, NRG_DS_VSPACE, d_ops, n, origin, d_resp, d_some);
+}
+
+int nrg_vspace_resolve_async(nrg_ctx* c, const uint64_t* d_vaddrs, uint64_t n, uint64_t* d_paddrs, uint8_t* d_found) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n > c->cfg.max_reads) return NRG_E_CAPACITY;
+    if (n && (!d_vaddrs || !d_paddrs || !d_found)) return NRG_E_INVAL;
+    return hip_fail(vs_resolve(c, d_vaddrs, n, d_paddrs, d_found));
+}
+
+int nrg_vspace_resolve(nrg_ctx* c, const uint64_t* vaddrs, uint64_t n, uint64_t* paddrs, uint8_t* found) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n > c->cfg.max_reads) return NRG_E_CAPACITY;
+    if (n == 0) return NRG_OK;
+    if (!vaddrs || !paddrs || !found) return NRG_E_INVAL;
+    Staging* s = stg(c);
+    if ((r = staging(s[0], n * 8)) || (r = staging(s[1], n * 8)) || (r = staging(s[2], n))) return r;
+    HIPCHK(hipMemcpyAsync(s[0].p, vaddrs, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(vs_resolve(c, (u64*)s[0].p, n, (u64*)s[1].p, (uint8_t*)s[2].p));
+    HIPCHK(hipMemcpyAsync(paddrs, s[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(found, s[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+// tables allocated from the pool
+static int vs_get_tables(nrg_ctx* c, uint64_t* n) {
+    VsState s{};
+    HIPCHK(hipMemcpyAsync(&s, c->d_vs_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    *n = s.ntables;
+    if (s.ntables > c->vs_cap) return NRG_E_HIP;  // (the allocation passes never hand out more than the pool holds)
+    return check_err(c);
+}
+
+int nrg_vspace_tables(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    return vs_get_tables(c, n);
+}
+
+// The leaves below table `tab` of level `level` (3 = PML4 .. 0 = PT) in ascending vaddr: slots are
+// walked in index order, so nothing depends on the order in which the tables were allocated.
+static void vs_collect(const uint64_t* pool, uint64_t ntab, uint64_t tab, int level, uint64_t va,
+                       std::vector<nrg_vspace_leaf>& out) {
+    const uint64_t ADDR = 0x000ffffffffff000ull;
+    for (uint64_t i = 0; i < 512; i++) {
+        const uint64_t e = pool[tab * 512 + i];
+        if (!(e & 1)) continue;
+        const uint64_t v = va | (i << (12 + 9 * level));
+        if (level == 0 || (level == 1 && (e & 0x80))) {
+            out.push_back(nrg_vspace_leaf{v, e});
+        } else {
+            const uint64_t next = (e & ADDR) >> 12;
+            if (next < ntab) vs_collect(pool, ntab, next, level - 1, v, out);
+        }
+    }
+}
+
+int nrg_vspace_dump(nrg_ctx* c, nrg_vspace_leaf* leaves, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    uint64_t ntab = 0;
+    if ((r = vs_get_tables(c, &ntab))) return r;
+    // Replica::verify's view, not a hot path: the allocated tables are copied out and walked here
+    std::vector<uint64_t> pool;
+    std::vector<nrg_vspace_leaf> out;
+    try {
+        pool.resize(ntab * 512);
+        HIPCHK(hipMemcpyAsync(pool.data(), c->d_vs_pool, ntab * 4096, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+        vs_collect(pool.data(), ntab, 0, 3, 0, out);
+    } catch (const std::bad_alloc&) {
+        return NRG_E_NOMEM;
+    }
+    *n = out.size();
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n) {
+        if (!leaves) return NRG_E_INVAL;
+        std::memcpy(leaves, out.data(), *n * sizeof(nrg_vspace_leaf));
     }
     return NRG_OK;
 }

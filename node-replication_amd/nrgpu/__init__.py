@@ -12,11 +12,17 @@ from .replica import (
     STACK_OP_DTYPE,
     SYNTH_OP_DTYPE,
     SYNTH_RD_DTYPE,
+    VSPACE_LEAF_DTYPE,
+    VSPACE_OP_DTYPE,
+    VSPACE_RESP_DTYPE,
     AbstractDataStructure,
     DeviceReplica,
     Get,
+    Identify,
     Len,
     Log,
+    Map,
+    MapDevice,
     NrHashMap,
     Peek,
     Pop,
@@ -28,6 +34,7 @@ from .replica import (
     Replica,
     ReplicaToken,
     Stack,
+    VSpace,
     WriteOnly,
 )
 
@@ -35,6 +42,7 @@ __all__ = [
     "_lib", "NrgError", "load", "Combiner", "PUT_DTYPE", "QUEUE_OP_DTYPE", "STACK_OP_DTYPE", "SYNTH_OP_DTYPE", "SYNTH_RD_DTYPE",
     "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
+    "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
 ]
 
 

@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("NRGPU_LIB") or os.path.join(PKG_ROOT, "lib", "libnrgpu.so")  # env: A/B builds
@@ -38,6 +40,7 @@ NRG_DS_HASHMAP = 1
 NRG_DS_STACK = 2
 NRG_DS_SYNTHETIC = 3
 NRG_DS_QUEUE = 4
+NRG_DS_VSPACE = 5
 
 NRG_STACK_POP = 0
 NRG_STACK_PUSH = 1
@@ -45,6 +48,13 @@ NRG_QUEUE_POP = 0
 NRG_QUEUE_PUSH = 1
 NRG_SYNTH_WRITE_ONLY = 0
 NRG_SYNTH_READ_WRITE = 1
+NRG_VSPACE_MAP = 0
+NRG_VSPACE_MAP_DEVICE = 1
+
+# nrg_vspace_op (32 B), nrg_vspace_resp (16 B) and nrg_vspace_leaf (16 B)
+VSPACE_OP_DTYPE = np.dtype([("vbase", "<u8"), ("pbase", "<u8"), ("len", "<u8"), ("op", "<u4"), ("rights", "<u4")])
+VSPACE_RESP_DTYPE = np.dtype([("a", "<u8"), ("b", "<u8")])
+VSPACE_LEAF_DTYPE = np.dtype([("vaddr", "<u8"), ("entry", "<u8")])
 
 
 class NrgError(RuntimeError):
@@ -150,6 +160,11 @@ SIGNATURES = {
     "nrg_queue_len": (C.c_int, [vp, u64p]),
     "nrg_queue_dump": (C.c_int, [vp, vp, u64, u64p]),
     "nrg_queue_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
+    "nrg_vspace_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
+    "nrg_vspace_resolve": (C.c_int, [vp, vp, u64, vp, vp]),
+    "nrg_vspace_resolve_async": (C.c_int, [vp, vp, u64, vp, vp]),
+    "nrg_vspace_tables": (C.c_int, [vp, u64p]),
+    "nrg_vspace_dump": (C.c_int, [vp, vp, u64, u64p]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

@@ -7,9 +7,9 @@
                                    sync / verify, with flat combining of the registered
                                    threads' pending ops into one log append + one replay
   ReplicaToken    nr::ReplicaToken
-  NrHashMap, Stack, AbstractDataStructure, Queue — the Dispatch plug-ins of the reference
+  NrHashMap, Stack, AbstractDataStructure, Queue, VSpace — the Dispatch plug-ins of the reference
                                    (benches/hashmap.rs, benches/stack.rs, benches/synthetic.rs,
-                                   benches/lockfree_comparisons.rs)
+                                   benches/lockfree_comparisons.rs, benches/vspace.rs)
 """
 from __future__ import annotations
 
@@ -28,6 +28,9 @@ STACK_OP_DTYPE = np.dtype([("val", "<u4"), ("op", "<u4")])
 QUEUE_OP_DTYPE = np.dtype([("val", "<u8"), ("op", "<u8")])
 SYNTH_OP_DTYPE = np.dtype([("tid", "<u8"), ("r1", "<u8"), ("r2", "<u8"), ("op", "<u8")])
 SYNTH_RD_DTYPE = np.dtype([("tid", "<u8"), ("r1", "<u8"), ("r2", "<u8")])
+VSPACE_OP_DTYPE = L.VSPACE_OP_DTYPE
+VSPACE_RESP_DTYPE = L.VSPACE_RESP_DTYPE
+VSPACE_LEAF_DTYPE = L.VSPACE_LEAF_DTYPE
 
 # nr/src/log.rs:22,26,36 ; nr/src/context.rs:12 ; nr/src/replica.rs:56
 DEFAULT_LOG_BYTES = 32 * 1024 * 1024
@@ -199,6 +202,8 @@ class DeviceReplica:
     def _resp_dtype(self):
         if self.kind == L.NRG_DS_STACK:
             return np.uint32
+        if self.kind == L.NRG_DS_VSPACE:
+            return VSPACE_RESP_DTYPE  # (a, b): Ok((a, b)), or Err(at = a) where some = 0
         # hashmap previous values, synthetic sums, queue pushed / popped values
         return np.uint64
 
@@ -240,6 +245,15 @@ class DeviceReplica:
         Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
         L.check(self._lib.nrg_queue_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
                 "queue_round")
+
+    @_stream_ordered
+    def vs_round_device(self, d_ops, n: int, origin: int, d_resp=None, d_some=None):
+        """Replica::combine for one page-table batch on device buffers: append + exec, the log
+        copy written by the replay (nrg_vspace_round_async); responses (16 B {a, b} each) for
+        these ops into d_resp / d_some.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_vspace_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
+                "vspace_round")
 
     def log_reset(self):
         L.check(self._lib.nrg_log_reset(self._h))
@@ -410,6 +424,39 @@ class DeviceReplica:
         L.check(self._lib.nrg_queue_dump(self._h, _ptr(out), n, C.byref(m)), "queue_dump")
         return out[: m.value]
 
+    # -- vspace --------------------------------------------------------------------
+    def vs_resolve(self, vaddrs):
+        """Identify for a batch of virtual addresses: (paddrs, found); paddr 0 where unmapped."""
+        vaddrs = np.ascontiguousarray(np.asarray(vaddrs, np.uint64))
+        n = len(vaddrs)
+        pa = np.zeros(max(n, 1), np.uint64)
+        found = np.zeros(max(n, 1), np.uint8)
+        L.check(self._lib.nrg_vspace_resolve(self._h, _ptr(vaddrs), n, _ptr(pa), _ptr(found)), "vspace_resolve")
+        return pa[:n], found[:n]
+
+    @_stream_ordered
+    def vs_resolve_device(self, d_vaddrs, n: int, d_paddrs, d_found):
+        """Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_vspace_resolve_async(self._h, _dptr(d_vaddrs), n, _dptr(d_paddrs), _dptr(d_found)),
+                "vspace_resolve")
+
+    def vs_tables(self) -> int:
+        """Tables allocated so far, the PML4 included."""
+        n = C.c_uint64()
+        L.check(self._lib.nrg_vspace_tables(self._h, C.byref(n)), "vspace_tables")
+        return n.value
+
+    def vs_dump(self) -> np.ndarray:
+        """Every leaf entry as (vaddr, entry), in ascending vaddr (VSPACE_LEAF_DTYPE)."""
+        n = C.c_uint64()
+        rc = self._lib.nrg_vspace_dump(self._h, None, 0, C.byref(n))  # the count: nothing fits in 0
+        if rc != L.NRG_E_CAPACITY:
+            L.check(rc, "vspace_dump")
+        out = np.zeros(max(n.value, 1), VSPACE_LEAF_DTYPE)
+        m = C.c_uint64()
+        L.check(self._lib.nrg_vspace_dump(self._h, _ptr(out), n.value, C.byref(m)), "vspace_dump")
+        return out[: m.value]
+
     # -- synthetic -----------------------------------------------------------------
     def sy_read(self, ops: np.ndarray) -> np.ndarray:
         ops = np.ascontiguousarray(ops, SYNTH_RD_DTYPE)
@@ -494,6 +541,26 @@ class Peek:  # nr/tests/stack.rs:26-29
 @dataclass(frozen=True)
 class Len:  # benches/lockfree.rs:49-52 (QueueRd::Len)
     pass
+
+
+@dataclass(frozen=True)
+class Map:  # benches/vspace.rs:485 OpcodeWr::Map(vbase, len, rights, pbase); rights 1..8 in MapAction order
+    vbase: int
+    len: int
+    rights: int
+    pbase: int
+
+
+@dataclass(frozen=True)
+class MapDevice:  # benches/vspace.rs:486 OpcodeWr::MapDevice(vbase, pbase, len)
+    vbase: int
+    pbase: int
+    len: int
+
+
+@dataclass(frozen=True)
+class Identify:  # benches/vspace.rs:491 OpcodeRd::Identify(vaddr)
+    vaddr: int
 
 
 @dataclass(frozen=True)
@@ -598,6 +665,39 @@ class Queue:
     @staticmethod
     def snapshot(dev: DeviceReplica):
         return dev.qu_dump().tolist()
+
+
+class VSpace:
+    """VSpaceDispatcher (benches/vspace.rs:494-526): an x86-64 four-level page table. Map ->
+    ("ok", pbase, len), MapDevice -> ("ok", 0, 0), either -> ("err", at) where the range meets an
+    existing mapping; Identify -> the physical address, 0 where nothing is mapped."""
+
+    kind = L.NRG_DS_VSPACE
+    rec_dtype = VSPACE_OP_DTYPE
+
+    @staticmethod
+    def encode(ops) -> np.ndarray:
+        r = np.zeros(len(ops), VSPACE_OP_DTYPE)
+        r["vbase"] = [o.vbase for o in ops]
+        r["pbase"] = [o.pbase for o in ops]
+        r["len"] = [o.len for o in ops]
+        r["op"] = [L.NRG_VSPACE_MAP if isinstance(o, Map) else L.NRG_VSPACE_MAP_DEVICE for o in ops]
+        r["rights"] = [o.rights if isinstance(o, Map) else 0 for o in ops]
+        return r
+
+    @staticmethod
+    def decode(resp, some) -> list:
+        return [("ok", int(r["a"]), int(r["b"])) if s else ("err", int(r["a"])) for r, s in zip(resp, some)]
+
+    @staticmethod
+    def read_batch(dev: DeviceReplica, ops) -> list:
+        pa, _ = dev.vs_resolve(np.array([o.vaddr for o in ops], np.uint64))
+        return [int(a) for a in pa]
+
+    @staticmethod
+    def snapshot(dev: DeviceReplica):
+        d = dev.vs_dump()
+        return list(zip(d["vaddr"].tolist(), d["entry"].tolist()))
 
 
 class AbstractDataStructure:
