@@ -14,7 +14,9 @@ extern "C" {
 /* stable sort of n (key, val) pairs by the low key_bits of key; d_vals may be NULL (0..n-1) */
 int nrg_test_sort_pairs(nrg_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_vals, uint64_t n,
                         int key_bits, uint32_t* d_out_keys, uint32_t* d_out_vals);
-/* M[p] = max{q <= p : q == 0 || keys[q-1] != keys[q] || (vals[q] & 0x80000000)} */
+/* M[p] = max{q <= p : q == 0 || keys[q-1] != keys[q] || (vals[q] & 0x80000000)}; a hook of the
+ * synthetic structure (the scan's look-back descriptors are its own): NRG_E_INVAL on a context of
+ * any other kind, or when n exceeds the context's max_batch * writes per op */
 int nrg_test_maxscan(nrg_ctx* ctx, const uint32_t* d_keys, const uint32_t* d_vals, uint64_t n,
                      uint32_t* d_out);
 /* The hardware property the synthetic replay's rankings rest on (synthetic.hip): a

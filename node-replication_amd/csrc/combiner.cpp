@@ -356,20 +356,20 @@ int launch(nrg_combiner* m, Batch& x, uint64_t k, uint32_t W, uint32_t R) {
     if (m->srv_running && (rc = serve_stop(m)) != NRG_OK) return rc;  // launches queue behind the server
     // hashmap rounds of <= 2048 Puts (>= 1) and <= 8192 Gets run as ONE small-round workgroup
     // (hashmap.hip small_round), whose last write can be the error copy
-    const bool small = m->kind == NRG_DS_HASHMAP && W > 0 && W <= c->small_max && W <= 2048 && R <= 8192;
+    const bool small = m->kind == NRG_DS_HASHMAP && W > 0 && W <= c->hm.small_max && W <= 2048 && R <= 8192;
     switch (m->kind) {
         case NRG_DS_HASHMAP:  // Put -> HashMap::insert's previous value (nr/examples/hashmap.rs:46-50)
             // a small round (one workgroup, the round's only launch) copies the error latch as its
-            // last write and clears c->err_out; any other round leaves it set (only
+            // last write and clears c->hm.err_out; any other round leaves it set (only
             // hm_small_round_kernel takes it) and gets comb_err_kernel behind it
-            if (small) c->err_out = x.err;
+            if (small) c->hm.err_out = x.err;
             rc = nrg_hashmap_round_async(c, (const nrg_put*)x.recs, W, origin, (const uint64_t*)x.reads, R,
                                          (uint64_t*)x.rresp, x.rsome, (uint64_t*)x.wresp, x.wsome);
             break;
         case NRG_DS_STACK:
             if (W) rc = nrg_stack_round_async(c, (const nrg_stack_op*)x.recs, W, origin, (uint32_t*)x.wresp, x.wsome);
             if (!rc && R) {
-                comb_peek_kernel<<<1, 256, 0, st>>>(c->d_ctl, c->d_stack, c->cfg.stack_capacity, R,
+                comb_peek_kernel<<<1, 256, 0, st>>>(c->d_ctl, c->st.d_stack, c->cfg.stack_capacity, R,
                                                     (uint32_t*)x.rresp, x.rsome);
                 if (hipGetLastError() != hipSuccess) rc = NRG_E_HIP;
             }
@@ -388,13 +388,13 @@ int launch(nrg_combiner* m, Batch& x, uint64_t k, uint32_t W, uint32_t R) {
         default: rc = NRG_E_INVAL; break;
     }
     if (!rc && nrg_join(c)) rc = NRG_E_HIP;  // a deferred round tail would write responses later
-    if (!rc && (!small || c->err_out)) {
+    if (!rc && (!small || c->hm.err_out)) {
         // no small round took the error copy as its last write
-        c->err_out = nullptr;
+        c->hm.err_out = nullptr;
         comb_err_kernel<<<1, 64, 0, st>>>(c->d_ctl, x.err);
         if (hipGetLastError() != hipSuccess) rc = NRG_E_HIP;
     }
-    c->err_out = nullptr;
+    c->hm.err_out = nullptr;
     return rc;
 }
 
@@ -598,7 +598,7 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
         comb_free(m);
         return NRG_E_NOMEM;
     }
-    if (kind == NRG_DS_HASHMAP && ctx->comb_serve != 0) {
+    if (kind == NRG_DS_HASHMAP && ctx->comb.serve != 0) {
         ok = (m->sc = (nrg::ServeCtl*)host_alloc(sizeof(nrg::ServeCtl))) &&
              (m->hdr = (nrg::SmallJobBlob*)host_alloc(NB * sizeof(nrg::SmallJobBlob)));
         if (!ok) {
@@ -617,27 +617,27 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
             return NRG_E_INVAL;
         }
         m->serve = true;
-        if (ctx->comb_serve >= 2) m->serve_max = (uint32_t)ctx->comb_serve;
+        if (ctx->comb.serve >= 2) m->serve_max = (uint32_t)ctx->comb.serve;
     }
     m->saved_pipeline = ctx->pipeline;
     ctx->pipeline = false;
     // hashmap rounds of up to 2048 Puts in one launch (hashmap.hip hm_small_round_kernel)
-    m->saved_small = ctx->small_max;
-    if (kind == NRG_DS_HASHMAP) ctx->small_max = 2048;
+    m->saved_small = ctx->hm.small_max;
+    if (kind == NRG_DS_HASHMAP) ctx->hm.small_max = 2048;
     // Waiting clients park, unless every client fits the CPUs the job may use: then up to
     // max_threads - 1 of them spin on their round (16 threads on a 16-CPU quota: 19.6 vs 18.0-19.0
     // M ops/s parked, profiles/r04_combiner.txt F). With more clients than CPUs spinning ones take
     // the quota from the combiner thread (64 threads: 22.3 vs 24.5 M ops/s parked,
     // profiles/r03_combiner_policy.txt).
-    if (ctx->comb_spin >= 0) {
-        m->spin_cap = ctx->comb_spin;
+    if (ctx->comb.spin >= 0) {
+        m->spin_cap = ctx->comb.spin;
     } else {
         const int cpus = usable_cpus();
         m->spin_cap = (int)max_threads <= cpus ? (int)max_threads - 1 : 0;
     }
-    if (ctx->comb_gather >= 0) m->gather_ns = (uint64_t)ctx->comb_gather * 1000ull;
-    if (ctx->comb_depth) {  // an explicit depth: no SECOND_MIN rule
-        m->depth = std::min<uint64_t>(ctx->comb_depth, NB - 2);
+    if (ctx->comb.gather >= 0) m->gather_ns = (uint64_t)ctx->comb.gather * 1000ull;
+    if (ctx->comb.depth) {  // an explicit depth: no SECOND_MIN rule
+        m->depth = std::min<uint64_t>(ctx->comb.depth, NB - 2);
         m->depth_auto = false;
     }
     m->b[0].round.store(0);
@@ -647,7 +647,7 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
         m->worker = std::thread(combiner_main, m);
     } catch (...) {
         ctx->pipeline = m->saved_pipeline;
-        ctx->small_max = m->saved_small;
+        ctx->hm.small_max = m->saved_small;
         comb_free(m);
         return NRG_E_NOMEM;
     }
@@ -667,7 +667,7 @@ extern "C" int nrg_combiner_close(nrg_combiner* m) {
     if (serve_stop(m) != NRG_OK) rc = NRG_E_HIP;
     if (hipStreamSynchronize((hipStream_t)nrg_get_stream(m->ctx)) != hipSuccess) rc = NRG_E_HIP;
     m->ctx->pipeline = m->saved_pipeline;
-    m->ctx->small_max = m->saved_small;
+    m->ctx->hm.small_max = m->saved_small;
     comb_free(m);
     return rc;
 }

@@ -37,6 +37,7 @@
 #include <cstring>
 
 #include "internal.hpp"
+#include "../../include/nrgpu_testing.h"
 
 namespace nrg {
 
@@ -1424,6 +1425,7 @@ __global__ __launch_bounds__(SM_TPB) void hm_serve_kernel(ServeCtl* sc, const Sm
 
 static RecSrc ring_src(nrg_ctx* c, const nrg_put* src, u64 lo);
 static hipError_t hm_flush(nrg_ctx* c);
+static hipError_t hm_count(nrg_ctx* c);  // DevCtl::nkeys_total = number of keys
 
 // A round through hm_small_round_kernel (hm_replay_chunk decides; n <= SM_W, R <= SM_R).
 static hipError_t small_round(nrg_ctx* c, const nrg_put* src, u64 lo, u64 n, bool write_ring, const u64* keys, u64 R,
@@ -1443,20 +1445,20 @@ static hipError_t small_round(nrg_ctx* c, const nrg_put* src, u64 lo, u64 n, boo
     j.R = keys ? (u32)R : 0u;
     j.vals = vals;
     j.found = found;
-    j.e_out = c->err_out;
-    c->err_out = nullptr;
-    j.created_acc = c->d_created;
-    NRG_LAUNCH(c, "hm_small", hm_small_round_kernel, 1, SM_TPB, 0, c->stream, j, c->d_table, c->slot_shift,
-               (u64)(c->slots - 1), c->d_ctl);
+    j.e_out = c->hm.err_out;
+    c->hm.err_out = nullptr;
+    j.created_acc = c->hm.d_created;
+    NRG_LAUNCH(c, "hm_small", hm_small_round_kernel, 1, SM_TPB, 0, c->stream, j, c->hm.d_table, c->hm.slot_shift,
+               (u64)(c->hm.slots - 1), c->d_ctl);
     return hipGetLastError();
 }
 
 // The job of a small round of records [lo, lo + W) (hm_small_round_kernel's, as small_round would
-// launch it with the log copy written) into `blob`, for hm_serve_kernel; runtime.cpp hm_small_job
+// launch it with the log copy written) into `blob`, for hm_serve_kernel; hm_small_job
 // does the replica's log bookkeeping around it.
 bool hm_small_fill(nrg_ctx* c, const nrg_put* recs, u64 lo, u64 W, const u64* keys, u64 R, u64* vals, uint8_t* found,
                    u64* prev, uint8_t* prevf, u32* e_out, SmallJobBlob* blob) {
-    if (W > SM_W || R > SERVE_R || c->pend.valid) return false;
+    if (W > SM_W || R > SERVE_R || c->hm.pend.valid) return false;
     if (!blob) return true;  // (the server's slots hold the fixed fields; only the checks)
     SmallJob j;
     j.rec = ring_src(c, recs, lo);
@@ -1472,7 +1474,7 @@ bool hm_small_fill(nrg_ctx* c, const nrg_put* recs, u64 lo, u64 W, const u64* ke
     j.vals = vals;
     j.found = found;
     j.e_out = e_out;
-    j.created_acc = c->d_created;
+    j.created_acc = c->hm.d_created;
     std::memcpy(blob->b, &j, sizeof j);
     return true;
 }
@@ -1481,7 +1483,7 @@ hipError_t hm_serve_launch(nrg_ctx* c, ServeCtl* sc, const SmallJobBlob* hdr, u3
                            u64 session, u64 idle_ticks) {
     if (nslots > SERVE_SLOTS) return hipErrorInvalidValue;
     NRG_LAUNCH(c, "hm_serve", hm_serve_kernel, 1, SM_TPB, 0, c->stream, sc, hdr, nslots, first, first_lo, session,
-               idle_ticks, c->d_table, c->slot_shift, (u64)(c->slots - 1), c->d_ctl);
+               idle_ticks, c->hm.d_table, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
     return hipGetLastError();
 }
 
@@ -1752,7 +1754,7 @@ static RecSrc ring_src(nrg_ctx* c, const nrg_put* src, u64 lo) {
 // 4 there the read blocks behind the index blocks start earlier, but without that many Gets 4
 // loses (1M Puts, 2M Puts). NRG_KNOB_K1 overrides.
 static u32 stamp_k1_for(const nrg_ctx* c, u64 n, u64 R) {
-    if (c->k1_items) return c->k1_items >= 4 ? 4u : c->k1_items >= 2 ? 2u : 1u;
+    if (c->hm.k1_items) return c->hm.k1_items >= 4 ? 4u : c->hm.k1_items >= 2 ? 2u : 1u;
     if (n <= (1u << 18)) return 1u;
     return n >= 655360 && R >= n ? 4u : 2u;
 }
@@ -1770,8 +1772,8 @@ struct Launch {
 
 // The deferred half of the last round rides in this launch: its apply (stamp rounds) and reads.
 static void attach_deferred(nrg_ctx* c, Launch& L) {
-    const HmDeferred& p = c->pend;
-    L.rj.epoch = c->epoch;  // reads without a deferred round: every round applied
+    const HmDeferred& p = c->hm.pend;
+    L.rj.epoch = c->hm.epoch;  // reads without a deferred round: every round applied
     if (p.valid) {
         const RecSrc rs = ring_src(c, p.src, p.lo);
         L.rj.keys = p.keys;
@@ -1784,24 +1786,24 @@ static void attach_deferred(nrg_ctx* c, Launch& L) {
         if (p.apply) {
             L.aj.rec = rs;
             L.aj.n = p.n;
-            L.aj.put_slot = c->d_put_slot[p.epoch & 1];
-            L.aj.win = L.aj.put_slot + c->stamp_alloc;
-            L.aj.over = L.aj.put_slot + 2 * c->stamp_alloc;
+            L.aj.put_slot = c->hm.d_put_slot[p.epoch & 1];
+            L.aj.win = L.aj.put_slot + c->hm.stamp_alloc;
+            L.aj.over = L.aj.put_slot + 2 * c->hm.stamp_alloc;
             L.aj.epoch = p.epoch;
             L.aj.nblocks = (u32)((p.n + TPB - 1) / TPB);
         }
     }
-    c->pend = HmDeferred{};
+    c->hm.pend = HmDeferred{};
 }
 
 template <int K1, int IX>
 static void launch_round(nrg_ctx* c, const Launch& L, u32 blocks, unsigned lds) {
     if ((L.ij.exp | L.sj.exp) != 0)
         NRG_LAUNCH(c, "hm_round", (hm_round_kernel<K1, IX, true>), blocks, TPB, lds, c->stream, L.ij, L.sj, L.aj, L.rj,
-                   c->d_table, c->slot_shift, (u64)(c->slots - 1), c->d_ctl);
+                   c->hm.d_table, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
     else
         NRG_LAUNCH(c, "hm_round", (hm_round_kernel<K1, IX, false>), blocks, TPB, lds, c->stream, L.ij, L.sj, L.aj,
-                   L.rj, c->d_table, c->slot_shift, (u64)(c->slots - 1), c->d_ctl);
+                   L.rj, c->hm.d_table, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
 }
 
 static hipError_t launch(nrg_ctx* c, Launch& L) {
@@ -1815,13 +1817,13 @@ static hipError_t launch(nrg_ctx* c, Launch& L) {
     u32 blocks = nix + L.aj.nblocks + L.rj.nblocks;
     if (blocks == 0) return hipSuccess;
     // a pending skew sample rides in the launch's last block. (The combiner's error copy,
-    // c->err_out, is taken only by hm_small_round_kernel, whose last write it is: a multi-block
+    // c->hm.err_out, is taken only by hm_small_round_kernel, whose last write it is: a multi-block
     // launch's tail block may run before its other blocks' responses land, nrg_combiner retire().)
-    if (c->sample_seq) {
-        L.rj.s_acc = c->d_dup + ((c->dup_seq - 1) & 1) * HM_DUP_SLOTS;  // the window just ended
-        L.rj.s_host = c->h_dup_dev;
-        L.rj.s_seq = c->sample_seq;
-        c->sample_seq = 0;
+    if (c->hm.sample_seq) {
+        L.rj.s_acc = c->hm.d_dup + ((c->hm.dup_seq - 1) & 1) * HM_DUP_SLOTS;  // the window just ended
+        L.rj.s_host = c->hm.h_dup_dev;
+        L.rj.s_seq = c->hm.sample_seq;
+        c->hm.sample_seq = 0;
         blocks++;
     }
     unsigned lds = 0;
@@ -1848,7 +1850,7 @@ static hipError_t launch(nrg_ctx* c, Launch& L) {
 
 // The deferred half of the last replayed round (its reads and, for a stamp round, its apply), if any.
 static hipError_t hm_flush(nrg_ctx* c) {
-    if (!c->pend.valid) return hipSuccess;
+    if (!c->hm.pend.valid) return hipSuccess;
     Launch L;
     attach_deferred(c, L);
     return launch(c, L);
@@ -1857,11 +1859,11 @@ static hipError_t hm_flush(nrg_ctx* c) {
 // Reads against the current state (no writes): attached to the deferred round if it has none.
 static hipError_t hm_reads(nrg_ctx* c, const u64* keys, u64 R, u64* vals, uint8_t* found) {
     if (R == 0) return hipSuccess;
-    if (c->pend.valid && c->pend.R == 0) {
-        c->pend.keys = keys;
-        c->pend.R = R;
-        c->pend.vals = vals;
-        c->pend.found = found;
+    if (c->hm.pend.valid && c->hm.pend.R == 0) {
+        c->hm.pend.keys = keys;
+        c->hm.pend.R = R;
+        c->hm.pend.vals = vals;
+        c->hm.pend.found = found;
         return hm_flush(c);
     }
     hipError_t e = hm_flush(c);
@@ -1880,35 +1882,36 @@ static hipError_t hm_alloc(nrg_ctx* c, u64 mb) {
     const u64 tiles = (mb + TPB - 1) / TPB;  // index tiles of >= TPB Puts
     const u64 ents = tiles * TPB;
     hipError_t e;
-    if ((e = hipMalloc(&c->d_bk_ent, ents * 16)) != hipSuccess) return e;
-    if ((e = hipMalloc(&c->d_bk_idx, ents * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&c->d_bk_cnt, (u64)HM_BK_MAX * tiles * sizeof(u32))) != hipSuccess) return e;
-    if (c->stamp_max > mb) c->stamp_max = mb;
+    if ((e = hipMalloc(&c->hm.d_bk_ent, ents * 16)) != hipSuccess) return e;
+    if ((e = hipMalloc(&c->hm.d_bk_idx, ents * 4)) != hipSuccess) return e;
+    if ((e = hipMalloc(&c->hm.d_bk_cnt, (u64)HM_BK_MAX * tiles * sizeof(u32))) != hipSuccess) return e;
+    if (c->hm.stamp_max > mb) c->hm.stamp_max = mb;
     // per parity: put_slot, win and over (stamp_max each; epoch tags, zeroed here and whenever
     // the epochs restart, hm_renorm)
-    for (int i = 0; i < 2 && c->stamp_max; i++) {
-        if ((e = hipMalloc(&c->d_put_slot[i], 3 * c->stamp_max * sizeof(u32))) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(c->d_put_slot[i], 0, 3 * c->stamp_max * sizeof(u32), c->stream)) != hipSuccess) return e;
+    for (int i = 0; i < 2 && c->hm.stamp_max; i++) {
+        if ((e = hipMalloc(&c->hm.d_put_slot[i], 3 * c->hm.stamp_max * sizeof(u32))) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_max * sizeof(u32), c->stream)) != hipSuccess) return e;
     }
     // two sets of duplicate counters, by sample-window parity: the launch that takes a window's
     // sample reads and clears its set while its own index blocks add to the other
-    if ((e = hipMalloc(&c->d_dup, 2 * HM_DUP_SLOTS * sizeof(u64))) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(c->d_dup, 0, 2 * HM_DUP_SLOTS * sizeof(u64), c->stream)) != hipSuccess) return e;
+    if ((e = hipMalloc(&c->hm.d_dup, 2 * HM_DUP_SLOTS * sizeof(u64))) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(c->hm.d_dup, 0, 2 * HM_DUP_SLOTS * sizeof(u64), c->stream)) != hipSuccess) return e;
     void* h = nullptr;
     if ((e = hipHostMalloc(&h, 2 * sizeof(u64), hipHostMallocMapped)) != hipSuccess) return e;
-    c->h_dup = (volatile u64*)h;
-    c->h_dup[0] = c->h_dup[1] = 0;
+    c->hm.h_dup = (volatile u64*)h;
+    c->hm.h_dup[0] = c->hm.h_dup[1] = 0;
     void* dp = nullptr;
     if ((e = hipHostGetDevicePointer(&dp, h, 0)) != hipSuccess) return e;
-    c->h_dup_dev = (u64*)dp;
+    c->hm.h_dup_dev = (u64*)dp;
     return hipSuccess;
 }
 
 static void hm_close(nrg_ctx* c) {
-    void* ptrs[] = {c->d_table, c->d_created, c->d_bk_ent, c->d_bk_idx, c->d_bk_cnt, c->d_put_slot[0],
-                    c->d_put_slot[1], c->d_dup};
+    void* ptrs[] = {c->hm.d_table, c->hm.d_created, c->hm.d_bk_ent, c->hm.d_bk_idx, c->hm.d_bk_cnt, c->hm.d_put_slot[0],
+                    c->hm.d_put_slot[1], c->hm.d_dup};
     for (void* p : ptrs) (void)hipFree(p);
-    if (c->h_dup) (void)hipHostFree((void*)c->h_dup);
+    if (c->hm.h_dup) (void)hipHostFree((void*)c->hm.h_dup);
+    pt_close(c);  // the scratch of this replica's key partitioning, if it ever partitioned
 }
 
 // Every dup_every rounds: read the previous sample (if it has landed) and decide whether the
@@ -1918,12 +1921,12 @@ static void hm_close(nrg_ctx* c) {
 // rounds (no atomics per Put) are faster at every size (Zipf 0.99 at 10 % / 50 % writes: 31.9 /
 // 55.3 us, profiles/r04_part_sweep.txt); uniform streams below PART_MIN take stamp rounds.
 static hipError_t skew_sample(nrg_ctx* c) {
-    if (c->dup_seq && c->h_dup[0] == c->dup_seq && c->dup_puts_sampled)
-        c->skewed = c->h_dup[1] * 64 > c->dup_puts_sampled;
-    c->sample_seq = ++c->dup_seq;  // taken by the next hm_round launch (its last block)
-    c->dup_puts_sampled = c->dup_puts;
-    c->dup_puts = 0;
-    c->dup_rounds = 0;
+    if (c->hm.dup_seq && c->hm.h_dup[0] == c->hm.dup_seq && c->hm.dup_puts_sampled)
+        c->hm.skewed = c->hm.h_dup[1] * 64 > c->hm.dup_puts_sampled;
+    c->hm.sample_seq = ++c->hm.dup_seq;  // taken by the next hm_round launch (its last block)
+    c->hm.dup_puts_sampled = c->hm.dup_puts;
+    c->hm.dup_puts = 0;
+    c->hm.dup_rounds = 0;
     return hipSuccess;
 }
 
@@ -1932,20 +1935,20 @@ static int hm_open(nrg_ctx* c) {
     // slot ids are < 2^30 (entry ids carry two flag values above them); replay chunks are
     // bounded by the partition rounds' 16-bit tile offsets (HM_MAX_BATCH)
     if (cf.log2_slots < 4 || cf.log2_slots > 30 || cf.max_batch > HM_MAX_BATCH) return NRG_E_INVAL;
-    c->grow_max_log2 = cf.hashmap_max_log2_slots;  // (checked by nrg_open; 0: a fixed table)
-    c->slots = 1ull << cf.log2_slots;
-    c->slot_shift = 64 - cf.log2_slots;
-    HIPCHK(hipMalloc(&c->d_table, c->slots * sizeof(Slot)));
-    hm_init_table_kernel<false><<<grid_for(c->slots, 16384), TPB, 0, c->stream>>>(c->d_table, c->slots);
+    c->hm.grow_max_log2 = cf.hashmap_max_log2_slots;  // (checked by nrg_open; 0: a fixed table)
+    c->hm.slots = 1ull << cf.log2_slots;
+    c->hm.slot_shift = 64 - cf.log2_slots;
+    HIPCHK(hipMalloc(&c->hm.d_table, c->hm.slots * sizeof(Slot)));
+    hm_init_table_kernel<false><<<grid_for(c->hm.slots, 16384), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMalloc(&c->d_created, HM_CREATED_SLOTS * sizeof(u64)));
-    HIPCHK(hipMemsetAsync(c->d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
+    HIPCHK(hipMalloc(&c->hm.d_created, HM_CREATED_SLOTS * sizeof(u64)));
+    HIPCHK(hipMemsetAsync(c->hm.d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
     // rounds without previous values replay in one launch (stamp rounds) unless the key
     // stream is skewed (skew_sample) or the round is large (PART_MIN); skewed, large and
     // previous-value rounds take partition rounds
-    c->stamp_max = HM_MAX_BATCH;       // (NRG_KNOB_STAMP_MAX lowers it for tests)
+    c->hm.stamp_max = HM_MAX_BATCH;       // (NRG_KNOB_STAMP_MAX lowers it for tests)
     HIPCHK(hm_alloc(c, cf.max_batch));  // clamps stamp_max to max_batch (the put_slot arrays' size)
-    c->stamp_alloc = c->stamp_max;
+    c->hm.stamp_alloc = c->hm.stamp_max;
     c->pipeline = cf.pipeline != 0;
     return NRG_OK;
 }
@@ -1954,7 +1957,7 @@ static int hm_open(nrg_ctx* c) {
 // HashMap<u64, u64> grows as it fills (nr/examples/hashmap.rs starts from an empty map;
 // benches/hashmap.rs:91-100 only pre-sizes it). Here: a synchronous rehash into a larger table,
 // rare, decided on the host from an upper bound of the key count (hm_room).
-u32 hm_slots_for(u64 keys) {
+static u32 hm_slots_for(u64 keys) {
     u32 l = 4;  // the smallest table nrg_open accepts
     while (l < 63 && (1ull << l) / HM_GROW_SLOTS_PER_KEY < keys) l++;
     return l;
@@ -1967,8 +1970,8 @@ u32 hm_slots_for(u64 keys) {
 // folded into DevCtl::nkeys (exact) and the created-key counters cleared. Then the stream is
 // synchronised, the old table freed and the new one installed. If the allocation fails nothing
 // has been launched but the flush: the old table stays installed and the replica is as it was.
-hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
-    if (new_log2 > 30 || (1ull << new_log2) <= c->slots) return hipErrorInvalidValue;
+static hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
+    if (new_log2 > 30 || (1ull << new_log2) <= c->hm.slots) return hipErrorInvalidValue;
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
     const u64 nslots = 1ull << new_log2;
@@ -1982,14 +1985,14 @@ hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
     else NRG_LAUNCH(c, "hm_grow_init", hm_init_table_kernel<false>, grid_for(nslots, 16384), TPB, 0, c->stream, nt, nslots);
     if ((e = hipGetLastError()) == hipSuccess) e = hipMemsetAsync(&c->d_ctl->nkeys, 0, sizeof(u64), c->stream);
     if (e == hipSuccess) {
-        const unsigned grid = (unsigned)((c->slots + RH_RUN - 1) / RH_RUN);
-        NRG_LAUNCH(c, "hm_rehash", hm_rehash_kernel, grid, RH_TPB, 0, c->stream, c->d_table, c->slots, nt,
+        const unsigned grid = (unsigned)((c->hm.slots + RH_RUN - 1) / RH_RUN);
+        NRG_LAUNCH(c, "hm_rehash", hm_rehash_kernel, grid, RH_TPB, 0, c->stream, c->hm.d_table, c->hm.slots, nt,
                    64 - new_log2, nslots - 1, c->d_ctl);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream);
-    for (int i = 0; i < 2 && c->d_put_slot[i] && e == hipSuccess; i++)
-        e = hipMemsetAsync(c->d_put_slot[i], 0, 3 * c->stamp_alloc * sizeof(u32), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->hm.d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream);
+    for (int i = 0; i < 2 && c->hm.d_put_slot[i] && e == hipSuccess; i++)
+        e = hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_alloc * sizeof(u32), c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) {
@@ -1997,11 +2000,11 @@ hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
         (void)hipFree(nt);
         return e;
     }
-    (void)hipFree(c->d_table);
-    c->d_table = nt;
-    c->slots = nslots;
-    c->slot_shift = 64 - new_log2;
-    c->epoch = 1;
+    (void)hipFree(c->hm.d_table);
+    c->hm.d_table = nt;
+    c->hm.slots = nslots;
+    c->hm.slot_shift = 64 - new_log2;
+    c->hm.epoch = 1;
     return hipSuccess;
 }
 
@@ -2016,12 +2019,12 @@ hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
 // the replicas of a group, which replay the same log in the same chunks, grow at the same round.
 hipError_t hm_room(nrg_ctx* c, u64 n, bool* due) {
     if (due) *due = false;
-    const u32 log2_slots = 64 - c->slot_shift;
-    if (!n || c->grow_max_log2 <= log2_slots) return hipSuccess;
+    const u32 log2_slots = 64 - c->hm.slot_shift;
+    if (!n || c->hm.grow_max_log2 <= log2_slots) return hipSuccess;
     if (n > (1ull << 31)) n = 1ull << 31;  // (more than any table holds; keeps the sums below from wrapping)
-    const u64 limit = c->slots / HM_GROW_SLOTS_PER_KEY;
-    if (c->keys_ub + n <= limit) {
-        c->keys_ub += n;
+    const u64 limit = c->hm.slots / HM_GROW_SLOTS_PER_KEY;
+    if (c->hm.keys_ub + n <= limit) {
+        c->hm.keys_ub += n;
         return hipSuccess;
     }
     if (due) {
@@ -2035,26 +2038,26 @@ hipError_t hm_room(nrg_ctx* c, u64 n, bool* due) {
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
     if (exact + n > limit) {
         u32 want = hm_slots_for(exact + n);
-        if (want > c->grow_max_log2) want = c->grow_max_log2;
+        if (want > c->hm.grow_max_log2) want = c->hm.grow_max_log2;
         if ((e = hm_grow(c, want)) != hipSuccess) return e;
     }
-    c->keys_ub = exact + n;
+    c->hm.keys_ub = exact + n;
     return hipSuccess;
 }
 
 // The next round's epoch; before the 32-bit epoch wraps, every stamp is renormalised to epoch 1.
 static hipError_t next_epoch(nrg_ctx* c, u32* e) {
-    if (c->epoch >= c->epoch_limit) {
+    if (c->hm.epoch >= c->hm.epoch_limit) {
         hipError_t r = hm_flush(c);
         if (r != hipSuccess) return r;
-        hm_renorm_kernel<<<grid_for(c->slots, 16384), TPB, 0, c->stream>>>(c->d_table, c->slots, c->d_ctl);
+        hm_renorm_kernel<<<grid_for(c->hm.slots, 16384), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl);
         if ((r = hipGetLastError()) != hipSuccess) return r;
-        for (int i = 0; i < 2 && c->d_put_slot[i]; i++)  // win / over epoch tags of the old epochs
-            if ((r = hipMemsetAsync(c->d_put_slot[i], 0, 3 * c->stamp_alloc * sizeof(u32), c->stream)) != hipSuccess)
+        for (int i = 0; i < 2 && c->hm.d_put_slot[i]; i++)  // win / over epoch tags of the old epochs
+            if ((r = hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_alloc * sizeof(u32), c->stream)) != hipSuccess)
                 return r;
-        c->epoch = 1;
+        c->hm.epoch = 1;
     }
-    *e = ++c->epoch;
+    *e = ++c->hm.epoch;
     return hipSuccess;
 }
 
@@ -2070,7 +2073,7 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
     const bool want_prev = d_prev && resp_lo < lo + n && resp_hi > lo;
     hipError_t eg = hm_room(c, n);  // every round kind below: the table grows first if it has to
     if (eg != hipSuccess) return eg;
-    if (c->small_max && n <= c->small_max && n <= SM_W && R <= SM_R) {  // one launch, nothing deferred
+    if (c->hm.small_max && n <= c->hm.small_max && n <= SM_W && R <= SM_R) {  // one launch, nothing deferred
         hipError_t e = small_round(c, src, lo, n, write_ring, d_get_keys, R, d_get_vals, d_get_found, resp_lo, resp_hi,
                                    want_prev ? d_prev : nullptr, d_prev_found);
         c->rounds++;
@@ -2090,8 +2093,8 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
     // 38.1 partition us, 200k + 900k 41.9 / 44.2, 400k + 900k 59.7 / 57.7, 800k + 900k 99.0 / 84.8,
     // 4M + 500k 413 / 271; previous values and skewed streams: partition rounds everywhere.
     constexpr u64 PART_MIN = 3ull << 17;
-    const bool stamp0 = !want_prev && c->stamp_max && n <= c->stamp_max && !c->skewed;
-    const bool part = !stamp0 || c->part_mode >= 2 || (c->part_mode == 1 && n >= PART_MIN);
+    const bool stamp0 = !want_prev && c->hm.stamp_max && n <= c->hm.stamp_max && !c->hm.skewed;
+    const bool part = !stamp0 || c->hm.part_mode >= 2 || (c->hm.part_mode == 1 && n >= PART_MIN);
     const bool stamp = stamp0 && !part;
     if (part) {
         // ---- partition round: {partition(e) | apply(e-1) | reads(e-1)}, then hm_papply_kernel(e) ----
@@ -2099,7 +2102,7 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         // [tile][bucket] count words stay <= n / 2
         const u32 K1 = n <= (1u << 14) ? 1u : n <= (1u << 16) ? 2u : n <= (1u << 18) ? 4u : 8u;
         const u32 tile = TPB * K1;
-        const u32 log2_slots = 64 - c->slot_shift;
+        const u32 log2_slots = 64 - c->hm.slot_shift;
         u32 nb_log = 0;
         while ((64ull << nb_log) < n && (1u << nb_log) < HM_BK_MAX) nb_log++;
         // apply workgroup width (NRG_KNOB_PA_TPB; 0: 512 threads over <= 512 buckets for rounds of
@@ -2108,7 +2111,7 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         // configs[2] 251.1-251.6 vs 255.0, 100 % writes 71.4 vs 72.9, 50 % 54.0 vs 55.1, Zipf 10 % 30.4
         // vs 30.8, Zipf 50 % 47.5 vs 47.9 (scrambled: equal)
         constexpr u64 PA_WIDE_MIN = 1ull << 16;
-        const u32 pa_t = want_prev ? 256u : c->pa_tpb ? c->pa_tpb : n >= PA_WIDE_MIN ? 512u : 256u;
+        const u32 pa_t = want_prev ? 256u : c->hm.pa_tpb ? c->hm.pa_tpb : n >= PA_WIDE_MIN ? 512u : 256u;
         const u32 pa_nb_log = pa_t == 1024 ? PaGeo<false, 1024>::NB_LOG : pa_t == 512 ? PaGeo<false, 512>::NB_LOG
                                                                                       : PaGeo<false, 256>::NB_LOG;
         if (nb_log > pa_nb_log) nb_log = pa_nb_log;
@@ -2116,7 +2119,7 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         // previous values keep every Put; otherwise a Put overwritten later in its tile is dropped
         // when the key stream is skewed (uniform streams have next to no such Puts: no LDS hash)
         // (the last round of every skew-sample window deduplicates too: it measures the skew)
-        L.ix = want_prev ? IX_PART_ALL : (c->skewed || c->dup_rounds + 1 >= c->dup_every) ? IX_PART : IX_PART_NODUP;
+        L.ix = want_prev ? IX_PART_ALL : (c->hm.skewed || c->hm.dup_rounds + 1 >= c->hm.dup_every) ? IX_PART : IX_PART_NODUP;
         measured = L.ix == IX_PART;
         L.K1 = K1;
         L.nb = 1u << nb_log;
@@ -2127,11 +2130,11 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         ij.nblocks = (u32)((n + tile - 1) / tile);
         ij.nb_log = nb_log;
         ij.bk_shift = log2_slots - nb_log;
-        ij.ent = (u64x2*)c->d_bk_ent;
-        ij.eidx = want_prev ? c->d_bk_idx : nullptr;
-        ij.cnt = c->d_bk_cnt;
+        ij.ent = (u64x2*)c->hm.d_bk_ent;
+        ij.eidx = want_prev ? c->hm.d_bk_idx : nullptr;
+        ij.cnt = c->hm.d_bk_cnt;
         ij.exp = 0;
-        ij.dup_acc = c->d_dup + (c->dup_seq & 1) * HM_DUP_SLOTS;
+        ij.dup_acc = c->hm.d_dup + (c->hm.dup_seq & 1) * HM_DUP_SLOTS;
         attach_deferred(c, L);  // the previous round's apply and reads ride along (partition only reads)
         if ((e = launch(c, L)) != hipSuccess) return e;
         PApplyJob aj{};
@@ -2141,11 +2144,11 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         aj.ntiles = ij.nblocks;
         aj.tile = tile;
         aj.nb = 1u << nb_log;
-        aj.table = c->d_table;
-        aj.shift = c->slot_shift;
-        aj.tmask = c->slots - 1;
+        aj.table = c->hm.d_table;
+        aj.shift = c->hm.slot_shift;
+        aj.tmask = c->hm.slots - 1;
         aj.ctl = c->d_ctl;
-        aj.created_acc = c->d_created;
+        aj.created_acc = c->hm.d_created;
         aj.lo = lo;
         aj.resp_lo = resp_lo;
         aj.resp_hi = resp_hi;
@@ -2173,18 +2176,18 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         L.sj.n = n;
         L.sj.nblocks = (u32)((n + tile - 1) / tile);
         L.sj.epoch = epoch;
-        L.sj.put_slot = c->d_put_slot[epoch & 1];
-        L.sj.win = L.sj.put_slot + c->stamp_alloc;
-        L.sj.over = L.sj.put_slot + 2 * c->stamp_alloc;
-        L.sj.created_acc = c->d_created;
-        L.sj.dup_acc = c->d_dup + (c->dup_seq & 1) * HM_DUP_SLOTS;
+        L.sj.put_slot = c->hm.d_put_slot[epoch & 1];
+        L.sj.win = L.sj.put_slot + c->hm.stamp_alloc;
+        L.sj.over = L.sj.put_slot + 2 * c->hm.stamp_alloc;
+        L.sj.created_acc = c->hm.d_created;
+        L.sj.dup_acc = c->hm.d_dup + (c->hm.dup_seq & 1) * HM_DUP_SLOTS;
         attach_deferred(c, L);
         if ((e = launch(c, L)) != hipSuccess) return e;
     }
     c->rounds++;
-    if (measured) c->dup_puts += n;  // the skew ratio is over the rounds that measured it
-    if (++c->dup_rounds >= c->dup_every && (e = skew_sample(c)) != hipSuccess) return e;
-    HmDeferred& p = c->pend;
+    if (measured) c->hm.dup_puts += n;  // the skew ratio is over the rounds that measured it
+    if (++c->hm.dup_rounds >= c->hm.dup_every && (e = skew_sample(c)) != hipSuccess) return e;
+    HmDeferred& p = c->hm.pend;
     p.valid = true;
     p.epoch = epoch;
     p.apply = stamp;
@@ -2199,7 +2202,7 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
     return hipSuccess;
 }
 
-hipError_t hm_get_only(nrg_ctx* c, const u64* d_keys, u64 n, u64* d_vals, uint8_t* d_found) {
+static hipError_t hm_get_only(nrg_ctx* c, const u64* d_keys, u64 n, u64* d_vals, uint8_t* d_found) {
     return hm_reads(c, d_keys, n, d_vals, d_found);
 }
 
@@ -2210,8 +2213,53 @@ static hipError_t hm_replay(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp
                            (u64*)d_resp, d_some);
 }
 
+// A deferred stamp round's apply and reads take values from the ring: the log is held back to its
+// first record.
+static u64 hm_floor(const nrg_ctx* c) {
+    const HmDeferred& p = c->hm.pend;
+    if (p.valid && p.apply && !p.src && p.lo < c->ltail) return p.lo;
+    return c->ltail;
+}
+
+static int hm_set_knob(nrg_ctx* c, int knob, uint64_t v) {
+    switch (knob) {
+        case NRG_KNOB_STAMP_MAX:
+            c->hm.stamp_max = std::min<uint64_t>(v, c->hm.stamp_alloc);
+            return NRG_OK;
+        case NRG_KNOB_SKEW_EVERY:
+            if (v < 1 || v > (1u << 30)) return NRG_E_INVAL;
+            c->hm.dup_every = (uint32_t)v;
+            return NRG_OK;
+        case NRG_KNOB_EPOCH_LIMIT:
+            if (v < 2 || v > 0xFFFFFFF0ull) return NRG_E_INVAL;
+            c->hm.epoch_limit = (uint32_t)v;
+            return NRG_OK;
+        case NRG_KNOB_K1:
+            if (v > 4) return NRG_E_INVAL;
+            c->hm.k1_items = (uint32_t)v;
+            return NRG_OK;
+        case NRG_KNOB_PART:
+            if (v > 2) return NRG_E_INVAL;  // 0: partition rounds only where stamp rounds cannot
+            c->hm.part_mode = (uint32_t)v;
+            return NRG_OK;
+        case NRG_KNOB_PA_TPB:
+            if (v != 0 && v != 256 && v != 512 && v != 1024) return NRG_E_INVAL;
+            c->hm.pa_tpb = (uint32_t)v;
+            return NRG_OK;
+        case NRG_KNOB_SMALL_MAX:
+            if (v > 2048) return NRG_E_INVAL;
+            c->hm.small_max = v;
+            return NRG_OK;
+        default: return NRG_E_INVAL;
+    }
+}
+
+// NRG_KNOB_EXP bit 2: 8 words per partition-round apply bucket
+static u64 hm_dbg_words(const nrg_ctx*) { return (u64)HM_BK_MAX * 8; }
+
 const DsOps* hm_ops() {
-    static const DsOps ops = {sizeof(nrg_put), sizeof(u64), hm_open, hm_close, hm_flush, hm_replay};
+    static const DsOps ops = {sizeof(nrg_put), sizeof(u64), hm_open, hm_close, hm_flush, hm_replay,
+                              hm_floor, hm_set_knob, hm_dbg_words, nullptr};
     return &ops;
 }
 
@@ -2220,38 +2268,38 @@ hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part, u32 parts) {
     if (e != hipSuccess) return e;
     // room for the keys first (growth enabled): all n, or a key partition's exact share of them
     u64 mine = n;
-    if (parts > 1 && c->grow_max_log2 > 64 - c->slot_shift) {
+    if (parts > 1 && c->hm.grow_max_log2 > 64 - c->hm.slot_shift) {
         mine = 0;
         for (u64 k = 0; k < n; k++) mine += key_owner(k, parts) == part;
     }
     if ((e = hm_room(c, mine)) != hipSuccess) return e;
-    hm_prefill_range_kernel<<<grid_for(n, 8192), TPB, 0, c->stream>>>(c->d_table, n, off, c->slot_shift,
-                                                                      c->slots - 1, c->d_ctl, part, parts);
+    hm_prefill_range_kernel<<<grid_for(n, 8192), TPB, 0, c->stream>>>(c->hm.d_table, n, off, c->hm.slot_shift,
+                                                                      c->hm.slots - 1, c->d_ctl, part, parts);
     return hipGetLastError();
 }
 
-hipError_t hm_count(nrg_ctx* c) {
+static hipError_t hm_count(nrg_ctx* c) {
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
-    hm_count_kernel<<<1, TPB, 0, c->stream>>>(c->d_created, HM_CREATED_SLOTS, c->d_ctl);
+    hm_count_kernel<<<1, TPB, 0, c->stream>>>(c->hm.d_created, HM_CREATED_SLOTS, c->d_ctl);
     return hipGetLastError();
 }
 
-hipError_t hm_dump(nrg_ctx* c, u64* d_keys, u64* d_vals) {
+static hipError_t hm_dump(nrg_ctx* c, u64* d_keys, u64* d_vals) {
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(&c->d_ctl->counter, 0, sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
-    hm_dump_kernel<<<grid_for(c->slots, 8192), TPB, 0, c->stream>>>(c->d_table, c->slots, c->d_ctl, d_keys, d_vals);
+    hm_dump_kernel<<<grid_for(c->hm.slots, 8192), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl, d_keys, d_vals);
     return hipGetLastError();
 }
 
-hipError_t hm_digest(nrg_ctx* c, u64* d_out3) {
+static hipError_t hm_digest(nrg_ctx* c, u64* d_out3) {
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
-    hm_digest_kernel<<<grid_for(c->slots, 8192), TPB, 0, c->stream>>>(c->d_table, c->slots, c->d_ctl, d_out3);
+    hm_digest_kernel<<<grid_for(c->hm.slots, 8192), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl, d_out3);
     return hipGetLastError();
 }
 
@@ -2272,4 +2320,213 @@ hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_strid
     return hipGetLastError();
 }
 
+// A round as nrg_hashmap_round_async would run it as a small round, its log bookkeeping done and
+// nothing launched (the combiner's round server runs it).
+int hm_small_job(nrg_ctx* c, const nrg_put* recs, u64 W, u32 origin, const u64* keys, u64 R, u64* vals,
+                 uint8_t* found, u64* prev, uint8_t* prevf, u32* e_out, SmallJobBlob* blob, u64* lo_out) {
+    if (!c || c->cfg.ds_kind != NRG_DS_HASHMAP || W > c->cfg.max_batch || c->ltail != c->tail) return NRG_E_INVAL;
+    if ((W && !recs) || (R && (!keys || !vals || !found))) return NRG_E_INVAL;
+    int r = reserve(c, W);  // (caught up and nothing deferred: only moves head, launches nothing)
+    if (r) return r == NRG_E_RING_FULL ? NRG_E_INVAL : r;  // more than the log ever holds: not a small round
+    const uint64_t lo = c->tail;
+    if (!hm_small_fill(c, recs, lo, W, keys, R, vals, found, prev, prevf, e_out, blob)) return NRG_E_INVAL;
+    // the round's Puts against the table's load limit (hm_room): a round before which the keys have
+    // to be counted or the table has to grow is not served but launched -- the combiner stops the
+    // server before any launch, and the launched round counts and grows in hm_replay_chunk
+    bool due = false;
+    if (hm_room(c, W, &due) != hipSuccess || due) return NRG_E_INVAL;
+    if (lo_out) *lo_out = lo;
+    c->rounds++;
+    if (W) note_origin(c, lo, W, origin);
+    commit_round(c, lo, W);
+    return NRG_OK;
+}
+
 }  // namespace nrg
+
+// ---- the NrHashMap entry points (include/nrgpu.h, nrgpu_testing.h) ----------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_hashmap_get_async(nrg_ctx* c, const uint64_t* d_keys, uint64_t n, uint64_t* d_vals, uint8_t* d_found) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n && (!d_keys || !d_vals || !d_found)) return NRG_E_INVAL;
+    return hip_fail(hm_get_only(c, d_keys, n, d_vals, d_found));
+}
+
+int nrg_hashmap_get(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint64_t* vals, uint8_t* found) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n == 0) return NRG_OK;
+    Staging* s = c->stg;
+    if ((r = staging(s[0], n * 8)) || (r = staging(s[1], n * 8)) || (r = staging(s[2], n))) return r;
+    HIPCHK(hipMemcpyAsync(s[0].p, keys, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hm_get_only(c, (u64*)s[0].p, n, (u64*)s[1].p, (uint8_t*)s[2].p));
+    HIPCHK(hipMemcpyAsync(vals, s[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(found, s[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_hashmap_round_async(nrg_ctx* c, const nrg_put* d_puts, uint64_t W, uint32_t origin,
+                            const uint64_t* d_get_keys, uint64_t R, uint64_t* d_get_vals, uint8_t* d_get_found,
+                            uint64_t* d_prev, uint8_t* d_prev_found) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (W > c->cfg.max_batch) return NRG_E_CAPACITY;
+    if ((W && !d_puts) || (R && (!d_get_keys || !d_get_vals || !d_get_found))) return NRG_E_INVAL;
+    // catch up on anything appended by others first (Replica::combine execs the whole log)
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    if ((r = reserve(c, W))) return r;
+    const uint64_t lo = c->tail;
+    if (!d_prev || !d_prev_found) d_prev = nullptr, d_prev_found = nullptr;
+    HIPCHK(hm_replay_chunk(c, d_puts, lo, W, true, d_get_keys, R, d_get_vals, d_get_found, lo, lo + W, d_prev,
+                           d_prev_found));
+    if (W) note_origin(c, lo, W, origin);
+    commit_round(c, lo, W);
+    return NRG_OK;
+}
+
+int nrg_hashmap_round_segments_async(nrg_ctx* c, const nrg_put* d_base, uint32_t nseg, uint64_t seg_stride,
+                                     const uint64_t* lens, const uint32_t* origins, uint32_t resp_seg,
+                                     const uint64_t* d_get_keys, uint64_t R, uint64_t* d_get_vals,
+                                     uint8_t* d_get_found, uint64_t* d_prev, uint8_t* d_prev_found) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (!lens || nseg == 0 || nseg > 64 || !d_base) return NRG_E_INVAL;
+    if (R && (!d_get_keys || !d_get_vals || !d_get_found)) return NRG_E_INVAL;
+    if (!d_prev || !d_prev_found) d_prev = nullptr, d_prev_found = nullptr;
+    uint64_t total = 0, own_off = 0;
+    bool dense = true;
+    for (uint32_t s = 0; s < nseg; s++) {
+        if (lens[s] > seg_stride) return NRG_E_INVAL;
+        if (s == resp_seg) own_off = total;
+        if (s + 1 < nseg && lens[s] != seg_stride) dense = false;
+        total += lens[s];
+    }
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    if ((r = reserve(c, total))) return r;
+    const uint64_t lo = c->tail;
+    const uint64_t rlo = resp_seg < nseg ? lo + own_off : 0;
+    const uint64_t rhi = resp_seg < nseg ? rlo + lens[resp_seg] : 0;
+    if (dense && total <= c->cfg.max_batch) {
+        // the gathered segments are already the contiguous round W_0 || W_1 || ...: replay them
+        // in place while K1 writes the log copy (no separate append pass)
+        HIPCHK(hm_replay_chunk(c, d_base, lo, total, true, d_get_keys, R, d_get_vals, d_get_found, rlo, rhi, d_prev,
+                               d_prev_found));
+        for (uint32_t s = 0, off = 0; s < nseg; off += (uint32_t)lens[s], s++)
+            if (lens[s]) note_origin(c, lo + off, lens[s], origins ? origins[s] : s + 1);
+        commit_round(c, lo, total);
+        return NRG_OK;
+    }
+    HIPCHK(copy_segments(c, d_base, nseg, seg_stride, lens, lo));
+    for (uint32_t s = 0; s < nseg; s++) {
+        if (lens[s]) note_origin(c, c->tail, lens[s], origins ? origins[s] : s + 1);
+        c->tail += lens[s];
+    }
+    // replay them and answer the reads against the final state, fused into the last chunk
+    if (c->ltail == c->tail) return hip_fail(hm_get_only(c, d_get_keys, R, d_get_vals, d_get_found));
+    const uint64_t last = c->ltail + (c->tail - c->ltail - 1) / c->cfg.max_batch * c->cfg.max_batch;
+    if ((r = exec_range(c, rlo, rhi, d_prev, d_prev_found, last))) return r;
+    HIPCHK(hm_replay_chunk(c, nullptr, last, c->tail - last, false, d_get_keys, R, d_get_vals, d_get_found, rlo, rhi,
+                           d_prev, d_prev_found));
+    commit_round(c, last, c->tail - last);
+    return NRG_OK;
+}
+
+int nrg_hashmap_prefill(nrg_ctx* c, const uint64_t* keys, const uint64_t* vals, uint64_t n) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    Staging* s = c->stg;
+    uint64_t done = 0;
+    const uint64_t chunk = c->cfg.max_batch;
+    if ((r = staging(s[0], (n < chunk ? n : chunk) * sizeof(nrg_put)))) return r;
+    while (done < n) {
+        const uint64_t m = n - done < chunk ? n - done : chunk;
+        nrg_put* h = (nrg_put*)std::malloc(m * sizeof(nrg_put));
+        if (!h) return NRG_E_NOMEM;
+        for (uint64_t i = 0; i < m; i++) h[i] = nrg_put{keys[done + i], vals[done + i]};
+        hipError_t e = hipMemcpyAsync(s[0].p, h, m * sizeof(nrg_put), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        std::free(h);
+        if (e != hipSuccess) return hip_fail(e);
+        // direct insert (no log traffic): replay the records through the round pipeline
+        // with a private log position, so duplicate keys keep last-writer-wins order.
+        HIPCHK(hm_replay_chunk(c, s[0].p, 0, m, false, nullptr, 0, nullptr, nullptr, 0, 0, nullptr, nullptr));
+        done += m;
+    }
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_hashmap_prefill_range(nrg_ctx* c, uint64_t n, uint64_t off) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    HIPCHK(hm_prefill_range(c, n, off));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+// HashMap::reserve / with_capacity (benches/hashmap.rs:91-100 pre-sizes the map; nr/examples/hashmap.rs
+// lets it grow): a table that holds n_keys keys in all at the load limit. Never shrinks.
+int nrg_hashmap_reserve(nrg_ctx* c, uint64_t n_keys) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (n_keys > (1ull << 30) / HM_GROW_SLOTS_PER_KEY) return NRG_E_INVAL;  // beyond nrg_open's largest table
+    const uint32_t want = hm_slots_for(n_keys);
+    if ((1ull << want) <= c->hm.slots) return NRG_OK;
+    HIPCHK(hm_grow(c, want));
+    return NRG_OK;
+}
+
+int nrg_hashmap_capacity(nrg_ctx* c, uint32_t* log2_slots) {
+    if (!c || !log2_slots || c->cfg.ds_kind != NRG_DS_HASHMAP) return NRG_E_INVAL;
+    *log2_slots = 64 - c->hm.slot_shift;
+    return NRG_OK;
+}
+
+int nrg_hashmap_size(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    HIPCHK(hm_count(c));
+    HIPCHK(hipMemcpyAsync(n, &c->d_ctl->nkeys_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_hashmap_dump(nrg_ctx* c, uint64_t* keys, uint64_t* vals, uint64_t cap, uint64_t* n) {
+    int r = nrg_hashmap_size(c, n);
+    if (r) return r;
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n == 0) return NRG_OK;
+    Staging* s = c->stg;
+    if ((r = staging(s[0], *n * 8)) || (r = staging(s[1], *n * 8))) return r;
+    HIPCHK(hm_dump(c, (u64*)s[0].p, (u64*)s[1].p));
+    HIPCHK(hipMemcpyAsync(keys, s[0].p, *n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(vals, s[1].p, *n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_hashmap_digest(nrg_ctx* c, uint64_t out[3]) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    Staging* s = c->stg;
+    if ((r = staging(s[3], 64))) return r;
+    HIPCHK(hm_digest(c, (u64*)s[3].p));
+    HIPCHK(hipMemcpyAsync(out, s[3].p, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_test_hm_skewed(nrg_ctx* c, int* out) {
+    if (!c || !out || c->cfg.ds_kind != NRG_DS_HASHMAP) return NRG_E_INVAL;
+    *out = c->hm.skewed ? 1 : 0;
+    return NRG_OK;
+}
+
+}  // extern "C"

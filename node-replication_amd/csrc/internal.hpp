@@ -1,4 +1,7 @@
-// internal.hpp — host-side structures shared by the runtime and the kernel launchers.
+// internal.hpp — what the host-side files share: the context (nrg_ctx: the log and what every kind
+// uses, plus one state struct per owner, each touched by its owner's file alone), each kind's ops
+// table (DsOps), the runtime helpers the structures' entry points use, and the few functions one
+// structure's file uses of another's.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -105,15 +108,115 @@ struct HostRun {  // origin tags of appended log ranges (the Entry::replica fiel
     u32 origin;
 };
 
+// ---- Host state of each owner, embedded in nrg_ctx. Only the owner's file touches its struct
+// ---- (and allocates and frees its buffers); the runtime touches none of them.
+
+struct HmHost {  // NrHashMap (hashmap.hip)
+    uint32_t slot_shift = 0;  // 64 - log2_slots
+    uint64_t slots = 0;
+    Slot* d_table = nullptr;
+    // Table growth (hm_room / hm_grow): the table may grow to 2^grow_max_log2 slots (0: fixed);
+    // keys_ub bounds the key count from above: the exact count when it was last taken plus every
+    // Put replayed and every key prefilled since.
+    uint32_t grow_max_log2 = 0;
+    uint64_t keys_ub = 0;
+    uint32_t k1_items = 0;  // Puts per index thread (0: by round size; NRG_KNOB_K1)
+    // Reads of the last replayed round: answered in the next launch beside the next round's
+    // index pass, or by nrg_join / nrg_sync / any call that reads the table. With
+    // pipeline == false they are flushed at the end of every call.
+    HmDeferred pend;
+    uint64_t small_max = 0;         // rounds of <= small_max Puts take the one-launch small round
+    uint64_t* d_created = nullptr;  // [HM_CREATED_SLOTS] keys created by replay rounds
+    void* d_bk_ent = nullptr;       // partition rounds: [tiles][tile] 16-B {key, value} entries
+    uint32_t* d_bk_idx = nullptr;   // partition rounds with previous values: [tiles][tile] round offset
+    uint32_t* d_bk_cnt = nullptr;   // [index tiles][bucket] offset << 16 | count
+    // Stamp rounds (<= stamp_max Puts, no previous values): per-Put slot ids by epoch parity.
+    uint64_t stamp_max = 0;
+    // Partition rounds (part_role + hm_papply_kernel), NRG_KNOB_PART: 1 (default) for previous
+    // values, skewed streams and rounds of >= 393216 Puts; 2 for every round; 0 only where a stamp
+    // round cannot (previous values, skew).
+    uint32_t part_mode = 1;
+    uint32_t pa_tpb = 0;       // NRG_KNOB_PA_TPB: partition-round apply workgroup width (0 = by round)
+    uint64_t stamp_alloc = 0;  // Puts the put_slot arrays hold (stamp_max <= stamp_alloc)
+    uint32_t epoch = 1;        // epoch of the last replay round (1: prefill / before any round)
+    uint32_t epoch_limit = 0xFFFFFFF0u;  // renormalise stamps here (NRG_KNOB_EPOCH_LIMIT for tests)
+    uint32_t* d_put_slot[2] = {nullptr, nullptr};
+    // Key skew (hm_dup_sample_kernel): Puts combined inside their index block, sampled every
+    // dup_every rounds into mapped host memory; a skewed stream takes partition rounds.
+    uint64_t* d_dup = nullptr;           // [HM_DUP_SLOTS]
+    volatile uint64_t* h_dup = nullptr;  // {seq, dups}, mapped pinned host memory
+    uint64_t* h_dup_dev = nullptr;       // its device address
+    uint64_t dup_seq = 0, dup_puts = 0, dup_puts_sampled = 0;
+    uint64_t sample_seq = 0;      // a sample the next hm_round launch takes (0: none pending)
+    uint32_t* err_out = nullptr;  // the next hm_round launch copies (and clears) the error latch here
+    uint32_t dup_rounds = 0, dup_every = 16;
+    bool skewed = false;
+};
+
+struct StHost {  // stack (stack.hip)
+    uint32_t* d_stack = nullptr;
+    void* d_aux = nullptr;       // per-tile minima, last-Push tables and cross-tile Pops
+    StDeferred pend;             // the last chunk's finish, if deferred
+    uint32_t par = 0;            // buffer parity of the next chunk
+    uint32_t* d_desc = nullptr;  // look-back descriptors of both parities (st_desc_words)
+    uint64_t desc_words = 0;
+};
+
+struct SyHost {  // synthetic (synthetic.hip)
+    uint64_t* d_words = nullptr;
+    uint64_t* d_sort_aux = nullptr;  // per-touch max-scan output
+    uint32_t key_bits = 0;
+    void* d_aux = nullptr;       // bucket replay scratch; nullptr: sort path
+    SyDeferred pend;             // the chunk whose sums are deferred, if any
+    SyDeferred pend_b;           // one launch per round: the chunk whose bucket pass is deferred
+    bool fused = true;           // one launch per round, chunks three deep (NRG_KNOB_SY_FUSED)
+    uint32_t round = 0;          // chunks replayed (the chunk epoch: scratch slots, 32-bit seen values)
+    uint64_t* d_tmp = nullptr;   // expand / sort scratch (max_batch * touches words)
+    uint32_t* d_desc = nullptr;  // look-back descriptors of the max-scan
+    uint64_t desc_words = 0;
+};
+
+struct QuHost {  // FIFO queue (queue.hip)
+    uint64_t* d_queue = nullptr;  // ring of `size` (power of two >= capacity + max_batch) values
+    uint64_t size = 0;
+    QuState* d_state = nullptr;
+    void* d_aux = nullptr;  // per-tile aggregates and scanned starts
+};
+
+struct VsHost {  // page table (vspace.hip)
+    uint64_t* d_pool = nullptr;  // `cap` tables of 512 entries; table 0 is the PML4
+    uint64_t cap = 0;
+    VsState* d_state = nullptr;
+    void* d_aux = nullptr;  // per-op scratch of one chunk
+};
+
+struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*
+    int32_t spin = -1;    // -1 = default
+    uint32_t depth = 0;   // 0 = default
+    int32_t gather = -1;  // us; -1 = default
+    int32_t serve = -1;   // -1 = default: on
+};
+
+struct PtHost {  // key partitioning (partition.hip): tile counts / offsets, grown on demand
+    void* d_buf = nullptr;
+    uint64_t words = 0;
+};
+
+struct GenHost {  // workload generators (workload.hip): zeta(zipf_n, zipf_theta)
+    uint64_t zipf_n = 0;
+    double zipf_theta = 0.0, zipf_zetan = 0.0;
+};
+
 // What the runtime knows about a data structure: one table per kind, defined beside the
-// structure's launchers (hashmap.hip, stack.hip, synthetic.hip, queue.hip, vspace.hip).
+// structure's launchers and entry points (hashmap.hip, stack.hip, synthetic.hip, queue.hip,
+// vspace.hip).
 struct DsOps {
     uint32_t rec_bytes;   // one log record
     uint32_t resp_bytes;  // one write response
     // validate c->cfg, allocate and initialise the structure; an NRG_* code (nrg_open closes the
     // context on failure, so nothing is released here)
     int (*open)(nrg_ctx* c);
-    // free what open, and growth since, allocated
+    // free what open, and growth since, allocated; the context may be half-opened
     void (*close)(nrg_ctx* c);
     // launch the work the last replayed chunk deferred, if any
     hipError_t (*flush)(nrg_ctx* c);
@@ -122,12 +225,23 @@ struct DsOps {
     // into d_resp / d_some (nullptr: none wanted)
     hipError_t (*replay)(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                          uint8_t* d_some);
+    // the lowest log position the kind's deferred work still reads from the ring (<= ltail): the
+    // log is collected up to here
+    u64 (*floor)(const nrg_ctx* c);
+    // nrg_test_set_knob for a knob the runtime does not own: NRG_OK, or NRG_E_INVAL for a knob the
+    // kind does not have or a value out of range (nullptr: the kind has no knobs)
+    int (*set_knob)(nrg_ctx* c, int knob, uint64_t v);
+    // u64 words of the timestamp buffer NRG_KNOB_EXP bit 2 needs (nullptr: the kind stamps nothing)
+    u64 (*dbg_words)(const nrg_ctx* c);
+    // where the kind's nrg_config defaults differ from the common ones (nullptr: nowhere)
+    void (*defaults)(nrg_config* cfg);
 };
 const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
 
 }  // namespace nrg
 
+// What every kind uses stays here; the rest is its owner's struct.
 struct nrg_ctx {
     int device = 0;
     nrg_config cfg{};
@@ -144,96 +258,23 @@ struct nrg_ctx {
 
     nrg::DevCtl* d_ctl = nullptr;
 
-    // ---- NrHashMap ----
-    uint32_t slot_shift = 0;  // 64 - log2_slots
-    uint64_t slots = 0;
-    nrg::Slot* d_table = nullptr;
-    // Table growth (hashmap.hip hm_room / hm_grow): the table may grow to 2^grow_max_log2 slots
-    // (0: fixed); keys_ub bounds the key count from above: the exact count when it was last taken
-    // plus every Put replayed and every key prefilled since.
-    uint32_t grow_max_log2 = 0;
-    uint64_t keys_ub = 0;
-    uint64_t rounds = 0;            // replay rounds launched (statistics)
-    // tuning and diagnostic knobs: set only through nrg_test_set_knob (include/nrgpu_testing.h)
-    uint32_t k1_items = 0;           // Puts per index thread (0: by round size; NRG_KNOB_K1)
-    uint32_t exp = 0;                // diagnostic bits (NRG_KNOB_EXP; see hashmap.hip StampJob)
-    // Reads of the last replayed round: answered in the next launch beside the next round's
-    // index pass, or by nrg_join / nrg_sync / any call that reads the table. With
-    // pipeline == false they are flushed at the end of every call.
-    bool pipeline = false;
-    nrg::HmDeferred pend;
-    nrg::StDeferred st_pend;  // stack: the last chunk's finish, if deferred
-    uint32_t st_par = 0;      // stack: buffer parity of the next chunk
-    nrg::SyDeferred sy_pend;    // synthetic: the chunk whose sums are deferred, if any
-    nrg::SyDeferred sy_pend_b;  // synthetic, one launch per round: the chunk whose bucket pass is deferred
-    bool sy_fused = true;       // synthetic: one launch per round, chunks three deep (NRG_KNOB_SY_FUSED)
-    uint32_t sy_round = 0;      // synthetic: chunks replayed (the chunk epoch: scratch slots, 32-bit seen values)
-    int32_t comb_spin = -1;   // combiner knobs (NRG_KNOB_COMB_SPIN / _DEPTH): -1 / 0 = defaults
-    uint64_t small_max = 0;   // hashmap: rounds of <= small_max Puts take the one-launch small round
-    uint32_t comb_depth = 0;
-    int32_t comb_gather = -1;  // NRG_KNOB_COMB_GATHER (us; -1 = default)
-    int32_t comb_serve = -1;   // NRG_KNOB_COMB_SERVE (-1 = default: on)
-    uint32_t stall = 0;       // NRG_KNOB_STALL (tests): 1 odd waves sleep at LDS reuse points, 2 (synthetic,
-                              // diagnostic: wrong results) without the bucket pass's tile-map barrier
-    uint64_t* d_created = nullptr;  // [HM_CREATED_SLOTS] keys created by replay rounds
-    void* d_bk_ent = nullptr;       // partition rounds: [tiles][tile] 16-B {key, value} entries
-    uint32_t* d_bk_idx = nullptr;   // partition rounds with previous values: [tiles][tile] round offset
-    uint32_t* d_bk_cnt = nullptr;   // [index tiles][bucket] offset << 16 | count
-    // Stamp rounds (<= stamp_max Puts, no previous values): per-Put slot ids by epoch parity.
-    uint64_t stamp_max = 0;
-    // Partition rounds (hashmap.hip part_role + hm_papply_kernel), NRG_KNOB_PART: 1 (default) for
-    // previous values, skewed streams and rounds of >= 393216 Puts; 2 for every round; 0 only
-    // where a stamp round cannot (previous values, skew).
-    uint32_t part_mode = 1;
-    uint32_t pa_tpb = 0;      // NRG_KNOB_PA_TPB: partition-round apply workgroup width (0 = by round)
-    uint64_t stamp_alloc = 0;  // Puts the put_slot arrays hold (stamp_max <= stamp_alloc)
-    uint32_t epoch = 1;  // epoch of the last replay round (1: prefill / before any round)
-    uint32_t epoch_limit = 0xFFFFFFF0u;  // renormalise stamps here (NRG_KNOB_EPOCH_LIMIT for tests)
-    uint32_t* d_put_slot[2] = {nullptr, nullptr};
-    // Key skew (hm_dup_sample_kernel): Puts combined inside their index block, sampled every
-    // dup_every rounds into mapped host memory; a skewed stream takes partition rounds.
-    uint64_t* d_dup = nullptr;            // [HM_DUP_SLOTS]
-    void* d_pt = nullptr;                 // partition.hip tile counts / offsets
-    uint64_t pt_words = 0;
-    volatile uint64_t* h_dup = nullptr;   // {seq, dups}, mapped pinned host memory
-    uint64_t* h_dup_dev = nullptr;        // its device address
-    uint64_t dup_seq = 0, dup_puts = 0, dup_puts_sampled = 0;
-    uint64_t sample_seq = 0;  // a sample the next hm_round launch takes (0: none pending)
-    uint32_t* err_out = nullptr;  // the next hm_round launch copies (and clears) the error latch here
-    uint32_t dup_rounds = 0, dup_every = 16;
-    bool skewed = false;
-    // Zipf generator cache: zeta(zipf_n, zipf_theta)
-    uint64_t zipf_n = 0;
-    double zipf_theta = 0.0, zipf_zetan = 0.0;
-    // ---- Stack ----
-    uint32_t* d_stack = nullptr;
-    void* d_st_aux = nullptr;  // per-tile minima, last-Push tables and cross-tile Pops (stack.hip)
+    uint64_t rounds = 0;  // replay rounds launched (statistics)
+    // set only through nrg_test_set_knob (include/nrgpu_testing.h)
+    uint32_t exp = 0;       // diagnostic bits (NRG_KNOB_EXP; see hashmap.hip StampJob)
+    bool pipeline = false;  // a chunk's deferred work waits for the next launch, nrg_join or a sync
+    uint32_t stall = 0;     // NRG_KNOB_STALL (tests): 1 odd waves sleep at LDS reuse points, 2 (synthetic,
+                            // diagnostic: wrong results) without the bucket pass's tile-map barrier
 
-    // ---- Synthetic ----
-    uint64_t* d_words = nullptr;
-    uint64_t* d_sort_aux = nullptr;  // per-touch max-scan output
-    uint32_t synth_key_bits = 0;
-    void* d_sy_aux = nullptr;  // bucket replay scratch (synthetic.hip); nullptr: sort path
+    nrg::HmHost hm;
+    nrg::StHost st;
+    nrg::SyHost sy;
+    nrg::QuHost qu;
+    nrg::VsHost vs;
+    nrg::CombKnobs comb;
+    nrg::PtHost pt;
+    nrg::GenHost gen;
 
-    // ---- Queue ----
-    uint64_t* d_queue = nullptr;          // ring of qu_size (power of two >= capacity + max_batch) values
-    uint64_t qu_size = 0;
-    nrg::QuState* d_qu_state = nullptr;
-    void* d_qu_aux = nullptr;             // per-tile aggregates and scanned starts (queue.hip)
-
-    // ---- VSpace ----
-    uint64_t* d_vs_pool = nullptr;        // vs_cap tables of 512 entries; table 0 is the PML4
-    uint64_t vs_cap = 0;
-    nrg::VsState* d_vs_state = nullptr;
-    void* d_vs_aux = nullptr;             // per-op scratch of one chunk (vspace.hip)
-
-    // ---- shared scratch ----
-    nrg::SortScratch sort;
-    uint64_t* d_tmp_u64 = nullptr;  // general scratch (max_batch words)
-    uint64_t tmp_words = 0;
-    uint32_t* d_scan_desc = nullptr;  // decoupled look-back descriptors for scans
-    uint64_t scan_desc_words = 0;
-
+    nrg::SortScratch sort;  // allocated by the synthetic's open, or on demand (nrg_test_sort_pairs)
     nrg::Staging stg[4];
     uint64_t* d_dbg = nullptr;  // diagnostic phase timestamps (NRG_KNOB_EXP), [tiles][16]
     uint64_t dbg_words = 0;     // u64 words d_dbg holds
@@ -266,6 +307,25 @@ bool timer_events(nrg_ctx* c, const char* name, hipEvent_t* start, hipEvent_t* s
 // make the context's device current for this thread (runtime.cpp; cached per thread)
 int ctx_use_device(nrg_ctx* c);
 
+// ---- what the structures' entry points use of the runtime (runtime.cpp) ----
+// NRG_E_INVAL unless c is a context of `kind`; then its device is made current
+int need(nrg_ctx* c, uint32_t kind);
+hipError_t flush_deferred(nrg_ctx* c);  // launch what the last chunk deferred
+hipError_t sync_all(nrg_ctx* c);        // flush_deferred and wait for the stream
+int check_err(nrg_ctx* c);              // read and clear the device's error latch: an NRG_* code
+// device scratch of the host-pointer entry points: grow slot st to `bytes`
+int staging(Staging& st, uint64_t bytes);
+// replay [ltail, min(tail, end)) in chunks of at most max_batch records
+int exec_range(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_resp, uint8_t* d_some, uint64_t end = ~0ull);
+int reserve(nrg_ctx* c, uint64_t n);  // room for n records (Log::append's GC path)
+void note_origin(nrg_ctx* c, uint64_t first, uint64_t n, uint32_t origin);
+void commit_round(nrg_ctx* c, uint64_t lo, uint64_t n);  // [lo, lo + n) appended and replayed
+// Replica::combine for one batch of a kind whose rounds carry no reads: one replay pass that also
+// writes the log copy
+int round_common(nrg_ctx* c, uint32_t kind, const void* d_ops, uint64_t n, uint32_t origin, void* d_resp,
+                 uint8_t* d_some);
+inline u64 floor_ltail(const nrg_ctx* c) { return c->ltail; }  // DsOps::floor of a kind that defers no ring reads
+
 inline int hip_fail(hipError_t e) {
     if (e == hipSuccess) return NRG_OK;
     if (e == hipErrorOutOfMemory) return NRG_E_NOMEM;
@@ -283,25 +343,17 @@ inline uint64_t pow2_at_least(uint64_t x) {
     return p;
 }
 
+// ---- what one file uses of another ----
 // hashmap.hip
 hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool write_ring,
                            const u64* d_get_keys, u64 R, u64* d_get_vals, uint8_t* d_get_found,
                            u64 resp_lo, u64 resp_hi, u64* d_prev, uint8_t* d_prev_found);
-hipError_t hm_get_only(nrg_ctx* c, const u64* d_keys, u64 n, u64* d_vals, uint8_t* d_found);
 hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part = 0, u32 parts = 1);
 // Table growth. hm_room: every path calls it before it replays n Puts (or prefills n keys): it adds
 // them to keys_ub and, when the load limit could be passed, counts the keys and grows the table
 // (synchronously). With `due` given it launches nothing: when a count or a grow would be needed it
 // sets *due, accounts nothing and returns (the combiner's round server must stop first).
-// hm_grow: rehash into a table of 2^new_log2_slots slots (larger than the current one);
-// hipErrorOutOfMemory leaves the old table installed and the replica as it was.
-// hm_slots_for: log2 of the smallest table that holds `keys` keys at the load limit.
 hipError_t hm_room(nrg_ctx* c, u64 n, bool* due = nullptr);
-hipError_t hm_grow(nrg_ctx* c, u32 new_log2_slots);
-u32 hm_slots_for(u64 keys);
-// partition.hip: stable partition of records (key in word 0) by key owner; answers routed back
-hipError_t pt_partition(nrg_ctx* c, const u64* in, u64 n, u32 words, u32 parts, u64* out, u32* pos, u64* total);
-hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, const u32* pos, u64 n, u64* dst, uint8_t* dst8);
 // the flat combiner's round server (hashmap.hip hm_serve_kernel), in mapped host memory
 // The host's words and the device's sit on separate 128-B lines: the GPU's L2 keeps host memory
 // lines it has written, and a poll of a word on a line the server itself dirtied read that stale
@@ -322,7 +374,7 @@ struct SmallJobBlob {  // one small round's job (hashmap.hip SmallJob)
 };
 bool hm_small_fill(nrg_ctx* c, const nrg_put* recs, u64 lo, u64 W, const u64* keys, u64 R, u64* vals, uint8_t* found,
                    u64* prev, uint8_t* prevf, u32* e_out, SmallJobBlob* blob);
-// runtime.cpp: a round as nrg_hashmap_round_async would run it as a small round, its log bookkeeping
+// a round as nrg_hashmap_round_async would run it as a small round, its log bookkeeping
 // done and nothing launched (the server runs it); *lo = its first log position. NRG_E_INVAL: not a
 // small round of a caught-up replica. blob (optional): the round's whole job.
 int hm_small_job(nrg_ctx* c, const nrg_put* recs, u64 W, u32 origin, const u64* keys, u64 R, u64* vals,
@@ -340,30 +392,10 @@ u64 pt_desc_words(u64 W, u64 R, u32 parts);
 hipError_t pt_route2(hipStream_t s, const u64* src_a, const uint8_t* src8_a, const u32* pos_a, u64 n_a, u64* dst_a,
                      uint8_t* dst8_a, const u64* src_b, const uint8_t* src8_b, const u32* pos_b, u64 n_b, u64* dst_b,
                      uint8_t* dst8_b);
-hipError_t hm_dump(nrg_ctx* c, u64* d_keys, u64* d_vals);
-hipError_t hm_count(nrg_ctx* c);  // DevCtl::nkeys_total = number of keys
-hipError_t hm_digest(nrg_ctx* c, u64* d_out3);
-hipError_t gen_uniform(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 span);
-hipError_t gen_raw(nrg_ctx* c, u64* d, u64 n, u64 seed);
-hipError_t gen_puts(nrg_ctx* c, nrg_put* d, const u64* k, const u64* v, u64 n);
-// workload.hip (also holds the three generators above)
-hipError_t gen_stack_ops(nrg_ctx* c, nrg_stack_op* d, u64 n, u64 seed);
-hipError_t gen_zipf(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 N, double theta, int scramble);
+void pt_close(nrg_ctx* c);  // partition.hip: free the partition scratch (the hashmap's close)
+// hashmap.hip: the log's segment copy (nrg_log_append_segments_async)
 hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_stride, const u64* lens,
                          u64 dst_lo);
-
 // queue.hip
-hipError_t qu_init_range(nrg_ctx* c, u64 n);  // values 0..n-1, front first
-hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads
-
-// vspace.hip
-hipError_t vs_resolve(nrg_ctx* c, const u64* d_va, u64 n, u64* d_pa, uint8_t* d_found);  // n Identify reads
-
-// synthetic.hip
-hipError_t sy_read(nrg_ctx* c, const nrg_synth_rd* d_ops, u64 n, u64* d_sums);
-bool sy_bucket_eligible(const nrg_config& cf);  // configs the sort-free bucket replay handles
-u64 sy_bucket_aux_bytes(const nrg_config& cf);  // size of nrg_ctx::d_sy_aux
-hipError_t sy_aux_init(nrg_ctx* c);              // after (re)allocating d_sy_aux
-hipError_t sy_maxscan(nrg_ctx* c, const u32* sk, const u32* sv, u64 n, u32* M);
-hipError_t sy_lds_add_order(nrg_ctx* c, u32 K, u32 trials, u32 blocks, u64* d_out);
+hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads (the combiner)
 }  // namespace nrg

@@ -393,25 +393,32 @@ u64 pt_desc_words(u64 W, u64 R, u32 parts) {
 // Scratch for the tile counts and offsets, grown on demand (the replica's stream is drained
 // before a reallocation).
 static hipError_t pt_scratch(nrg_ctx* c, u64 words) {
-    if (c->pt_words >= words) return hipSuccess;
+    if (c->pt.words >= words) return hipSuccess;
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return e;
-    if (c->d_pt) (void)hipFree(c->d_pt);
-    c->d_pt = nullptr;
-    c->pt_words = 0;
-    if ((e = hipMalloc(&c->d_pt, words * sizeof(u32))) != hipSuccess) return e;
-    c->pt_words = words;
+    if (c->pt.d_buf) (void)hipFree(c->pt.d_buf);
+    c->pt.d_buf = nullptr;
+    c->pt.words = 0;
+    if ((e = hipMalloc(&c->pt.d_buf, words * sizeof(u32))) != hipSuccess) return e;
+    c->pt.words = words;
     return hipSuccess;
 }
 
-hipError_t pt_partition(nrg_ctx* c, const u64* in, u64 n, u32 words, u32 parts, u64* out, u32* pos, u64* total) {
+void pt_close(nrg_ctx* c) {
+    if (c->pt.d_buf) (void)hipFree(c->pt.d_buf);
+    c->pt.d_buf = nullptr;
+    c->pt.words = 0;
+}
+
+// stable partition of records (key in word 0) by key owner
+static hipError_t pt_partition(nrg_ctx* c, const u64* in, u64 n, u32 words, u32 parts, u64* out, u32* pos, u64* total) {
     if (parts == 0 || parts > PT_MAX_PARTS) return hipErrorInvalidValue;
     if (n == 0) return hipMemsetAsync(total, 0, parts * sizeof(u64), c->stream);
     const u64 ntiles = (n + PT_TILE - 1) / PT_TILE;
     if (ntiles > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
     hipError_t e = pt_scratch(c, 2 * ntiles * parts);
     if (e != hipSuccess) return e;
-    u32* tcnt = (u32*)c->d_pt;
+    u32* tcnt = (u32*)c->pt.d_buf;
     u32* toff = tcnt + ntiles * parts;
     pt_count_kernel<<<(unsigned)ntiles, PT_TPB, 0, c->stream>>>(in, n, words, parts, tcnt);
     pt_scan_kernel<<<parts, PT_TPB, 0, c->stream>>>(tcnt, (u32)ntiles, parts, toff, total);
@@ -419,7 +426,7 @@ hipError_t pt_partition(nrg_ctx* c, const u64* in, u64 n, u32 words, u32 parts, 
     return hipGetLastError();
 }
 
-hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, const u32* pos, u64 n, u64* dst, uint8_t* dst8) {
+static hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, const u32* pos, u64 n, u64* dst, uint8_t* dst8) {
     if (n == 0) return hipSuccess;
     const u64 blocks = (n + PT_TPB - 1) / PT_TPB;
     pt_gather_kernel<<<(unsigned)(blocks < 4096 ? blocks : 4096), PT_TPB, 0, c->stream>>>(src, src8, pos, n, dst, dst8);
@@ -427,3 +434,45 @@ hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, const u32*
 }
 
 }  // namespace nrg
+
+// ---- the key-partitioning entry points (include/nrgpu.h) -------------------------
+using namespace nrg;
+
+extern "C" {
+
+uint32_t nrg_key_owner(uint64_t key, uint32_t parts) { return parts ? nrg::key_owner(key, parts) : 0u; }
+
+int nrg_hashmap_partition_async(nrg_ctx* c, const nrg_put* d_puts, uint64_t W, const uint64_t* d_keys, uint64_t R,
+                                uint32_t parts, nrg_put* d_puts_out, uint32_t* d_put_pos, uint64_t* d_keys_out,
+                                uint32_t* d_get_pos, uint64_t* d_counts) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (parts == 0 || parts > NRG_MAX_PARTS || !d_counts) return NRG_E_INVAL;
+    if ((W && (!d_puts || !d_puts_out || !d_put_pos)) || (R && (!d_keys || !d_keys_out || !d_get_pos)))
+        return NRG_E_INVAL;
+    if (W >= (1ull << 32) || R >= (1ull << 32)) return NRG_E_CAPACITY;
+    HIPCHK(pt_partition(c, (const u64*)d_puts, W, 2, parts, (u64*)d_puts_out, d_put_pos, d_counts));
+    HIPCHK(pt_partition(c, d_keys, R, 1, parts, d_keys_out, d_get_pos, d_counts + parts));
+    return NRG_OK;
+}
+
+int nrg_route_back_async(nrg_ctx* c, const uint64_t* d_src, const uint8_t* d_src8, const uint32_t* d_pos, uint64_t n,
+                         uint64_t* d_dst, uint8_t* d_dst8) {
+    if (!c) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    if (n && (!d_pos || (d_dst && !d_src) || (d_dst8 && !d_src8))) return NRG_E_INVAL;
+    HIPCHK(pt_gather(c, d_src, d_src8, d_pos, n, d_dst, d_dst8));
+    return NRG_OK;
+}
+
+int nrg_hashmap_prefill_partition(nrg_ctx* c, uint64_t n, uint64_t off, uint32_t part, uint32_t parts) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (parts == 0 || parts > NRG_MAX_PARTS || part >= parts) return NRG_E_INVAL;
+    HIPCHK(hm_prefill_range(c, n, off, part, parts));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+}  // extern "C"

@@ -366,12 +366,12 @@ static hipError_t qu_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     j.rhi = want ? resp_hi : 0;
     j.resp = want ? (u64*)d_resp : nullptr;
     j.some = want ? d_some : nullptr;
-    j.q = c->d_queue;
-    j.qmask = c->qu_size - 1;
+    j.q = c->qu.d_queue;
+    j.qmask = c->qu.size - 1;
     j.cap = c->cfg.queue_capacity;
-    j.st = c->d_qu_state;
+    j.st = c->qu.d_state;
     j.tiles = (u32)((n + QU_TILE - 1) / QU_TILE);
-    j.agg = (QuAgg*)c->d_qu_aux;
+    j.agg = (QuAgg*)c->qu.d_aux;
     j.start = (QuStart*)(j.agg + qu_max_tiles(c->cfg.max_batch));
     j.ctl = c->d_ctl;
     j.stall = c->stall;
@@ -387,13 +387,13 @@ static hipError_t qu_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     return hipGetLastError();
 }
 
-hipError_t qu_init_range(nrg_ctx* c, u64 n) {
-    qu_range_kernel<<<(unsigned)((n + 255) / 256 + (n == 0)), 256, 0, c->stream>>>(c->d_queue, n, c->d_qu_state);
+static hipError_t qu_init_range(nrg_ctx* c, u64 n) {
+    qu_range_kernel<<<(unsigned)((n + 255) / 256 + (n == 0)), 256, 0, c->stream>>>(c->qu.d_queue, n, c->qu.d_state);
     return hipGetLastError();
 }
 
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some) {
-    qu_len_kernel<<<1, 256, 0, c->stream>>>(c->d_qu_state, n, d_out, d_some);
+    qu_len_kernel<<<1, 256, 0, c->stream>>>(c->qu.d_state, n, d_out, d_some);
     return hipGetLastError();
 }
 
@@ -404,26 +404,103 @@ static int qu_open(nrg_ctx* c) {
     // u64 values
     if (!cf.queue_capacity || cf.queue_capacity > (1ull << 32) || mb > (1ull << 24)) return NRG_E_INVAL;
     // capacity + max_batch slots: the positions one chunk touches never alias
-    c->qu_size = pow2_at_least(cf.queue_capacity + mb);
-    HIPCHK(hipMalloc(&c->d_queue, c->qu_size * sizeof(u64)));
-    HIPCHK(hipMalloc(&c->d_qu_state, sizeof(QuState)));
-    HIPCHK(hipMemsetAsync(c->d_qu_state, 0, sizeof(QuState), c->stream));
-    HIPCHK(hipMalloc(&c->d_qu_aux, qu_aux_bytes(mb)));
+    c->qu.size = pow2_at_least(cf.queue_capacity + mb);
+    HIPCHK(hipMalloc(&c->qu.d_queue, c->qu.size * sizeof(u64)));
+    HIPCHK(hipMalloc(&c->qu.d_state, sizeof(QuState)));
+    HIPCHK(hipMemsetAsync(c->qu.d_state, 0, sizeof(QuState), c->stream));
+    HIPCHK(hipMalloc(&c->qu.d_aux, qu_aux_bytes(mb)));
     c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
     return NRG_OK;
 }
 
 static void qu_close(nrg_ctx* c) {
-    (void)hipFree(c->d_queue);
-    (void)hipFree(c->d_qu_state);
-    (void)hipFree(c->d_qu_aux);
+    (void)hipFree(c->qu.d_queue);
+    (void)hipFree(c->qu.d_state);
+    (void)hipFree(c->qu.d_aux);
 }
 
 static hipError_t qu_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
 
 const DsOps* qu_ops() {
-    static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk};
+    static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk,
+                              floor_ltail, nullptr, nullptr, nullptr};
     return &ops;
 }
 
 }  // namespace nrg
+
+// ---- the queue's entry points (include/nrgpu.h) -----------------------------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_queue_round_async(nrg_ctx* c, const nrg_queue_op* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                          uint8_t* d_some) {
+    return round_common(c, NRG_DS_QUEUE, d_ops, n, origin, d_resp, d_some);
+}
+
+static int qu_set_state(nrg_ctx* c, uint64_t n) {
+    QuState s{};
+    s.len = n;
+    HIPCHK(hipMemcpyAsync(c->qu.d_state, &s, sizeof(s), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_queue_init(nrg_ctx* c, const uint64_t* vals, uint64_t n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (n > c->cfg.queue_capacity) return NRG_E_CAPACITY;
+    if (n && !vals) return NRG_E_INVAL;
+    // head = 0: the n values sit at the start of the ring (capacity <= its size)
+    if (n) HIPCHK(hipMemcpyAsync(c->qu.d_queue, vals, n * 8, hipMemcpyHostToDevice, c->stream));
+    return qu_set_state(c, n);
+}
+
+int nrg_queue_init_range(nrg_ctx* c, uint64_t n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (n > c->cfg.queue_capacity) return NRG_E_CAPACITY;
+    HIPCHK(qu_init_range(c, n));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+// the front's monotonic position and the length, never more than the capacity
+static int qu_get_state(nrg_ctx* c, uint64_t* head, uint64_t* len) {
+    QuState s{};
+    HIPCHK(hipMemcpyAsync(&s, c->qu.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    *head = s.head;
+    *len = s.len > c->cfg.queue_capacity ? c->cfg.queue_capacity : s.len;
+    return check_err(c);
+}
+
+int nrg_queue_len(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    uint64_t head = 0;
+    return qu_get_state(c, &head, n);
+}
+
+int nrg_queue_dump(nrg_ctx* c, uint64_t* vals, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    uint64_t head = 0;
+    if ((r = qu_get_state(c, &head, n))) return r;
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n) {
+        if (!vals) return NRG_E_INVAL;
+        const uint64_t phys = head & (c->qu.size - 1);
+        const uint64_t first = *n < c->qu.size - phys ? *n : c->qu.size - phys;
+        HIPCHK(hipMemcpyAsync(vals, c->qu.d_queue + phys, first * 8, hipMemcpyDeviceToHost, c->stream));
+        if (first < *n)
+            HIPCHK(hipMemcpyAsync(vals + first, c->qu.d_queue, (*n - first) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    return NRG_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // radix_sort.hip — stable LSD radix sort of (u32 key, u32 value) pairs for gfx950.
 //
-// Used by the replay pipelines to group log records by target (BLT entry / stack slot /
-// synthetic word) while preserving log order inside each group (SURVEY.md §2.2 K1/K3/K4;
-// BASELINE.json north_star: "stable LDS/wavefront radix sort by key").
+// Used by the synthetic structure's sort fallback (synthetic.hip, configurations the bucket replay
+// does not handle, or NRG_KNOB_SY_SORT) to group touch records by word while preserving log order
+// inside each group, and by the nrg_test_sort_pairs hook below. The hashmap, stack, queue and page
+// table replay without sorting.
 //
 // Structure (one launch per 8-bit digit + one histogram launch):
 //   rs_hist   : every block histograms its slice for all passes in LDS, then one global
@@ -287,3 +288,30 @@ hipError_t sort_pairs(SortScratch& s, const u32* keys_in, const u32* vals_in, u6
 }
 
 }  // namespace nrg
+
+// ---- test hook (include/nrgpu_testing.h) ------------------------------------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_test_sort_pairs(nrg_ctx* c, const uint32_t* d_keys, const uint32_t* d_vals, uint64_t n,
+                                   int key_bits, uint32_t* d_ok, uint32_t* d_ov) {
+    if (!c) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    if (n > c->sort.cap) {  // stack contexts replay without sorting: scratch on demand
+        HIPCHK(sync_all(c));
+        sort_free(c->sort);
+        if (sort_alloc(c->sort, n) != NRG_OK) return NRG_E_NOMEM;
+    }
+    u32 *sk = nullptr, *sv = nullptr;
+    HIPCHK(sort_pairs(c->sort, d_keys, d_vals, n, key_bits, c->stream, &sk, &sv));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(d_ok, sk, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_ov, sv, n * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+}  // extern "C"

@@ -907,8 +907,8 @@ static StPass st_pass(nrg_ctx* c, u32 par) {
     s.ring_mask = c->log_size - 1;
     // descriptors: [32 u64 unused] [parity][max tiles] u64; zero at open, and each chunk's finish
     // clears what its tile pass used (no memset launch per chunk)
-    s.desc = (u64*)c->d_scan_desc + 32 + par * mt;
-    char* base = (char*)c->d_st_aux + par * st_parity_bytes(mt);
+    s.desc = (u64*)c->st.d_desc + 32 + par * mt;
+    char* base = (char*)c->st.d_aux + par * st_parity_bytes(mt);
     s.tl.tmin = (long long*)base;
     s.tl.ucnt = (u32*)(s.tl.tmin + mt);
     s.tl.tend = s.tl.ucnt + mt;
@@ -921,23 +921,23 @@ static StPass st_pass(nrg_ctx* c, u32 par) {
 static hipError_t st_launch(nrg_ctx* c, const StPass& A, const StPass& P) {
     const unsigned grid = A.tiles + P.tiles;
     const size_t dyn = P.tiles ? (size_t)(P.tiles + P.tiles / 8 + P.tiles / 64 + 2) * 8 : 0;
-    st_round_kernel<<<grid, ST_LANES, dyn, c->stream>>>(A, P, c->d_ctl, c->d_stack, c->cfg.stack_capacity,
+    st_round_kernel<<<grid, ST_LANES, dyn, c->stream>>>(A, P, c->d_ctl, c->st.d_stack, c->cfg.stack_capacity,
                                                          (int)c->cfg.stack_push_resp, (c->exp & 2) ? c->d_dbg : nullptr);
     return hipGetLastError();
 }
 
 // The finish of the last replayed chunk (its cross-tile Pops and its commit), if still pending.
 static hipError_t st_flush(nrg_ctx* c) {
-    if (!c->st_pend.valid) return hipSuccess;
-    StPass P = st_pass(c, c->st_pend.par);
-    P.lo = c->st_pend.lo;
-    P.n = c->st_pend.n;
-    P.tiles = c->st_pend.tiles;
-    P.rlo = c->st_pend.rlo;
-    P.rhi = c->st_pend.rhi;
-    P.resp = c->st_pend.resp;
-    P.some = c->st_pend.some;
-    c->st_pend.valid = false;
+    if (!c->st.pend.valid) return hipSuccess;
+    StPass P = st_pass(c, c->st.pend.par);
+    P.lo = c->st.pend.lo;
+    P.n = c->st.pend.n;
+    P.tiles = c->st.pend.tiles;
+    P.rlo = c->st.pend.rlo;
+    P.rhi = c->st.pend.rhi;
+    P.resp = c->st.pend.resp;
+    P.some = c->st.pend.some;
+    c->st.pend.valid = false;
     StPass A{};
     return st_launch(c, A, P);
 }
@@ -948,7 +948,7 @@ static hipError_t st_flush(nrg_ctx* c) {
 static hipError_t st_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
     if (n == 0) return st_flush(c);  // an empty round still completes the last round's deferred finish
-    StPass A = st_pass(c, c->st_par);
+    StPass A = st_pass(c, c->st.par);
     A.src = (const nrg_stack_op*)src;
     A.lo = lo;
     A.n = n;
@@ -959,29 +959,29 @@ static hipError_t st_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     A.resp = want ? (uint32_t*)d_resp : nullptr;
     A.some = want ? d_some : nullptr;
     StPass P{};
-    if (c->st_pend.valid) {
-        P = st_pass(c, c->st_pend.par);
-        P.lo = c->st_pend.lo;
-        P.n = c->st_pend.n;
-        P.tiles = c->st_pend.tiles;
-        P.rlo = c->st_pend.rlo;
-        P.rhi = c->st_pend.rhi;
-        P.resp = c->st_pend.resp;
-        P.some = c->st_pend.some;
+    if (c->st.pend.valid) {
+        P = st_pass(c, c->st.pend.par);
+        P.lo = c->st.pend.lo;
+        P.n = c->st.pend.n;
+        P.tiles = c->st.pend.tiles;
+        P.rlo = c->st.pend.rlo;
+        P.rhi = c->st.pend.rhi;
+        P.resp = c->st.pend.resp;
+        P.some = c->st.pend.some;
     }
     timer_begin(c, "st_replay");
     hipError_t e = st_launch(c, A, P);
     timer_end(c, "st_replay");
     if (e != hipSuccess) return e;
-    c->st_pend = StDeferred{true, lo, n, A.tiles, A.par, A.rlo, A.rhi, A.resp, A.some};
-    c->st_par ^= 1;
+    c->st.pend = StDeferred{true, lo, n, A.tiles, A.par, A.rlo, A.rhi, A.resp, A.some};
+    c->st.par ^= 1;
     return c->pipeline ? hipSuccess : st_flush(c);
 }
 
 // [32 u64 unused] [parity][max tiles] u64 (st_pass)
 static u64 st_desc_words(u64 max_batch) { return 2 * (32 + 2 * ((max_batch + ST_TILE - 1) / ST_TILE)); }
 
-// size of nrg_ctx::d_st_aux
+// size of StHost::d_aux
 static u64 st_aux_bytes(u64 max_batch) { return 2 * st_parity_bytes((max_batch + ST_TILE - 1) / ST_TILE); }
 
 static int st_open(nrg_ctx* c) {
@@ -989,25 +989,96 @@ static int st_open(nrg_ctx* c) {
     const u64 mb = cf.max_batch;
     // max_batch <= 2^24: the finish stages one minimum per tile in LDS
     if (!cf.stack_capacity || cf.stack_capacity >= (1ull << 31) || mb > (1ull << 24)) return NRG_E_INVAL;
-    HIPCHK(hipMalloc(&c->d_stack, cf.stack_capacity * sizeof(uint32_t)));
-    // look-back descriptors of both tile parities (st_pass), and at least what
-    // nrg_test_maxscan's 2048-key tiles use
-    c->scan_desc_words = std::max<u64>(st_desc_words(mb), 2 * (32 + (mb + 2047) / 2048));
-    HIPCHK(hipMalloc(&c->d_scan_desc, c->scan_desc_words * 4));
-    HIPCHK(hipMemsetAsync(c->d_scan_desc, 0, c->scan_desc_words * 4, c->stream));
-    HIPCHK(hipMalloc(&c->d_st_aux, st_aux_bytes(mb)));
+    HIPCHK(hipMalloc(&c->st.d_stack, cf.stack_capacity * sizeof(uint32_t)));
+    // look-back descriptors of both tile parities (st_pass)
+    c->st.desc_words = st_desc_words(mb);
+    HIPCHK(hipMalloc(&c->st.d_desc, c->st.desc_words * 4));
+    HIPCHK(hipMemsetAsync(c->st.d_desc, 0, c->st.desc_words * 4, c->stream));
+    HIPCHK(hipMalloc(&c->st.d_aux, st_aux_bytes(mb)));
     c->pipeline = cf.pipeline != 0;
     return NRG_OK;
 }
 
 static void st_close(nrg_ctx* c) {
-    (void)hipFree(c->d_stack);
-    (void)hipFree(c->d_st_aux);
+    (void)hipFree(c->st.d_stack);
+    (void)hipFree(c->st.d_aux);
+    (void)hipFree(c->st.d_desc);
 }
 
+// NRG_KNOB_EXP bit 2: 16 words per tile, the finish workgroups' from row 128 on (st_round_kernel)
+static u64 st_dbg_words(const nrg_ctx* c) { return std::max<u64>(256, (c->cfg.max_batch + 2047) / 2048) * 16; }
+
 const DsOps* st_ops() {
-    static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk};
+    static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk,
+                              floor_ltail, nullptr, st_dbg_words, nullptr};
     return &ops;
 }
 
 }  // namespace nrg
+
+// ---- the stack's entry points (include/nrgpu.h) -----------------------------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_stack_round_async(nrg_ctx* c, const nrg_stack_op* d_ops, uint64_t n, uint32_t origin, uint32_t* d_pop_vals,
+                          uint8_t* d_some_bits) {
+    return round_common(c, NRG_DS_STACK, d_ops, n, origin, d_pop_vals, d_some_bits);
+}
+
+int nrg_stack_init(nrg_ctx* c, const uint32_t* vals, uint64_t n) {
+    int r = need(c, NRG_DS_STACK);
+    if (r) return r;
+    if (n > c->cfg.stack_capacity) return NRG_E_CAPACITY;
+    HIPCHK(flush_deferred(c));  // a deferred chunk finish commits before the stack is replaced
+    if (n) HIPCHK(hipMemcpyAsync(c->st.d_stack, vals, n * 4, hipMemcpyHostToDevice, c->stream));
+    long long d = (long long)n;
+    HIPCHK(hipMemcpyAsync(&c->d_ctl->depth, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    // the depth slot the next chunk starts from (a chunk of parity p reads slot p ^ 1)
+    HIPCHK(hipMemcpyAsync(&c->d_ctl->depth0 + (c->st.par ^ 1), &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_stack_len(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_STACK);
+    if (r) return r;
+    long long d = 0;
+    HIPCHK(flush_deferred(c));  // a deferred chunk finish publishes the length
+    HIPCHK(hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    // an overflowing chunk latches ERR_CAPACITY once but keeps counting: never report (or
+    // let dump/peek copy) more elements than the allocation holds
+    if (d < 0) d = 0;
+    if ((uint64_t)d > c->cfg.stack_capacity) d = (long long)c->cfg.stack_capacity;
+    *n = (uint64_t)d;
+    return check_err(c);
+}
+
+int nrg_stack_peek(nrg_ctx* c, uint32_t* val, uint8_t* some) {
+    int r = need(c, NRG_DS_STACK);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    uint64_t n = 0;
+    if ((r = nrg_stack_len(c, &n))) return r;
+    *some = n > 0;
+    *val = 0;
+    if (n) {
+        HIPCHK(hipMemcpyAsync(val, c->st.d_stack + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    return NRG_OK;
+}
+
+int nrg_stack_dump(nrg_ctx* c, uint32_t* vals, uint64_t cap, uint64_t* n) {
+    int r = nrg_stack_len(c, n);
+    if (r) return r;
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n) {
+        HIPCHK(hipMemcpyAsync(vals, c->st.d_stack, *n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    return NRG_OK;
+}
+
+}  // extern "C"

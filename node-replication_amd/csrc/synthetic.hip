@@ -14,6 +14,7 @@
 //               wrapping u64 adds commute, so the sum is exact whatever the order)
 //   sy_commit   each word's last touch writes its final value
 #include "internal.hpp"
+#include "../../include/nrgpu_testing.h"
 
 namespace nrg {
 
@@ -1076,7 +1077,7 @@ static u64 sy_bucket_words(u64 span) {
     const u64 nbw = SY_MAX_NB - SY_B0_PARTS;
     return span > 1 ? (span - 1 + nbw - 1) / nbw : 1;
 }
-bool sy_bucket_eligible(const nrg_config& cf) {
+static bool sy_bucket_eligible(const nrg_config& cf) {
     const u64 span = cf.synth_n - cf.synth_hot_reads;
     return cf.synth_cold_writes >= 1 && cf.synth_cold_writes <= SY_MAX_CW && cf.synth_hot_reads <= SY_MAX_HOT &&
            span <= 1 + (u64)(SY_MAX_NB - SY_B0_PARTS) * SYB_WORDS && cf.max_batch <= (u64)SY_MAX_TILES * SYA_OPS;
@@ -1122,7 +1123,7 @@ static SyAux sy_aux(void* base, const nrg_config& cf) {
 static u16* sy_ew(const SyAux& x, u32 epoch) { return (u16*)x.E[epoch % 3]; }
 static u16* sy_eo(const SyAux& x, u32 epoch) { return (u16*)x.E[epoch % 3] + x.te; }
 
-u64 sy_bucket_aux_bytes(const nrg_config& cf) {
+static u64 sy_bucket_aux_bytes(const nrg_config& cf) {
     const u64 tiles = (cf.max_batch + SYA_OPS - 1) / SYA_OPS;
     const u64 te = tiles * SYA_OPS * cf.synth_cold_writes;
     return te * (2 * 8 + 3 * 4) + 2 * sy_nb(cf) * tiles * 4 + 3 * tiles * cf.synth_hot_reads * sizeof(SyHot) + 256 +
@@ -1130,17 +1131,17 @@ u64 sy_bucket_aux_bytes(const nrg_config& cf) {
 }
 
 // Fresh scratch: the words may hold anything (sort-path chunks ran before), so the next chunk
-// (epoch sy_round + 1) takes 8-B seen values: big[sy_round & 1] = sy_round.
-hipError_t sy_aux_init(nrg_ctx* c) {
-    SyAux x = sy_aux(c->d_sy_aux, c->cfg);
+// (epoch sy.round + 1) takes 8-B seen values: big[sy.round & 1] = sy.round.
+static hipError_t sy_aux_init(nrg_ctx* c) {
+    SyAux x = sy_aux(c->sy.d_aux, c->cfg);
     SyFlags f{};
-    f.big[0] = f.big[1] = c->sy_round;  // the other slot is compared with sy_round + 1 + 2k: never equal
+    f.big[0] = f.big[1] = c->sy.round;  // the other slot is compared with sy.round + 1 + 2k: never equal
     return hipMemcpy(x.fl, &f, sizeof f, hipMemcpyHostToDevice);
 }
 
 static SySumArgs sy_sum_args(nrg_ctx* c, const SyDeferred& d) {
     const nrg_config& cf = c->cfg;
-    SyAux x = sy_aux(c->d_sy_aux, cf);
+    SyAux x = sy_aux(c->sy.d_aux, cf);
     SySumArgs S{};
     if (!d.valid) return S;
     S.blocks = (d.t1 - d.t0 + SYS_T - 1) / SYS_T;
@@ -1159,7 +1160,7 @@ static SySumArgs sy_sum_args(nrg_ctx* c, const SyDeferred& d) {
     S.ntiles = d.ntiles;
     S.HR = cf.synth_hot_reads;
     S.CW = cf.synth_cold_writes;
-    S.words = c->d_words;
+    S.words = c->sy.d_words;
     S.v32 = &x.fl->v32[d.epoch & 1];
     S.dbg = (c->exp & 2) ? c->d_dbg : nullptr;
     S.plain = !((c->exp >> 9) & 1);
@@ -1176,7 +1177,7 @@ static u32 sy_NB(const nrg_config& cf) {
 
 static SyBucketArgs sy_bucket_args(nrg_ctx* c, const SyDeferred& d) {
     const nrg_config& cf = c->cfg;
-    SyAux x = sy_aux(c->d_sy_aux, cf);
+    SyAux x = sy_aux(c->sy.d_aux, cf);
     SyBucketArgs B{};
     B.Ew = sy_ew(x, d.epoch);
     B.Eo = sy_eo(x, d.epoch);
@@ -1185,7 +1186,7 @@ static SyBucketArgs sy_bucket_args(nrg_ctx* c, const SyDeferred& d) {
     B.ntiles = d.ntiles;
     B.tile_entries = SYA_OPS * cf.synth_cold_writes;
     B.V = x.V[d.epoch & 1];
-    B.words = c->d_words;
+    B.words = c->sy.d_words;
     B.N = cf.synth_n;
     B.HR = cf.synth_hot_reads;
     B.W = sy_W(cf);
@@ -1205,7 +1206,7 @@ static SyPartArgs sy_part_args(nrg_ctx* c, u64 lo, u64 n, const nrg_synth_op* sr
     const nrg_config& cf = c->cfg;
     const u32 HR = cf.synth_hot_reads;
     const u64 span = cf.synth_n - HR;
-    SyAux x = sy_aux(c->d_sy_aux, cf);
+    SyAux x = sy_aux(c->sy.d_aux, cf);
     SyPartArgs A;
     A.src = src;
     A.ring = (nrg_synth_op*)c->d_ring;
@@ -1352,27 +1353,27 @@ static hipError_t sy_launch_bucket(nrg_ctx* c, const SyDeferred& d) {
 // The deferred work of the last replayed chunks, if any: the sums (and hot-word fold) of the
 // last chunk; with one launch per round also the bucket pass of the last chunk, then its sums.
 static hipError_t sy_flush(nrg_ctx* c) {
-    if (c->sy_fused) {
-        while (c->sy_pend_b.valid || c->sy_pend.valid) {
-            const SySumArgs S = sy_sum_args(c, c->sy_pend);
+    if (c->sy.fused) {
+        while (c->sy.pend_b.valid || c->sy.pend.valid) {
+            const SySumArgs S = sy_sum_args(c, c->sy.pend);
             SyPartArgs A{};
-            hipError_t e = sy_launch_fused(c, A, c->sy_pend_b, S);
+            hipError_t e = sy_launch_fused(c, A, c->sy.pend_b, S);
             if (e != hipSuccess) return e;
-            c->sy_pend = c->sy_pend_b;  // its sums next
-            c->sy_pend_b.valid = false;
+            c->sy.pend = c->sy.pend_b;  // its sums next
+            c->sy.pend_b.valid = false;
         }
         return hipSuccess;
     }
-    if (!c->sy_pend.valid) return hipSuccess;
-    const SySumArgs S = sy_sum_args(c, c->sy_pend);
-    c->sy_pend.valid = false;
+    if (!c->sy.pend.valid) return hipSuccess;
+    const SySumArgs S = sy_sum_args(c, c->sy.pend);
+    c->sy.pend.valid = false;
     SyPartArgs A{};
     return sy_launch_part(c, A, S);
 }
 
 static hipError_t sy_bucket_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, u64* d_resp, uint8_t* d_some,
                                   const nrg_synth_op* src) {
-    const u32 epoch = ++c->sy_round;
+    const u32 epoch = ++c->sy.round;
     const SyPartArgs A = sy_part_args(c, lo, n, src, epoch);
     SyDeferred d;
     d.valid = true;
@@ -1393,23 +1394,23 @@ static hipError_t sy_bucket_chunk(nrg_ctx* c, u64 lo, u64 n, u64 resp_lo, u64 re
     d.rhi = resp_hi;
     d.resp = d.want ? d_resp : nullptr;
     d.some = d.want ? d_some : nullptr;
-    const SySumArgs S = sy_sum_args(c, c->sy_pend);
+    const SySumArgs S = sy_sum_args(c, c->sy.pend);
     hipError_t e;
     timer_begin(c, "sy_replay");
-    if (c->sy_fused) {
+    if (c->sy.fused) {
         // one launch: this chunk's partition, the last chunk's bucket pass, the one before's sums
-        e = sy_launch_fused(c, A, c->sy_pend_b, S);
+        e = sy_launch_fused(c, A, c->sy.pend_b, S);
         timer_end(c, "sy_replay");
         if (e != hipSuccess) return e;
-        c->sy_pend = c->sy_pend_b;
-        c->sy_pend_b = d;
+        c->sy.pend = c->sy.pend_b;
+        c->sy.pend_b = d;
     } else {
         // two launches: this chunk's partition beside the last chunk's sums, then its bucket pass
         e = sy_launch_part(c, A, S);
         if (e == hipSuccess) e = sy_launch_bucket(c, d);
         timer_end(c, "sy_replay");
         if (e != hipSuccess) return e;
-        c->sy_pend = d;
+        c->sy.pend = d;
     }
     return c->pipeline ? hipSuccess : sy_flush(c);
 }
@@ -1445,7 +1446,7 @@ __global__ __launch_bounds__(512) void sy_lds_add_order_kernel(u32 K, u32 trials
     atomicAdd((unsigned long long*)&out[1], (unsigned long long)nbad);
 }
 
-hipError_t sy_lds_add_order(nrg_ctx* c, u32 K, u32 trials, u32 blocks, u64* d_out) {
+static hipError_t sy_lds_add_order(nrg_ctx* c, u32 K, u32 trials, u32 blocks, u64* d_out) {
     if (K < 1 || K > 512) return hipErrorInvalidValue;
     sy_lds_add_order_kernel<<<blocks, 512, 0, c->stream>>>(K, trials, d_out);
     return hipGetLastError();
@@ -1456,7 +1457,7 @@ static hipError_t sy_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 
     const nrg_synth_op* src = (const nrg_synth_op*)src_recs;
     u64* d_resp = (u64*)d_resp_v;
     if (n == 0) return sy_flush(c);  // an empty round still completes the last round's deferred sums
-    if (c->d_sy_aux) return sy_bucket_chunk(c, lo, n, resp_lo, resp_hi, d_resp, d_some, src);
+    if (c->sy.d_aux) return sy_bucket_chunk(c, lo, n, resp_lo, resp_hi, d_resp, d_some, src);
     if (src) {  // the sort path replays from the ring: append the ops first (wrapping)
         const u64 mask = c->log_size - 1, first = std::min<u64>(n, c->log_size - (lo & mask));
         nrg_synth_op* ring = (nrg_synth_op*)c->d_ring;
@@ -1474,10 +1475,10 @@ static hipError_t sy_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 
     const u64 nt = n * T;
     const u64 ring_mask = c->log_size - 1;
     const nrg_synth_op* ring = (const nrg_synth_op*)c->d_ring;
-    const u32 sentinel = (u32)((1ull << c->synth_key_bits) - 1);
-    u32* keys = (u32*)c->d_tmp_u64;
+    const u32 sentinel = (u32)((1ull << c->sy.key_bits) - 1);
+    u32* keys = (u32*)c->sy.d_tmp;
     u32* vals = keys + (u64)cf.max_batch * T;
-    u32* M = (u32*)c->d_sort_aux;
+    u32* M = (u32*)c->sy.d_sort_aux;
     hipError_t e;
     const bool want = d_resp != nullptr && resp_lo < lo + n && resp_hi > lo;
     if (want) {
@@ -1491,35 +1492,35 @@ static hipError_t sy_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 
     if (g > 8192) g = 8192;
     sy_expand_kernel<<<(unsigned)g, 256, 0, st>>>(ring, ring_mask, lo, n, cf.synth_n, HR, HW, CW, sentinel, keys, vals);
     u32 *sk = nullptr, *sv = nullptr;
-    if ((e = sort_pairs(c->sort, keys, vals, nt, (int)c->synth_key_bits, st, &sk, &sv)) != hipSuccess) return e;
+    if ((e = sort_pairs(c->sort, keys, vals, nt, (int)c->sy.key_bits, st, &sk, &sv)) != hipSuccess) return e;
     const u64 tiles = (nt + MS_TILE - 1) / MS_TILE;
-    if ((e = hipMemsetAsync(c->d_scan_desc, 0, (32 + tiles) * sizeof(u64), st)) != hipSuccess) return e;
-    sy_maxscan_kernel<<<(unsigned)tiles, MS_TPB, 0, st>>>(sk, sv, nt, (u64*)c->d_scan_desc + 32, c->d_scan_desc, M);
+    if ((e = hipMemsetAsync(c->sy.d_desc, 0, (32 + tiles) * sizeof(u64), st)) != hipSuccess) return e;
+    sy_maxscan_kernel<<<(unsigned)tiles, MS_TPB, 0, st>>>(sk, sv, nt, (u64*)c->sy.d_desc + 32, c->sy.d_desc, M);
     const unsigned gb = (unsigned)((nt + 255) / 256);
     if (want)
-        sy_resolve_kernel<<<gb, 256, 0, st>>>(sk, sv, M, nt, ring, ring_mask, lo, c->d_words, HW, T, sentinel, resp_lo,
+        sy_resolve_kernel<<<gb, 256, 0, st>>>(sk, sv, M, nt, ring, ring_mask, lo, c->sy.d_words, HW, T, sentinel, resp_lo,
                                              resp_hi, d_resp);
-    sy_commit_kernel<<<gb, 256, 0, st>>>(sk, sv, M, nt, ring, ring_mask, lo, c->d_words, T, sentinel);
+    sy_commit_kernel<<<gb, 256, 0, st>>>(sk, sv, M, nt, ring, ring_mask, lo, c->sy.d_words, T, sentinel);
     timer_end(c, "sy_replay");
     return hipGetLastError();
 }
 
-hipError_t sy_maxscan(nrg_ctx* c, const u32* sk, const u32* sv, u64 n, u32* M) {
+static hipError_t sy_maxscan(nrg_ctx* c, const u32* sk, const u32* sv, u64 n, u32* M) {
     const u64 tiles = (n + MS_TILE - 1) / MS_TILE;
-    hipError_t e = hipMemsetAsync(c->d_scan_desc, 0, (32 + tiles) * sizeof(u64), c->stream);
+    hipError_t e = hipMemsetAsync(c->sy.d_desc, 0, (32 + tiles) * sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
-    sy_maxscan_kernel<<<(unsigned)tiles, MS_TPB, 0, c->stream>>>(sk, sv, n, (u64*)c->d_scan_desc + 32,
-                                                                c->d_scan_desc, M);
+    sy_maxscan_kernel<<<(unsigned)tiles, MS_TPB, 0, c->stream>>>(sk, sv, n, (u64*)c->sy.d_desc + 32,
+                                                                c->sy.d_desc, M);
     return hipGetLastError();
 }
 
-hipError_t sy_read(nrg_ctx* c, const nrg_synth_rd* d_ops, u64 n, u64* d_sums) {
+static hipError_t sy_read(nrg_ctx* c, const nrg_synth_rd* d_ops, u64 n, u64* d_sums) {
     if (n == 0) return hipSuccess;
     hipError_t e = sy_flush(c);  // reads see the hot words of every replayed chunk
     if (e != hipSuccess) return e;
     const nrg_config& cf = c->cfg;
     sy_read_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(
-        d_ops, n, c->d_words, cf.synth_n, cf.synth_hot_reads, cf.synth_hot_writes, cf.synth_cold_reads, d_sums);
+        d_ops, n, c->sy.d_words, cf.synth_n, cf.synth_hot_reads, cf.synth_hot_writes, cf.synth_cold_reads, d_sums);
     return hipGetLastError();
 }
 
@@ -1529,35 +1530,132 @@ static int sy_open(nrg_ctx* c) {
     if (!cf.synth_n || cf.synth_hot_reads == 0 || cf.synth_n <= cf.synth_hot_reads || T == 0 || T > 64 ||
         mb * T >= (1ull << 31) || cf.synth_n >= (1ull << 31))
         return NRG_E_INVAL;
-    HIPCHK(hipMalloc(&c->d_words, cf.synth_n * sizeof(u64)));
-    c->synth_key_bits = 1;  // the smallest b with 2^b - 1 >= synth_n
-    while (((1ull << c->synth_key_bits) - 1) < cf.synth_n) c->synth_key_bits++;
-    HIPCHK(hipMalloc(&c->d_tmp_u64, mb * T * sizeof(u64)));
-    c->tmp_words = mb * T;
-    HIPCHK(hipMalloc(&c->d_sort_aux, mb * T * sizeof(u32)));
-    c->scan_desc_words = 2 * (32 + (mb * T + 2047) / 2048);
-    HIPCHK(hipMalloc(&c->d_scan_desc, c->scan_desc_words * 4));
+    HIPCHK(hipMalloc(&c->sy.d_words, cf.synth_n * sizeof(u64)));
+    c->sy.key_bits = 1;  // the smallest b with 2^b - 1 >= synth_n
+    while (((1ull << c->sy.key_bits) - 1) < cf.synth_n) c->sy.key_bits++;
+    HIPCHK(hipMalloc(&c->sy.d_tmp, mb * T * sizeof(u64)));
+    HIPCHK(hipMalloc(&c->sy.d_sort_aux, mb * T * sizeof(u32)));
+    c->sy.desc_words = 2 * (32 + (mb * T + 2047) / 2048);
+    HIPCHK(hipMalloc(&c->sy.d_desc, c->sy.desc_words * 4));
     if (sort_alloc(c->sort, mb * T) != NRG_OK) return NRG_E_NOMEM;
     // sort-free bucket replay where the config allows it (the sort path stays for the rest;
     // nrg_test_set_knob(NRG_KNOB_SY_SORT) forces it for tests)
     if (sy_bucket_eligible(cf)) {
-        HIPCHK(hipMalloc(&c->d_sy_aux, sy_bucket_aux_bytes(cf)));
+        HIPCHK(hipMalloc(&c->sy.d_aux, sy_bucket_aux_bytes(cf)));
         HIPCHK(sy_aux_init(c));
     }
     c->pipeline = cf.pipeline != 0;
-    sy_init_kernel<<<1024, 256, 0, c->stream>>>(c->d_words, cf.synth_n);
+    sy_init_kernel<<<1024, 256, 0, c->stream>>>(c->sy.d_words, cf.synth_n);
     return hip_fail(hipGetLastError());
 }
 
 static void sy_close(nrg_ctx* c) {
-    (void)hipFree(c->d_words);
-    (void)hipFree(c->d_sort_aux);
-    (void)hipFree(c->d_sy_aux);
+    (void)hipFree(c->sy.d_words);
+    (void)hipFree(c->sy.d_sort_aux);
+    (void)hipFree(c->sy.d_aux);
+    (void)hipFree(c->sy.d_tmp);
+    (void)hipFree(c->sy.d_desc);
 }
 
+// Known gap, left as it is here (ADVICE.md, medium finding): with one launch per round the deferred
+// bucket pass of pend_b still reads ring[lo + op] after ltail has moved past it, so this should
+// hold the log back to pend_b.lo. That is a change of behaviour with a test of its own.
+static u64 sy_floor(const nrg_ctx* c) { return c->ltail; }
+
+static int sy_set_knob(nrg_ctx* c, int knob, uint64_t v) {
+    switch (knob) {
+        case NRG_KNOB_SY_SORT:
+            if (v > 1) return NRG_E_INVAL;
+            if (v && c->sy.d_aux) {  // sort path: the bucket scratch goes away
+                HIPCHK(hipFree(c->sy.d_aux));
+                c->sy.d_aux = nullptr;
+            } else if (!v && !c->sy.d_aux && sy_bucket_eligible(c->cfg)) {
+                HIPCHK(hipMalloc(&c->sy.d_aux, sy_bucket_aux_bytes(c->cfg)));
+                HIPCHK(sy_aux_init(c));
+            }
+            return NRG_OK;
+        case NRG_KNOB_SY_FUSED:
+            if (v > 1) return NRG_E_INVAL;
+            c->sy.fused = v != 0;
+            return NRG_OK;
+        default: return NRG_E_INVAL;
+    }
+}
+
+// NRG_KNOB_EXP bit 2: 16 words per bucket, partition tile and sum workgroup
+static u64 sy_dbg_words(const nrg_ctx*) { return (u64)SY_DBG_ROWS * 16; }
+
 const DsOps* sy_ops() {
-    static const DsOps ops = {sizeof(nrg_synth_op), sizeof(u64), sy_open, sy_close, sy_flush, sy_replay_chunk};
+    static const DsOps ops = {sizeof(nrg_synth_op), sizeof(u64), sy_open, sy_close, sy_flush, sy_replay_chunk,
+                              sy_floor, sy_set_knob, sy_dbg_words, nullptr};
     return &ops;
 }
 
 }  // namespace nrg
+
+// ---- the synthetic structure's entry points (include/nrgpu.h, nrgpu_testing.h) ----------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_synth_round_async(nrg_ctx* c, const nrg_synth_op* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                          uint8_t* d_some) {
+    return round_common(c, NRG_DS_SYNTHETIC, d_ops, n, origin, d_resp, d_some);
+}
+
+int nrg_synth_read_async(nrg_ctx* c, const nrg_synth_rd* d_ops, uint64_t n, uint64_t* d_sums) {
+    int r = need(c, NRG_DS_SYNTHETIC);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    return hip_fail(sy_read(c, d_ops, n, d_sums));
+}
+
+int nrg_synth_read(nrg_ctx* c, const nrg_synth_rd* ops, uint64_t n, uint64_t* sums) {
+    int r = need(c, NRG_DS_SYNTHETIC);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (!n) return NRG_OK;
+    Staging* s = c->stg;
+    if ((r = staging(s[0], n * sizeof(nrg_synth_rd))) || (r = staging(s[1], n * 8))) return r;
+    HIPCHK(hipMemcpyAsync(s[0].p, ops, n * sizeof(nrg_synth_rd), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(sy_read(c, (const nrg_synth_rd*)s[0].p, n, (u64*)s[1].p));
+    HIPCHK(hipMemcpyAsync(sums, s[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_synth_dump(nrg_ctx* c, uint64_t* words, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_SYNTHETIC);
+    if (r) return r;
+    *n = c->cfg.synth_n;
+    if (*n > cap) return NRG_E_CAPACITY;
+    HIPCHK(flush_deferred(c));  // deferred sums fold the hot words
+    HIPCHK(hipMemcpyAsync(words, c->sy.d_words, *n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_test_maxscan(nrg_ctx* c, const uint32_t* d_keys, const uint32_t* d_vals, uint64_t n, uint32_t* d_out) {
+    int r = need(c, NRG_DS_SYNTHETIC);  // the scan's look-back descriptors are the synthetic's
+    if (r) return r;
+    if ((n + 2047) / 2048 + 32 > c->sy.desc_words / 2) return NRG_E_INVAL;
+    HIPCHK(sy_maxscan(c, d_keys, d_vals, n, d_out));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_test_lds_add_order(nrg_ctx* c, uint32_t keys, uint32_t trials, uint32_t blocks, uint64_t out[2]) {
+    if (!c || !out || keys < 1 || keys > 512 || blocks < 1 || blocks > 65536 || trials > 4096) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    u64* d = nullptr;
+    HIPCHK(hipMallocAsync((void**)&d, 16, c->stream));
+    HIPCHK(hipMemsetAsync(d, 0, 16, c->stream));
+    HIPCHK(sy_lds_add_order(c, keys, trials, blocks, d));
+    HIPCHK(hipMemcpyAsync(out, d, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipFreeAsync(d, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+}  // extern "C"

@@ -37,6 +37,9 @@
 //                    contiguous 8-B stores by consecutive lanes) and the response
 //   vs_seq_kernel    one workgroup: every other op of a 4096-op slice in log order: walk without
 //                    stores, capacity check, inner tables, walk with stores
+#include <cstring>
+#include <new>
+
 #include "internal.hpp"
 
 namespace nrg {
@@ -540,11 +543,11 @@ static hipError_t vs_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     j.rhi = want ? resp_hi : 0;
     j.resp = want ? (nrg_vspace_resp*)d_resp : nullptr;
     j.some = want ? d_some : nullptr;
-    j.pool = c->d_vs_pool;
-    j.cap = c->vs_cap;
-    j.st = c->d_vs_state;
+    j.pool = c->vs.d_pool;
+    j.cap = c->vs.cap;
+    j.st = c->vs.d_state;
     j.ctl = c->d_ctl;
-    j.glo = (u32*)c->d_vs_aux;
+    j.glo = (u32*)c->vs.d_aux;
     j.ghi = j.glo + mb;
     j.npt = j.ghi + mb;
     j.key = j.npt + mb;
@@ -564,10 +567,10 @@ static hipError_t vs_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     return hipGetLastError();
 }
 
-hipError_t vs_resolve(nrg_ctx* c, const u64* d_va, u64 n, u64* d_pa, uint8_t* d_found) {
+static hipError_t vs_resolve(nrg_ctx* c, const u64* d_va, u64 n, u64* d_pa, uint8_t* d_found) {
     if (n == 0) return hipSuccess;
     NRG_LAUNCH(c, "vs_resolve", vs_resolve_kernel, (unsigned)((n + 255) / 256), 256, 0, c->stream,
-               (const u64*)c->d_vs_pool, d_va, n, d_pa, d_found);
+               (const u64*)c->vs.d_pool, d_va, n, d_pa, d_found);
     return hipGetLastError();
 }
 
@@ -575,30 +578,134 @@ static int vs_open(nrg_ctx* c) {
     const nrg_config& cf = c->cfg;
     // log2_slots: the pool holds 2^log2_slots tables; max_batch <= 2^16: one workgroup scans a chunk
     if (cf.log2_slots < 2 || cf.log2_slots > 22 || cf.max_batch > (1ull << 16)) return NRG_E_INVAL;
-    c->vs_cap = 1ull << cf.log2_slots;
-    HIPCHK(hipMalloc(&c->d_vs_pool, c->vs_cap * 4096));
-    HIPCHK(hipMemsetAsync(c->d_vs_pool, 0, c->vs_cap * 4096, c->stream));
-    HIPCHK(hipMalloc(&c->d_vs_state, sizeof(VsState)));
+    c->vs.cap = 1ull << cf.log2_slots;
+    HIPCHK(hipMalloc(&c->vs.d_pool, c->vs.cap * 4096));
+    HIPCHK(hipMemsetAsync(c->vs.d_pool, 0, c->vs.cap * 4096, c->stream));
+    HIPCHK(hipMalloc(&c->vs.d_state, sizeof(VsState)));
     const VsState s0{1};  // table 0, the PML4 (VSpace::default, :165-174)
-    HIPCHK(hipMemcpyAsync(c->d_vs_state, &s0, sizeof(s0), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->vs.d_state, &s0, sizeof(s0), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // (s0 is on this frame)
-    HIPCHK(hipMalloc(&c->d_vs_aux, vs_aux_bytes(cf.max_batch)));
+    HIPCHK(hipMalloc(&c->vs.d_aux, vs_aux_bytes(cf.max_batch)));
     c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
     return NRG_OK;
 }
 
 static void vs_close(nrg_ctx* c) {
-    (void)hipFree(c->d_vs_pool);
-    (void)hipFree(c->d_vs_state);
-    (void)hipFree(c->d_vs_aux);
+    (void)hipFree(c->vs.d_pool);
+    (void)hipFree(c->vs.d_state);
+    (void)hipFree(c->vs.d_aux);
 }
 
 static hipError_t vs_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
 
+static void vs_defaults(nrg_config* cfg) {
+    cfg->log2_slots = 18;       // the pool: 2^18 tables of 4 KiB, 1 GiB
+    cfg->max_batch = 1u << 16;  // the largest chunk a page table replays
+}
+
 const DsOps* vs_ops() {
     static const DsOps ops = {sizeof(nrg_vspace_op), sizeof(nrg_vspace_resp), vs_open, vs_close, vs_flush,
-                              vs_replay_chunk};
+                              vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults};
     return &ops;
 }
 
 }  // namespace nrg
+
+// ---- the page table's entry points (include/nrgpu.h) ------------------------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_vspace_round_async(nrg_ctx* c, const nrg_vspace_op* d_ops, uint64_t n, uint32_t origin,
+                           nrg_vspace_resp* d_resp, uint8_t* d_some) {
+    return round_common(c, NRG_DS_VSPACE, d_ops, n, origin, d_resp, d_some);
+}
+
+int nrg_vspace_resolve_async(nrg_ctx* c, const uint64_t* d_vaddrs, uint64_t n, uint64_t* d_paddrs, uint8_t* d_found) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n > c->cfg.max_reads) return NRG_E_CAPACITY;
+    if (n && (!d_vaddrs || !d_paddrs || !d_found)) return NRG_E_INVAL;
+    return hip_fail(vs_resolve(c, d_vaddrs, n, d_paddrs, d_found));
+}
+
+int nrg_vspace_resolve(nrg_ctx* c, const uint64_t* vaddrs, uint64_t n, uint64_t* paddrs, uint8_t* found) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n > c->cfg.max_reads) return NRG_E_CAPACITY;
+    if (n == 0) return NRG_OK;
+    if (!vaddrs || !paddrs || !found) return NRG_E_INVAL;
+    Staging* s = c->stg;
+    if ((r = staging(s[0], n * 8)) || (r = staging(s[1], n * 8)) || (r = staging(s[2], n))) return r;
+    HIPCHK(hipMemcpyAsync(s[0].p, vaddrs, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(vs_resolve(c, (u64*)s[0].p, n, (u64*)s[1].p, (uint8_t*)s[2].p));
+    HIPCHK(hipMemcpyAsync(paddrs, s[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(found, s[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+// tables allocated from the pool
+static int vs_get_tables(nrg_ctx* c, uint64_t* n) {
+    VsState s{};
+    HIPCHK(hipMemcpyAsync(&s, c->vs.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    *n = s.ntables;
+    if (s.ntables > c->vs.cap) return NRG_E_HIP;  // (the allocation passes never hand out more than the pool holds)
+    return check_err(c);
+}
+
+int nrg_vspace_tables(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    return vs_get_tables(c, n);
+}
+
+// The leaves below table `tab` of level `level` (3 = PML4 .. 0 = PT) in ascending vaddr: slots are
+// walked in index order, so nothing depends on the order in which the tables were allocated.
+static void vs_collect(const uint64_t* pool, uint64_t ntab, uint64_t tab, int level, uint64_t va,
+                       std::vector<nrg_vspace_leaf>& out) {
+    const uint64_t ADDR = 0x000ffffffffff000ull;
+    for (uint64_t i = 0; i < 512; i++) {
+        const uint64_t e = pool[tab * 512 + i];
+        if (!(e & 1)) continue;
+        const uint64_t v = va | (i << (12 + 9 * level));
+        if (level == 0 || (level == 1 && (e & 0x80))) {
+            out.push_back(nrg_vspace_leaf{v, e});
+        } else {
+            const uint64_t next = (e & ADDR) >> 12;
+            if (next < ntab) vs_collect(pool, ntab, next, level - 1, v, out);
+        }
+    }
+}
+
+int nrg_vspace_dump(nrg_ctx* c, nrg_vspace_leaf* leaves, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    uint64_t ntab = 0;
+    if ((r = vs_get_tables(c, &ntab))) return r;
+    // Replica::verify's view, not a hot path: the allocated tables are copied out and walked here
+    std::vector<uint64_t> pool;
+    std::vector<nrg_vspace_leaf> out;
+    try {
+        pool.resize(ntab * 512);
+        HIPCHK(hipMemcpyAsync(pool.data(), c->vs.d_pool, ntab * 4096, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+        vs_collect(pool.data(), ntab, 0, 3, 0, out);
+    } catch (const std::bad_alloc&) {
+        return NRG_E_NOMEM;
+    }
+    *n = out.size();
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n) {
+        if (!leaves) return NRG_E_INVAL;
+        std::memcpy(leaves, out.data(), *n * sizeof(nrg_vspace_leaf));
+    }
+    return NRG_OK;
+}
+
+}  // extern "C"

@@ -66,35 +66,35 @@ __global__ void gen_stack_ops_kernel(nrg_stack_op* out, u64 n, u64 seed) {
     }
 }
 
-hipError_t gen_uniform(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 span) {
+static hipError_t gen_uniform(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 span) {
     gen_uniform_kernel<<<gen_grid(n), GEN_TPB, 0, c->stream>>>(d, n, seed, span);
     return hipGetLastError();
 }
-hipError_t gen_raw(nrg_ctx* c, u64* d, u64 n, u64 seed) {
+static hipError_t gen_raw(nrg_ctx* c, u64* d, u64 n, u64 seed) {
     gen_raw_kernel<<<gen_grid(n), GEN_TPB, 0, c->stream>>>(d, n, seed);
     return hipGetLastError();
 }
-hipError_t gen_puts(nrg_ctx* c, nrg_put* d, const u64* k, const u64* v, u64 n) {
+static hipError_t gen_puts(nrg_ctx* c, nrg_put* d, const u64* k, const u64* v, u64 n) {
     gen_puts_kernel<<<gen_grid(n), GEN_TPB, 0, c->stream>>>(d, k, v, n);
     return hipGetLastError();
 }
-hipError_t gen_stack_ops(nrg_ctx* c, nrg_stack_op* d, u64 n, u64 seed) {
+static hipError_t gen_stack_ops(nrg_ctx* c, nrg_stack_op* d, u64 n, u64 seed) {
     gen_stack_ops_kernel<<<gen_grid(n), GEN_TPB, 0, c->stream>>>(d, n, seed);
     return hipGetLastError();
 }
 
 // Host part of the Zipf generator: zeta(N, theta) summed in the oracle's order (i = 1..N),
 // cached per (N, theta) in the context.
-hipError_t gen_zipf(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 N, double theta, int scramble) {
+static hipError_t gen_zipf(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 N, double theta, int scramble) {
     if (N == 0 || !(theta > 0.0) || theta == 1.0) return hipErrorInvalidValue;
-    if (c->zipf_n != N || c->zipf_theta != theta) {
+    if (c->gen.zipf_n != N || c->gen.zipf_theta != theta) {
         double z = 0.0;
         for (u64 i = 1; i <= N; i++) z += pow((double)i, -theta);
-        c->zipf_n = N;
-        c->zipf_theta = theta;
-        c->zipf_zetan = z;
+        c->gen.zipf_n = N;
+        c->gen.zipf_theta = theta;
+        c->gen.zipf_zetan = z;
     }
-    const double zetan = c->zipf_zetan;
+    const double zetan = c->gen.zipf_zetan;
     const double zeta2 = 1.0 + pow(2.0, -theta);
     const double alpha = 1.0 / (1.0 - theta);
     const double eta = (1.0 - pow(2.0 / (double)N, 1.0 - theta)) / (1.0 - zeta2 / zetan);
@@ -104,3 +104,45 @@ hipError_t gen_zipf(nrg_ctx* c, u64* d, u64 n, u64 seed, u64 N, double theta, in
 }
 
 }  // namespace nrg
+
+// ---- the generators' entry points (include/nrgpu.h) -------------------------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_gen_uniform_async(nrg_ctx* c, uint64_t* d, uint64_t n, uint64_t seed, uint64_t span) {
+    if (!c) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    return hip_fail(gen_uniform(c, d, n, seed, span));
+}
+int nrg_gen_raw_async(nrg_ctx* c, uint64_t* d, uint64_t n, uint64_t seed) {
+    if (!c) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    return hip_fail(gen_raw(c, d, n, seed));
+}
+int nrg_gen_puts_async(nrg_ctx* c, nrg_put* d, const uint64_t* k, const uint64_t* v, uint64_t n) {
+    if (!c) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    return hip_fail(gen_puts(c, d, k, v, n));
+}
+
+int nrg_gen_zipf_async(nrg_ctx* c, uint64_t* d, uint64_t n, uint64_t seed, uint64_t N, double theta,
+                       int scramble) {
+    if (!c || (n && !d)) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    if (N == 0 || !(theta > 0.0) || theta == 1.0) return NRG_E_INVAL;
+    return hip_fail(gen_zipf(c, d, n, seed, N, theta, scramble));
+}
+
+int nrg_gen_stack_ops_async(nrg_ctx* c, nrg_stack_op* d, uint64_t n, uint64_t seed) {
+    if (!c || (n && !d)) return NRG_E_INVAL;
+    int r = ctx_use_device(c);
+    if (r) return r;
+    return hip_fail(gen_stack_ops(c, d, n, seed));
+}
+
+}  // extern "C"
