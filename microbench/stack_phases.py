@@ -18,7 +18,7 @@ import nrgpu  # noqa: E402
 from nrgpu import _lib as L  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-dev = nrgpu.DeviceReplica(L.NRG_DS_STACK, 0, knobs={"EXP": int(os.environ.get("EXP", "2"), 0)}, max_batch=N, stack_capacity=N * 4 + 100_000, pipeline=int(os.environ.get("PIPE", "1")),
+dev = nrgpu.DeviceReplica(L.NRG_DS_STACK, 0, knobs={"EXP": 2}, max_batch=N, stack_capacity=N * 4 + 100_000, pipeline=int(os.environ.get("PIPE", "1")),
                           log_bytes=64 * 4 * max(N, 8192))
 dev.use_torch_stream()
 dev.st_init(list(range(50_000)))
@@ -29,7 +29,7 @@ for i, o in enumerate(opsl):
     dev.gen_stack_ops_device(o, N, 12345 + i)
 resps = [torch.empty(N, dtype=torch.int32, device="cuda") for _ in range(2)]
 somes = [torch.empty(N, dtype=torch.uint8, device="cuda") for _ in range(2)]
-TILE = int(os.environ.get("ST_TILE", "2048"))  # ops per tile of the build (256 lanes x NRG_ST_OPS)
+TILE = 2048  # ops per tile (256 lanes x 8 ops, stack.hip ST_TILE)
 tiles = (N + TILE - 1) // TILE
 names = ["loads", "local pass", "scan+responses", "lookback", "query list+sparse table", "queries", "table"]
 acc = np.zeros((tiles, 9))

@@ -123,9 +123,8 @@ struct Member {
     uint64_t cap_p[PT_DEPTH] = {}, cap_k[PT_DEPTH] = {};  // its owner-region capacities (n, n_gets)
     PtPlan plan[PT_DEPTH];
     uint32_t pt_epoch = 0;      // look-back descriptor tag of the last fused partition
-    hipStream_t pstream = nullptr;  // a one-rank group's partitions and route-backs, beside the replay
+    hipStream_t pstream = nullptr;  // a one-rank group's partitions, beside the replay
     hipEvent_t pin_ev = nullptr;    // the replica stream's work up to a post (inputs, older rounds)
-    hipEvent_t rd_ev = nullptr;     // a one-rank group: the replay launch that answered a round's reads
     uint64_t xwords[8] = {};    // this rank's host words of the exchange
     uint64_t xw1[PT_DEPTH][8] = {};  // a one-rank group: the words of the round of that slot (its
                                      // "exchange" needs no wait: its counts are its own n, n_gets)
@@ -195,7 +194,6 @@ int member_init(Member& m, int nranks) {
     GCHK(hipEventCreateWithFlags(&m.pt_ev, hipEventDisableTiming));
     for (int q = 0; q < PT_DEPTH; q++) GCHK(hipEventCreateWithFlags(&m.cnt_ev[q], hipEventDisableTiming));
     GCHK(hipEventCreateWithFlags(&m.pin_ev, hipEventDisableTiming));
-    GCHK(hipEventCreateWithFlags(&m.rd_ev, hipEventDisableTiming));
     GCHK(hipStreamCreateWithFlags(&m.pstream, hipStreamNonBlocking));
     for (int b = 0; b < NBUF; b++) {
         GCHK(hipEventCreateWithFlags(&m.gathered[b], hipEventDisableTiming));
@@ -273,7 +271,6 @@ void member_free(Member& m, const Rccl* R) {
     if (m.pstream) (void)hipStreamSynchronize(m.pstream);
     if (m.pstream) (void)hipStreamDestroy(m.pstream);
     if (m.pin_ev) (void)hipEventDestroy(m.pin_ev);
-    if (m.rd_ev) (void)hipEventDestroy(m.rd_ev);
     if (m.in_ev) (void)hipEventDestroy(m.in_ev);
     if (m.cstream) (void)hipStreamDestroy(m.cstream);
     m = Member{};
@@ -1033,17 +1030,8 @@ static int pt_stage_b(nrg_group* g, uint64_t e) {
                                     hipMemcpyDeviceToDevice, s));
             }
         }
-        hipStream_t rs = c->stream;
-        if (G == 1 && (c->exp & 0x8000)) {  // NRG_KNOB_EXP bit 15
-            // (A/B) beside the next replay, on the side stream, after everything queued on the
-            // replica's stream so far: the launch that answered this round's reads (the replay of
-            // the round after, or a join) is the last of it
-            rs = m.pstream;
-            GCHK(hipEventRecord(m.rd_ev, c->stream));
-            GCHK(hipStreamWaitEvent(rs, m.rd_ev, 0));
-        }
         const hipError_t he = nrg::pt_route2(
-            rs, (const uint64_t*)aval, (const uint8_t*)afound, (const uint32_t*)m.pp[sl][PP_GPOS].p, x.n_gets,
+            c->stream, (const uint64_t*)aval, (const uint8_t*)afound, (const uint32_t*)m.pp[sl][PP_GPOS].p, x.n_gets,
             x.get_vals, x.get_found, (const uint64_t*)aprev, (const uint8_t*)aprevf,
             (const uint32_t*)m.pp[sl][PP_PPOS].p, mine ? x.n : 0, mine ? (uint64_t*)x.resp : nullptr, mine ? x.some : nullptr);
         if (he != hipSuccess) return hip_rc(he);
@@ -1071,7 +1059,7 @@ static int pt_flush(nrg_group* g) {
         if (g->broken) return g->broken;
         if (r && rc == NRG_OK) rc = r;
     }
-    if (g->nranks == 1)  // a one-rank group's route-backs ran on its side stream: ordered again
+    if (g->nranks == 1)  // a one-rank group's partitions ran on its side stream: ordered again
         for (Member& m : g->m) {
             RCHK(nrg::ctx_use_device(m.ctx));
             RCHK(order(m, m.pstream, m.ctx->stream));

@@ -47,7 +47,7 @@ typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 // reads-only launches: plain stores leave them dirty in the XCD's L2 for the kernel-end write-back
 // after the last workgroup; streamed, they drain during the kernel. N = 8 per-GPU round 78.7 vs
 // 80.5 us, configs[2] 256.9 vs 263.4; stamp rounds keep plain stores (B1 34.5-34.7 plain vs
-// 34.7-35.0 streamed; profiles/r04_nt_stores.txt). NRG_KNOB_EXP bit 6 = plain everywhere (A/B).
+// 34.7-35.0 streamed; profiles/r04_nt_stores.txt).
 // Round 6: the compiler merges st_out's two branches into one plain store and drops the hint, so
 // only the 16-B log copy (st_rec) is streamed; the responses are plain stores. Streamed for real
 // (the plain branch as a relaxed wavefront-scope atomic store, which is not merged) they measured
@@ -64,26 +64,16 @@ __device__ __forceinline__ void st_rec(nrg_put* p, const nrg_put& r, bool plain)
     else __builtin_nontemporal_store(u64x2{r.key, r.val}, (u64x2*)p);
 }
 
-// Round 6 (profiles/r06/b1_apply_nt.txt): the stamp-round apply's random value stores are streamed
-// (NRG_HM_APPLY_NT): they drain during the launch instead of in its end-of-kernel L2 write-back.
-// Same box, three pairs: 34.16-34.20 -> 33.93-34.02 us per B1 step (window 34.03-34.13 ->
-// 33.80-33.97); the driver's 20 steps 27,507-27,866 -> 27,823-27,875 Mops/s. Streaming the index
-// role's put_slot / win / over words (NRG_HM_TAG_NT) was slower (34.49-34.53 vs 34.25). Build
-// with =0 / =1 for the A/B.
-#ifndef NRG_HM_APPLY_NT
-#define NRG_HM_APPLY_NT 1
-#endif
-#ifndef NRG_HM_TAG_NT
-#define NRG_HM_TAG_NT 0
-#endif
+// Round 6 (profiles/r06/b1_apply_nt.txt): the stamp-round apply's random value stores are streamed:
+// they drain during the launch instead of in its end-of-kernel L2 write-back. Same box, three
+// pairs: 34.16-34.20 -> 33.93-34.02 us per B1 step (window 34.03-34.13 -> 33.80-33.97); the
+// driver's 20 steps 27,507-27,866 -> 27,823-27,875 Mops/s. The index role's put_slot / win / over
+// words stay plain stores: streamed they were slower (34.49-34.53 vs 34.25).
 // The partition apply's value stores are streamed in rounds of at most PA_NT_MAX Puts: same box,
 // two pairs, N = 8 per-GPU round (800k Puts + 900k Gets) 77.24-77.35 -> 75.35-75.57 us, 50 % writes
 // 53.7-53.8 -> 53.1-53.2; configs[2]'s 4M Puts slower streamed (251.1-251.3 -> 257.3-258.3), so
-// they stay plain above it (profiles/r06/papply_nt.txt). NRG_HM_PA_NT=0 builds it plain throughout.
-#ifndef NRG_HM_PA_NT
-#define NRG_HM_PA_NT 1
-#endif
-constexpr u64 PA_NT_MAX = NRG_HM_PA_NT ? 2000000 : 0;
+// they stay plain above it (profiles/r06/papply_nt.txt).
+constexpr u64 PA_NT_MAX = 2000000;
 template <bool NT, typename T>
 __device__ __forceinline__ void st_pol(T* p, T v) {
     if constexpr (NT) __builtin_nontemporal_store(v, p);
@@ -112,8 +102,6 @@ struct IndexJob {
     u64x2* ent;    // [nblocks][tile] {id << 32 | i+1, value}
     u32* eidx;     // partition rounds: [nblocks][tile] round offset i of each entry (previous values)
     u32* cnt;      // [bucket][nblocks] start << 16 | count
-    u32 exp;       // diagnostic knobs (NRG_EXP; results are wrong when set): 1 no dedup, 2 no
-                   // probe (every key new), 4 no ranking/entries
     u64* dup_acc;  // [HM_DUP_SLOTS] Puts overwritten inside their block (key skew statistic)
     bool plain;    // plain stores for the log copy (st_out)
 };
@@ -348,9 +336,6 @@ struct StampJob {
     u32* win;       // [n] = epoch: the Put took its slot's stamp (it was the largest so far)
     u32* over;      // [n] = epoch: a later Put of the key took the stamp from it
     u64* created_acc;
-    // diagnostic ablations of a round launch (NRG_KNOB_EXP >> 20; RESULTS WRONG, timing only):
-    // 1 no stamp atomics, 2 no apply role, 4 no index role, 8 no read role
-    u32 exp;
     bool plain;  // plain stores for the log copy (st_out)
 };
 struct ApplyJob {
@@ -438,16 +423,16 @@ __device__ __forceinline__ void stamp_index_role(const StampJob& j, u32 blk, Slo
                 created++;
             }
             atomicMax(&s_side, (u32)(i + 1));
-            st_pol<NRG_HM_TAG_NT>(&j.put_slot[i], SIDE_SLOT);
+            j.put_slot[i] = SIDE_SLOT;
             continue;
         }
         const long long s = find_or_claim_marked(table, k, home[q], tmask, key0[q], e, &created);
         if (s < 0) {
             atomicOr(&ctl->err, ERR_TABLE_FULL);
-            st_pol<NRG_HM_TAG_NT>(&j.put_slot[i], FULL_SLOT);
+            j.put_slot[i] = FULL_SLOT;
             continue;
         }
-        st_pol<NRG_HM_TAG_NT>(&j.put_slot[i], (u32)s);
+        j.put_slot[i] = (u32)s;
         u32 h = (u32)(mix64((u64)s) & (HT - 1));
         for (;;) {
             const u32 old = atomicCAS(&s_slot[h], 0xFFFFFFFFu, (u32)s);
@@ -469,12 +454,12 @@ __device__ __forceinline__ void stamp_index_role(const StampJob& j, u32 blk, Slo
     // slot's stamp (n8: 31 us of apply for 800k Puts).
     for (int q = threadIdx.x; q < HT; q += TPB) {
         const u32 sl = s_slot[q];
-        if (sl != 0xFFFFFFFFu && !(j.exp & 1)) {
+        if (sl != 0xFFFFFFFFu) {
             const u64 mine = stamp_make(e, s_max[q]);
             const u64 old = atomicMax((unsigned long long*)&table[sl].st[par], (unsigned long long)mine);
             if (old < mine) {
-                st_pol<NRG_HM_TAG_NT>(&j.win[s_max[q] - 1], e);
-                if (stamp_epoch(old) == e && (u32)old) st_pol<NRG_HM_TAG_NT>(&j.over[(u32)old - 1], e);
+                j.win[s_max[q] - 1] = e;
+                if (stamp_epoch(old) == e && (u32)old) j.over[(u32)old - 1] = e;
             }
         }
     }
@@ -497,7 +482,7 @@ __device__ __forceinline__ void apply_role(const ApplyJob& j, u32 blk, Slot* tab
     } else if (s != FULL_SLOT) {
         // (a 16-B {key, val} store costs the same: a partial-line write is priced per line,
         // profiles/r03_apply_store_width.txt)
-        if (j.win[i] == j.epoch && j.over[i] != j.epoch) st_pol<NRG_HM_APPLY_NT>(&table[s].val, j.rec.at(i).val);
+        if (j.win[i] == j.epoch && j.over[i] != j.epoch) __builtin_nontemporal_store(j.rec.at(i).val, &table[s].val);
     }
 }
 
@@ -608,17 +593,11 @@ constexpr int IX_PART_NODUP = 5;  // partition round, every Put kept, no previou
 // empty). Index blocks come first so the latency-bound pass starts first.
 // <= 80 SGPRs: 256-thread blocks are admitted 8 per CU only up to 80 SGPRs (82-96: 7 per CU,
 // MI355X_MICROARCH.md "Residency"), and the read role needs every resident wave.
-// DIAG: the instantiation that honours the diagnostic ablation bits (NRG_KNOB_EXP); the release
-// instantiations fold them away and are the only ones launched unless such a bit is set.
-template <int K1, int IX, bool DIAG>
+template <int K1, int IX>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_num_sgpr(80))) void hm_round_kernel(IndexJob ij, StampJob sj,
                                                                                              ApplyJob aj, ReadJob rj,
                                                        Slot* table, u32 shift, u64 tmask, DevCtl* ctl) {
     extern __shared__ __attribute__((aligned(16))) char s_lds[];
-    if constexpr (!DIAG) {
-        ij.exp = 0;
-        sj.exp = 0;
-    }
     u32 b = blockIdx.x;
     if (rj.s_seq && b == gridDim.x - 1) {  // the tail block
         // the skew sample (counters read and cleared atomically)
@@ -636,18 +615,17 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_num_sgpr(80))) void hm_r
     }
     const u32 nix = IX == IX_STAMP ? sj.nblocks : ij.nblocks;
     if (b < nix) {
-        if (sj.exp & 4) return;
         if constexpr (IX == IX_STAMP) stamp_index_role<K1>(sj, b, table, shift, tmask, ctl, s_lds);
         else part_role<K1, IX == IX_PART>(ij, b, shift, s_lds);
         return;
     }
     b -= nix;
     if (b < aj.nblocks) {
-        if (!(sj.exp & 2)) apply_role(aj, b, table, ctl);
+        apply_role(aj, b, table, ctl);
         return;
     }
     b -= aj.nblocks;
-    if (!(sj.exp & 8)) read_role(rj, b, table, shift, tmask, ctl);
+    read_role(rj, b, table, shift, tmask, ctl);
 }
 
 // ---- hm_papply_kernel: partition rounds' table pass, one workgroup per bucket ---------------------
@@ -1487,16 +1465,14 @@ hipError_t hm_serve_launch(nrg_ctx* c, ServeCtl* sc, const SmallJobBlob* hdr, u3
     return hipGetLastError();
 }
 
-// NT (hm_grow's A/B, NRG_KNOB_EXP bit 7): streamed stores
-template <bool NT = false>
 __global__ __launch_bounds__(TPB) void hm_init_table_kernel(Slot* table, u64 slots) {
     for (u64 s = blockIdx.x * (u64)TPB + threadIdx.x; s < slots; s += (u64)gridDim.x * TPB) {
         u64x2 z;
         z.x = EMPTY_KEY;
         z.y = 0;
-        st_pol<NT>((u64x2*)&table[s], z);
+        *(u64x2*)&table[s] = z;
         z.x = z.y = 0;
-        st_pol<NT>((u64x2*)&table[s].st[0], z);
+        *(u64x2*)&table[s].st[0] = z;
     }
 }
 
@@ -1798,19 +1774,14 @@ static void attach_deferred(nrg_ctx* c, Launch& L) {
 
 template <int K1, int IX>
 static void launch_round(nrg_ctx* c, const Launch& L, u32 blocks, unsigned lds) {
-    if ((L.ij.exp | L.sj.exp) != 0)
-        NRG_LAUNCH(c, "hm_round", (hm_round_kernel<K1, IX, true>), blocks, TPB, lds, c->stream, L.ij, L.sj, L.aj, L.rj,
-                   c->hm.d_table, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
-    else
-        NRG_LAUNCH(c, "hm_round", (hm_round_kernel<K1, IX, false>), blocks, TPB, lds, c->stream, L.ij, L.sj, L.aj,
-                   L.rj, c->hm.d_table, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
+    NRG_LAUNCH(c, "hm_round", (hm_round_kernel<K1, IX>), blocks, TPB, lds, c->stream, L.ij, L.sj, L.aj, L.rj,
+               c->hm.d_table, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
 }
 
 static hipError_t launch(nrg_ctx* c, Launch& L) {
     L.rj.nblocks = (u32)((L.rj.R + TPB * RPT - 1) / (TPB * RPT));
-    L.sj.exp = c->exp >> 20;
     const u32 nix = L.ix == IX_STAMP ? L.sj.nblocks : L.ij.nblocks;
-    L.ij.plain = L.sj.plain = L.rj.plain = ((c->exp >> 6) & 1) || (L.ix == IX_STAMP && nix);
+    L.ij.plain = L.sj.plain = L.rj.plain = L.ix == IX_STAMP && nix;  // stamp rounds keep plain stores (st_out)
     // reads beside a bucket or partition pass (which only read the table, or not even that), or
     // alone, with no stamp round's apply riding along: the table is quiescent
     L.rj.quiet = (L.ix != IX_STAMP || nix == 0) && L.aj.nblocks == 0;
@@ -1939,7 +1910,7 @@ static int hm_open(nrg_ctx* c) {
     c->hm.slots = 1ull << cf.log2_slots;
     c->hm.slot_shift = 64 - cf.log2_slots;
     HIPCHK(hipMalloc(&c->hm.d_table, c->hm.slots * sizeof(Slot)));
-    hm_init_table_kernel<false><<<grid_for(c->hm.slots, 16384), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots);
+    hm_init_table_kernel<<<grid_for(c->hm.slots, 16384), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMalloc(&c->hm.d_created, HM_CREATED_SLOTS * sizeof(u64)));
     HIPCHK(hipMemsetAsync(c->hm.d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
@@ -1980,9 +1951,8 @@ static hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
         (void)hipGetLastError();  // (the failure is reported by the return value alone)
         return hipErrorOutOfMemory;
     }
-    const bool nt_init = (c->exp >> 7) & 1;  // (A/B: streamed init stores; measured 2.6x slower)
-    if (nt_init) NRG_LAUNCH(c, "hm_grow_init", hm_init_table_kernel<true>, grid_for(nslots, 16384), TPB, 0, c->stream, nt, nslots);
-    else NRG_LAUNCH(c, "hm_grow_init", hm_init_table_kernel<false>, grid_for(nslots, 16384), TPB, 0, c->stream, nt, nslots);
+    // (plain stores: streamed, the init measured 2.6x slower)
+    NRG_LAUNCH(c, "hm_grow_init", hm_init_table_kernel, grid_for(nslots, 16384), TPB, 0, c->stream, nt, nslots);
     if ((e = hipGetLastError()) == hipSuccess) e = hipMemsetAsync(&c->d_ctl->nkeys, 0, sizeof(u64), c->stream);
     if (e == hipSuccess) {
         const unsigned grid = (unsigned)((c->hm.slots + RH_RUN - 1) / RH_RUN);
@@ -2133,7 +2103,6 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         ij.ent = (u64x2*)c->hm.d_bk_ent;
         ij.eidx = want_prev ? c->hm.d_bk_idx : nullptr;
         ij.cnt = c->hm.d_bk_cnt;
-        ij.exp = 0;
         ij.dup_acc = c->hm.d_dup + (c->hm.dup_seq & 1) * HM_DUP_SLOTS;
         attach_deferred(c, L);  // the previous round's apply and reads ride along (partition only reads)
         if ((e = launch(c, L)) != hipSuccess) return e;

@@ -23,20 +23,17 @@
 
 namespace nrg {
 
-#ifndef NRG_ST_OPS
 // ops per lane, measured at 1M-op rounds (bench.py --workload stack): 8 -> 17.4 us, 16 -> 18.8 us,
 // 32 -> 21.2 us (session 7, before the branch-free query walk: 21.5 / 20.6 / 22.7 us); round 6:
 // 4 (1024-op tiles, four per CU) 23.7 us against 8's 14.0 on one box (profiles/r06/stack_resp_policy.txt)
-#define NRG_ST_OPS 8
-#endif
-constexpr int SW_OPS = NRG_ST_OPS;          // ops per lane, replayed in order by that lane (<= 32)
+constexpr int SW_OPS = 8;                   // ops per lane, replayed in order by that lane
 constexpr int ST_WAVES = 4;                 // a tile is one workgroup of 4 waves
 constexpr int ST_LANES = 64 * ST_WAVES;     // 256 lanes
 constexpr int ST_TILE = ST_LANES * SW_OPS;  // 2048 ops
-constexpr int ST_PB = SW_OPS == 32 ? 13 : SW_OPS == 16 ? 12 : 11;  // bits of a position in the tile
+constexpr int ST_PB = 11;                   // bits of a position in the tile
 constexpr u32 ST_PMASK = (1u << ST_PB) - 1;
 static_assert(ST_TILE == 1 << ST_PB, "positions");
-static_assert(SW_OPS == 8 || SW_OPS == 16 || SW_OPS == 32, "ops per lane");
+static_assert(SW_OPS == 8, "the lane's `some` bytes are one 8-B store; its records and responses 16-B units");
 
 struct Fn {
     long long b;
@@ -209,14 +206,13 @@ struct StPass {
     u32* resp;
     uint8_t* some;
     u32 stall;  // NRG_KNOB_STALL (tests)
-    u32 plain;  // (A/B, NRG_KNOB_EXP bit 6) plain stores instead of streaming ones for the tile outputs
 };
 
 // Streaming (nt) stores for outputs no later work of this launch reads (the log copy, the
 // responses): with plain stores they stay dirty in the XCD's L2 until the kernel-end write-back,
 // which then runs after the last workgroup (~13 MB per 1M-op round); streamed, they drain while
 // the look-back waits. 15.35-15.50 -> 14.88-14.90 us per round on one box, 15.37-15.42 -> 15.14-15.24
-// on another (profiles/r04_nt_stores.txt). NRG_KNOB_EXP bit 6 = plain stores (A/B).
+// on another (profiles/r04_nt_stores.txt).
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void nt_store4(uint4* p, uint4 v) {
     const u32x4_t t = {v.x, v.y, v.z, v.w};
@@ -225,29 +221,15 @@ __device__ __forceinline__ void nt_store4(uint4* p, uint4 v) {
 
 // A tile's Pop responses: the lane's wide store and the later single-op stores (the answers to
 // its unmatched Pops, from any wave of the tile, after a barrier) take the same cache policy, so
-// no ordering between a streamed and a plain store to one word is relied on. The plain form is a
-// relaxed wavefront-scope atomic store (the same plain store in the ISA): two plain-vs-streamed
-// stores on either side of a branch are merged by the compiler into one plain store, the hint
-// dropped (profiles/r06/stack_resp_policy.txt).
-__device__ __forceinline__ void st_resp(u32* p, u32 v, u32 plain) {
-    if (plain) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    else __builtin_nontemporal_store(v, p);
-}
-
-// Round 6: the `some` bytes (the lane's 8-B store and the patches, NRG_ST_SOME_NT) and the finish's
-// stores (cross-tile answers and the commit, NRG_ST_FIN_NT) are streamed as well. Same box, two
-// pairs: 13.87-13.96 -> 13.71-13.78 us per 1M-op round (finish alone 13.73-13.84, some alone no
-// change; profiles/r06/stack_stream_some_finish.txt). Build with =0 for the plain A/B.
-#ifndef NRG_ST_SOME_NT
-#define NRG_ST_SOME_NT 1
-#endif
-#ifndef NRG_ST_FIN_NT
-#define NRG_ST_FIN_NT 1
-#endif
-template <bool NT, typename T>
-__device__ __forceinline__ void st_pol(T* p, T v) {
-    if constexpr (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
+// no ordering between a streamed and a plain store to one word is relied on
+// (profiles/r06/stack_resp_policy.txt).
+// Round 6: the `some` bytes (the lane's 8-B store and the patches) and the finish's stores
+// (cross-tile answers and the commit) are streamed as well. Same box, two pairs: 13.87-13.96 ->
+// 13.71-13.78 us per 1M-op round (finish alone 13.73-13.84, some alone no change;
+// profiles/r06/stack_stream_some_finish.txt).
+template <typename T>
+__device__ __forceinline__ void st_nt(T* p, T v) {
+    __builtin_nontemporal_store(v, p);
 }
 
 __device__ __forceinline__ void wave_sync() {  // LDS written by other lanes of this wave
@@ -468,13 +450,8 @@ __device__ __forceinline__ void st_tile_role(const StPass& A, const StPass& P, u
     if (copy_later) {  // Log::append's copy of the wave's records
         if (ring_run) {
             uint4* w4 = (uint4*)(ring + rw0);
-            if (!A.plain) {
 #pragma unroll
-                for (int i = 0; i < SW_OPS / 2; i++) nt_store4(&w4[64 * i + lane], x[i]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < SW_OPS / 2; i++) w4[64 * i + lane] = x[i];
-            }
+            for (int i = 0; i < SW_OPS / 2; i++) nt_store4(&w4[64 * i + lane], x[i]);
         } else {
 #pragma unroll
             for (int i = 0; i < SW_OPS / 2; i++) {
@@ -491,37 +468,21 @@ __device__ __forceinline__ void st_tile_role(const StPass& A, const StPass& P, u
         const bool in = full && g0 >= resp_lo && g0 + SW_OPS <= resp_hi;
         u32* rp = resp + (g0 - resp_lo);
         uint8_t* sp = some + (g0 - resp_lo);
-        if (in && !((uintptr_t)rp & 15) && !((uintptr_t)sp & (SW_OPS >= 16 ? 15 : 7))) {
-            if (!A.plain) {
+        if (in && !((uintptr_t)rp & 15) && !((uintptr_t)sp & 7)) {
 #pragma unroll
-                for (int j = 0; j < SW_OPS / 4; j++)
-                    nt_store4(&((uint4*)rp)[j], uint4{rt[4 * j], rt[4 * j + 1], rt[4 * j + 2], rt[4 * j + 3]});
-            } else {
-#pragma unroll
-                for (int j = 0; j < SW_OPS / 4; j++)
-                    ((uint4*)rp)[j] = uint4{rt[4 * j], rt[4 * j + 1], rt[4 * j + 2], rt[4 * j + 3]};
-            }
-            if constexpr (SW_OPS >= 16) {
-#pragma unroll
-                for (int j = 0; j < SW_OPS / 16; j++) {
-                    uint4 b;
-                    u32* bb = (u32*)&b;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) bb[k] = (((smask >> (16 * j + 4 * k)) & 15u) * 0x204081u) & 0x01010101u;
-                    ((uint4*)sp)[j] = b;
-                }
-            } else {  // 8 ops per lane: one 8-B store
-                const uint2 b = uint2{((smask & 15u) * 0x204081u) & 0x01010101u,
-                                      (((smask >> 4) & 15u) * 0x204081u) & 0x01010101u};
-                st_pol<NRG_ST_SOME_NT>((u64*)sp, (u64)b.x | ((u64)b.y << 32));
-            }
+            for (int j = 0; j < SW_OPS / 4; j++)
+                nt_store4(&((uint4*)rp)[j], uint4{rt[4 * j], rt[4 * j + 1], rt[4 * j + 2], rt[4 * j + 3]});
+            // 8 ops per lane: one 8-B store
+            const uint2 b = uint2{((smask & 15u) * 0x204081u) & 0x01010101u,
+                                  (((smask >> 4) & 15u) * 0x204081u) & 0x01010101u};
+            st_nt((u64*)sp, (u64)b.x | ((u64)b.y << 32));
         } else if (resp) {
 #pragma unroll
             for (int q = 0; q < SW_OPS; q++) {
                 const u64 g = g0 + q;
                 if (base + q < n && g >= resp_lo && g < resp_hi) {
-                    st_resp(&resp[g - resp_lo], rt[q], A.plain);
-                    st_pol<NRG_ST_SOME_NT>(&some[g - resp_lo], (uint8_t)((smask >> q) & 1));
+                    st_nt(&resp[g - resp_lo], rt[q]);
+                    st_nt(&some[g - resp_lo], (uint8_t)((smask >> q) & 1));
                 }
             }
         }
@@ -655,8 +616,8 @@ __device__ __forceinline__ void st_tile_role(const StPass& A, const StPass& P, u
                 if (v[i] >= 0) {
                     const u64 g = lo + tbase + pos;
                     if (resp && g >= resp_lo && g < resp_hi) {
-                        st_resp(&resp[g - resp_lo], rv[i], A.plain);
-                        st_pol<NRG_ST_SOME_NT>(&some[g - resp_lo], (uint8_t)1);
+                        st_nt(&resp[g - resp_lo], rv[i]);
+                        st_nt(&some[g - resp_lo], (uint8_t)1);
                     }
                 } else {  // its Push is in an earlier tile or before the chunk
                     const u32 x = atomicAdd(&s_ucnt, 1u);
@@ -750,8 +711,8 @@ __device__ __forceinline__ void st_tile_role(const StPass& A, const StPass& P, u
         for (u32 um = umask; um; um &= um - 1) {
             const u64 g = g0 + (u64)__builtin_ctz(um);
             if (resp && g >= resp_lo && g < resp_hi) {
-                st_resp(&resp[g - resp_lo], 0u, A.plain);
-                st_pol<NRG_ST_SOME_NT>(&some[g - resp_lo], (uint8_t)0);
+                st_nt(&resp[g - resp_lo], 0u);
+                st_nt(&some[g - resp_lo], (uint8_t)0);
             }
         }
         if (t == 0) s_ucnt = 0;
@@ -857,11 +818,11 @@ __device__ __forceinline__ void st_finish_role(const StPass& P, u32 tile, DevCtl
         hi = hi < later ? hi : later;
         const u32* tab = tl.table + (u64)tile * ST_TILE;
         for (long long sl = tmin + t; sl < hi; sl += 256)
-            if ((u64)sl < cap) st_pol<NRG_ST_FIN_NT>(&stack[sl], tab[sl - tmin]);
+            if ((u64)sl < cap) st_nt(&stack[sl], tab[sl - tmin]);
     }
     if (pg != ~0ull) {
-        st_pol<NRG_ST_FIN_NT>(&resp[pg - resp_lo], pval);
-        st_pol<NRG_ST_FIN_NT>(&some[pg - resp_lo], (uint8_t)1);
+        st_nt(&resp[pg - resp_lo], pval);
+        st_nt(&some[pg - resp_lo], (uint8_t)1);
     }
     if (!one) {
         for (u32 j = t; j < cnt; j += 256) {
@@ -870,9 +831,9 @@ __device__ __forceinline__ void st_finish_role(const StPass& P, u32 tile, DevCtl
             if (g < resp_lo || g >= resp_hi) continue;
             const long long s = tmin + (v >> ST_PB);
             const int k = st_walk(s_tm, s_g8, s_gm, (int)tile - 1, s);
-            st_pol<NRG_ST_FIN_NT>(&resp[g - resp_lo], k >= 0 ? tl.table[(u64)k * ST_TILE + (u64)(s - s_tm[k])]
+            st_nt(&resp[g - resp_lo], k >= 0 ? tl.table[(u64)k * ST_TILE + (u64)(s - s_tm[k])]
                                                         : (j == (u32)t ? uv0 : tl.uval[(u64)tile * ST_TILE + j]));
-            st_pol<NRG_ST_FIN_NT>(&some[g - resp_lo], (uint8_t)1);
+            st_nt(&some[g - resp_lo], (uint8_t)1);
         }
     }
 }
@@ -902,7 +863,6 @@ static StPass st_pass(nrg_ctx* c, u32 par) {
     StPass s{};
     s.par = par;
     s.stall = c->stall;
-    s.plain = (c->exp >> 6) & 1;
     s.ring = (nrg_stack_op*)c->d_ring;
     s.ring_mask = c->log_size - 1;
     // descriptors: [32 u64 unused] [parity][max tiles] u64; zero at open, and each chunk's finish

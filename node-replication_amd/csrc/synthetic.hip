@@ -20,38 +20,13 @@ namespace nrg {
 
 constexpr u32 SETBIT = 0x80000000u;
 
-// Streaming (nt) stores for the streamed outputs (log copy, touch records, seen values,
-// responses), an A/B variant (NRG_KNOB_EXP bits 6 / 7 / 8 / 9 for the log copy / touch records /
-// seen values / responses): they drain during the kernel instead of in the
-// kernel-end L2 write-back, which pays on the stack and the hashmap's partition rounds, but not
-// here (56.6-56.9 vs 56.1-56.6 us per round plain; profiles/r04_nt_stores.txt): plain by default.
-typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-// Round 6: the compiler merges st_out's two branches into one plain store and drops the hint, so
-// bits 7-9 compile to plain stores; only the 16-B log copy (st_op, bit 6) is streamed. Streamed
-// for real (the plain branch as a relaxed atomic store, not merged) every variant was slower on
-// one box, and the atomic form cost the plain default its merged wider stores: 44.9-45.8 us per
-// round before, 47.7-48.0 with the atomic plain form, 49.5-50.5 touch records or seen values
-// streamed, 47.5-47.6 responses streamed (profiles/r06/nt_single_stores.txt).
-template <typename T>
-__device__ __forceinline__ void st_out(T* p, T v, bool plain) {
-    if (plain) *p = v;
-    else __builtin_nontemporal_store(v, p);
-}
-__device__ __forceinline__ void st_op(nrg_synth_op* p, const nrg_synth_op& o, bool plain) {
-    if (plain) {
-        *p = o;
-        return;
-    }
-    const u64x2_t a = {o.tid, o.r1}, b = {o.r2, o.op};
-    __builtin_nontemporal_store(a, (u64x2_t*)p);
-    __builtin_nontemporal_store(b, (u64x2_t*)p + 1);
-}
-// Round 6: the sums' responses are streamed (compile-time, since st_out's hint is dropped): same box,
-// three pairs, 45.40-45.66 -> 44.35-44.61 us per 1M-op round (profiles/r06/synth_resp_nt.txt).
-// NRG_SY_RESP_NT=0 restores st_out (plain unless the A/B bit 9 asks, which compiles plain too).
-#ifndef NRG_SY_RESP_NT
-#define NRG_SY_RESP_NT 1
-#endif
+// Store policy of the streamed outputs. The log copy, the touch records and the seen values are
+// plain stores: streaming (nt) stores, which drain during the kernel instead of in the kernel-end L2
+// write-back, pay on the stack and the hashmap's partition rounds but not here (56.6-56.9 vs
+// 56.1-56.6 us per round plain, profiles/r04_nt_stores.txt; round 6, each alone on one box: 49.5-50.5
+// touch records or seen values streamed against 44.9-45.8, profiles/r06/nt_single_stores.txt).
+// Only the sums' responses are streamed: same box, three pairs, 45.40-45.66 -> 44.35-44.61 us per
+// 1M-op round (profiles/r06/synth_resp_nt.txt).
 constexpr int MS_TPB = 256;
 constexpr int MS_ITEMS = 8;
 constexpr int MS_TILE = MS_TPB * MS_ITEMS;
@@ -265,37 +240,25 @@ constexpr u32 SY_MAX_NB = 512, SY_MAX_HOT = 16, SY_MAX_TILES = 4096, SY_MAX_CW =
 // its seen values are then its value plus the touch's rank, so each part takes a contiguous
 // range of the touches. The bucket pass launches SY_MAX_NB workgroups in all (two per CU), so
 // words 1.. go to SY_MAX_NB - SY_B0_PARTS buckets.
-#ifndef NRG_SY_B0_PARTS
-#define NRG_SY_B0_PARTS 4
-#endif
-constexpr u32 SY_B0_PARTS = NRG_SY_B0_PARTS;
-#ifndef NRG_SYB_PER
-#define NRG_SYB_PER 10  // 1M-op rounds: 8 -> 57.2 us, 10 -> 56.4 (two passes per bucket, not three; E positions
-                        // recomputed, not kept per touch); 12 spills (profiles/r03_synth_pass_size.txt)
-#endif
+constexpr u32 SY_B0_PARTS = 4;
 // Rankings: the partition and the bucket pass's SET-free passes rank a wave's touches with one
 // returning LDS add per touch on a wave-private count. A returning LDS add hands the lanes of one
 // instruction that hit the same count their old values in lane order (checked on the hardware:
 // microbench/lds_add_order.hip, 2.1 G lanes; nrg_test_lds_add_order in the GPU suite), so the
 // ranks follow log order. Round 4's peer masks (OR, read back, leader update: three LDS round
 // trips per touch) ran 55.5 us per 1M-op round against 51.8 (profiles/r05_synth_lds_add.txt).
-#ifndef NRG_SYP_PD
-#define NRG_SYP_PD 1  // partition: wave rounds of op records in flight ahead of the one ranked
-#endif
-constexpr int SYP_PD = NRG_SYP_PD;
-constexpr int SYB_TPB = 512, SYB_WAVES = SYB_TPB / 64, SYB_PER = NRG_SYB_PER;
+constexpr int SYP_PD = 1;  // partition: wave rounds of op records in flight ahead of the one ranked
+constexpr int SYB_TPB = 512, SYB_WAVES = SYB_TPB / 64;
+// bucket-pass touches per thread per pass. 1M-op rounds: 8 -> 57.2 us, 10 -> 56.4 (two passes per
+// bucket, not three; E positions recomputed, not kept per touch); 12 spills (profiles/r03_synth_pass_size.txt)
+constexpr int SYB_PER = 10;
 constexpr int SYC_TPB = 512;
-#ifndef NRG_SYS_T
-// tiles per sum workgroup (A/B builds). With 1 the 489 sum workgroups of a 1M-op chunk queue
-// behind the partition tiles for the launch's LDS slots (3 per CU) and end ~4 us after them;
-// 2 puts every workgroup of the launch on the chip at once but doubles each sum workgroup's
-// span: 58.3-58.6 vs 56.6-57.2 us per round (profiles/r03_synth_sum_tiles.txt)
-#define NRG_SYS_T 1
-#endif
-#ifndef NRG_SYS_U
-#define NRG_SYS_U 10  // touch entries per thread in flight before their LDS adds
-#endif
-constexpr int SYS_T = NRG_SYS_T, SYS_U = NRG_SYS_U;
+// tiles per sum workgroup. With 1 the 489 sum workgroups of a 1M-op chunk queue behind the
+// partition tiles for the launch's LDS slots (3 per CU) and end ~4 us after them; 2 puts every
+// workgroup of the launch on the chip at once but doubles each sum workgroup's span: 58.3-58.6 vs
+// 56.6-57.2 us per round (profiles/r03_synth_sum_tiles.txt)
+constexpr int SYS_T = 1;
+constexpr int SYS_U = 10;  // touch entries per thread in flight before their LDS adds
 constexpr u32 NOTOUCH = 0xFFFFFFFFu;
 
 // Buckets of cold words (x relative to hot_reads). Cold word 0 has bucket 0 to itself: an op's
@@ -413,8 +376,6 @@ struct SyPartArgs {
     SyFlags* fl;
     u32 epoch;
     u64* dbg;  // NRG_EXP & 2 (diagnostic): phase stamps of tile t in row SY_DBG_PART + t
-    bool plain;    // plain stores for the log copy (default; st_out)
-    bool plain_e;  // plain stores for the touch records (default)
 };
 // rows of the diagnostic stamp buffer: bucket b in row b, partition tile t in SY_DBG_PART + t,
 // sum workgroup k in SY_DBG_SUM + k (tiles beyond 1024 are not stamped)
@@ -432,7 +393,6 @@ struct SySumArgs {
     u64* words;
     const u32* v32;  // the chunk's seen-value width flag (SyFlags::v32[par]): 1 = 4-B seen values
     u64* dbg;
-    bool plain;  // plain stores for the responses (default; st_out)
 };
 
 // LDS of a partition workgroup: ranking tables and staged words, then (same bytes) the tile's
@@ -497,7 +457,7 @@ __device__ __forceinline__ void sy_part_role(const SyPartArgs& A, u32 tile, SyPa
         if (orr + SYP_PD < SYA_OROUNDS && op0 + opw + (orr + SYP_PD) * 64 < n)
             nx[orr % SYP_PD] = src ? src[op0 + opw + (orr + SYP_PD) * 64]
                                    : ring[(lo + op0 + opw + (orr + SYP_PD) * 64) & ring_mask];
-        if (src && valid) st_op(&ring[(lo + op0 + opw + orr * 64) & ring_mask], o, A.plain);
+        if (src && valid) ring[(lo + op0 + opw + orr * 64) & ring_mask] = o;
         const bool set = valid && o.op == NRG_SYNTH_WRITE_ONLY;
         if (set && (o.tid >> 31)) A.fl->set_epoch[A.epoch & 1] = A.epoch;  // this chunk's seen values may pass 2^32
         if (set) A.fl->wo_epoch[A.epoch & 1] = A.epoch;                    // this chunk holds a WriteOnly
@@ -628,8 +588,8 @@ __device__ __forceinline__ void sy_part_role(const SyPartArgs& A, u32 tile, SyPa
     const u32 ne = nops * CW;
     for (u32 i = tid; 2 * i < ne; i += SYA_TPB) {
         const u32 a = s_u.stage[2 * i], b = 2 * i + 1 < ne ? s_u.stage[2 * i + 1] : 0u;
-        st_out(&Ewt[i], (u32)ent_w(a) | ((u32)ent_w(b) << 16), A.plain_e);
-        st_out(&Eot[i], (u32)ent_o(a) | ((u32)ent_o(b) << 16), A.plain_e);
+        Ewt[i] = (u32)ent_w(a) | ((u32)ent_w(b) << 16);
+        Eot[i] = (u32)ent_o(a) | ((u32)ent_o(b) << 16);
     }
     if (dbg) {
         dbg[4] = wall_clock64();
@@ -643,10 +603,7 @@ __device__ __forceinline__ void sy_part_role(const SyPartArgs& A, u32 tile, SyPa
 // w-th contiguous SYB_PER rounds of 64: wave-private per-word counts rank the wave's
 // touches without barriers, then per-word prefixes over the waves place them. A pass with a
 // WriteOnly in it is applied wave by wave instead (values depend on the last SET).
-// (<= 128 VGPRs: two 8-wave workgroups per CU)
-#ifndef NRG_SYB_WPE
-#define NRG_SYB_WPE 4  // waves per SIMD the bucket pass is compiled for (4: 128 VGPRs, two workgroups per CU)
-#endif
+constexpr int SYB_WPE = 4;  // waves per SIMD the bucket pass is compiled for (4: 128 VGPRs, two 8-wave workgroups per CU)
 // Arguments of the bucket pass of one chunk.
 struct SyBucketArgs {
     const u16* Ew;
@@ -663,7 +620,6 @@ struct SyBucketArgs {
     u32 epoch, vslot;  // the chunk's epoch; its seen values' slot (SyFlags::v32[vslot])
     u64* dbg;
     u32 stall;
-    bool plain;
 };
 // LDS of a bucket workgroup; its dynamic part (s_pre[ntiles + 1], s_off[ntiles] u16) follows
 template <int PER>
@@ -693,7 +649,6 @@ __device__ __forceinline__ void sy_bucket_role(const SyBucketArgs& B, u32 blk, u
     SyFlags* __restrict__ fl = B.fl;
     u64* __restrict__ dbg = B.dbg;
     const u32 stall = B.stall;
-    const bool plain = B.plain;
     // dbg (NRG_EXP & 2, diagnostic): per block, thread 0's wall clock at the phase edges
     // [0] start [1] prologue loaded [2] scanned, then summed over passes [3] tile map [4] gather
     // [5] rank + place [6] stores, [7] end, [8] passes
@@ -917,14 +872,14 @@ __device__ __forceinline__ void sy_bucket_role(const SyBucketArgs& B, u32 blk, u
             for (int q = 0; q < SYB_PER; q++)
                 if (base + (u32)w * (SYB_PER * 64) + q * 64 + lane < end) {
                     const u32 gp = gpos_of(base, cmap, base + (u32)w * (SYB_PER * 64) + q * 64 + lane);
-                    if (gp < vcap) st_out(&((u32*)V)[gp], (u32)sv[q], plain);
+                    if (gp < vcap) ((u32*)V)[gp] = (u32)sv[q];
                 }
         } else {
 #pragma unroll
             for (int q = 0; q < SYB_PER; q++)
                 if (base + (u32)w * (SYB_PER * 64) + q * 64 + lane < end) {
                     const u32 gp = gpos_of(base, cmap, base + (u32)w * (SYB_PER * 64) + q * 64 + lane);
-                    if (gp < vcap) st_out(&V[gp], sv[q], plain);
+                    if (gp < vcap) V[gp] = sv[q];
                 }
         }
         // the stores above read this pass's tile map (cmap); the next pass's map is built into
@@ -956,7 +911,7 @@ __device__ __forceinline__ void sy_bucket_role(const SyBucketArgs& B, u32 blk, u
 #undef SY_ACC
 }
 
-__global__ __launch_bounds__(SYB_TPB) __attribute__((amdgpu_waves_per_eu(NRG_SYB_WPE))) void sy_bucket_kernel(SyBucketArgs B) {
+__global__ __launch_bounds__(SYB_TPB) __attribute__((amdgpu_waves_per_eu(SYB_WPE))) void sy_bucket_kernel(SyBucketArgs B) {
     extern __shared__ u32 s_dyn[];  // s_pre[ntiles + 1], s_off[ntiles] (u16)
     __shared__ SyBucketLds<SYB_PER> L;
     sy_bucket_role<SYB_PER>(B, blockIdx.x, gridDim.x, L, s_dyn);
@@ -1020,13 +975,8 @@ __device__ __forceinline__ void sy_sum_role(const SySumArgs& S, u32 blk, u64* s_
         for (u32 i = tid; i < nops; i += SYC_TPB) {
             const u64 g = lo + op0 + i;
             if (g >= resp_lo && g < resp_hi) {
-#if NRG_SY_RESP_NT
                 __builtin_nontemporal_store(s_sum[i], &resp[g - resp_lo]);
                 if (some) __builtin_nontemporal_store((uint8_t)1, &some[g - resp_lo]);
-#else
-                st_out(&resp[g - resp_lo], s_sum[i], S.plain);
-                if (some) st_out(&some[g - resp_lo], (uint8_t)1, S.plain);
-#endif
             }
         }
     }
@@ -1163,7 +1113,6 @@ static SySumArgs sy_sum_args(nrg_ctx* c, const SyDeferred& d) {
     S.words = c->sy.d_words;
     S.v32 = &x.fl->v32[d.epoch & 1];
     S.dbg = (c->exp & 2) ? c->d_dbg : nullptr;
-    S.plain = !((c->exp >> 9) & 1);
     return S;
 }
 
@@ -1198,7 +1147,6 @@ static SyBucketArgs sy_bucket_args(nrg_ctx* c, const SyDeferred& d) {
     B.vslot = d.epoch & 1;
     B.dbg = (c->exp & 2) ? c->d_dbg : nullptr;
     B.stall = c->stall;
-    B.plain = !((c->exp >> 8) & 1);
     return B;
 }
 
@@ -1230,8 +1178,6 @@ static SyPartArgs sy_part_args(nrg_ctx* c, u64 lo, u64 n, const nrg_synth_op* sr
     A.fl = x.fl;
     A.epoch = epoch;
     A.dbg = (c->exp & 2) ? c->d_dbg : nullptr;
-    A.plain = !((c->exp >> 6) & 1);
-    A.plain_e = !((c->exp >> 7) & 1);
     return A;
 }
 
@@ -1256,10 +1202,11 @@ static hipError_t sy_launch_part(nrg_ctx* c, const SyPartArgs& A, const SySumArg
 // partition streams records at memory bandwidth, the bucket pass is LDS- and latency-bound),
 // and the sums follow. No role waits on another in the launch: the three chunks share no buffer.
 constexpr u32 SY_FUSED_WG = SY_MAX_NB;  // = the bucket pass's workgroups: 2 per CU on 256 CUs
-#ifndef NRG_SYF_PER
-#define NRG_SYF_PER 10  // bucket-pass touches per thread per pass in the fused kernel
-#endif
-constexpr int SYF_PER = NRG_SYF_PER;
+constexpr int SYF_PER = 10;  // bucket-pass touches per thread per pass in the fused kernel (as SYB_PER)
+// workgroups below this partition first: the first of each CU's two (0 .. 255, one per CU). Passed
+// to the kernel as an argument (part_first_below), always this value: compiled in as a constant the
+// 1M-op round measured 2 % slower on one box (44.7-45.1 us against 43.8-44.4 as an argument).
+constexpr u32 SY_PART_FIRST = SY_FUSED_WG / 2;
 // The roles read their arguments through a laundered kernarg pointer at their point of use:
 // the compiler cannot then keep the fields of the roles that run later live in registers across
 // the roles that run first (kept live, they pushed the bucket role from 125 VGPRs into scratch).
@@ -1283,7 +1230,7 @@ __device__ __forceinline__ void sy_round_part(u32 w, unsigned char* s_raw) {
     }
 }
 template <int CW>
-__global__ __launch_bounds__(SYB_TPB) __attribute__((amdgpu_waves_per_eu(NRG_SYB_WPE))) void sy_round_kernel(
+__global__ __launch_bounds__(SYB_TPB) __attribute__((amdgpu_waves_per_eu(SYB_WPE))) void sy_round_kernel(
     SyPartArgs A, SyBucketArgs B, SySumArgs S, u32 nblk_b, u32 part_first_below) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     const u32 w = blockIdx.x;
@@ -1322,9 +1269,6 @@ static hipError_t sy_launch_fused(nrg_ctx* c, const SyPartArgs& A, const SyDefer
         dyn_b = ((sizeof(SyBucketLds<SYF_PER>) + 15) & ~(size_t)15) + sy_bucket_dyn_bytes(B.ntiles);
     }
     hipStream_t st = c->stream;
-    // the first of each CU's two workgroups (0 .. 255, one per CU) partitions first (A/B, NRG_KNOB_EXP
-    // bit 12: every workgroup partitions first; bit 13: every workgroup replays its bucket first)
-    const u32 pfb = (c->exp & 0x1000) ? SY_FUSED_WG : (c->exp & 0x2000) ? 0u : SY_FUSED_WG / 2;
 #define SY_FUSED(CWV)                                                                                      \
     case CWV: {                                                                                            \
         const size_t dyn = std::max(sizeof(SyPartLds<CWV>), dyn_b);                                        \
@@ -1333,7 +1277,7 @@ static hipError_t sy_launch_fused(nrg_ctx* c, const SyPartArgs& A, const SyDefer
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);     \
             if (e_ != hipSuccess) return e_;                                                               \
         }                                                                                                  \
-        sy_round_kernel<CWV><<<SY_FUSED_WG, SYB_TPB, dyn, st>>>(A, B, S, nblk_b, pfb);                     \
+        sy_round_kernel<CWV><<<SY_FUSED_WG, SYB_TPB, dyn, st>>>(A, B, S, nblk_b, SY_PART_FIRST);           \
         break;                                                                                             \
     }
     switch (cf.synth_cold_writes) {

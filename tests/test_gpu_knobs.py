@@ -33,7 +33,8 @@ KNOB_TABLE = {
     "SKEW_EVERY": (HM, [1, 1 << 30, 16], [0, (1 << 30) + 1]),
     "EPOCH_LIMIT": (HM, [0xFFFFFFF0], [1, 0, 0xFFFFFFF1]),
     "K1": (HM, [1, 2, 4, 0], [5]),
-    "EXP": (ALL, [2, 0], [1 << 32]),
+    # two bits: 2 phase timestamps, 0x10000 one-rank group moves its data; a retired ablation bit is refused
+    "EXP": (ALL, [2, 0x10000, 0x10002, 0], [1, 0x40, 0x80, 0x1000, 0x8000, 0x100000, 1 << 32]),
     "SY_SORT": (SY, [1, 0], [2]),
     "PIPELINE": (ALL, [1, 0], [2]),
     "SY_FUSED": (SY, [0, 1], [2]),
