@@ -18,6 +18,8 @@
  *   nrg_hashmap_round_async       Replica::combine (append+exec) + read batch   nr/src/replica.rs:544-595
  *   nrg_hashmap_prefill*          NrHashMap::default                 benches/hashmap.rs:91-100
  *   nrg_hashmap_dump / digest     Replica::verify(closure)           nr/src/replica.rs:443-467
+ *   nrg_digest* / nrg_group_verify Replica::verify on the device: one  nr/src/replica.rs:443-467
+ *                                 triple per replica, every kind
  *   nrg_stack_*                   Stack Dispatch                     benches/stack.rs:36-84, nr/tests/stack.rs:31-96
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
  *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
@@ -219,6 +221,28 @@ int nrg_sync(nrg_ctx* ctx);
 /* Order outstanding side-stream reads (config.pipeline = 1) on the context's stream without
  * blocking the host; a no-op when nothing is outstanding. */
 int nrg_join(nrg_ctx* ctx);
+
+/* Replica::verify (nr/src/replica.rs:443-467) without the state leaving the GPU: a digest of the
+ * replica's data structure, the same definition for every kind. out = {count, sum, xor} over the
+ * structure's items of h = mix64(k ^ mix64(v)) (mix64: the splitmix64 finaliser; the sum wraps in
+ * u64), with (k, v) per kind:
+ *   hashmap    (key, value)                                  (= nrg_hashmap_digest)
+ *   stack      (index from the bottom, the u32 element zero-extended)
+ *   queue      (index from the front, the element): the logical position, not the ring slot
+ *   synthetic  (word index, the word); count = synth_n
+ *   vspace     (the leaf's first virtual address as nrg_vspace_dump reports it, the leaf entry),
+ *              4 KiB and 2 MiB leaves alike; inner entries contribute nothing
+ * An empty structure gives {0, 0, 0}; the triple depends on the contents alone, not on the table's
+ * size, the ring position or the order in which page tables were allocated. Two replicas that
+ * replayed the same log hold equal triples; nrgpu/digest.py computes the triple from a host
+ * snapshot or a CPU model. Both calls first launch what the last chunk deferred
+ * (config.pipeline = 1) and digest the state replayed so far: they do not need ltail == tail.
+ * Like the dumps and every direct call, they are not allowed while a combiner is open on the
+ * context. nrg_digest_async takes a device pointer to three u64, is ordered on the context's
+ * stream and makes no host round trip; the page table's first digest allocates 8 B per pool table
+ * of scratch. */
+int nrg_digest(nrg_ctx* ctx, uint64_t out[3]);
+int nrg_digest_async(nrg_ctx* ctx, uint64_t* d_out3);
 
 const char* nrg_strerror(int code);
 /* Library build identifier ("nrgpu <version> gfx950"). */
@@ -510,6 +534,17 @@ int nrg_group_set_input_stream(nrg_group* g, int member, void* hip_stream);
 int nrg_group_round_async(nrg_group* g, const nrg_round* rounds, const uint64_t* seg_lens);
 /* Wait for all queued group work and report latched device errors of every local replica. */
 int nrg_group_sync(nrg_group* g);
+/* Replica::verify (nr/src/replica.rs:443-467) across the group: are the replicas identical? A
+ * collective: every rank calls it. It completes queued group work as nrg_group_sync does (a posted
+ * partitioned round included, latched device errors reported), runs nrg_digest_async on every
+ * local member's replica stream, all-gathers the three words per rank on the comm stream and reads
+ * them back under the group's deadline (a missing peer: NRG_E_TIMEOUT). `digests` (nullable)
+ * receives nranks * 3 words in rank order; *identical = 1 iff every rank's triple is the same. A
+ * difference is a result, not an error: the call returns NRG_OK and the group stays usable. A rank
+ * whose own sync reported a latched device error still takes part and then returns that error.
+ * The members of a partitioned group hold one partition each, so *identical is 0 by design there:
+ * such callers add the triples (count and sum add, xor xors) and compare with the whole map's. */
+int nrg_group_verify(nrg_group* g, uint64_t* digests, int* identical);
 /* Deadline of every wait on the peer ranks (default NRG_GROUP_DEFAULT_TIMEOUT_MS): the host round
  * trips of the length / count exchanges, buffer regrowth and nrg_group_sync. A rank whose peers do
  * not post their part of a collective in time gets NRG_E_TIMEOUT instead of hanging (its

@@ -31,6 +31,10 @@ int nrg_test_ring_read(nrg_ctx* ctx, uint64_t phys, void* out);
 /* diagnostic phase timestamps of the last replay (a stack or synthetic context with NRG_KNOB_EXP
  * bit 2 set); NRG_E_INVAL when `words` exceeds the buffer */
 int nrg_test_debug_read(nrg_ctx* ctx, uint64_t* out, uint64_t words);
+/* copy the 512 entries of pool table `table` (< the pool's size) of a page-table context to host
+ * memory `out`, inner entries as stored; syncs first. Lets tests see that two replicas whose leaves
+ * agree allocated their tables in different orders. */
+int nrg_test_vspace_table(nrg_ctx* ctx, uint64_t table, uint64_t out[512]);
 
 /* Tuning and diagnostic knobs of an OPEN context. The product never reads the environment:
  * these setters are the only way to change them, so a stray variable in a caller's environment

@@ -109,6 +109,48 @@ __device__ __forceinline__ void test_stall(u32 on, int wave) {
         for (int i = 0; i < 32; i++) __builtin_amdgcn_s_sleep(127);
 }
 
+// The state digest (nrg_digest, Replica::verify nr/src/replica.rs:443-467): {count, sum, xor} of
+// dg_item(k, v) over a structure's items; (k, v) per kind is in include/nrgpu.h. Every kind's
+// digest kernel runs workgroups of DG_TPB lanes and ends in dg_commit.
+constexpr int DG_TPB = 256;
+constexpr u32 DG_MAX_GRID = 1024;
+__host__ __device__ __forceinline__ u64 dg_item(u64 k, u64 v) { return mix64(k ^ mix64(v)); }
+// workgroups of a grid-stride digest over at most `items` items
+inline u32 dg_grid(u64 items) {
+    const u64 g = (items + DG_TPB - 1) / DG_TPB;
+    return g < 1 ? 1u : (g > DG_MAX_GRID ? DG_MAX_GRID : (u32)g);
+}
+// Every lane's partial triple, reduced per wave, then per workgroup, then added into out3 (zeroed
+// earlier in stream order) with one set of atomics per workgroup that found anything.
+__device__ __forceinline__ void dg_commit(u64 c, u64 sm, u64 x, u64* out3) {
+    __shared__ u64 s_dg[3][DG_TPB / 64];
+    for (int off = 32; off > 0; off >>= 1) {
+        c += __shfl_xor(c, off, 64);
+        sm += __shfl_xor(sm, off, 64);
+        x ^= __shfl_xor(x, off, 64);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_dg[0][w] = c;
+        s_dg[1][w] = sm;
+        s_dg[2][w] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        c = sm = x = 0;
+        for (int v = 0; v < DG_TPB / 64; v++) {
+            c += s_dg[0][v];
+            sm += s_dg[1][v];
+            x ^= s_dg[2][v];
+        }
+        if (c) {
+            atomicAdd(&out3[0], c);
+            atomicAdd(&out3[1], sm);
+            atomicXor(&out3[2], x);
+        }
+    }
+}
+
 // Wave-wide (64-lane) inclusive scan helpers.
 __device__ __forceinline__ u32 lane_id() { return threadIdx.x & 63; }
 

@@ -137,6 +137,10 @@ struct Member {
     uint64_t* lx = nullptr;
     uint64_t* glx = nullptr;
     uint64_t* h_glx = nullptr;  // pinned host copy of glx
+    //   dg      this member's digest triple (nrg_group_verify); gdg every rank's
+    uint64_t* dg = nullptr;
+    uint64_t* gdg = nullptr;
+    uint64_t* h_gdg = nullptr;  // pinned host copy of gdg
     void* xmem = nullptr;
 };
 
@@ -200,7 +204,7 @@ int member_init(Member& m, int nranks) {
         GCHK(hipEventCreateWithFlags(&m.freed[b], hipEventDisableTiming));
     }
     const uint64_t G = (uint64_t)nranks;
-    GCHK(hipMalloc(&m.xmem, (NBUF * (2 + 2 * G) + 2 + 2 * G) * 8));
+    GCHK(hipMalloc(&m.xmem, (NBUF * (2 + 2 * G) + 2 + 2 * G + 3 + 3 * G) * 8));
     uint64_t* x = (uint64_t*)m.xmem;
     for (int b = 0; b < NBUF; b++, x += 2 + 2 * G) {
         m.hdr[b] = x;
@@ -208,7 +212,10 @@ int member_init(Member& m, int nranks) {
     }
     m.lx = x;
     m.glx = x + 2;
+    m.dg = x + 2 + 2 * G;
+    m.gdg = m.dg + 3;
     GCHK(hipHostMalloc(&m.h_glx, 2 * G * 8, hipHostMallocDefault));
+    GCHK(hipHostMalloc(&m.h_gdg, 3 * G * 8, hipHostMallocDefault));
     // the fixed-size buffers of a partitioned round's count and status exchanges
     const uint64_t CW = 2 * G + XW_N;
     for (int q = 0; q < PT_DEPTH; q++) {
@@ -256,6 +263,7 @@ void member_free(Member& m, const Rccl* R) {
     if (m.sbuf) (void)hipFree(m.sbuf);
     if (m.xmem) (void)hipFree(m.xmem);
     if (m.h_glx) (void)hipHostFree(m.h_glx);
+    if (m.h_gdg) (void)hipHostFree(m.h_gdg);
     for (DBuf& d : m.pt)
         if (d.p) (void)hipFree(d.p);
     for (int q = 0; q < PT_DEPTH; q++) {
@@ -1136,6 +1144,46 @@ int nrg_group_sync(nrg_group* g) {
             r = group_fail(g, NRG_E_INVAL, "ranks disagreed on a round's segment lengths: replicas diverged");
         if (r && rc == NRG_OK) rc = r;
     }
+    return rc;
+}
+
+// Replica::verify (nr/src/replica.rs:443-467) across the group: every rank's digest triple, all-
+// gathered. Members of a partitioned group hold one partition each, so their triples differ by
+// design (*identical = 0): such callers add them (count and sum add, xor xors).
+int nrg_group_verify(nrg_group* g, uint64_t* digests, int* identical) {
+    if (!g || !identical) return NRG_E_INVAL;
+    if (g->broken) return g->broken;
+    const Rccl* R = g->R;
+    if (!R) return NRG_E_COMM;
+    const int nl = (int)g->m.size(), G = g->nranks;
+    // queued group work first; a latched device error of this rank (not sticky) is reported at the
+    // end: the rank still posts its part, so that its peers are not left inside the collective
+    const int rc = nrg_group_sync(g);
+    if (g->broken) return g->broken;
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        RCHK(nrg::ctx_use_device(m.ctx));
+        RCHK(nrg_digest_async(m.ctx, m.dg));
+        RCHK(order(m, m.ctx->stream, m.cstream));
+    }
+    if (R->group_start() != ncclSuccess) return NRG_E_COMM;
+    ncclResult_t res = ncclSuccess;
+    for (int i = 0; i < nl && res == ncclSuccess; i++)
+        res = R->all_gather(g->m[i].dg, g->m[i].gdg, 3, ncclUint64, g->m[i].comm, g->m[i].cstream);
+    RCHK(group_end(g, "verify"));
+    if (res != ncclSuccess) return group_fail(g, NRG_E_COMM, "verify: all-gather refused");
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        RCHK(nrg::ctx_use_device(m.ctx));
+        GCHK(hipMemcpyAsync(m.h_gdg, m.gdg, 3 * (uint64_t)G * 8, hipMemcpyDeviceToHost, m.cstream));
+        RCHK(wait_stream(g, m.cstream, "verify"));
+    }
+    const uint64_t* H = g->m[0].h_gdg;  // identical on every rank
+    int same = 1;
+    for (int r = 1; r < G; r++)
+        if (std::memcmp(H, H + 3 * r, 24) != 0) same = 0;
+    if (digests) std::memcpy(digests, H, 3 * (uint64_t)G * 8);
+    *identical = same;
     return rc;
 }
 

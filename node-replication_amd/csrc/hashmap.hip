@@ -2226,9 +2226,11 @@ static int hm_set_knob(nrg_ctx* c, int knob, uint64_t v) {
 // NRG_KNOB_EXP bit 2: 8 words per partition-round apply bucket
 static u64 hm_dbg_words(const nrg_ctx*) { return (u64)HM_BK_MAX * 8; }
 
+static hipError_t hm_digest(nrg_ctx* c, u64* d_out3);
+
 const DsOps* hm_ops() {
     static const DsOps ops = {sizeof(nrg_put), sizeof(u64), hm_open, hm_close, hm_flush, hm_replay,
-                              hm_floor, hm_set_knob, hm_dbg_words, nullptr};
+                              hm_floor, hm_set_knob, hm_dbg_words, nullptr, hm_digest};
     return &ops;
 }
 
@@ -2484,12 +2486,7 @@ int nrg_hashmap_dump(nrg_ctx* c, uint64_t* keys, uint64_t* vals, uint64_t cap, u
 int nrg_hashmap_digest(nrg_ctx* c, uint64_t out[3]) {
     int r = need(c, NRG_DS_HASHMAP);
     if (r) return r;
-    Staging* s = c->stg;
-    if ((r = staging(s[3], 64))) return r;
-    HIPCHK(hm_digest(c, (u64*)s[3].p));
-    HIPCHK(hipMemcpyAsync(out, s[3].p, 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_all(c));
-    return check_err(c);
+    return nrg_digest(c, out);
 }
 
 int nrg_test_hm_skewed(nrg_ctx* c, int* out) {

@@ -188,6 +188,7 @@ struct VsHost {  // page table (vspace.hip)
     uint64_t cap = 0;
     VsState* d_state = nullptr;
     void* d_aux = nullptr;  // per-op scratch of one chunk
+    uint64_t* d_tag = nullptr;  // the digest's tag per pool table, allocated by the first digest
 };
 
 struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*
@@ -235,6 +236,9 @@ struct DsOps {
     u64 (*dbg_words)(const nrg_ctx* c);
     // where the kind's nrg_config defaults differ from the common ones (nullptr: nowhere)
     void (*defaults)(nrg_config* cfg);
+    // nrg_digest: zero d_out3 and add {count, sum, xor} of mix64(k ^ mix64(v)) over the structure's
+    // items into it (common.hpp dg_item), on the context's stream, with nothing read on the host
+    hipError_t (*digest)(nrg_ctx* c, u64* d_out3);
 };
 const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind

@@ -421,9 +421,34 @@ static void qu_close(nrg_ctx* c) {
 
 static hipError_t qu_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
 
+// nrg_digest: item i from the front is (i, q[(head + i) & mask]): the logical position, whatever
+// ring slot holds it; head and the length are read here, the length clamped as nrg_queue_len clamps it
+__global__ __launch_bounds__(DG_TPB) void qu_digest_kernel(const u64* __restrict__ q, u64 qmask, const QuState* st,
+                                                           u64 cap, u64* out3) {
+    const u64 head = st->head;
+    const u64 n = st->len > cap ? cap : st->len;
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 h = dg_item(i, q[(head + i) & qmask]);
+        c++;
+        sm += h;
+        x ^= h;
+    }
+    dg_commit(c, sm, x, out3);
+}
+
+static hipError_t qu_digest(nrg_ctx* c, u64* d_out3) {
+    hipError_t e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream);
+    if (e != hipSuccess) return e;
+    NRG_LAUNCH(c, "qu_digest", qu_digest_kernel, dg_grid(c->cfg.queue_capacity), DG_TPB, 0, c->stream,
+               (const u64*)c->qu.d_queue, (u64)(c->qu.size - 1), (const QuState*)c->qu.d_state,
+               (u64)c->cfg.queue_capacity, d_out3);
+    return hipGetLastError();
+}
+
 const DsOps* qu_ops() {
     static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk,
-                              floor_ltail, nullptr, nullptr, nullptr};
+                              floor_ltail, nullptr, nullptr, nullptr, qu_digest};
     return &ops;
 }
 

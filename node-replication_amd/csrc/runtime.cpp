@@ -406,6 +406,28 @@ int nrg_join(nrg_ctx* c) {
     return NRG_OK;
 }
 
+// Replica::verify (nr/src/replica.rs:443-467) without the state leaving the device: the kind's
+// digest of what has been replayed so far, after what the last chunk deferred.
+int nrg_digest_async(nrg_ctx* c, uint64_t* d_out3) {
+    if (!c || !d_out3) return NRG_E_INVAL;
+    int r = use_device(c);
+    if (r) return r;
+    HIPCHK(flush_deferred(c));
+    HIPCHK(c->ops->digest(c, d_out3));
+    return NRG_OK;
+}
+
+int nrg_digest(nrg_ctx* c, uint64_t out[3]) {
+    if (!c || !out) return NRG_E_INVAL;
+    int r = use_device(c);
+    if (r) return r;
+    if ((r = staging(c->stg[3], 64))) return r;
+    if ((r = nrg_digest_async(c, (uint64_t*)c->stg[3].p))) return r;
+    HIPCHK(hipMemcpyAsync(out, c->stg[3].p, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
 // ---- Log -------------------------------------------------------------------------------
 static int append_common(nrg_ctx* c, const void* recs, uint64_t n, uint32_t origin, uint64_t* first_idx,
                          hipMemcpyKind kind) {

@@ -968,9 +968,35 @@ static void st_close(nrg_ctx* c) {
 // NRG_KNOB_EXP bit 2: 16 words per tile, the finish workgroups' from row 128 on (st_round_kernel)
 static u64 st_dbg_words(const nrg_ctx* c) { return std::max<u64>(256, (c->cfg.max_batch + 2047) / 2048) * 16; }
 
+// nrg_digest: item i from the bottom is (i, stack[i]); the length is read here, clamped as
+// nrg_stack_len clamps it
+__global__ __launch_bounds__(DG_TPB) void st_digest_kernel(const u32* __restrict__ stack, const DevCtl* ctl, u64 cap,
+                                                           u64* out3) {
+    long long d = ctl->depth;
+    if (d < 0) d = 0;
+    const u64 n = (u64)d > cap ? cap : (u64)d;
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 h = dg_item(i, stack[i]);
+        c++;
+        sm += h;
+        x ^= h;
+    }
+    dg_commit(c, sm, x, out3);
+}
+
+static hipError_t st_digest(nrg_ctx* c, u64* d_out3) {
+    hipError_t e = st_flush(c);  // a deferred chunk finish commits the length
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream)) != hipSuccess) return e;
+    NRG_LAUNCH(c, "st_digest", st_digest_kernel, dg_grid(c->cfg.stack_capacity), DG_TPB, 0, c->stream,
+               (const u32*)c->st.d_stack, (const DevCtl*)c->d_ctl, (u64)c->cfg.stack_capacity, d_out3);
+    return hipGetLastError();
+}
+
 const DsOps* st_ops() {
     static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk,
-                              floor_ltail, nullptr, st_dbg_words, nullptr};
+                              floor_ltail, nullptr, st_dbg_words, nullptr, st_digest};
     return &ops;
 }
 

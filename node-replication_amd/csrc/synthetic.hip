@@ -1529,9 +1529,30 @@ static int sy_set_knob(nrg_ctx* c, int knob, uint64_t v) {
 // NRG_KNOB_EXP bit 2: 16 words per bucket, partition tile and sum workgroup
 static u64 sy_dbg_words(const nrg_ctx*) { return (u64)SY_DBG_ROWS * 16; }
 
+// nrg_digest: item i is (i, words[i]), all synth_n of them
+__global__ __launch_bounds__(DG_TPB) void sy_digest_kernel(const u64* __restrict__ words, u64 n, u64* out3) {
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 h = dg_item(i, words[i]);
+        c++;
+        sm += h;
+        x ^= h;
+    }
+    dg_commit(c, sm, x, out3);
+}
+
+static hipError_t sy_digest(nrg_ctx* c, u64* d_out3) {
+    hipError_t e = sy_flush(c);  // deferred sums fold the hot words
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream)) != hipSuccess) return e;
+    NRG_LAUNCH(c, "sy_digest", sy_digest_kernel, dg_grid(c->cfg.synth_n), DG_TPB, 0, c->stream,
+               (const u64*)c->sy.d_words, (u64)c->cfg.synth_n, d_out3);
+    return hipGetLastError();
+}
+
 const DsOps* sy_ops() {
     static const DsOps ops = {sizeof(nrg_synth_op), sizeof(u64), sy_open, sy_close, sy_flush, sy_replay_chunk,
-                              sy_floor, sy_set_knob, sy_dbg_words, nullptr};
+                              sy_floor, sy_set_knob, sy_dbg_words, nullptr, sy_digest};
     return &ops;
 }
 

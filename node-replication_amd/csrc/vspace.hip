@@ -594,9 +594,96 @@ static void vs_close(nrg_ctx* c) {
     (void)hipFree(c->vs.d_pool);
     (void)hipFree(c->vs.d_state);
     (void)hipFree(c->vs.d_aux);
+    (void)hipFree(c->vs.d_tag);
 }
 
 static hipError_t vs_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
+
+// ---- nrg_digest: {count, sum, xor} of dg_item(leaf's first vaddr, leaf entry) over the leaves ----
+// A pool table knows neither its level nor the addresses it maps, so the digest goes top-down, a
+// launch per level, none of which waits on another workgroup. tag[t] = base vaddr of table t |
+// (level + 1), level 3 = PML4 .. 0 = PT; the low 12 bits of a base are free and 0 = never reached.
+// Tables are never freed or moved and never change level, so a tag an earlier digest wrote is
+// still right and a pass that writes it again stores the same value.
+//   level 3   one workgroup: the PML4 tags its PDPTs and zeroes the output
+//   level 2   the tables tagged as PDPTs tag their PDs
+//   level 1   the tables tagged as PDs hash their 2 MiB leaves and tag their PTs
+//   level 0   the tables tagged as PTs hash their leaves
+// Levels 2..0 grid-stride over the tables [1, ntables) with ntables read on the device, a wave per
+// table: four 16-B loads per lane, each instruction 1 KiB contiguous. A table is read by the pass of
+// its level alone, so a digest reads every allocated table once: ntables * 4 KiB, plus 8 B of tag
+// per table in each of the three passes. A child index >= ntables is skipped, as vs_collect skips it.
+constexpr u32 VS_DG_MAX_GRID = 2048;
+
+template <int LEVEL>
+__device__ __forceinline__ void vs_digest_entry(u64 e, u64 base, u32 idx, u64 ntab, u64* tag, u64& c, u64& sm,
+                                                u64& x) {
+    if (!(e & VS_P)) return;
+    const u64 va = base | ((u64)idx << (12 + 9 * LEVEL));
+    if (LEVEL == 0 || (LEVEL == 1 && (e & VS_PS))) {
+        const u64 h = dg_item(va, e);
+        c++;
+        sm += h;
+        x ^= h;
+    } else {
+        const u64 child = (e & VS_ADDR) >> 12;
+        if (child != 0 && child < ntab) tag[child] = va | (u64)LEVEL;  // the child's level + 1
+    }
+}
+
+template <int LEVEL>
+__device__ __forceinline__ void vs_digest_table(const u64* __restrict__ tab, u64 base, u64 ntab, u64* tag, u64& c,
+                                                u64& sm, u64& x) {
+    const u32 lane = threadIdx.x & 63;
+#pragma unroll
+    for (u32 q = 0; q < 4; q++) {
+        const u32 idx = q * 128 + lane * 2;
+        const ulonglong2 e = *(const ulonglong2*)(tab + idx);
+        vs_digest_entry<LEVEL>(e.x, base, idx, ntab, tag, c, sm, x);
+        vs_digest_entry<LEVEL>(e.y, base, idx + 1, ntab, tag, c, sm, x);
+    }
+}
+
+__global__ __launch_bounds__(DG_TPB) void vs_digest_root_kernel(const u64* __restrict__ pool, const VsState* st,
+                                                                u64 cap, u64* tag, u64* out3) {
+    const u64 ntab = st->ntables < cap ? st->ntables : cap;
+    if (threadIdx.x < 3) out3[threadIdx.x] = 0;
+    u64 c = 0, sm = 0, x = 0;  // (a PML4 slot is never a leaf)
+    if (threadIdx.x < 64) vs_digest_table<3>(pool, 0, ntab, tag, c, sm, x);
+}
+
+template <int LEVEL>
+__global__ __launch_bounds__(DG_TPB) void vs_digest_level_kernel(const u64* __restrict__ pool, const VsState* st,
+                                                                 u64 cap, u64* tag, u64* out3) {
+    const u64 ntab = st->ntables < cap ? st->ntables : cap;
+    const u64 waves = (u64)gridDim.x * (DG_TPB / 64);
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 t = 1 + blockIdx.x * (u64)(DG_TPB / 64) + (threadIdx.x >> 6); t < ntab; t += waves) {
+        const u64 tg = tag[t];  // the same in every lane of the wave
+        if ((tg & 4095) != (u64)LEVEL + 1) continue;
+        vs_digest_table<LEVEL>(pool + t * 512, tg & ~4095ull, ntab, tag, c, sm, x);
+    }
+    if (LEVEL <= 1) dg_commit(c, sm, x, out3);
+}
+
+static hipError_t vs_digest(nrg_ctx* c, u64* d_out3) {
+    hipError_t e;
+    if (!c->vs.d_tag) {
+        if ((e = hipMalloc(&c->vs.d_tag, c->vs.cap * sizeof(u64))) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(c->vs.d_tag, 0, c->vs.cap * sizeof(u64), c->stream)) != hipSuccess) return e;
+    }
+    const u64* pool = c->vs.d_pool;
+    const VsState* st = c->vs.d_state;
+    u64* tag = c->vs.d_tag;
+    const u64 cap = c->vs.cap;
+    const u64 g = (cap + DG_TPB / 64 - 1) / (DG_TPB / 64);
+    const unsigned grid = g > VS_DG_MAX_GRID ? VS_DG_MAX_GRID : (unsigned)g;
+    NRG_LAUNCH(c, "vs_digest", vs_digest_root_kernel, 1, DG_TPB, 0, c->stream, pool, st, cap, tag, d_out3);
+    NRG_LAUNCH(c, "vs_digest", vs_digest_level_kernel<2>, grid, DG_TPB, 0, c->stream, pool, st, cap, tag, d_out3);
+    NRG_LAUNCH(c, "vs_digest", vs_digest_level_kernel<1>, grid, DG_TPB, 0, c->stream, pool, st, cap, tag, d_out3);
+    NRG_LAUNCH(c, "vs_digest", vs_digest_level_kernel<0>, grid, DG_TPB, 0, c->stream, pool, st, cap, tag, d_out3);
+    return hipGetLastError();
+}
 
 static void vs_defaults(nrg_config* cfg) {
     cfg->log2_slots = 18;       // the pool: 2^18 tables of 4 KiB, 1 GiB
@@ -605,7 +692,7 @@ static void vs_defaults(nrg_config* cfg) {
 
 const DsOps* vs_ops() {
     static const DsOps ops = {sizeof(nrg_vspace_op), sizeof(nrg_vspace_resp), vs_open, vs_close, vs_flush,
-                              vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults};
+                              vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults, vs_digest};
     return &ops;
 }
 
@@ -662,6 +749,15 @@ int nrg_vspace_tables(nrg_ctx* c, uint64_t* n) {
     if (r) return r;
     if (!n) return NRG_E_INVAL;
     return vs_get_tables(c, n);
+}
+
+int nrg_test_vspace_table(nrg_ctx* c, uint64_t table, uint64_t out[512]) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (!out || table >= c->vs.cap) return NRG_E_INVAL;
+    HIPCHK(hipMemcpyAsync(out, c->vs.d_pool + table * 512, 4096, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
 }
 
 // The leaves below table `tab` of level `level` (3 = PML4 .. 0 = PT) in ascending vaddr: slots are

@@ -127,6 +127,9 @@ SIGNATURES = {
     "nrg_own_stream": (vp, [vp]),
     "nrg_sync": (C.c_int, [vp]),
     "nrg_join": (C.c_int, [vp]),
+    "nrg_digest": (C.c_int, [vp, vp]),
+    "nrg_digest_async": (C.c_int, [vp, vp]),
+    "nrg_group_verify": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
     "nrg_strerror": (C.c_char_p, [C.c_int]),
     "nrg_version": (C.c_char_p, []),
     "nrg_device_count": (C.c_int, []),
@@ -217,6 +220,7 @@ TEST_SIGNATURES = {
     "nrg_test_lds_add_order": (C.c_int, [vp, u32, u32, u32, vp]),
     "nrg_test_ring_read": (C.c_int, [vp, u64, vp]),
     "nrg_test_debug_read": (C.c_int, [vp, vp, u64]),
+    "nrg_test_vspace_table": (C.c_int, [vp, u64, vp]),
     "nrg_test_hm_skewed": (C.c_int, [vp, vp]),
     "nrg_test_set_knob": (C.c_int, [vp, C.c_int, u64]),
     "nrg_test_loopback_collectives": (C.c_int, [C.c_int]),

@@ -116,6 +116,19 @@ class ReplicaGroup:
     def sync(self):
         self._check(self._lib.nrg_group_sync(self._h), "nrg_group_sync")
 
+    def verify(self):
+        """nrg_group_verify (a collective: every rank calls it): (identical, digests), digests an
+        ndarray [world, 3] of every rank's (count, sum, xor) in rank order. Replicas that differ
+        are a result (identical False), not an error. The members of a partitioned group hold one
+        partition each, so they are never identical: add their triples (nrgpu.digest.combine)."""
+        import numpy as np
+
+        out = np.zeros((self.world, 3), np.uint64)
+        same = C.c_int(0)
+        self._check(self._lib.nrg_group_verify(self._h, C.c_void_p(out.ctypes.data), C.byref(same)),
+                    "nrg_group_verify")
+        return bool(same.value), out
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.nrg_group_close(self._h)

@@ -258,6 +258,20 @@ class DeviceReplica:
     def log_reset(self):
         L.check(self._lib.nrg_log_reset(self._h))
 
+    # -- verify --------------------------------------------------------------------
+    def digest(self):
+        """nrg_digest: (count, sum, xor) of the structure's items, any kind; nrgpu.digest mirrors
+        the definition. On a hashmap the same as hm_digest()."""
+        out = np.zeros(3, np.uint64)
+        L.check(self._lib.nrg_digest(self._h, _ptr(out)), "digest")
+        return tuple(int(x) for x in out)
+
+    @_stream_ordered
+    def digest_device(self, d_out3):
+        """nrg_digest_async: the triple into three u64 on the device, no host round trip.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_digest_async(self._h, _dptr(d_out3)), "digest")
+
     # -- hashmap -------------------------------------------------------------------
     def hm_get(self, keys: np.ndarray):
         keys = np.ascontiguousarray(keys, np.uint64)
@@ -974,3 +988,11 @@ class Replica:
                 self.dev.log_exec()
                 self.dev.sync()
                 v(self.ds.snapshot(self.dev))
+
+    def digest(self):
+        """Replica::verify's device-side form: catch up on the log as verify does, then the
+        replica's digest triple (DeviceReplica.digest); nothing is materialised on the host."""
+        with self._combiner:
+            with self.log.lock:
+                self.dev.log_exec()
+                return self.dev.digest()
