@@ -20,7 +20,9 @@
  *   nrg_hashmap_dump / digest     Replica::verify(closure)           nr/src/replica.rs:443-467
  *   nrg_digest* / nrg_group_verify Replica::verify on the device: one  nr/src/replica.rs:443-467
  *                                 triple per replica, every kind
- *   nrg_stack_*                   Stack Dispatch                     benches/stack.rs:36-84, nr/tests/stack.rs:31-96
+ *   nrg_snapshot_* / nrg_restore  Replica::new from a state, not  nr/src/replica.rs:184-232, :443-467
+ *   / nrg_group_resync            from log index 0; verify's view
+ *   nrg_stack_*                   Stack Dispatch                    benches/stack.rs:36-84, nr/tests/stack.rs:31-96
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
  *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
  *   nrg_vspace_*                  VSpace Dispatch (x86-64 page table) benches/vspace.rs:177-381, :436-467, :499-526
@@ -243,6 +245,76 @@ int nrg_join(nrg_ctx* ctx);
  * of scratch. */
 int nrg_digest(nrg_ctx* ctx, uint64_t out[3]);
 int nrg_digest_async(nrg_ctx* ctx, uint64_t* d_out3);
+
+/* ---- snapshot and restore ---------------------------------------------------------------
+ * Replica::new (nr/src/replica.rs:184-232) gives a replica that replays the log from index 0, and
+ * Replica::verify (:443-467) is the reference's only view of a replica's state. A snapshot is a
+ * compact image of that state whose size depends on the contents, not on the table, ring or pool
+ * that holds them; nrg_restore builds a replica from one, so a replica can join a log that was
+ * garbage-collected, a diverged group member can be brought back (nrg_group_resync), and a
+ * structure outlives its context. The image is one buffer, the same on the device, on the host
+ * and on disk: a 64-byte header of eight little-endian u64 words, then the payload.
+ *   word 0     magic, the ASCII bytes "NRGSNAP1"
+ *   word 1     ds_kind in the low 32 bits, the format version (1) in the high 32
+ *   word 2     items
+ *   word 3     bytes = 64 + payload, rounded up to a multiple of 64 (the padding is zero)
+ *   word 4     log_idx: the source's ltail; the state is the replay of [0, log_idx)
+ *   words 5-7  the nrg_digest triple {count, sum, xor} of the state
+ * Payload by kind:
+ *   hashmap    items records of nrg_put layout {key, value}, in any order, the key 2^64 - 1 among them
+ *   stack      items u32 elements, bottom first
+ *   queue      items u64 elements, front first: the logical order, not the ring's
+ *   synthetic  items = synth_n u64 words
+ *   vspace     items = the tables allocated (nrg_vspace_tables), 4 KiB each: the pool image, inner
+ *              entries as stored (table_index * 4096 | flags). The indices point into the image
+ *              itself, so it restores into any pool of at least that many tables.
+ * Two replicas with equal state need not produce byte-equal images: the hashmap's record order and
+ * the page table's table numbering depend on how the state came about. Their digest words are
+ * equal. Like the dumps and every direct call, none of these calls is allowed while a combiner is
+ * open on the context. */
+typedef struct {
+    uint32_t ds_kind, version;
+    uint64_t items, bytes, log_idx;
+    uint64_t digest[3];
+} nrg_snapshot_info;
+
+/* What a snapshot taken now would hold (Replica::verify's view, sized): launches what the last
+ * chunk deferred, waits for the stream and reads the exact item count from the device (the
+ * hashmap's key count as nrg_hashmap_size takes it, the stack's and the queue's length, the page
+ * table's tables). Fills kind, version, items, bytes and log_idx; digest is zero. Synchronous. */
+int nrg_snapshot_size(nrg_ctx* ctx, nrg_snapshot_info* out);
+/* Replica::verify's view as an image in device memory `d_buf` (16-B aligned) of `cap` bytes:
+ * launches what the last chunk deferred, writes header and payload and runs the kind's digest
+ * straight into header words 5-7. Stream ordered, no host round trip; like the digest it does not
+ * need ltail == tail and snapshots what has been replayed. Nothing is stored at or past
+ * d_buf + cap: a state that does not fit leaves magic = 0 (when cap >= 64) and latches
+ * NRG_E_CAPACITY for the next nrg_sync. */
+int nrg_snapshot_async(nrg_ctx* ctx, void* d_buf, uint64_t cap);
+/* The header of the image at device pointer `d_buf`, of which the caller holds `bytes` bytes,
+ * copied to the host and validated: magic, version, a known kind, `bytes` in the header equal to
+ * what `items` items of the kind take and at most the argument. NRG_E_INVAL otherwise. */
+int nrg_snapshot_info_read(nrg_ctx* ctx, const void* d_buf, uint64_t bytes, nrg_snapshot_info* out);
+/* Replica::new from a state instead of from log index 0: replace the replica's contents with the
+ * image's. `d_buf` (16-B aligned) is any device pointer the context's device can read, complete
+ * when the call is made. Synchronous. In order:
+ *   1  the header is validated as nrg_snapshot_info_read validates it (NRG_E_INVAL);
+ *   2  and checked against the context: another kind, or a synthetic image of another synth_n,
+ *      NRG_E_INVAL; more stack or queue elements than stack_capacity / queue_capacity, or more
+ *      tables than the pool holds, NRG_E_CAPACITY; more keys than a fixed table has slots, or
+ *      than a table of 2^hashmap_max_log2_slots slots holds at one key per two slots,
+ *      NRG_E_TABLE_FULL. A failure up to here leaves the replica and its log untouched;
+ *   3  queued work completes, deferred work included, and the device error latch is cleared;
+ *   4  the contents are replaced and the bookkeeping a replay would have left is rebuilt (the
+ *      hashmap's key count, stamps and epochs, with growth on a table sized for `items` keys as a
+ *      replay would have sized it; the queue's front at ring position 0; the pool beyond the
+ *      image zeroed), so that dumps, sizes, reads and the responses of every later round are
+ *      those of a replica that replayed the log. The destination's table, ring and pool sizes
+ *      may differ from the source's;
+ *   5  head = tail = ctail = ltail = log_idx and no origin runs: the next append returns log_idx;
+ *   6  the digest of the rebuilt state is compared with the header's. A mismatch (a corrupted
+ *      payload; also a fixed table that took items <= slots but whose probe overran) returns
+ *      NRG_E_INVAL and leaves unspecified contents: restore again, or close the context. */
+int nrg_restore(nrg_ctx* ctx, const void* d_buf, uint64_t bytes);
 
 const char* nrg_strerror(int code);
 /* Library build identifier ("nrgpu <version> gfx950"). */
@@ -545,6 +617,19 @@ int nrg_group_sync(nrg_group* g);
  * The members of a partitioned group hold one partition each, so *identical is 0 by design there:
  * such callers add the triples (count and sum add, xor xors) and compare with the whole map's. */
 int nrg_group_verify(nrg_group* g, uint64_t* digests, int* identical);
+/* What to do about *identical = 0: every rank's replica becomes rank `root_rank`'s (Replica::new,
+ * nr/src/replica.rs:184-232, from the root's state as Replica::verify, :443-467, sees it). A
+ * collective: every rank calls it with the same root. It completes queued group work as
+ * nrg_group_sync does (a sticky failure returns its code; a latched device error of a replica is
+ * cleared, its contents are about to be replaced), the ranks learn the root's image size through one
+ * small all-gather read back under the group's deadline (a missing peer: NRG_E_TIMEOUT), every
+ * member grows a group-owned buffer, the root snapshots into its own (nrg_snapshot_async) and, inside
+ * one ncclGroupStart / ncclGroupEnd on the comm streams, sends it to every other rank; every other
+ * member then calls nrg_restore from its buffer, log positions included. A member whose restore
+ * fails returns that code (a single-process group: the first such code); the others return NRG_OK.
+ * For replicated groups: on a group that runs partitioned rounds every rank would end up with the
+ * root's partition. */
+int nrg_group_resync(nrg_group* g, int root_rank);
 /* Deadline of every wait on the peer ranks (default NRG_GROUP_DEFAULT_TIMEOUT_MS): the host round
  * trips of the length / count exchanges, buffer regrowth and nrg_group_sync. A rank whose peers do
  * not post their part of a collective in time gets NRG_E_TIMEOUT instead of hanging (its
@@ -632,7 +717,8 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
  * unperturbed). The main replay kernel ("hm_round") is timed with start/stop events stamped
  * from its own dispatch (hipExtLaunchKernelGGL); multi-kernel pipelines ("hm_prev",
  * "st_replay", "sy_replay") with event records around them; a table growth's two passes are
- * "hm_grow_init" and "hm_rehash". nrg_kernel_time reads (timed
+ * "hm_grow_init" and "hm_rehash", a snapshot's table scan "hm_snapshot", a restore's two passes
+ * "hm_restore_init" and "hm_restore". nrg_kernel_time reads (timed
  * launches, their total milliseconds) after synchronising. */
 int nrg_kernel_timing(nrg_ctx* ctx, int enable);
 /* Restrict timing to one kernel name (NULL or "" = all). */

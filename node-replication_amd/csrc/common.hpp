@@ -151,6 +151,34 @@ __device__ __forceinline__ void dg_commit(u64 c, u64 sm, u64 x, u64* out3) {
     }
 }
 
+// The snapshot image (nrg_snapshot_async / nrg_restore, include/nrgpu.h): a 64-byte header of eight
+// u64 words {magic, kind | version << 32, items, bytes, log_idx, digest[3]} and the kind's payload,
+// the whole rounded up to a multiple of 64 bytes with the padding zeroed.
+constexpr u64 SNAP_MAGIC = 0x3150414E5347524Eull;  // the ASCII bytes "NRGSNAP1", little endian
+constexpr u32 SNAP_VERSION = 1;
+constexpr u64 SNAP_HDR = 64;
+__host__ __device__ __forceinline__ u64 snap_bytes(u64 payload) { return (SNAP_HDR + payload + 63) & ~63ull; }
+// One thread of a snapshot kernel, for a payload of `payload` bytes (a multiple of 4): header words
+// 0..4 and the zeroed padding when the image fits into cap bytes (the digest fills words 5..7
+// afterwards); else magic = 0 where the header itself fits, and ERR_CAPACITY. Nothing is stored
+// at or past buf + cap either way.
+__device__ __forceinline__ void snap_head(u64* buf, u64 cap, u32 kind, u64 items, u64 payload, u64 log_idx,
+                                          DevCtl* ctl) {
+    const u64 bytes = snap_bytes(payload);
+    if (bytes > cap) {
+        if (cap >= SNAP_HDR) buf[0] = 0;
+        atomicOr(&ctl->err, ERR_CAPACITY);
+        return;
+    }
+    buf[0] = SNAP_MAGIC;
+    buf[1] = (u64)kind | ((u64)SNAP_VERSION << 32);
+    buf[2] = items;
+    buf[3] = bytes;
+    buf[4] = log_idx;
+    u32* pad = (u32*)((char*)buf + SNAP_HDR + payload);
+    for (u64 i = 0; i < (bytes - SNAP_HDR - payload) / 4; i++) pad[i] = 0;
+}
+
 // Wave-wide (64-lane) inclusive scan helpers.
 __device__ __forceinline__ u32 lane_id() { return threadIdx.x & 63; }
 

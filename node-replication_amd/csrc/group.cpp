@@ -141,6 +141,7 @@ struct Member {
     uint64_t* dg = nullptr;
     uint64_t* gdg = nullptr;
     uint64_t* h_gdg = nullptr;  // pinned host copy of gdg
+    DBuf snap;                  // nrg_group_resync: the root's snapshot, sent or received
     void* xmem = nullptr;
 };
 
@@ -261,6 +262,7 @@ void member_free(Member& m, const Rccl* R) {
         if (m.freed[b]) (void)hipEventDestroy(m.freed[b]);
     }
     if (m.sbuf) (void)hipFree(m.sbuf);
+    if (m.snap.p) (void)hipFree(m.snap.p);
     if (m.xmem) (void)hipFree(m.xmem);
     if (m.h_glx) (void)hipHostFree(m.h_glx);
     if (m.h_gdg) (void)hipHostFree(m.h_gdg);
@@ -1184,6 +1186,76 @@ int nrg_group_verify(nrg_group* g, uint64_t* digests, int* identical) {
         if (std::memcmp(H, H + 3 * r, 24) != 0) same = 0;
     if (digests) std::memcpy(digests, H, 3 * (uint64_t)G * 8);
     *identical = same;
+    return rc;
+}
+
+// Replica::new from the root's state (include/nrgpu.h): the root's snapshot to every other rank,
+// which restores from it. The size exchange uses the length exchange's words (lx / glx): after the
+// sync below no round is in flight.
+int nrg_group_resync(nrg_group* g, int root) {
+    if (!g || root < 0 || root >= g->nranks) return NRG_E_INVAL;
+    if (g->broken) return g->broken;
+    const Rccl* R = g->R;
+    if (!R || !R->send || !R->recv) return NRG_E_COMM;
+    const int nl = (int)g->m.size(), G = g->nranks;
+    // queued group work first; a replica's latched device error is cleared by this (nrg_sync
+    // reports it once): the contents it speaks of are about to be replaced
+    (void)nrg_group_sync(g);
+    if (g->broken) return g->broken;
+    // the root's image size to every rank
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        RCHK(nrg::ctx_use_device(m.ctx));
+        nrg_snapshot_info info{};
+        if (m.rank == root) RCHK(nrg_snapshot_size(m.ctx, &info));
+        grp_put2_kernel<<<1, 64, 0, m.cstream>>>(m.lx, info.bytes, 0);
+        GCHK(hipGetLastError());
+    }
+    if (R->group_start() != ncclSuccess) return NRG_E_COMM;
+    ncclResult_t res = ncclSuccess;
+    for (int i = 0; i < nl && res == ncclSuccess; i++)
+        res = R->all_gather(g->m[i].lx, g->m[i].glx, 2, ncclUint64, g->m[i].comm, g->m[i].cstream);
+    RCHK(group_end(g, "resync size exchange"));
+    if (res != ncclSuccess) return group_fail(g, NRG_E_COMM, "resync size exchange: all-gather refused");
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        RCHK(nrg::ctx_use_device(m.ctx));
+        GCHK(hipMemcpyAsync(m.h_glx, m.glx, 2 * (uint64_t)G * 8, hipMemcpyDeviceToHost, m.cstream));
+        RCHK(wait_stream(g, m.cstream, "resync size exchange"));
+    }
+    const uint64_t bytes = g->m[0].h_glx[2 * root];  // identical on every rank
+    if (bytes < 64 || (bytes & 63)) return group_fail(g, NRG_E_COMM, "resync: the root sent no snapshot size");
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        RCHK(nrg::ctx_use_device(m.ctx));
+        RCHK(grow_buf(m, m.snap, bytes));
+        if (m.rank != root) continue;
+        RCHK(nrg_snapshot_async(m.ctx, m.snap.p, bytes));
+        RCHK(order(m, m.ctx->stream, m.cstream));
+    }
+    if (G > 1) {
+        if (R->group_start() != ncclSuccess) return NRG_E_COMM;
+        for (int i = 0; i < nl && res == ncclSuccess; i++) {
+            Member& m = g->m[i];
+            if (m.rank != root) {
+                res = R->recv(m.snap.p, bytes / 8, ncclUint64, root, m.comm, m.cstream);
+                continue;
+            }
+            for (int o = 0; o < G && res == ncclSuccess; o++)
+                if (o != root) res = R->send(m.snap.p, bytes / 8, ncclUint64, o, m.comm, m.cstream);
+        }
+        RCHK(group_end(g, "resync send/recv"));
+        if (res != ncclSuccess) return group_fail(g, NRG_E_COMM, "resync send/recv refused");
+    }
+    int rc = NRG_OK;
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        RCHK(nrg::ctx_use_device(m.ctx));
+        RCHK(wait_stream(g, m.cstream, "resync send/recv"));
+        if (m.rank == root) continue;
+        const int r = nrg_restore(m.ctx, m.snap.p, bytes);
+        if (r && rc == NRG_OK) rc = r;
+    }
     return rc;
 }
 

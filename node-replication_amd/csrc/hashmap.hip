@@ -1687,6 +1687,119 @@ __global__ __launch_bounds__(TPB) void hm_digest_kernel(const Slot* __restrict__
     }
 }
 
+// ---- nrg_snapshot_async / nrg_restore ----------------------------------------------------------
+// hm_snapshot_kernel: the present {key, value} pairs of the whole table, written densely, in any
+// order. The table is read as hm_digest_kernel reads it (a lane loads the 16 B {key, value} of its
+// slot). A workgroup takes tiles of SN_TILE consecutive slots (128 KiB of table): every lane holds
+// SN_Q slots, a wave counts each of its SN_Q rows with a ballot, the SN_Q * 4 row counts are
+// scanned by the first wave (one per lane), and ONE returning atomic per tile on DevCtl::counter
+// reserves the tile's run of the output: 2^26 slots make 16384 atomics on that word, about 30 per
+// us of the scan, a third of what one word takes (the dump's one atomic per key: 10M). A tile
+// whose run would pass cap_items stores nothing, but still counts, so the head kernel sees the
+// overrun. No workgroup waits for another.
+constexpr int SN_Q = 16;
+constexpr u64 SN_TILE = (u64)TPB * SN_Q;
+static_assert(SN_Q * (TPB / 64) == 64, "the row counts of a tile are scanned by one wave, one per lane");
+__global__ __launch_bounds__(TPB) void hm_snapshot_kernel(const Slot* __restrict__ table, u64 slots, DevCtl* ctl,
+                                                          u64x2* __restrict__ out, u64 cap_items) {
+    __shared__ u32 s_cnt[64];
+    __shared__ u64 s_base;
+    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const u64 tiles = (slots + SN_TILE - 1) / SN_TILE;
+    for (u64 t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const u64 s0 = t * SN_TILE + threadIdx.x;
+        u64x2 e[SN_Q];
+        u32 rank[SN_Q];
+#pragma unroll
+        for (int q = 0; q < SN_Q; q++) {
+            const u64 s = s0 + (u64)q * TPB;
+            e[q].x = EMPTY_KEY;
+            e[q].y = 0;
+            if (s < slots) e[q] = *(const u64x2*)&table[s];
+        }
+#pragma unroll
+        for (int q = 0; q < SN_Q; q++) {
+            const u64 b = __ballot(e[q].x != EMPTY_KEY);
+            rank[q] = (u32)__popcll(b & ((1ull << lane) - 1));
+            if (lane == 0) s_cnt[q * (TPB / 64) + w] = (u32)__popcll(b);
+        }
+        __syncthreads();
+        if (w == 0) {
+            const u32 c = s_cnt[lane];
+            u32 incl = c;
+            for (int off = 1; off < 64; off <<= 1) {
+                const u32 v = __shfl_up(incl, off, 64);
+                if ((int)lane >= off) incl += v;
+            }
+            s_cnt[lane] = incl - c;  // where the row's pairs start inside the tile's run
+            if (lane == 63) {
+                u64 base = ~0ull;
+                if (incl) {
+                    base = atomicAdd((unsigned long long*)&ctl->counter, (unsigned long long)incl);
+                    if (base + incl > cap_items) base = ~0ull;
+                }
+                s_base = base;
+            }
+        }
+        __syncthreads();
+        const u64 base = s_base;
+        if (base != ~0ull) {
+#pragma unroll
+            for (int q = 0; q < SN_Q; q++)
+                if (e[q].x != EMPTY_KEY) out[base + s_cnt[q * (TPB / 64) + w] + rank[q]] = e[q];
+        }
+        __syncthreads();  // (s_cnt and s_base are the next tile's too)
+    }
+}
+
+// After the scan: the side key's pair behind the table's, then the header or the refusal.
+__global__ void hm_snapshot_head_kernel(DevCtl* ctl, u64* buf, u64 cap, u64 log_idx) {
+    if (threadIdx.x || blockIdx.x) return;
+    u64 n = ctl->counter;
+    const u64 cap_items = cap >= SNAP_HDR ? (cap - SNAP_HDR) / 16 : 0;
+    if (ctl->sp_claim) {
+        if (n < cap_items) {
+            buf[SNAP_HDR / 8 + 2 * n] = EMPTY_KEY;
+            buf[SNAP_HDR / 8 + 2 * n + 1] = ctl->sp.val;
+        }
+        n++;
+    }
+    snap_head(buf, cap, NRG_DS_HASHMAP, n, n * 16, log_idx, ctl);
+}
+
+// The snapshot's pairs into a table hm_init_table_kernel has just initialised: claimed from the
+// home slot as hm_prefill_range_kernel claims them, stamps "present since before the replay
+// rounds", the key EMPTY_KEY into the side slot. Fresh claims are counted into DevCtl::nkeys, so a
+// payload that repeats a key restores fewer keys than its header says and fails the digest check.
+__global__ __launch_bounds__(TPB) void hm_restore_kernel(Slot* table, const u64x2* __restrict__ recs, u64 n, u32 shift,
+                                                         u64 tmask, DevCtl* ctl) {
+    __shared__ u32 s_ins;
+    if (threadIdx.x == 0) s_ins = 0;
+    __syncthreads();
+    u32 inserted = 0;
+    for (u64 i = blockIdx.x * (u64)TPB + threadIdx.x; i < n; i += (u64)gridDim.x * TPB) {
+        const u64x2 r = recs[i];
+        if (r.x == EMPTY_KEY) {
+            inserted += atomicExch(&ctl->sp_claim, 1u) == 0;
+            ctl->sp.val = r.y;
+            ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
+            continue;
+        }
+        bool fresh;
+        const long long s = claim_slot(table, r.x, table_home(r.x, shift), tmask, &fresh);
+        if (s < 0) {
+            atomicOr(&ctl->err, ERR_TABLE_FULL);
+            continue;
+        }
+        table[s].val = r.y;
+        table[s].st[0] = table[s].st[1] = STAMP_PRESENT;
+        inserted += fresh;
+    }
+    if (inserted) atomicAdd(&s_ins, inserted);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_ins) atomicAdd((unsigned long long*)&ctl->nkeys, (unsigned long long)s_ins);
+}
+
 struct SegArgs {
     u64 start[64];  // exclusive prefix of lens (in records)
     u64 total;
@@ -2227,10 +2340,14 @@ static int hm_set_knob(nrg_ctx* c, int knob, uint64_t v) {
 static u64 hm_dbg_words(const nrg_ctx*) { return (u64)HM_BK_MAX * 8; }
 
 static hipError_t hm_digest(nrg_ctx* c, u64* d_out3);
+static int hm_items(nrg_ctx* c, u64* n);
+static hipError_t hm_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx);
+static int hm_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only);
 
 const DsOps* hm_ops() {
     static const DsOps ops = {sizeof(nrg_put), sizeof(u64), hm_open, hm_close, hm_flush, hm_replay,
-                              hm_floor, hm_set_knob, hm_dbg_words, nullptr, hm_digest};
+                              hm_floor, hm_set_knob, hm_dbg_words, nullptr, hm_digest,
+                              hm_items, hm_snapshot, hm_restore};
     return &ops;
 }
 
@@ -2261,7 +2378,8 @@ static hipError_t hm_dump(nrg_ctx* c, u64* d_keys, u64* d_vals) {
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(&c->d_ctl->counter, 0, sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
-    hm_dump_kernel<<<grid_for(c->hm.slots, 8192), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl, d_keys, d_vals);
+    NRG_LAUNCH(c, "hm_dump", hm_dump_kernel, grid_for(c->hm.slots, 8192), TPB, 0, c->stream, (const Slot*)c->hm.d_table,
+               (u64)c->hm.slots, c->d_ctl, d_keys, d_vals);
     return hipGetLastError();
 }
 
@@ -2270,8 +2388,82 @@ static hipError_t hm_digest(nrg_ctx* c, u64* d_out3) {
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
-    hm_digest_kernel<<<grid_for(c->hm.slots, 8192), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl, d_out3);
+    NRG_LAUNCH(c, "hm_digest", hm_digest_kernel, grid_for(c->hm.slots, 8192), TPB, 0, c->stream,
+               (const Slot*)c->hm.d_table, (u64)c->hm.slots, (const DevCtl*)c->d_ctl, d_out3);
     return hipGetLastError();
+}
+
+// the exact key count, as nrg_hashmap_size takes it
+static int hm_items(nrg_ctx* c, u64* n) {
+    HIPCHK(hm_count(c));
+    HIPCHK(hipMemcpyAsync(n, &c->d_ctl->nkeys_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return NRG_OK;
+}
+
+// The scan (one atomic per tile on DevCtl::counter), then the side key and the header. The grid
+// covers the tiles up to 8192 workgroups: 2^26 slots are 16384 tiles, two per workgroup.
+static hipError_t hm_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    hipError_t e = hm_flush(c);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(&c->d_ctl->counter, 0, sizeof(u64), c->stream)) != hipSuccess) return e;
+    const u64 cap_items = cap >= SNAP_HDR ? (cap - SNAP_HDR) / 16 : 0;
+    const u64 tiles = (c->hm.slots + SN_TILE - 1) / SN_TILE;
+    NRG_LAUNCH(c, "hm_snapshot", hm_snapshot_kernel, (unsigned)(tiles < 8192 ? tiles : 8192), TPB, 0, c->stream,
+               (const Slot*)c->hm.d_table, (u64)c->hm.slots, c->d_ctl, (u64x2*)((char*)d_buf + SNAP_HDR), cap_items);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hm_snapshot_head_kernel<<<1, 64, 0, c->stream>>>(c->d_ctl, (u64*)d_buf, cap, log_idx);
+    return hipGetLastError();
+}
+
+// A restored map is one that holds the pairs since before any replay round: the table sized as
+// hm_room would have sized it for `items` keys (growth on) and initialised as hm_grow initialises a
+// new one, every key claimed and stamped "present", the count exact in DevCtl::nkeys, the created-key
+// counters, the epochs and their tags, the key bound and the skew sampler as after nrg_open.
+static int hm_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    const u32 cur = 64 - c->hm.slot_shift;
+    const bool grows = c->hm.grow_max_log2 > cur;
+    if (check_only) {
+        const u64 limit = grows ? (1ull << c->hm.grow_max_log2) / HM_GROW_SLOTS_PER_KEY : c->hm.slots;
+        return items > limit ? NRG_E_TABLE_FULL : NRG_OK;
+    }
+    if (!d_payload) items = 0;
+    if (grows) {
+        u32 want = hm_slots_for(items);
+        if (want > c->hm.grow_max_log2) want = c->hm.grow_max_log2;
+        if ((1ull << want) > c->hm.slots) {
+            Slot* nt = nullptr;
+            if (hipMalloc(&nt, (1ull << want) * sizeof(Slot)) != hipSuccess) {
+                (void)hipGetLastError();
+                return NRG_E_NOMEM;  // the old table stays installed, its contents as they were
+            }
+            (void)hipFree(c->hm.d_table);
+            c->hm.d_table = nt;
+            c->hm.slots = 1ull << want;
+            c->hm.slot_shift = 64 - want;
+        }
+    }
+    c->hm.pend.valid = false;
+    NRG_LAUNCH(c, "hm_restore_init", hm_init_table_kernel, grid_for(c->hm.slots, 16384), TPB, 0, c->stream,
+               c->hm.d_table, c->hm.slots);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(c->d_ctl, 0, sizeof(DevCtl), c->stream));
+    HIPCHK(hipMemsetAsync(c->hm.d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
+    for (int i = 0; i < 2 && c->hm.d_put_slot[i]; i++)
+        HIPCHK(hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_alloc * sizeof(u32), c->stream));
+    HIPCHK(hipMemsetAsync(c->hm.d_dup, 0, 2 * HM_DUP_SLOTS * sizeof(u64), c->stream));
+    c->hm.h_dup[0] = c->hm.h_dup[1] = 0;
+    c->hm.dup_seq = c->hm.dup_puts = c->hm.dup_puts_sampled = c->hm.sample_seq = 0;
+    c->hm.dup_rounds = 0;
+    c->hm.skewed = false;
+    c->hm.epoch = 1;
+    c->hm.keys_ub = items;
+    if (items) {
+        NRG_LAUNCH(c, "hm_restore", hm_restore_kernel, grid_for(items, 8192), TPB, 0, c->stream, c->hm.d_table,
+                   (const u64x2*)d_payload, items, c->hm.slot_shift, (u64)(c->hm.slots - 1), c->d_ctl);
+        HIPCHK(hipGetLastError());
+    }
+    return NRG_OK;
 }
 
 hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_stride, const u64* lens, u64 dst_lo) {

@@ -239,6 +239,18 @@ struct DsOps {
     // nrg_digest: zero d_out3 and add {count, sum, xor} of mix64(k ^ mix64(v)) over the structure's
     // items into it (common.hpp dg_item), on the context's stream, with nothing read on the host
     hipError_t (*digest)(nrg_ctx* c, u64* d_out3);
+    // nrg_snapshot_size: the exact number of snapshot items (keys, elements, words, tables) of what
+    // has been replayed, read from the device; synchronous, the stream has been drained
+    int (*items)(nrg_ctx* c, u64* n);
+    // nrg_snapshot_async: header words 0..4 (common.hpp snap_head) and the payload into d_buf, on
+    // the context's stream, nothing stored at or past d_buf + cap; a state that does not fit writes
+    // magic = 0 and latches ERR_CAPACITY. Deferred work has been launched.
+    hipError_t (*snapshot)(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx);
+    // nrg_restore. check_only: may a payload of `items` items go into this context? An NRG_* code,
+    // nothing touched. Else: replace the structure's contents and rebuild its bookkeeping from the
+    // payload (the stream has been drained, nothing is deferred). d_payload == nullptr: the empty
+    // structure of a fresh context instead (after a restore whose digest did not match).
+    int (*restore)(nrg_ctx* c, const void* d_payload, u64 items, bool check_only);
 };
 const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind

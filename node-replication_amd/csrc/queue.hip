@@ -446,9 +446,58 @@ static hipError_t qu_digest(nrg_ctx* c, u64* d_out3) {
     return hipGetLastError();
 }
 
+// ---- nrg_snapshot_async / nrg_restore: the elements, front first ---------------------------------
+static int qu_items(nrg_ctx* c, u64* n) {
+    QuState s{};
+    HIPCHK(hipMemcpyAsync(&s, c->qu.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = s.len > c->cfg.queue_capacity ? c->cfg.queue_capacity : s.len;  // clamped as nrg_queue_len clamps it
+    return NRG_OK;
+}
+
+// The logical order, whatever ring slots hold it: out[i] = q[(head + i) & mask], head and the
+// length read here. The image must fit whole or nothing of the payload is stored.
+__global__ __launch_bounds__(DG_TPB) void qu_snapshot_kernel(const u64* __restrict__ q, u64 qmask, const QuState* st,
+                                                             u64 elems, u64* buf, u64 cap, u64 log_idx, DevCtl* ctl) {
+    const u64 head = st->head;
+    const u64 n = st->len > elems ? elems : st->len;
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_QUEUE, n, n * 8, log_idx, ctl);
+    if (snap_bytes(n * 8) > cap) return;
+    u64* out = buf + SNAP_HDR / 8;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB)
+        out[i] = q[(head + i) & qmask];
+}
+
+static hipError_t qu_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    NRG_LAUNCH(c, "qu_snapshot", qu_snapshot_kernel, dg_grid(c->cfg.queue_capacity), DG_TPB, 0, c->stream,
+               (const u64*)c->qu.d_queue, (u64)(c->qu.size - 1), (const QuState*)c->qu.d_state,
+               (u64)c->cfg.queue_capacity, (u64*)d_buf, cap, log_idx, c->d_ctl);
+    return hipGetLastError();
+}
+
+// ring positions [0, n) and the state of a queue initialised with these values (nrg_queue_init):
+// front at 0, the checkpoint fields clear
+__global__ __launch_bounds__(DG_TPB) void qu_restore_kernel(u64* q, const u64* __restrict__ src, u64 n, QuState* st) {
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) q[i] = src[i];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st->head = 0;
+        st->len = n;
+        st->ck_head = st->ck_len = st->ck_pops = 0;
+    }
+}
+
+static int qu_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    if (check_only) return items > c->cfg.queue_capacity ? NRG_E_CAPACITY : NRG_OK;
+    if (!d_payload) items = 0;
+    NRG_LAUNCH(c, "qu_restore", qu_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->qu.d_queue,
+               (const u64*)d_payload, items, c->qu.d_state);
+    return hip_fail(hipGetLastError());
+}
+
 const DsOps* qu_ops() {
     static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk,
-                              floor_ltail, nullptr, nullptr, nullptr, qu_digest};
+                              floor_ltail, nullptr, nullptr, nullptr, qu_digest,
+                              qu_items, qu_snapshot, qu_restore};
     return &ops;
 }
 

@@ -994,9 +994,58 @@ static hipError_t st_digest(nrg_ctx* c, u64* d_out3) {
     return hipGetLastError();
 }
 
+// ---- nrg_snapshot_async / nrg_restore: the elements, bottom first --------------------------------
+static int st_items(nrg_ctx* c, u64* n) {
+    long long d = 0;
+    HIPCHK(st_flush(c));  // a deferred chunk finish publishes the length
+    HIPCHK(hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (d < 0) d = 0;  // clamped as nrg_stack_len clamps it
+    *n = (u64)d > c->cfg.stack_capacity ? c->cfg.stack_capacity : (u64)d;
+    return NRG_OK;
+}
+
+// The length is read here, clamped as the digest clamps it; the image must fit whole or nothing of
+// the payload is stored.
+__global__ __launch_bounds__(DG_TPB) void st_snapshot_kernel(const u32* __restrict__ stack, DevCtl* ctl, u64 elems,
+                                                             u64* buf, u64 cap, u64 log_idx) {
+    long long d = ctl->depth;
+    if (d < 0) d = 0;
+    const u64 n = (u64)d > elems ? elems : (u64)d;
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_STACK, n, n * 4, log_idx, ctl);
+    if (snap_bytes(n * 4) > cap) return;
+    u32* out = (u32*)(buf + SNAP_HDR / 8);
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) out[i] = stack[i];
+}
+
+static hipError_t st_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    hipError_t e = st_flush(c);
+    if (e != hipSuccess) return e;
+    NRG_LAUNCH(c, "st_snapshot", st_snapshot_kernel, dg_grid(c->cfg.stack_capacity), DG_TPB, 0, c->stream,
+               (const u32*)c->st.d_stack, c->d_ctl, (u64)c->cfg.stack_capacity, (u64*)d_buf, cap, log_idx);
+    return hipGetLastError();
+}
+
+// the elements and the length, in the slots a chunk of either parity starts from as well
+__global__ __launch_bounds__(DG_TPB) void st_restore_kernel(u32* stack, const u32* __restrict__ src, u64 n,
+                                                            DevCtl* ctl) {
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) stack[i] = src[i];
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->depth = ctl->depth0 = ctl->depth_next = (long long)n;
+}
+
+static int st_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    if (check_only) return items > c->cfg.stack_capacity ? NRG_E_CAPACITY : NRG_OK;
+    if (!d_payload) items = 0;
+    c->st.pend.valid = false;
+    NRG_LAUNCH(c, "st_restore", st_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->st.d_stack,
+               (const u32*)d_payload, items, c->d_ctl);
+    return hip_fail(hipGetLastError());
+}
+
 const DsOps* st_ops() {
     static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk,
-                              floor_ltail, nullptr, st_dbg_words, nullptr, st_digest};
+                              floor_ltail, nullptr, st_dbg_words, nullptr, st_digest,
+                              st_items, st_snapshot, st_restore};
     return &ops;
 }
 

@@ -1550,9 +1550,51 @@ static hipError_t sy_digest(nrg_ctx* c, u64* d_out3) {
     return hipGetLastError();
 }
 
+// ---- nrg_snapshot_async / nrg_restore: the synth_n words ------------------------------------------
+static int sy_items(nrg_ctx* c, u64* n) {
+    *n = c->cfg.synth_n;
+    return NRG_OK;
+}
+
+__global__ __launch_bounds__(DG_TPB) void sy_snapshot_kernel(const u64* __restrict__ words, u64 n, u64* buf, u64 cap,
+                                                             u64 log_idx, DevCtl* ctl) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_SYNTHETIC, n, n * 8, log_idx, ctl);
+    if (snap_bytes(n * 8) > cap) return;
+    u64* out = buf + SNAP_HDR / 8;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) out[i] = words[i];
+}
+
+static hipError_t sy_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    hipError_t e = sy_flush(c);  // deferred sums fold the hot words
+    if (e != hipSuccess) return e;
+    NRG_LAUNCH(c, "sy_snapshot", sy_snapshot_kernel, dg_grid(c->cfg.synth_n), DG_TPB, 0, c->stream,
+               (const u64*)c->sy.d_words, (u64)c->cfg.synth_n, (u64*)d_buf, cap, log_idx, c->d_ctl);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(DG_TPB) void sy_restore_kernel(u64* words, const u64* __restrict__ src, u64 n) {
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) words[i] = src[i];
+}
+
+// The words are the whole state. Nothing is deferred when this runs (nrg_restore drained the
+// stream), and a chunk's scratch is tagged by the chunk counter sy.round, which goes on from where
+// it stands, as it does after any completed chunk.
+static int sy_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    if (check_only) return items != c->cfg.synth_n ? NRG_E_INVAL : NRG_OK;
+    c->sy.pend.valid = c->sy.pend_b.valid = false;
+    if (!d_payload) {
+        sy_init_kernel<<<1024, 256, 0, c->stream>>>(c->sy.d_words, c->cfg.synth_n);
+        return hip_fail(hipGetLastError());
+    }
+    NRG_LAUNCH(c, "sy_restore", sy_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->sy.d_words,
+               (const u64*)d_payload, items);
+    return hip_fail(hipGetLastError());
+}
+
 const DsOps* sy_ops() {
     static const DsOps ops = {sizeof(nrg_synth_op), sizeof(u64), sy_open, sy_close, sy_flush, sy_replay_chunk,
-                              sy_floor, sy_set_knob, sy_dbg_words, nullptr, sy_digest};
+                              sy_floor, sy_set_knob, sy_dbg_words, nullptr, sy_digest,
+                              sy_items, sy_snapshot, sy_restore};
     return &ops;
 }
 

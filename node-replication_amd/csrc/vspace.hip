@@ -690,9 +690,69 @@ static void vs_defaults(nrg_config* cfg) {
     cfg->max_batch = 1u << 16;  // the largest chunk a page table replays
 }
 
+// ---- nrg_snapshot_async / nrg_restore: the pool image [0, ntables) ---------------------------------
+typedef u64 vs_u64x2 __attribute__((ext_vector_type(2)));  // 16 B moved by one lane
+
+static int vs_items(nrg_ctx* c, u64* n) {
+    VsState s{};
+    HIPCHK(hipMemcpyAsync(&s, c->vs.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = s.ntables < c->vs.cap ? s.ntables : c->vs.cap;
+    return NRG_OK;
+}
+
+// ntables * 4 KiB as they are, inner entries included (table_index * 4096 | flags: the indices stay
+// valid in any pool of at least ntables tables); ntables is read here. A lane moves 16 B, a wave
+// 1 KiB contiguous. The image must fit whole or nothing of the payload is stored.
+__global__ __launch_bounds__(DG_TPB) void vs_snapshot_kernel(const u64* __restrict__ pool, const VsState* st,
+                                                             u64 tables, u64* buf, u64 cap, u64 log_idx, DevCtl* ctl) {
+    const u64 ntab = st->ntables < tables ? st->ntables : tables;
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_VSPACE, ntab, ntab * 4096, log_idx, ctl);
+    if (snap_bytes(ntab * 4096) > cap) return;
+    const vs_u64x2* src = (const vs_u64x2*)pool;
+    vs_u64x2* out = (vs_u64x2*)(buf + SNAP_HDR / 8);
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < ntab * 256; i += (u64)gridDim.x * DG_TPB) out[i] = src[i];
+}
+
+static hipError_t vs_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    const u64 g = c->vs.cap;  // a workgroup per table where the pool is small
+    NRG_LAUNCH(c, "vs_snapshot", vs_snapshot_kernel, (unsigned)(g > VS_DG_MAX_GRID ? VS_DG_MAX_GRID : g), DG_TPB, 0,
+               c->stream, (const u64*)c->vs.d_pool, (const VsState*)c->vs.d_state, (u64)c->vs.cap, (u64*)d_buf, cap,
+               log_idx, c->d_ctl);
+    return hipGetLastError();
+}
+
+// The tables [0, items) from the payload, the rest of the pool zeroed, and the table count ntab.
+__global__ __launch_bounds__(DG_TPB) void vs_restore_kernel(u64* pool, const u64* __restrict__ payload, u64 items,
+                                                            u64 tables, u64 ntab, VsState* st) {
+    const vs_u64x2* src = (const vs_u64x2*)payload;
+    vs_u64x2* dst = (vs_u64x2*)pool;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < tables * 256; i += (u64)gridDim.x * DG_TPB) {
+        vs_u64x2 v = {0, 0};
+        if (i < items * 256) v = src[i];
+        dst[i] = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->ntables = ntab;
+}
+
+// The tags of an earlier digest describe tables that no longer exist (a table that was a PT may now
+// be a PD, or unreachable): they are cleared, so the next digest tags from the PML4 down again.
+// Without a payload: the PML4 alone, zeroed (VSpace::default).
+static int vs_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    if (check_only) return items == 0 ? NRG_E_INVAL : (items > c->vs.cap ? NRG_E_CAPACITY : NRG_OK);
+    const u64 g = c->vs.cap;
+    NRG_LAUNCH(c, "vs_restore", vs_restore_kernel, (unsigned)(g > VS_DG_MAX_GRID ? VS_DG_MAX_GRID : g), DG_TPB, 0,
+               c->stream, c->vs.d_pool, (const u64*)d_payload, (u64)(d_payload ? items : 0), (u64)c->vs.cap,
+               (u64)(d_payload ? items : 1), c->vs.d_state);
+    HIPCHK(hipGetLastError());
+    if (c->vs.d_tag) HIPCHK(hipMemsetAsync(c->vs.d_tag, 0, c->vs.cap * sizeof(u64), c->stream));
+    return NRG_OK;
+}
+
 const DsOps* vs_ops() {
     static const DsOps ops = {sizeof(nrg_vspace_op), sizeof(nrg_vspace_resp), vs_open, vs_close, vs_flush,
-                              vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults, vs_digest};
+                              vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults, vs_digest,
+                              vs_items, vs_snapshot, vs_restore};
     return &ops;
 }
 

@@ -3,7 +3,7 @@
 The data plane lives in libnrgpu.so (HIP kernels for gfx950 behind the C ABI of
 include/nrgpu.h). This package mirrors the reference `nr` crate's API on top of it.
 """
-from . import _lib, digest
+from . import _lib, digest, snapshot
 from ._lib import NrgError, load
 from .combiner import Combiner
 from .replica import (
@@ -39,7 +39,7 @@ from .replica import (
 )
 
 __all__ = [
-    "_lib", "digest", "NrgError", "load", "Combiner", "PUT_DTYPE", "QUEUE_OP_DTYPE", "STACK_OP_DTYPE", "SYNTH_OP_DTYPE", "SYNTH_RD_DTYPE",
+    "_lib", "digest", "snapshot", "NrgError", "load", "Combiner", "PUT_DTYPE", "QUEUE_OP_DTYPE", "STACK_OP_DTYPE", "SYNTH_OP_DTYPE", "SYNTH_RD_DTYPE",
     "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",

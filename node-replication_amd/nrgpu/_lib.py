@@ -97,6 +97,19 @@ class LogInfo(C.Structure):
     ]
 
 
+class SnapshotInfo(C.Structure):
+    """nrg_snapshot_info: a snapshot's header, validated."""
+
+    _fields_ = [
+        ("ds_kind", C.c_uint32),
+        ("version", C.c_uint32),
+        ("items", C.c_uint64),
+        ("bytes", C.c_uint64),
+        ("log_idx", C.c_uint64),
+        ("digest", C.c_uint64 * 3),
+    ]
+
+
 class Round(C.Structure):
     """nrg_round: one group member's part of a round (device pointers on its GPU)."""
 
@@ -130,6 +143,11 @@ SIGNATURES = {
     "nrg_digest": (C.c_int, [vp, vp]),
     "nrg_digest_async": (C.c_int, [vp, vp]),
     "nrg_group_verify": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
+    "nrg_snapshot_size": (C.c_int, [vp, C.POINTER(SnapshotInfo)]),
+    "nrg_snapshot_async": (C.c_int, [vp, vp, u64]),
+    "nrg_snapshot_info_read": (C.c_int, [vp, vp, u64, C.POINTER(SnapshotInfo)]),
+    "nrg_restore": (C.c_int, [vp, vp, u64]),
+    "nrg_group_resync": (C.c_int, [vp, C.c_int]),
     "nrg_strerror": (C.c_char_p, [C.c_int]),
     "nrg_version": (C.c_char_p, []),
     "nrg_device_count": (C.c_int, []),

@@ -129,6 +129,12 @@ class ReplicaGroup:
                     "nrg_group_verify")
         return bool(same.value), out
 
+    def resync(self, root: int = 0):
+        """nrg_group_resync (a collective: every rank calls it with the same root): rank `root`'s
+        replica is snapshotted and every other rank's replica restored from it, log positions
+        included; what to do when verify() says the replicas differ. For replicated groups."""
+        self._check(self._lib.nrg_group_resync(self._h, int(root)), "nrg_group_resync")
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.nrg_group_close(self._h)

@@ -22,6 +22,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
+from . import snapshot as _snapshot
 
 PUT_DTYPE = np.dtype([("key", "<u8"), ("val", "<u8")])
 STACK_OP_DTYPE = np.dtype([("val", "<u4"), ("op", "<u4")])
@@ -114,6 +115,9 @@ class DeviceReplica:
     # -- lifetime ------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_snap", (0, 0))[0]:  # the snapshot buffer (snapshot_device / restore)
+                self._lib.nrg_dev_free(self._h, C.c_void_p(self._snap[0]))
+                self._snap = (0, 0)
             self._lib.nrg_close(self._h)
             self._h = None
 
@@ -271,6 +275,63 @@ class DeviceReplica:
         """nrg_digest_async: the triple into three u64 on the device, no host round trip.
         Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
         L.check(self._lib.nrg_digest_async(self._h, _dptr(d_out3)), "digest")
+
+    # -- snapshot / restore ----------------------------------------------------------
+    def _info(self, s: "L.SnapshotInfo"):
+        from .snapshot import Info
+
+        return Info(s.ds_kind, s.version, s.items, s.bytes, s.log_idx, tuple(int(x) for x in s.digest))
+
+    def snapshot_info(self):
+        """nrg_snapshot_size: what a snapshot taken now would hold (snapshot.Info; digest zero)."""
+        s = L.SnapshotInfo()
+        L.check(self._lib.nrg_snapshot_size(self._h, C.byref(s)), "snapshot_size")
+        return self._info(s)
+
+    def _snap_buf(self, nbytes: int) -> int:
+        """a device buffer of this replica's, kept and grown for its snapshots and restores"""
+        if getattr(self, "_snap", (0, 0))[1] < nbytes:
+            if getattr(self, "_snap", (0, 0))[0]:
+                L.check(self._lib.nrg_dev_free(self._h, C.c_void_p(self._snap[0])), "dev_free")
+                self._snap = (0, 0)
+            p = C.c_void_p()
+            L.check(self._lib.nrg_dev_alloc(self._h, nbytes, C.byref(p)), "dev_alloc")
+            self._snap = (p.value, nbytes)
+        return self._snap[0]
+
+    def snapshot_device(self):
+        """nrg_snapshot_async into a device buffer this replica owns: (device pointer, bytes, info),
+        complete on return. The buffer is reused by the next snapshot or host restore and freed
+        with the replica: restore from it, or copy it, before then."""
+        want = self.snapshot_info()
+        p = self._snap_buf(want.bytes)
+        L.check(self._lib.nrg_snapshot_async(self._h, C.c_void_p(p), want.bytes), "snapshot")
+        self.sync()
+        s = L.SnapshotInfo()
+        L.check(self._lib.nrg_snapshot_info_read(self._h, C.c_void_p(p), want.bytes, C.byref(s)), "snapshot_info_read")
+        return p, int(s.bytes), self._info(s)
+
+    def snapshot(self) -> np.ndarray:
+        """The replica's state as a snapshot image on the host (u8 array; nrgpu.snapshot.unpack
+        reads it, DeviceReplica.restore takes it back, tofile() keeps it)."""
+        p, nbytes, _ = self.snapshot_device()
+        out = np.zeros(nbytes, np.uint8)
+        L.check(self._lib.nrg_memcpy_d2h(self._h, _ptr(out), C.c_void_p(p), nbytes), "d2h")
+        return out
+
+    def restore(self, buf, nbytes: Optional[int] = None):
+        """nrg_restore: replace this replica's contents and log positions with a snapshot's. `buf`
+        is a host image (u8 array or bytes) or, with `nbytes`, a device pointer (int or torch
+        tensor) whose contents are complete."""
+        if nbytes is None:
+            b = _snapshot.as_u8(buf)
+            if b.size < 64:
+                raise L.NrgError(L.NRG_E_INVAL, "restore")
+            p = self._snap_buf(b.size)
+            L.check(self._lib.nrg_memcpy_h2d(self._h, C.c_void_p(p), _ptr(b), b.size), "h2d")
+            L.check(self._lib.nrg_restore(self._h, C.c_void_p(p), b.size), "restore")
+        else:
+            L.check(self._lib.nrg_restore(self._h, _dptr(buf), nbytes), "restore")
 
     # -- hashmap -------------------------------------------------------------------
     def hm_get(self, keys: np.ndarray):
@@ -800,12 +861,40 @@ class Log:
         self._live: list = []  # (first log index, records, origin) of the batches in [head, tail)
         self.lock = threading.RLock()
 
-    def register(self, replica: "Replica") -> Optional[int]:
+    def register(self, replica: "Replica", clone_from: Optional["Replica"] = None) -> Optional[int]:
         """Log::register (nr/src/log.rs:272-292): ids 1.., None at MAX_REPLICAS. A replica
         registered after appends starts at ltail 0 like the reference's; its copy of the log is
         filled with the live entries, which it replays on its next combine or sync. If GC has
         already moved head past entry 0 the reference's exec would panic ("Local tail not within
-        the shared log", nr/src/log.rs:486-488): here registration fails with RuntimeError."""
+        the shared log", nr/src/log.rs:486-488): here registration fails with RuntimeError.
+
+        With `clone_from`, a replica registered on this log, the new replica starts from that
+        peer's state instead of from entry 0: the peer is synced to the log's tail and
+        snapshotted, and the new replica restored from the image (nrg_restore), so its ltail is
+        the tail and no live entry is copied. That works after GC too."""
+        if clone_from is not None:
+            # (the peer's combiner lock before the log's, the order Replica._combine takes them in)
+            with clone_from._combiner, self.lock:
+                if self._next >= MAX_REPLICAS:
+                    return None
+                if clone_from not in self._replicas:
+                    raise ValueError("clone_from is not registered with this log")
+                clone_from.dev.log_exec()  # to the tail: every copy holds every appended entry
+                if clone_from.dev.device == replica.dev.device:
+                    p, nbytes, info = clone_from.dev.snapshot_device()
+                    if info.log_idx == self.tail:
+                        replica.dev.restore(p, nbytes)
+                else:  # through the host: the new replica's GPU need not read the peer's memory
+                    img = clone_from.dev.snapshot()
+                    info = _snapshot.header(img)
+                    if info.log_idx == self.tail:
+                        replica.dev.restore(img)
+                if info.log_idx != self.tail:
+                    raise RuntimeError("log copies diverged")
+                idx = self._next
+                self._next += 1
+                self._replicas.append(replica)
+                return idx
         with self.lock:
             if self._next >= MAX_REPLICAS:
                 return None
@@ -867,11 +956,14 @@ class Replica:
     """nr::Replica<D> (nr/src/replica.rs:72-595) over a GPU replica backend."""
 
     def __init__(self, log: Log, ds, device: int = 0, **cfg):
+        """`clone_from=peer` (not a config field): start from that registered replica's state
+        instead of replaying the log from entry 0 (Log.register); the only way in after GC."""
+        clone_from = cfg.pop("clone_from", None)
         self.ds = ds
         self.log = log
         cfg.setdefault("log_bytes", log.bytes)
         self.dev = DeviceReplica(ds.kind, device, **cfg)
-        idx = log.register(self)
+        idx = log.register(self, clone_from) if clone_from is not None else log.register(self)
         if idx is None:
             raise RuntimeError("too many replicas registered with the log")
         self.idx = idx
