@@ -23,6 +23,8 @@
  *   nrg_snapshot_* / nrg_restore  Replica::new from a state, not  nr/src/replica.rs:184-232, :443-467
  *   / nrg_group_resync            from log index 0; verify's view
  *   nrg_stack_*                   Stack Dispatch                    benches/stack.rs:36-84, nr/tests/stack.rs:31-96
+ *   nrg_*_reserve / _capacity,    Vec::reserve / capacity, SegQueue's  benches/stack.rs:36-84,
+ *   nrg_set_max_capacity          segments, VSpace's heap tables     benches/lockfree_comparisons.rs:75-101, benches/vspace.rs:388-419
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
  *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
  *   nrg_vspace_*                  VSpace Dispatch (x86-64 page table) benches/vspace.rs:177-381, :436-467, :499-526
@@ -163,7 +165,8 @@ typedef struct {
                                  larger exec ranges are replayed in order, in chunks
                                  (< 2^30; stack, queue: <= 2^24; vspace: <= 2^16, its default) */
     uint64_t max_reads;       /* largest read batch per call                               */
-    uint64_t stack_capacity;  /* stack: maximum number of elements                          */
+    uint64_t stack_capacity;  /* stack: maximum number of elements (< 2^31) at nrg_open;
+                                 nrg_stack_reserve and nrg_set_max_capacity raise it later     */
     uint64_t synth_n;         /* synthetic: number of words (default 200000)               */
     uint32_t synth_cold_reads, synth_cold_writes, synth_hot_reads, synth_hot_writes; /* 20,5,2,1 */
     uint32_t stack_push_resp; /* 0: Push -> None (benches/stack.rs:77-80, nr/examples/stack.rs:70-73)
@@ -223,6 +226,27 @@ int nrg_sync(nrg_ctx* ctx);
 /* Order outstanding side-stream reads (config.pipeline = 1) on the context's stream without
  * blocking the host; a no-op when nothing is outstanding. */
 int nrg_join(nrg_ctx* ctx);
+
+/* Automatic growth of the stack and the queue, as Vec<u32> grows under push (benches/stack.rs:36-84)
+ * and SegQueue never refuses one (benches/lockfree_comparisons.rs:75-101). max_items = 0, the state
+ * after nrg_open, is a fixed capacity (config.stack_capacity / queue_capacity). With a bound, before
+ * a replay chunk of n records could take the length past the capacity the structure is reallocated,
+ * synchronously, to at least twice the capacity and at least length + n elements, clipped to
+ * max_items; only past max_items does a replay latch NRG_E_CAPACITY, as a fixed structure does at its
+ * capacity. The length is tracked on the host as an upper bound (exact when last read, plus every
+ * record replayed since): a chunk whose bound stays within the capacity costs one comparison, and a
+ * balanced Push/Pop stream re-reads its length now and then but never reallocates. Growth happens
+ * inside the round call, so it works under a combiner and in a replica group (set the bound on
+ * every member's replica); replicas that replay the same log in the same chunks with the same bound
+ * grow at the same record, and nothing observable depends on the capacity except where
+ * NRG_E_CAPACITY would appear. With a bound, nrg_restore (and nrg_group_resync) accept an image of
+ * up to max_items items and grow first. The config is not involved: nrg_config's size and offsets
+ * are ABI. NRG_E_INVAL: a hashmap (it has config.hashmap_max_log2_slots), a synthetic or a vspace
+ * context; a nonzero bound below the current capacity or above the kind's nrg_open bound (stack
+ * < 2^31, queue <= 2^32). NRG_E_NOMEM from a round call: the larger buffer could not be allocated;
+ * nothing of the chunk was launched and the replica is unchanged. Synchronous; like every direct
+ * call, not allowed while a combiner is open on the context. */
+int nrg_set_max_capacity(nrg_ctx* ctx, uint64_t max_items);
 
 /* Replica::verify (nr/src/replica.rs:443-467) without the state leaving the GPU: a digest of the
  * replica's data structure, the same definition for every kind. out = {count, sum, xor} over the
@@ -462,6 +486,16 @@ int nrg_combiner_stats(nrg_combiner* comb, uint64_t* rounds, uint64_t* ops);
 /* ---- Stack --------------------------------------------------------------------------- */
 /* Stack::default(): storage = vals[0..n) (bottom first). */
 int nrg_stack_init(nrg_ctx* ctx, const uint32_t* vals, uint64_t n);
+/* Vec::reserve / Vec::capacity (the reference's Stack is a Vec<u32>, benches/stack.rs:36-84): make
+ * room for `n_elems` elements in all, with automatic growth (nrg_set_max_capacity) on or off. It
+ * never shrinks: a request the stack already satisfies returns NRG_OK and does nothing; a stack
+ * reserved beyond its growth bound is a fixed one. NRG_E_INVAL: not a stack, or n_elems >= 2^31
+ * (nrg_open's bound). NRG_E_NOMEM: the new buffer could not be allocated; the old one is intact and
+ * the replica usable. Synchronous (one copy of the elements); like every direct call, not allowed
+ * while a combiner is open on the context. */
+int nrg_stack_reserve(nrg_ctx* ctx, uint64_t n_elems);
+/* The current capacity in elements: config.stack_capacity, or what growth made of it. */
+int nrg_stack_capacity(nrg_ctx* ctx, uint64_t* n_elems);
 /* Replica::combine for one stack batch (nr/src/replica.rs:544-595): Log::append of the n ops
  * in d_ops (device) with `origin`, then Log::exec, fused into one replay pass that writes the
  * log copy itself. Pop responses for these ops (d_pop_vals[i], d_some_bits[i]; nullable) as
@@ -485,15 +519,27 @@ int nrg_synth_read_async(nrg_ctx* ctx, const nrg_synth_rd* d_ops, uint64_t n, ui
 int nrg_synth_dump(nrg_ctx* ctx, uint64_t* words, uint64_t cap, uint64_t* n);
 
 /* ---- FIFO queue (SegQueueWrapper) ------------------------------------------------------- */
-/* The queue holds at most config.queue_capacity elements. A replay during which the length
- * exceeds it latches NRG_E_CAPACITY once (reported by the next nrg_sync / synchronous call), as
+/* The queue holds at most config.queue_capacity elements unless nrg_queue_reserve or automatic
+ * growth (nrg_set_max_capacity) raised that; nrg_queue_capacity reads the current value. A replay
+ * during which the length exceeds it latches NRG_E_CAPACITY once (reported by the next nrg_sync / synchronous call), as
  * the stack does; afterwards nrg_queue_len and nrg_queue_dump never report or copy more than
- * queue_capacity elements. */
+ * the capacity. */
 /* SegQueueWrapper::default with caller values: the queue holds vals[0..n) (front first). */
 int nrg_queue_init(nrg_ctx* ctx, const uint64_t* vals, uint64_t n);
 /* SegQueueWrapper::default (benches/lockfree_comparisons.rs:80-88): values 0..n-1 pushed in
  * order, generated on the device. */
 int nrg_queue_init_range(nrg_ctx* ctx, uint64_t n);
+/* The reference's queue is a SegQueue, which allocates segments as it fills
+ * (benches/lockfree_comparisons.rs:75-101); here, as Vec::reserve / Vec::capacity for the stack:
+ * make room for `n_elems` elements in all. The ring is reallocated to the power of two at or above
+ * n_elems + max_batch and the elements keep their ring positions modulo the new size. It never
+ * shrinks: a request already satisfied returns NRG_OK and does nothing. NRG_E_INVAL: not a queue, or
+ * n_elems > 2^32 (nrg_open's bound). NRG_E_NOMEM: the new ring could not be allocated; the old one
+ * is intact and the replica usable. Synchronous; like every direct call, not allowed while a
+ * combiner is open on the context. */
+int nrg_queue_reserve(nrg_ctx* ctx, uint64_t n_elems);
+/* The current capacity in elements: config.queue_capacity, or what growth made of it. */
+int nrg_queue_capacity(nrg_ctx* ctx, uint64_t* n_elems);
 /* Dispatch::dispatch(QueueRd::Len) (benches/lockfree_comparisons.rs:99): the length. */
 int nrg_queue_len(nrg_ctx* ctx, uint64_t* n);
 /* Copy out the elements, front first. `*n` receives their number; if it exceeds `cap`, nothing
@@ -507,8 +553,8 @@ int nrg_queue_round_async(nrg_ctx* ctx, const nrg_queue_op* d_ops, uint64_t n, u
                           uint64_t* d_resp, uint8_t* d_some);
 
 /* ---- VSpace: the replicated x86-64 page table (VSpaceDispatcher) ---------------------------- */
-/* The replica's tables live in a device pool of 2^config.log2_slots tables of 4 KiB, zeroed at
- * open; table 0 is the PML4, and an inner entry holds table_index * 4096 | P|RW|US where the
+/* The replica's tables live in a device pool of 2^config.log2_slots tables of 4 KiB (more after
+ * nrg_vspace_reserve), zeroed at open; table 0 is the PML4, and an inner entry holds table_index * 4096 | P|RW|US where the
  * reference stores a heap pointer (nothing observable depends on it). A replay that needs more
  * tables than the pool holds latches NRG_E_CAPACITY once (reported by the next nrg_sync /
  * synchronous call): exactly the ops whose tables do not fit when their turn comes in log order
@@ -533,6 +579,17 @@ int nrg_vspace_resolve_async(nrg_ctx* ctx, const uint64_t* d_vaddrs, uint64_t n,
                              uint8_t* d_found);
 /* Tables allocated so far, the PML4 included (VSpace::allocs.len() + 1, :384-404). */
 int nrg_vspace_tables(nrg_ctx* ctx, uint64_t* n);
+/* VSpace takes every page table from the heap (benches/vspace.rs:388-419 new_pt / new_pd / new_pdpt);
+ * here the pool is made larger: room for `n_tables` tables in all, the allocated ones copied (inner
+ * entries hold table indices, which stay valid) and the rest zeroed. It never shrinks: a request the
+ * pool already satisfies returns NRG_OK and does nothing. There is no automatic growth for the page
+ * table: the tables a chunk needs are only known on the device. NRG_E_INVAL: not a vspace, or
+ * n_tables > 2^22 (nrg_open's bound). NRG_E_NOMEM: the new pool could not be allocated; the old one
+ * is intact and the replica usable. Synchronous; nrg_restore accepts an image that fits the pool as
+ * reserved. */
+int nrg_vspace_reserve(nrg_ctx* ctx, uint64_t n_tables);
+/* The tables the pool holds: 2^config.log2_slots, or what nrg_vspace_reserve made of it. */
+int nrg_vspace_capacity(nrg_ctx* ctx, uint64_t* n_tables);
 /* Replica::verify's view (nr/src/replica.rs:443-467): every leaf entry, one record each, in
  * ascending vaddr, whatever order the tables were allocated in. `*n` receives their number; if it
  * exceeds `cap`, nothing is copied and NRG_E_CAPACITY is returned (as nrg_queue_dump). */

@@ -120,6 +120,12 @@ inline u32 dg_grid(u64 items) {
     const u64 g = (items + DG_TPB - 1) / DG_TPB;
     return g < 1 ? 1u : (g > DG_MAX_GRID ? DG_MAX_GRID : (u32)g);
 }
+// workgroups of a grid-stride copy of `units` lane-sized units (the growth kernels): up to eight
+// per CU, the rest by stride
+inline u32 copy_grid(u64 units) {
+    const u64 g = (units + DG_TPB - 1) / DG_TPB;
+    return g < 1 ? 1u : (g > 2048 ? 2048u : (u32)g);
+}
 // Every lane's partial triple, reduced per wave, then per workgroup, then added into out3 (zeroed
 // earlier in stream order) with one set of atomics per workgroup that found anything.
 __device__ __forceinline__ void dg_commit(u64 c, u64 sm, u64 x, u64* out3) {

@@ -160,6 +160,10 @@ struct StHost {  // stack (stack.hip)
     uint32_t par = 0;            // buffer parity of the next chunk
     uint32_t* d_desc = nullptr;  // look-back descriptors of both parities (st_desc_words)
     uint64_t desc_words = 0;
+    // Growth (st_room / st_grow): the buffer may grow to max_items elements (0: fixed); len_ub bounds
+    // the length from above: the exact length when it was last read plus every record replayed since.
+    uint64_t max_items = 0;
+    uint64_t len_ub = 0;
 };
 
 struct SyHost {  // synthetic (synthetic.hip)
@@ -181,6 +185,10 @@ struct QuHost {  // FIFO queue (queue.hip)
     uint64_t size = 0;
     QuState* d_state = nullptr;
     void* d_aux = nullptr;  // per-tile aggregates and scanned starts
+    // Growth (qu_room / qu_grow), as the stack's: the bound on the capacity (0: fixed) and the upper
+    // bound of the length.
+    uint64_t max_items = 0;
+    uint64_t len_ub = 0;
 };
 
 struct VsHost {  // page table (vspace.hip)
@@ -251,6 +259,9 @@ struct DsOps {
     // payload (the stream has been drained, nothing is deferred). d_payload == nullptr: the empty
     // structure of a fresh context instead (after a restore whose digest did not match).
     int (*restore)(nrg_ctx* c, const void* d_payload, u64 items, bool check_only);
+    // nrg_set_max_capacity: the bound automatic growth stops at (0: fixed capacity); an NRG_* code.
+    // The stream has been drained. nullptr: the kind has no such bound.
+    int (*set_max)(nrg_ctx* c, u64 max_items);
 };
 const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind

@@ -26,6 +26,8 @@
 //                     answered directly, the length checked against the capacity; a Pop of one of
 //                     the chunk's own Pushes leaves its slot in its response word
 //   qu_gather_kernel  those Pops read their slot (skipped when the chunk has none)
+#include <algorithm>
+
 #include "internal.hpp"
 
 namespace nrg {
@@ -349,11 +351,96 @@ static u64 qu_max_tiles(u64 max_batch) { return (max_batch + QU_TILE - 1) / QU_T
 
 static u64 qu_aux_bytes(u64 max_batch) { return qu_max_tiles(max_batch) * (sizeof(QuAgg) + sizeof(QuStart)); }
 
+// ---- growth (SegQueue never refuses a push: benches/lockfree_comparisons.rs:75-101) ---------------
+// A re-layout, not a copy: the live elements are the ring positions [head, head + len) under the
+// old mask (the range may wrap the old ring's end) and go to the same positions under the new mask,
+// so head stays monotonic and QuState is unchanged. head and the length are read here, the length
+// clamped as nrg_queue_len clamps it; consecutive lanes take consecutive elements.
+__global__ __launch_bounds__(DG_TPB) void qu_grow_kernel(const u64* __restrict__ from, u64 from_mask,
+                                                         u64* __restrict__ to, u64 to_mask, const QuState* st,
+                                                         u64 from_cap) {
+    const u64 head = st->head;
+    const u64 n = st->len > from_cap ? from_cap : st->len;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB)
+        to[(head + i) & to_mask] = from[(head + i) & from_mask];
+}
+
+// The exact length, clamped as nrg_queue_len clamps it. Drains the stream.
+static hipError_t qu_exact_len(nrg_ctx* c, u64* n) {
+    u64 len = 0;
+    hipError_t e = hipMemcpyAsync(&len, &c->qu.d_state->len, sizeof(len), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    *n = len > c->cfg.queue_capacity ? c->cfg.queue_capacity : len;
+    return hipSuccess;
+}
+
+// The ring is reallocated to the power of two at or above new_cap + max_batch (qu_open's invariant);
+// where that is the ring it has, only the capacity changes. The re-layout, then the stream is
+// synchronised (there is no stream-ordered free), the old ring freed and the new one installed with
+// the capacity every launch and clamp reads (cfg.queue_capacity, qu.size). If the allocation fails
+// nothing has been launched: the replica is as it was.
+static hipError_t qu_grow(nrg_ctx* c, u64 new_cap) {
+    const u64 cap = c->cfg.queue_capacity;
+    if (new_cap <= cap || new_cap > (1ull << 32)) return hipErrorInvalidValue;
+    const u64 nsize = pow2_at_least(new_cap + c->cfg.max_batch);
+    if (nsize != c->qu.size) {
+        u64* nq = nullptr;
+        if (hipMalloc(&nq, nsize * sizeof(u64)) != hipSuccess) {
+            (void)hipGetLastError();  // (the failure is reported by the return value alone)
+            return hipErrorOutOfMemory;
+        }
+        NRG_LAUNCH(c, "qu_grow", qu_grow_kernel, copy_grid(cap), DG_TPB, 0, c->stream, (const u64*)c->qu.d_queue,
+                   c->qu.size - 1, nq, nsize - 1, (const QuState*)c->qu.d_state, cap);
+        hipError_t e = hipGetLastError();
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) {
+            (void)hipFree(nq);
+            return e;
+        }
+        (void)hipFree(c->qu.d_queue);
+        c->qu.d_queue = nq;
+        c->qu.size = nsize;
+    }
+    c->cfg.queue_capacity = new_cap;
+    return hipSuccess;
+}
+
+// the capacity automatic growth goes to for `need` elements: at least double, clipped to the bound
+static u64 qu_grown(const nrg_ctx* c, u64 need) {
+    u64 want = 2 * c->cfg.queue_capacity;
+    if (want < need) want = need;
+    return want > c->qu.max_items ? c->qu.max_items : want;
+}
+
+// The growth policy, the stack's (st_room): the n records about to be replayed are added to the
+// upper bound len_ub; only when the bound passes the capacity is QuState::len read, and only if
+// exact + n still passes it does the queue grow. At the bound the queue is a fixed one.
+static hipError_t qu_room(nrg_ctx* c, u64 n) {
+    QuHost& q = c->qu;
+    if (!q.max_items || c->cfg.queue_capacity >= q.max_items) return hipSuccess;
+    if (q.len_ub + n <= c->cfg.queue_capacity) {
+        q.len_ub += n;
+        return hipSuccess;
+    }
+    u64 exact = 0;
+    timer_begin(c, "qu_room");  // (nrg_kernel_time counts the re-reads)
+    hipError_t e = qu_exact_len(c, &exact);
+    timer_end(c, "qu_room");
+    if (e != hipSuccess) return e;
+    if (exact + n > c->cfg.queue_capacity && (e = qu_grow(c, qu_grown(c, exact + n))) != hipSuccess) return e;
+    q.len_ub = exact + n;
+    return hipSuccess;
+}
+
 // One chunk of at most max_batch records: log indices [lo, lo + n), read from the ring or, for a
 // fused round, from `src` (the log copy is then written by the aggregate pass).
 static hipError_t qu_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
     if (n == 0) return hipSuccess;
+    const hipError_t eg = qu_room(c, n);  // the ring grows first if it has to (one comparison if not)
+    if (eg != hipSuccess) return eg;
     QuJob j{};
     j.src = (const nrg_queue_op*)src;
     j.ring = (nrg_queue_op*)c->d_ring;
@@ -487,17 +574,31 @@ __global__ __launch_bounds__(DG_TPB) void qu_restore_kernel(u64* q, const u64* _
 }
 
 static int qu_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
-    if (check_only) return items > c->cfg.queue_capacity ? NRG_E_CAPACITY : NRG_OK;
+    // with a growth bound the image may be as large as the bound: the ring grows first
+    if (check_only)
+        return items <= std::max<u64>(c->cfg.queue_capacity, c->qu.max_items) ? NRG_OK : NRG_E_CAPACITY;
     if (!d_payload) items = 0;
+    if (items > c->cfg.queue_capacity) HIPCHK(qu_grow(c, qu_grown(c, items)));
     NRG_LAUNCH(c, "qu_restore", qu_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->qu.d_queue,
                (const u64*)d_payload, items, c->qu.d_state);
+    c->qu.len_ub = items;
     return hip_fail(hipGetLastError());
+}
+
+// nrg_set_max_capacity: the bound, and the length bound restarts from the exact length
+static int qu_set_max(nrg_ctx* c, u64 max_items) {
+    if (max_items && (max_items < c->cfg.queue_capacity || max_items > (1ull << 32))) return NRG_E_INVAL;
+    u64 exact = 0;
+    HIPCHK(qu_exact_len(c, &exact));
+    c->qu.max_items = max_items;
+    c->qu.len_ub = exact;
+    return NRG_OK;
 }
 
 const DsOps* qu_ops() {
     static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk,
                               floor_ltail, nullptr, nullptr, nullptr, qu_digest,
-                              qu_items, qu_snapshot, qu_restore};
+                              qu_items, qu_snapshot, qu_restore, qu_set_max};
     return &ops;
 }
 
@@ -528,7 +629,9 @@ int nrg_queue_init(nrg_ctx* c, const uint64_t* vals, uint64_t n) {
     if (n && !vals) return NRG_E_INVAL;
     // head = 0: the n values sit at the start of the ring (capacity <= its size)
     if (n) HIPCHK(hipMemcpyAsync(c->qu.d_queue, vals, n * 8, hipMemcpyHostToDevice, c->stream));
-    return qu_set_state(c, n);
+    if ((r = qu_set_state(c, n))) return r;
+    c->qu.len_ub = n;
+    return NRG_OK;
 }
 
 int nrg_queue_init_range(nrg_ctx* c, uint64_t n) {
@@ -537,6 +640,22 @@ int nrg_queue_init_range(nrg_ctx* c, uint64_t n) {
     if (n > c->cfg.queue_capacity) return NRG_E_CAPACITY;
     HIPCHK(qu_init_range(c, n));
     HIPCHK(sync_all(c));
+    c->qu.len_ub = n;
+    return NRG_OK;
+}
+
+int nrg_queue_reserve(nrg_ctx* c, uint64_t n_elems) {
+    int r = need(c, NRG_DS_QUEUE);
+    if (r) return r;
+    if (n_elems > (1ull << 32)) return NRG_E_INVAL;  // nrg_open's bound
+    if (n_elems <= c->cfg.queue_capacity) return NRG_OK;
+    HIPCHK(qu_grow(c, n_elems));
+    return NRG_OK;
+}
+
+int nrg_queue_capacity(nrg_ctx* c, uint64_t* n) {
+    if (!c || !n || c->cfg.ds_kind != NRG_DS_QUEUE) return NRG_E_INVAL;
+    *n = c->cfg.queue_capacity;
     return NRG_OK;
 }
 

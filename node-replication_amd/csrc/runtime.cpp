@@ -398,6 +398,16 @@ int nrg_sync(nrg_ctx* c) {
     return check_err(c);
 }
 
+// The bound of a kind that grows under replay as its reference structure does (Vec, SegQueue);
+// what it means is the kind's (DsOps::set_max).
+int nrg_set_max_capacity(nrg_ctx* c, uint64_t max_items) {
+    if (!c || !c->ops->set_max) return NRG_E_INVAL;
+    int r = use_device(c);
+    if (r) return r;
+    HIPCHK(sync_all(c));
+    return c->ops->set_max(c, max_items);
+}
+
 int nrg_join(nrg_ctx* c) {
     if (!c) return NRG_E_INVAL;
     int r = use_device(c);

@@ -902,12 +902,104 @@ static hipError_t st_flush(nrg_ctx* c) {
     return st_launch(c, A, P);
 }
 
+// ---- growth (Vec::reserve, and the Vec growing under push: benches/stack.rs:36-84) ---------------
+// The elements [0, length) into a larger buffer, the length read here and clamped as nrg_stack_len
+// clamps it. A lane moves 16 B (both buffers are allocations of their own, so 16-B aligned); the
+// last length % 4 elements go one per lane.
+__global__ __launch_bounds__(DG_TPB) void st_grow_kernel(const u32* __restrict__ from, u32* __restrict__ to,
+                                                         const DevCtl* ctl, u64 from_cap) {
+    long long d = ctl->depth;
+    if (d < 0) d = 0;
+    const u64 n = (u64)d > from_cap ? from_cap : (u64)d;
+    const u64 n4 = n / 4, gid = blockIdx.x * (u64)DG_TPB + threadIdx.x;
+    const u32x4_t* s4 = (const u32x4_t*)from;
+    u32x4_t* d4 = (u32x4_t*)to;
+    for (u64 i = gid; i < n4; i += (u64)gridDim.x * DG_TPB) d4[i] = s4[i];
+    const u64 r = n4 * 4 + gid;
+    if (r < n) to[r] = from[r];
+}
+
+// The stack's exact length (the deferred finish publishes it), clamped as nrg_stack_len clamps it.
+// Drains the stream.
+static hipError_t st_exact_len(nrg_ctx* c, u64* n) {
+    long long d = 0;
+    hipError_t e = st_flush(c);
+    if (e == hipSuccess) e = hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    if (d < 0) d = 0;
+    *n = (u64)d > c->cfg.stack_capacity ? c->cfg.stack_capacity : (u64)d;
+    return hipSuccess;
+}
+
+// Steps, in stream order: the deferred finish of the last chunk commits into the old buffer; the
+// copy; then the stream is synchronised (there is no stream-ordered free), the old buffer freed and
+// the new one installed, with the capacity every launch and clamp reads (cfg.stack_capacity). If the
+// allocation fails nothing has been launched but the flush: the replica is as it was.
+static hipError_t st_grow(nrg_ctx* c, u64 new_cap) {
+    const u64 cap = c->cfg.stack_capacity;
+    if (new_cap <= cap || new_cap >= (1ull << 31)) return hipErrorInvalidValue;
+    hipError_t e = st_flush(c);
+    if (e != hipSuccess) return e;
+    u32* nb = nullptr;
+    if (hipMalloc(&nb, new_cap * sizeof(u32)) != hipSuccess) {
+        (void)hipGetLastError();  // (the failure is reported by the return value alone)
+        return hipErrorOutOfMemory;
+    }
+    NRG_LAUNCH(c, "st_grow", st_grow_kernel, copy_grid(cap / 4 + 1), DG_TPB, 0, c->stream, (const u32*)c->st.d_stack, nb,
+               (const DevCtl*)c->d_ctl, cap);
+    e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        (void)hipFree(nb);
+        return e;
+    }
+    (void)hipFree(c->st.d_stack);
+    c->st.d_stack = nb;
+    c->cfg.stack_capacity = new_cap;
+    return hipSuccess;
+}
+
+// the capacity automatic growth goes to for `need` elements: at least double, clipped to the bound
+static u64 st_grown(const nrg_ctx* c, u64 need) {
+    u64 want = 2 * c->cfg.stack_capacity;
+    if (want < need) want = need;
+    return want > c->st.max_items ? c->st.max_items : want;
+}
+
+// The growth policy, as hm_room's. The n records about to be replayed are added to the upper bound
+// len_ub; only when the bound passes the capacity is the exact length read (the deferred finish, an
+// 8-B copy and a stream synchronise), and only if exact + n still passes it does the buffer grow.
+// A balanced Push/Pop stream re-reads its length now and then and never reallocates. At the bound
+// the stack is a fixed one: nothing is read, and a chunk that overflows latches ERR_CAPACITY as it
+// always did. The decision depends on the log prefix, the chunking and the bound alone, so replicas
+// that replay the same log in the same chunks grow at the same record.
+static hipError_t st_room(nrg_ctx* c, u64 n) {
+    StHost& s = c->st;
+    if (!s.max_items || c->cfg.stack_capacity >= s.max_items) return hipSuccess;
+    if (s.len_ub + n <= c->cfg.stack_capacity) {
+        s.len_ub += n;
+        return hipSuccess;
+    }
+    u64 exact = 0;
+    timer_begin(c, "st_room");  // (nrg_kernel_time counts the re-reads)
+    hipError_t e = st_exact_len(c, &exact);
+    timer_end(c, "st_room");
+    if (e != hipSuccess) return e;
+    if (exact + n > c->cfg.stack_capacity && (e = st_grow(c, st_grown(c, exact + n))) != hipSuccess) return e;
+    s.len_ub = exact + n;
+    return hipSuccess;
+}
+
 // One chunk: its tile pass, fused with the previous chunk's finish in one launch. The chunk's
 // own finish runs in the next chunk's launch (config.pipeline = 1, until nrg_join or a sync)
 // or right away.
 static hipError_t st_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
     if (n == 0) return st_flush(c);  // an empty round still completes the last round's deferred finish
+    const hipError_t eg = st_room(c, n);  // the buffer grows first if it has to (one comparison if not)
+    if (eg != hipSuccess) return eg;
     StPass A = st_pass(c, c->st.par);
     A.src = (const nrg_stack_op*)src;
     A.lo = lo;
@@ -1034,18 +1126,32 @@ __global__ __launch_bounds__(DG_TPB) void st_restore_kernel(u32* stack, const u3
 }
 
 static int st_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
-    if (check_only) return items > c->cfg.stack_capacity ? NRG_E_CAPACITY : NRG_OK;
+    // with a growth bound the image may be as large as the bound: the buffer grows first
+    if (check_only)
+        return items <= std::max<u64>(c->cfg.stack_capacity, c->st.max_items) ? NRG_OK : NRG_E_CAPACITY;
     if (!d_payload) items = 0;
+    if (items > c->cfg.stack_capacity) HIPCHK(st_grow(c, st_grown(c, items)));
     c->st.pend.valid = false;
     NRG_LAUNCH(c, "st_restore", st_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->st.d_stack,
                (const u32*)d_payload, items, c->d_ctl);
+    c->st.len_ub = items;
     return hip_fail(hipGetLastError());
+}
+
+// nrg_set_max_capacity: the bound, and the length bound restarts from the exact length
+static int st_set_max(nrg_ctx* c, u64 max_items) {
+    if (max_items && (max_items < c->cfg.stack_capacity || max_items >= (1ull << 31))) return NRG_E_INVAL;
+    u64 exact = 0;
+    HIPCHK(st_exact_len(c, &exact));
+    c->st.max_items = max_items;
+    c->st.len_ub = exact;
+    return NRG_OK;
 }
 
 const DsOps* st_ops() {
     static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk,
                               floor_ltail, nullptr, st_dbg_words, nullptr, st_digest,
-                              st_items, st_snapshot, st_restore};
+                              st_items, st_snapshot, st_restore, st_set_max};
     return &ops;
 }
 
@@ -1072,6 +1178,22 @@ int nrg_stack_init(nrg_ctx* c, const uint32_t* vals, uint64_t n) {
     // the depth slot the next chunk starts from (a chunk of parity p reads slot p ^ 1)
     HIPCHK(hipMemcpyAsync(&c->d_ctl->depth0 + (c->st.par ^ 1), &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     HIPCHK(sync_all(c));
+    c->st.len_ub = n;
+    return NRG_OK;
+}
+
+int nrg_stack_reserve(nrg_ctx* c, uint64_t n_elems) {
+    int r = need(c, NRG_DS_STACK);
+    if (r) return r;
+    if (n_elems >= (1ull << 31)) return NRG_E_INVAL;  // nrg_open's bound
+    if (n_elems <= c->cfg.stack_capacity) return NRG_OK;
+    HIPCHK(st_grow(c, n_elems));
+    return NRG_OK;
+}
+
+int nrg_stack_capacity(nrg_ctx* c, uint64_t* n) {
+    if (!c || !n || c->cfg.ds_kind != NRG_DS_STACK) return NRG_E_INVAL;
+    *n = c->cfg.stack_capacity;
     return NRG_OK;
 }
 

@@ -749,6 +749,53 @@ static int vs_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_o
     return NRG_OK;
 }
 
+// ---- growth of the pool (VSpace takes its tables from the heap: benches/vspace.rs:388-419) --------
+// The tables [0, ntables) into a larger pool and the rest of it zeroed, in one launch (the rest of
+// the code relies on a zeroed pool); ntables is read here. Inner entries are table indices, so they
+// stay valid. A lane moves 16 B, a wave 1 KiB contiguous.
+__global__ __launch_bounds__(DG_TPB) void vs_grow_kernel(const u64* __restrict__ from, u64 from_tables, u64* to,
+                                                         u64 to_tables, const VsState* st) {
+    const u64 ntab = st->ntables < from_tables ? st->ntables : from_tables;
+    const vs_u64x2* src = (const vs_u64x2*)from;
+    vs_u64x2* dst = (vs_u64x2*)to;
+    // (four zero stores in flight per lane and turn instead of one: 0.920 against 0.935 ms for the
+    // 2^18 -> 2^20 pool of microbench/capacity_grow.py, so the loop stays vs_restore_kernel's)
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < to_tables * 256; i += (u64)gridDim.x * DG_TPB) {
+        vs_u64x2 v = {0, 0};
+        if (i < ntab * 256) v = src[i];
+        dst[i] = v;
+    }
+}
+
+// The copy, then the stream is synchronised (there is no stream-ordered free), the old pool freed
+// and the new one installed with the capacity every launch reads (vs.cap). The digest's tags are
+// sized by the pool: they are dropped, and the next digest allocates them for the new pool and tags
+// from the PML4 down again. If the allocation fails nothing has been launched: the replica is as it
+// was.
+static hipError_t vs_grow(nrg_ctx* c, u64 new_cap) {
+    if (new_cap <= c->vs.cap || new_cap > (1ull << 22)) return hipErrorInvalidValue;
+    u64* np = nullptr;
+    if (hipMalloc(&np, new_cap * 4096) != hipSuccess) {
+        (void)hipGetLastError();  // (the failure is reported by the return value alone)
+        return hipErrorOutOfMemory;
+    }
+    NRG_LAUNCH(c, "vs_grow", vs_grow_kernel, (unsigned)(new_cap > VS_DG_MAX_GRID ? VS_DG_MAX_GRID : new_cap), DG_TPB, 0,
+               c->stream, (const u64*)c->vs.d_pool, (u64)c->vs.cap, np, new_cap, (const VsState*)c->vs.d_state);
+    hipError_t e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        (void)hipFree(np);
+        return e;
+    }
+    (void)hipFree(c->vs.d_pool);
+    (void)hipFree(c->vs.d_tag);
+    c->vs.d_pool = np;
+    c->vs.d_tag = nullptr;
+    c->vs.cap = new_cap;
+    return hipSuccess;
+}
+
 const DsOps* vs_ops() {
     static const DsOps ops = {sizeof(nrg_vspace_op), sizeof(nrg_vspace_resp), vs_open, vs_close, vs_flush,
                               vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults, vs_digest,
@@ -809,6 +856,21 @@ int nrg_vspace_tables(nrg_ctx* c, uint64_t* n) {
     if (r) return r;
     if (!n) return NRG_E_INVAL;
     return vs_get_tables(c, n);
+}
+
+int nrg_vspace_reserve(nrg_ctx* c, uint64_t n_tables) {
+    int r = need(c, NRG_DS_VSPACE);
+    if (r) return r;
+    if (n_tables > (1ull << 22)) return NRG_E_INVAL;  // nrg_open's bound
+    if (n_tables <= c->vs.cap) return NRG_OK;
+    HIPCHK(vs_grow(c, n_tables));
+    return NRG_OK;
+}
+
+int nrg_vspace_capacity(nrg_ctx* c, uint64_t* n) {
+    if (!c || !n || c->cfg.ds_kind != NRG_DS_VSPACE) return NRG_E_INVAL;
+    *n = c->vs.cap;
+    return NRG_OK;
 }
 
 int nrg_test_vspace_table(nrg_ctx* c, uint64_t table, uint64_t out[512]) {

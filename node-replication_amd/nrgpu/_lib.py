@@ -140,6 +140,7 @@ SIGNATURES = {
     "nrg_own_stream": (vp, [vp]),
     "nrg_sync": (C.c_int, [vp]),
     "nrg_join": (C.c_int, [vp]),
+    "nrg_set_max_capacity": (C.c_int, [vp, u64]),
     "nrg_digest": (C.c_int, [vp, vp]),
     "nrg_digest_async": (C.c_int, [vp, vp]),
     "nrg_group_verify": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
@@ -176,16 +177,22 @@ SIGNATURES = {
     "nrg_stack_peek": (C.c_int, [vp, C.POINTER(u32), C.POINTER(C.c_uint8)]),
     "nrg_stack_len": (C.c_int, [vp, u64p]),
     "nrg_stack_dump": (C.c_int, [vp, vp, u64, u64p]),
+    "nrg_stack_reserve": (C.c_int, [vp, u64]),
+    "nrg_stack_capacity": (C.c_int, [vp, u64p]),
     "nrg_queue_init": (C.c_int, [vp, vp, u64]),
     "nrg_queue_init_range": (C.c_int, [vp, u64]),
     "nrg_queue_len": (C.c_int, [vp, u64p]),
     "nrg_queue_dump": (C.c_int, [vp, vp, u64, u64p]),
+    "nrg_queue_reserve": (C.c_int, [vp, u64]),
+    "nrg_queue_capacity": (C.c_int, [vp, u64p]),
     "nrg_queue_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
     "nrg_vspace_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
     "nrg_vspace_resolve": (C.c_int, [vp, vp, u64, vp, vp]),
     "nrg_vspace_resolve_async": (C.c_int, [vp, vp, u64, vp, vp]),
     "nrg_vspace_tables": (C.c_int, [vp, u64p]),
     "nrg_vspace_dump": (C.c_int, [vp, vp, u64, u64p]),
+    "nrg_vspace_reserve": (C.c_int, [vp, u64]),
+    "nrg_vspace_capacity": (C.c_int, [vp, u64p]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

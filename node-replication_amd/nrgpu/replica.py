@@ -476,7 +476,46 @@ class DeviceReplica:
         L.check(self._lib.nrg_stack_dump(self._h, _ptr(out), n, C.byref(m)), "stack_dump")
         return out[: m.value]
 
+    def _reserve(self, fn, kind: int, what: str, n: int):
+        if self.kind != kind:
+            raise TypeError(f"{what} needs another kind of replica")
+        n = int(n)
+        if n < 0 or n >= 2**64:
+            raise ValueError("the size must be a u64")
+        L.check(fn(self._h, n), what)
+
+    def _capacity(self, fn, kind: int, what: str) -> int:
+        if self.kind != kind:
+            raise TypeError(f"{what} needs another kind of replica")
+        n = C.c_uint64()
+        L.check(fn(self._h, C.byref(n)), what)
+        return n.value
+
+    def set_max_capacity(self, max_items: int):
+        """Automatic growth of a stack or queue replica up to `max_items` elements; 0 (the state after
+        open) is a fixed capacity (nrg_set_max_capacity). Synchronous."""
+        max_items = int(max_items)
+        if max_items < 0 or max_items >= 2**64:
+            raise ValueError("max_items must be a u64")
+        L.check(self._lib.nrg_set_max_capacity(self._h, max_items), "set_max_capacity")
+
+    def st_reserve(self, n_elems: int):
+        """Vec::reserve: room for `n_elems` elements in all; never shrinks (nrg_stack_reserve)."""
+        self._reserve(self._lib.nrg_stack_reserve, L.NRG_DS_STACK, "st_reserve", n_elems)
+
+    def st_capacity(self) -> int:
+        """Vec::capacity: the elements the stack has room for (nrg_stack_capacity)."""
+        return self._capacity(self._lib.nrg_stack_capacity, L.NRG_DS_STACK, "st_capacity")
+
     # -- queue ---------------------------------------------------------------------
+    def qu_reserve(self, n_elems: int):
+        """Room for `n_elems` elements in all; never shrinks (nrg_queue_reserve)."""
+        self._reserve(self._lib.nrg_queue_reserve, L.NRG_DS_QUEUE, "qu_reserve", n_elems)
+
+    def qu_capacity(self) -> int:
+        """The elements the queue has room for (nrg_queue_capacity)."""
+        return self._capacity(self._lib.nrg_queue_capacity, L.NRG_DS_QUEUE, "qu_capacity")
+
     def qu_init(self, vals):
         """The queue holds `vals`, front first."""
         vals = np.ascontiguousarray(np.asarray(vals, np.uint64))
@@ -500,6 +539,14 @@ class DeviceReplica:
         return out[: m.value]
 
     # -- vspace --------------------------------------------------------------------
+    def vs_reserve(self, n_tables: int):
+        """A pool of `n_tables` page tables in all; never shrinks (nrg_vspace_reserve)."""
+        self._reserve(self._lib.nrg_vspace_reserve, L.NRG_DS_VSPACE, "vs_reserve", n_tables)
+
+    def vs_capacity(self) -> int:
+        """The page tables the pool holds (nrg_vspace_capacity)."""
+        return self._capacity(self._lib.nrg_vspace_capacity, L.NRG_DS_VSPACE, "vs_capacity")
+
     def vs_resolve(self, vaddrs):
         """Identify for a batch of virtual addresses: (paddrs, found); paddr 0 where unmapped."""
         vaddrs = np.ascontiguousarray(np.asarray(vaddrs, np.uint64))
