@@ -3,6 +3,7 @@
 Mirrors nr/tests/stack.rs `sequential_test` (:102-168: random push/pop/peek vs a Vec
 model, then verify storage and popped values) and benches/stack.rs (50/50 push/pop over
 an initial 50,000-element stack, :50-63, :87-102), with seeded streams.
+Deep and structured streams (the arms a random walk never reaches): tests/test_gpu_stack_streams.py.
 """
 import numpy as np
 import pytest
