@@ -502,9 +502,16 @@ __device__ __forceinline__ bool resolve(u64 val, u64 st, const ReadJob& j, u64* 
 // round: RPT 1 34.4 us, 2 36.2, 4 39.8; the N=8 per-GPU round 99.3 / 100.8 / 105.4 us.
 constexpr int RPT = 1;
 
+// STAMP: the role inside a stamp round's kernel, which launch() uses only with index blocks: the
+// table is being written (never quiet) and the responses are plain stores. With both flags known
+// when the kernel is compiled the loop below measured 2 us faster per 900k Gets than with the flags
+// read from the job (microbench/read_chain.hip dyn2 against dyn3, profiles/read_chain.txt).
+template <bool STAMP>
 __device__ __forceinline__ void read_role(const ReadJob& j, u32 blk, const Slot* table, u32 shift, u64 tmask,
                                           const DevCtl* ctl) {
     const u32 par = j.epoch & 1;
+    const auto quiet = [&] { return STAMP ? false : j.quiet; };
+    const auto plain = [&] { return STAMP ? true : j.plain; };
     const u64 q0 = (u64)blk * TPB * RPT + threadIdx.x;
     u64 k[RPT], s[RPT];
     bool on[RPT];
@@ -528,7 +535,7 @@ __device__ __forceinline__ void read_role(const ReadJob& j, u32 blk, const Slot*
             // (round 6: with the streaming hint on these two loads, 34.04-34.13 -> 44.25-44.36 us per
             // B1 round; profiles/r06/b1_apply_nt.txt)
             w[r] = *(const u64x2*)&table[s[r]];
-            if (!j.quiet) st[r] = table[s[r]].st[par];
+            if (!quiet()) st[r] = table[s[r]].st[par];
         }
     }
 #pragma unroll
@@ -538,14 +545,14 @@ __device__ __forceinline__ void read_role(const ReadJob& j, u32 blk, const Slot*
         bool f = false;
         if (k[r] == EMPTY_KEY) {
             if (ctl->sp_claim) {
-                if (j.quiet) {
+                if (quiet()) {
                     f = true;
                     v = ctl->sp.val;
                 } else {
                     f = resolve(ctl->sp.val, ctl->sp.st[par], j, &v);
                 }
             }
-        } else if (j.quiet) {
+        } else if (quiet()) {
             u64 kk = w[r].x, vv = w[r].y, sl = s[r];
             for (u64 pr = 0; pr <= tmask; pr++) {
                 if (kk == k[r]) {
@@ -578,8 +585,8 @@ __device__ __forceinline__ void read_role(const ReadJob& j, u32 blk, const Slot*
         }
         if (!f) v = 0;
         const u64 q = q0 + (u64)r * TPB;
-        st_out(&j.vals[q], v, j.plain);
-        st_out(&j.found[q], (uint8_t)(f ? 1 : 0), j.plain);
+        st_out(&j.vals[q], v, plain());
+        st_out(&j.found[q], (uint8_t)(f ? 1 : 0), plain());
     }
 }
 
@@ -625,7 +632,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_num_sgpr(80))) void hm_r
         return;
     }
     b -= aj.nblocks;
-    read_role(rj, b, table, shift, tmask, ctl);
+    read_role<IX == IX_STAMP>(rj, b, table, shift, tmask, ctl);
 }
 
 // ---- hm_papply_kernel: partition rounds' table pass, one workgroup per bucket ---------------------
