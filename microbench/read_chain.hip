@@ -13,8 +13,15 @@
 //            trip to memory carries a full wave of probes. Slower than chain at N = 2, 4, 8.
 //   dyn1..6, round, round_q   the product's read role rebuilt around chain one difference at a
 //            time (see read_role below): what the bisect of chain against the product used.
-// It also counts how many Gets need a second, third, ... probe and how many trips a 64-Get wave
-// makes, and checks every variant's answers against chain's. Results: profiles/read_chain.txt.
+//   groupA, groupB, groupA_q, groupB_q, groupA_s   over a second table filled in the line-grouped
+//            probe sequence (common.hpp probe_slot): a quad of lanes loads a Get's whole four-slot
+//            group per trip (group_role below). A: a block owns 256 Gets, four passes of 16 per
+//            wave, answers shuffled back to one Get per lane; B: one pass, 64 Gets per block;
+//            _q: the quiet reads of a reads-only round (against round_q); _s: A with one coalesced
+//            key load and the passes' keys by shuffle. The yardsticks above stay on linear probing.
+// It also counts how many Gets need a second, third, ... probe (a second group, on the grouped
+// table) and how many trips a 64-Get wave makes, and checks chain's answers against a CPU lookup
+// and every variant's against chain's. Results: profiles/read_chain.txt, profiles/read_group.txt.
 // Usage: read_chain [gets_per_launch]   (default 900000, B1's Gets)
 #include <hip/hip_runtime.h>
 
@@ -386,6 +393,139 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_num_sgpr(80))) void roun
     read_role<3>(rj, b, table, shift, tmask, ctl);
 }
 
+// ---- the line-grouped probe sequence: a quad of lanes reads a Get's whole 128-B group per trip ----
+// (common.hpp probe_slot, restated) round the home's four-slot group from the home slot, then the
+// next group from the same offset, ...: a present key lies in the first group of its sequence that
+// had an empty slot when it was inserted, so a group with an empty slot and no match ends a search.
+__host__ __device__ constexpr u64 probe_slot(u64 home, u64 p, u64 tmask) {
+    return ((((home >> 2) + (p >> 2)) << 2) | ((home + p) & 3)) & tmask;
+}
+
+// quad_perm DPP moves (lane ^ 1, lane ^ 2 inside each four lanes) and the OR over a quad
+__device__ __forceinline__ u32 quad_x1(u32 x) { return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true); }
+__device__ __forceinline__ u32 quad_x2(u32 x) { return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true); }
+__device__ __forceinline__ u64 quad_or(u64 x) {
+    u32 lo = (u32)x, hi = (u32)(x >> 32);
+    lo |= quad_x1(lo);
+    hi |= quad_x1(hi);
+    lo |= quad_x2(lo);
+    hi |= quad_x2(hi);
+    return ((u64)hi << 32) | lo;
+}
+
+// A wave owns 16 * PASSES consecutive Gets; in pass p the quad of lanes 4g .. 4g+3 owns Get 16 p + g
+// and lane sub = lane & 3 loads slot sub of the Get's home group: {key, val} and the stamp, back to
+// back, every pass's loads issued before the first wait. At most one lane of a quad matches (a key
+// sits in one slot), so the quad's answer is the OR of its lanes' (0 where there is no match); a
+// quad with no match and no empty slot goes on to the next group (rare: a full group).
+// PASSES 4 = (A): a block owns 256 Gets as today, and the answers go back to one Get per lane (one
+// 64-bit shuffle), so a wave stores whole 512-B / 64-B runs. PASSES 1 = (B): 64 Gets per block,
+// lane 0 of each quad stores. STAMP as the product's read_role<STAMP>.
+template <int PASSES, bool STAMP, bool KSHFL = false>
+__device__ __forceinline__ void group_role(const ReadJob& j, u32 blk, const Slot* table, u32 shift, u64 tmask,
+                                           const Ctl* ctl) {
+    const u32 par = j.epoch & 1;
+    const auto quiet = [&] { return STAMP ? false : j.quiet; };
+    const auto plain = [&] { return STAMP ? true : j.plain; };
+    const u32 lane = threadIdx.x & 63, sub = lane & 3, quad = lane >> 2, qsh = lane & ~3u;
+    const u64 wbase = ((u64)blk * (TPB / 64) + (threadIdx.x >> 6)) * (16 * PASSES);
+    if (wbase >= j.R) return;
+    u64 k[PASSES], s[PASSES], st[PASSES];
+    u64x2 w[PASSES];
+    bool probe[PASSES];
+    if (KSHFL) {  // one coalesced key load per wave, the passes' keys by shuffle
+        const u64 kown = wbase + lane < j.R ? j.keys[wbase + lane] : EMPTY_KEY;
+#pragma unroll
+        for (int p = 0; p < PASSES; p++) k[p] = __shfl(kown, (int)(p * 16 + quad), 64);
+    } else {
+#pragma unroll
+        for (int p = 0; p < PASSES; p++) {
+            const u64 q = wbase + p * 16 + quad;
+            k[p] = q < j.R ? j.keys[q] : EMPTY_KEY;  // (a Get past the end reads as the side key and is not stored)
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < PASSES; p++) {
+        s[p] = (((mix64(k[p]) >> shift) & ~3ull) | sub) & tmask;
+        probe[p] = k[p] != EMPTY_KEY;
+        w[p].x = EMPTY_KEY;
+        w[p].y = 0;
+        st[p] = 0;
+        if (probe[p]) {
+            w[p] = *(const u64x2*)&table[s[p]];
+            if (!quiet()) st[p] = table[s[p]].st[par];
+        }
+    }
+    u64 rv[PASSES], fb[PASSES];
+#pragma unroll
+    for (int p = 0; p < PASSES; p++) {
+        u64 kk = w[p].x, vv = w[p].y, stt = st[p], sl = s[p], v = 0;
+        asm volatile("" : "+v"(kk), "+v"(vv), "+v"(stt));
+        bool f = false, act = probe[p];
+        for (u64 g = 0;; g++) {
+            const bool hit = act && kk == k[p];
+            if (hit) {
+                if (quiet()) {
+                    f = true;
+                    v = vv;
+                } else {
+                    f = resolve(vv, stt, j, &v);
+                }
+            }
+            // the quad is done on a match or an empty slot (a lane that does not probe reads as empty)
+            const u64 done = __ballot(hit || !act || kk == EMPTY_KEY);
+            act = ((done >> qsh) & 15) == 0 && g < (tmask >> 2);
+            if (!__ballot(act)) break;
+            if (act) {
+                sl = (sl + 4) & tmask;
+                const u64x2 x = *(const u64x2*)&table[sl];
+                if (!quiet()) stt = table[sl].st[par];
+                kk = x.x;
+                vv = x.y;
+            }
+        }
+        if (k[p] == EMPTY_KEY && sub == 0 && ctl->sp_claim) {  // the side key
+            if (quiet()) {
+                f = true;
+                v = ctl->sp.val;
+            } else {
+                f = resolve(ctl->sp.val, ctl->sp.st[par], j, &v);
+            }
+        }
+        if (!f) v = 0;
+        rv[p] = quad_or(v);
+        fb[p] = __ballot(f);
+    }
+    if (PASSES == 1) {
+        const u64 q = wbase + quad;
+        if (sub == 0 && q < j.R) {
+            st_out(&j.vals[q], rv[0], plain());
+            st_out(&j.found[q], (unsigned char)(((fb[0] >> qsh) & 15) != 0), plain());
+        }
+    } else {
+        // lane l holds pass (l & 3)'s answer of its quad; Get L = 16 p + g sits in lane 4 g + p
+        u64 c = rv[0], b = fb[0];
+#pragma unroll
+        for (int p = 1; p < PASSES; p++) {
+            if (sub == (u32)p) c = rv[p];
+            if ((lane >> 4) == (u32)p) b = fb[p];
+        }
+        const u64 v = __shfl(c, (int)(4 * (lane & 15) + (lane >> 4)), 64);
+        const u64 q = wbase + lane;
+        if (q < j.R) {
+            st_out(&j.vals[q], v, plain());
+            st_out(&j.found[q], (unsigned char)(((b >> (4 * (lane & 15))) & 15) != 0), plain());
+        }
+    }
+}
+
+template <int PASSES, bool STAMP, bool KSHFL = false>
+__global__ __launch_bounds__(TPB) __attribute__((amdgpu_num_sgpr(80))) void group_kernel(ReadJob rj, const Slot* table,
+                                                                                          u32 shift, u64 tmask,
+                                                                                          const Ctl* ctl) {
+    group_role<PASSES, STAMP, KSHFL>(rj, blockIdx.x, table, shift, tmask, ctl);
+}
+
 __global__ void init_table(Slot* t, u64 slots) {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < slots; i += (u64)gridDim.x * blockDim.x) {
         Slot s;
@@ -396,10 +536,13 @@ __global__ void init_table(Slot* t, u64 slots) {
     }
 }
 
-// as hm_prefill_range_kernel: claim by CAS from the home slot, linear probing
+// as hm_prefill_range_kernel: claim by CAS from the home slot; GROUPED: the line-grouped sequence
+// (probe_slot), else linear probing (the yardsticks' table)
+template <bool GROUPED>
 __global__ void prefill(Slot* t, u64 n) {
     for (u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (u64)gridDim.x * blockDim.x) {
-        u64 s = mix64(k) >> SHIFT;
+        const u64 home = mix64(k) >> SHIFT;
+        u64 s = home;
         for (u64 pr = 0; pr <= TMASK; pr++) {
             const u64 old = atomicCAS(&t[s].key, EMPTY_KEY, k);
             if (old == EMPTY_KEY || old == k) {
@@ -407,9 +550,25 @@ __global__ void prefill(Slot* t, u64 n) {
                 t[s].st[0] = t[s].st[1] = STAMP_PRESENT;
                 break;
             }
-            s = (s + 1) & TMASK;
+            s = GROUPED ? probe_slot(home, pr + 1, TMASK) : (s + 1) & TMASK;
         }
     }
+}
+
+// groups read by every Get of a batch over the grouped table (1 = answered from its home group), capped at 16
+__global__ void count_groups(const Slot* __restrict__ t, const u64* __restrict__ keys, u64 n, unsigned char* groups) {
+    const u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const u64 k = keys[q];
+    u64 g = (mix64(k) >> SHIFT) & ~3ull;
+    u32 p = 1;
+    for (; p < 16; p++) {
+        bool end = false;
+        for (int x = 0; x < 4; x++) end = end || t[g + x].key == k || t[g + x].key == EMPTY_KEY;
+        if (end) break;
+        g = (g + 4) & TMASK;
+    }
+    groups[q] = (unsigned char)p;
 }
 
 // probes of every Get of a batch (1 = ends at its home slot), capped at 16
@@ -426,7 +585,7 @@ __global__ void count_probes(const Slot* __restrict__ t, const u64* __restrict__
     probes[q] = (unsigned char)p;
 }
 
-enum Variant { V_FIRST, V_CHAIN, V_REFILL2, V_REFILL4, V_REFILL8, V_DYN1, V_DYN2, V_DYN3, V_DYN4, V_DYN5, V_DYN6, V_ROUND, V_ROUNDQ };
+enum Variant { V_FIRST, V_CHAIN, V_REFILL2, V_REFILL4, V_REFILL8, V_DYN1, V_DYN2, V_DYN3, V_DYN4, V_DYN5, V_DYN6, V_ROUND, V_ROUNDQ, V_GROUPA, V_GROUPB, V_GROUPAQ, V_GROUPBQ, V_GROUPAS };
 static Ctl* g_ctl;
 
 static void launch(Variant v, const Slot* t, Job j, hipStream_t st) {
@@ -438,7 +597,7 @@ static void launch(Variant v, const Slot* t, Job j, hipStream_t st) {
     case V_REFILL4: refill_kernel<4><<<(unsigned)((n + TPB * 4 - 1) / (TPB * 4)), TPB, 0, st>>>(t, j); break;
     case V_REFILL8: refill_kernel<8><<<(unsigned)((n + TPB * 8 - 1) / (TPB * 8)), TPB, 0, st>>>(t, j); break;
     default: {
-        const unsigned grid = (unsigned)((n + TPB - 1) / TPB);
+        const unsigned grid = (unsigned)((n + TPB - 1) / TPB), grid_b = (unsigned)((n + 63) / 64);
         IndexJob ij{};
         StampJob sj{};
         ApplyJob aj{};
@@ -452,14 +611,20 @@ static void launch(Variant v, const Slot* t, Job j, hipStream_t st) {
         rj.use_rec = j.use_rec;
         rj.rec.ring = j.rec;
         rj.rec.mask = 255;
-        rj.quiet = v == V_ROUNDQ;  // reads-only rounds: no stamps read, streamed responses asked for
-        rj.plain = v != V_ROUNDQ;
+        // reads-only rounds: no stamps read, streamed responses asked for
+        rj.quiet = v == V_ROUNDQ || v == V_GROUPAQ || v == V_GROUPBQ;
+        rj.plain = !rj.quiet;
         if (v == V_DYN1) dyn_kernel<1><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
         else if (v == V_DYN2) dyn_kernel<2><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
         else if (v == V_DYN3) dyn_kernel<3><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
         else if (v == V_DYN4) dyn_kernel<4><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
         else if (v == V_DYN5) dyn_kernel<5><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
         else if (v == V_DYN6) dyn_kernel<6><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
+        else if (v == V_GROUPA) group_kernel<4, true><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
+        else if (v == V_GROUPAS) group_kernel<4, true, true><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
+        else if (v == V_GROUPB) group_kernel<1, true><<<grid_b, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
+        else if (v == V_GROUPAQ) group_kernel<4, false><<<grid, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
+        else if (v == V_GROUPBQ) group_kernel<1, false><<<grid_b, TPB, 0, st>>>(rj, t, SHIFT, TMASK, g_ctl);
         else round_kernel<<<grid, TPB, 0, st>>>(ij, sj, aj, rj, (Slot*)t, SHIFT, TMASK, g_ctl);
     }
     }
@@ -494,10 +659,13 @@ static double run(Variant v, const char* name, const Slot* t, u64* const* keys, 
 int main(int argc, char** argv) {
     const u64 n = argc > 1 ? strtoull(argv[1], 0, 10) : 900000ull;
     const u64 slots = 1ull << LOG2_SLOTS;
-    Slot* t;
+    Slot *t, *tg;  // the linear-probing table of the yardsticks and the line-grouped one
     CHK(hipMalloc((void**)&t, slots * sizeof(Slot)));
+    CHK(hipMalloc((void**)&tg, slots * sizeof(Slot)));
     init_table<<<4096, 256>>>(t, slots);
-    prefill<<<4096, 256>>>(t, NKEYS);
+    init_table<<<4096, 256>>>(tg, slots);
+    prefill<false><<<4096, 256>>>(t, NKEYS);
+    prefill<true><<<4096, 256>>>(tg, NKEYS);
     CHK(hipDeviceSynchronize());
     u64* keys[16];
     u64* h = (u64*)malloc(n * 8);
@@ -547,6 +715,23 @@ int main(int argc, char** argv) {
                (double)wave_trips / waves, 100.0 * wt[1] / waves, 100.0 * (waves - wt[1] - wt[2]) / waves,
                100.0 * (waves - wt[1] - wt[2] - wt[3]) / waves);
     }
+    count_groups<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(tg, keys[0], n, probes);
+    CHK(hipMemcpyAsync(hp, probes, n, hipMemcpyDeviceToHost, st));
+    CHK(hipStreamSynchronize(st));
+    {
+        u64 more = 0, waves = 0, wmore = 0;
+        for (u64 i = 0; i < n; i += 64) {
+            bool any = false;
+            for (u64 q = i; q < i + 64 && q < n; q++) {
+                more += hp[q] > 1;
+                any = any || hp[q] > 1;
+            }
+            wmore += any;
+            waves++;
+        }
+        printf("line-grouped table: Gets needing >= 2 groups %.4f %%; 64-Get runs with such a Get %.2f %%\n",
+               100.0 * more / n, 100.0 * wmore / waves);
+    }
     free(hp);
 
     Job j;
@@ -571,12 +756,23 @@ int main(int argc, char** argv) {
         CHK(hipMemcpyAsync(hv, vals, n * 8, hipMemcpyDeviceToHost, st));
         CHK(hipMemcpyAsync(hf, found, n, hipMemcpyDeviceToHost, st));
         CHK(hipStreamSynchronize(st));
-        const Variant rv[11] = {V_REFILL2, V_REFILL4, V_REFILL8, V_DYN1, V_DYN2, V_DYN3, V_DYN4, V_DYN5, V_DYN6, V_ROUND, V_ROUNDQ};
-        const char* rn[11] = {"refill2", "refill4", "refill8", "dyn1", "dyn2", "dyn3", "dyn4", "dyn5", "dyn6", "round", "round_q"};
-        for (int x = 0; x < 11; x++) {
+        // chain's own answers against the CPU's: key k < NKEYS holds k + 1
+        for (u64 i = 0; i < n; i++) {
+            const u64 k = mix64(0x9e3779b97f4a7c15ull * (i + 1)) % 10000000ull;  // batch 0's Get i
+            if (hf[i] != (k < NKEYS) || hv[i] != (k < NKEYS ? k + 1 : 0)) {
+                printf("chain answers DIFFER FROM the CPU lookup at Get %llu\n", (unsigned long long)i);
+                return 1;
+            }
+        }
+        printf("chain answers equal the CPU lookup\n");
+        const Variant rv[16] = {V_REFILL2, V_REFILL4, V_REFILL8, V_DYN1, V_DYN2, V_DYN3, V_DYN4, V_DYN5, V_DYN6, V_ROUND, V_ROUNDQ,
+                                V_GROUPA, V_GROUPB, V_GROUPAQ, V_GROUPBQ, V_GROUPAS};
+        const char* rn[16] = {"refill2", "refill4", "refill8", "dyn1", "dyn2", "dyn3", "dyn4", "dyn5", "dyn6", "round", "round_q",
+                              "groupA", "groupB", "groupA_q", "groupB_q", "groupA_s"};
+        for (int x = 0; x < 16; x++) {
             CHK(hipMemsetAsync(vals2, 0xAB, n * 8, st));
             CHK(hipMemsetAsync(found2, 0xAB, n, st));
-            launch(rv[x], t, b, st);
+            launch(rv[x], rv[x] >= V_GROUPA ? tg : t, b, st);
             CHK(hipMemcpyAsync(hv2, vals2, n * 8, hipMemcpyDeviceToHost, st));
             CHK(hipMemcpyAsync(hf2, found2, n, hipMemcpyDeviceToHost, st));
             CHK(hipStreamSynchronize(st));
@@ -594,7 +790,7 @@ int main(int argc, char** argv) {
     }
     free(h);
 
-    for (int rep = 0; rep < 2; rep++) {
+    for (int rep = 0; rep < 3; rep++) {
         run(V_FIRST, "first", t, keys, j, st);
         run(V_CHAIN, "chain", t, keys, j, st);
         run(V_REFILL2, "refill2", t, keys, j, st);
@@ -608,6 +804,11 @@ int main(int argc, char** argv) {
         run(V_DYN6, "dyn6", t, keys, j, st);
         run(V_ROUND, "round", t, keys, j, st);
         run(V_ROUNDQ, "round_q", t, keys, j, st);
+        run(V_GROUPA, "groupA", tg, keys, j, st);
+        run(V_GROUPB, "groupB", tg, keys, j, st);
+        run(V_GROUPAQ, "groupA_q", tg, keys, j, st);
+        run(V_GROUPBQ, "groupB_q", tg, keys, j, st);
+        run(V_GROUPAS, "groupA_s", tg, keys, j, st);
     }
     CHK(hipStreamSynchronize(st));
     for (int b = 0; b < 16; b++) CHK(hipFree(keys[b]));
@@ -619,5 +820,6 @@ int main(int argc, char** argv) {
     CHK(hipFree(rec));
     CHK(hipFree(g_ctl));
     CHK(hipFree(t));
+    CHK(hipFree(tg));
     return 0;
 }

@@ -31,10 +31,12 @@ constexpr u32 HM_BK_MAX = 1024;
 // u16 per tile of 2048 Puts) and 16-bit tile offsets within bounds.
 constexpr u64 HM_MAX_BATCH = 1ull << 23;
 // Table growth (nrg_config.hashmap_max_log2_slots, nrg_hashmap_reserve): a table of S slots that
-// growth manages holds at most S / HM_GROW_SLOTS_PER_KEY keys, a load of 0.5. A miss under linear
-// probing costs about (1 + 1/(1-a)^2) / 2 probes: 2.5 at a = 0.5, 8.5 at a = 0.75. Every probe
-// past the home slot's 128-B line (4 slots) is another random line, and random lines are what the
-// read role's time is made of: at 0.5 most chains end inside the first line, at 0.75 few do.
+// growth manages holds at most S / HM_GROW_SLOTS_PER_KEY keys, a load of 0.5. A Get reads its key's
+// home group (a 128-B line of 4 slots, probe_slot below) and goes on to the next group only when
+// that one is full and does not hold the key; every further group is another random line, and
+// random lines are what the read role's time is made of. With uniform homes (a sequential model of
+// 2^20 slots): at a = 0.5 16 % of the groups are full, a hit reads 1.05 groups and a miss 1.23; at
+// a = 0.75 49 % are full, a hit reads 1.27 and a miss 2.69.
 constexpr u64 HM_GROW_SLOTS_PER_KEY = 2;
 
 // splitmix64 finaliser — identical constants to oracle/nr_oracle.c (orc_mix64) so that
@@ -58,6 +60,44 @@ __host__ __device__ __forceinline__ u32 key_owner(u64 key, u32 parts) {
 
 // Home slot of a key: top bits of the mixed key.
 __device__ __forceinline__ u64 table_home(u64 key, u32 shift) { return mix64(key) >> shift; }
+
+// The probe sequence of a key with home slot `home`, p = 0, 1, 2, ...: round the home's group of four
+// slots (one 128-B line) from the home slot on, then round the next group from the same offset, and so
+// on, wrapping at the table's end. It is a function of the key alone, every walk of a chain goes
+// through it, and no key is ever deleted (a full group stays full), so a present key lies in the first
+// group of its sequence that had an empty slot when the key was inserted: a reader that sees a group
+// with an empty slot and no match has its answer, absent, without looking at a later group.
+__host__ __device__ constexpr u64 probe_slot(u64 home, u64 p, u64 tmask) {
+    return ((((home >> 2) + (p >> 2)) << 2) | ((home + p) & 3)) & tmask;
+}
+// The same sequence one step at a time, for walks that keep the slot and not the home: slot p + 1 of
+// the sequence whose slot p is s (the next slot of s's group, or of the following group after every
+// fourth step).
+__host__ __device__ constexpr u64 probe_next(u64 s, u64 p, u64 tmask) {
+    return probe_slot(s, ((p + 1) & 3) ? 1 : 5, tmask);
+}
+namespace probe_check {
+// p = 0 .. slots-1 visits every slot exactly once from every home, p = 0 .. 3 stays in the home's group,
+// and probe_next walks the same sequence
+constexpr bool covers(u64 slots) {
+    for (u64 home = 0; home < slots; home++) {
+        u64 seen = 0;
+        for (u64 p = 0; p < slots; p++) {
+            const u64 s = probe_slot(home, p, slots - 1);
+            if (s >= slots || ((seen >> s) & 1)) return false;
+            if (p < 4 && (s >> 2) != (home >> 2)) return false;
+            if (probe_next(s, p, slots - 1) != probe_slot(home, p + 1, slots - 1)) return false;
+            seen |= 1ull << s;
+        }
+    }
+    return true;
+}
+static_assert(probe_slot(6, 0, 15) == 6 && probe_slot(6, 1, 15) == 7 && probe_slot(6, 2, 15) == 4 &&
+                  probe_slot(6, 3, 15) == 5 && probe_slot(6, 4, 15) == 10 && probe_slot(14, 5, 15) == 3,
+              "round the home group from the home slot, then the next group from the same offset, wrapping");
+static_assert(covers(16), "a 16-slot table: every slot once from every home, the first four in the home group");
+static_assert(covers(64), "a 64-slot table: every slot once from every home, the first four in the home group");
+}  // namespace probe_check
 
 // 32-byte table slot, four per 128-B line (2^26 slots = 2 GiB). A random read costs one 128-B
 // line at the memory side whatever its width (profiles/r01_rdreq_size.txt), so the replay's

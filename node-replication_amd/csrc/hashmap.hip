@@ -4,8 +4,9 @@
 // benches/hashmap.rs:114-119, nr/examples/hashmap.rs:46-50) and the read path
 // Replica::read_only -> dispatch (nr/src/replica.rs:483-497, benches/hashmap.rs:107-111).
 //
-// Table: 2^k open-addressing slots of 32 B {key, value, stamp[2]} (common.hpp), linear probing
-// from mix64(key) >> (64 - k); the one key equal to the empty marker lives in DevCtl::sp. Every
+// Table: 2^k open-addressing slots of 32 B {key, value, stamp[2]} (common.hpp), probed from
+// mix64(key) >> (64 - k) round the home slot's group of four (one 128-B line), then group by group
+// (common.hpp probe_slot); the one key equal to the empty marker lives in DevCtl::sp. Every
 // replay round covers the log records [lo, lo+n) and takes a fresh epoch e. Two schedules:
 //
 // Stamp rounds (no previous-value responses, key stream not skewed): ONE launch per round,
@@ -305,9 +306,10 @@ __device__ __forceinline__ void part_role(const IndexJob& j, u32 blk, u32 shift,
 }
 
 // claim (or find) k's slot from its home slot; *fresh = this call inserted it; -1: table full
-__device__ __forceinline__ long long claim_slot(Slot* table, u64 k, u64 s, u64 tmask, bool* fresh) {
+__device__ __forceinline__ long long claim_slot(Slot* table, u64 k, u64 home, u64 tmask, bool* fresh) {
     *fresh = false;
     for (u64 pr = 0; pr <= tmask; pr++) {
+        const u64 s = probe_slot(home, pr, tmask);
         const u64 key = ld_relaxed(&table[s].key);
         if (key == k) return (long long)s;
         if (key == EMPTY_KEY) {
@@ -319,7 +321,6 @@ __device__ __forceinline__ long long claim_slot(Slot* table, u64 k, u64 s, u64 t
             }
             if (old == k) return (long long)s;
         }
-        s = (s + 1) & tmask;
     }
     return -1;
 }
@@ -374,7 +375,7 @@ __device__ __forceinline__ long long find_or_claim_marked(Slot* table, u64 k, u6
             }
             if (old == k) return (long long)s;
         }
-        s = (s + 1) & tmask;
+        s = probe_next(s, pr, tmask);
         key = ld_relaxed(&table[s].key);
     }
     return -1;
@@ -497,96 +498,127 @@ __device__ __forceinline__ bool resolve(u64 val, u64 st, const ReadJob& j, u64* 
     return true;
 }
 
-// RPT Gets per thread, q = blk * TPB * RPT + r * TPB + tid: every key load and every home-line
-// load of the thread in flight together. Measured on one box (profiles/r03_read_rpt.txt), B1 per
-// round: RPT 1 34.4 us, 2 36.2, 4 39.8; the N=8 per-GPU round 99.3 / 100.8 / 105.4 us.
+// A block's reads: TPB * RPT consecutive Gets. (RPT: Gets per thread with every key load and every
+// home-line load of the thread in flight together, measured on one box, profiles/r03_read_rpt.txt, B1
+// per round: RPT 1 34.4 us, 2 36.2, 4 39.8; the N=8 per-GPU round 99.3 / 100.8 / 105.4 us.)
 constexpr int RPT = 1;
+static_assert(RPT == 1, "read_role gives a wave 64 consecutive Gets");
 
+// quad_perm DPP moves (lane ^ 1 and lane ^ 2 inside each four lanes) and the OR over a quad of lanes
+__device__ __forceinline__ u32 quad_x1(u32 x) { return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true); }
+__device__ __forceinline__ u32 quad_x2(u32 x) { return (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true); }
+__device__ __forceinline__ u64 quad_or(u64 x) {
+    u32 lo = (u32)x, hi = (u32)(x >> 32);
+    lo |= quad_x1(lo);
+    hi |= quad_x1(hi);
+    lo |= quad_x2(lo);
+    hi |= quad_x2(hi);
+    return ((u64)hi << 32) | lo;
+}
+
+// A Get reads its key's whole home group (four slots, one 128-B line) in one trip: the probe sequence
+// (common.hpp probe_slot) keeps a key in its home group whenever the group had room, so a group with
+// a match or an empty slot answers the Get, and only a full group without the key (4e-4 of the
+// groups at B1's load) sends it on to the next group. A wave owns 64 consecutive Gets and takes them
+// in READ_PASSES passes of 16: in pass p the quad of lanes 4g .. 4g+3 owns Get 16 p + g, and lane
+// sub = lane & 3 loads {key, val} and the stamp of slot sub of the group, two loads of one line
+// issued back to back, every pass's loads in flight before the first wait (one wave instruction
+// touches 16 lines, 4 lanes each). At most one lane of a quad matches (a key sits in one slot), so
+// the quad's answer is the OR of its lanes' (0 where nothing matched); the answers then go back to
+// one Get per lane, so a wave stores whole 512-B / 64-B runs. Against the per-lane chain walk:
+// 22.8-22.9 us against 23.8-23.9 per 900k Gets (microbench/read_chain.hip groupA against dyn2;
+// 64 Gets per block and one pass measured slower, groupB; profiles/read_group.txt).
+//
 // STAMP: the role inside a stamp round's kernel, which launch() uses only with index blocks: the
 // table is being written (never quiet) and the responses are plain stores. With both flags known
-// when the kernel is compiled the loop below measured 2 us faster per 900k Gets than with the flags
+// when the kernel is compiled the chain walk measured 2 us faster per 900k Gets than with the flags
 // read from the job (microbench/read_chain.hip dyn2 against dyn3, profiles/read_chain.txt).
+constexpr int READ_PASSES = 4;
+static_assert(READ_PASSES * 16 == 64, "a wave's passes of 16 quads cover its 64 Gets");
 template <bool STAMP>
 __device__ __forceinline__ void read_role(const ReadJob& j, u32 blk, const Slot* table, u32 shift, u64 tmask,
                                           const DevCtl* ctl) {
     const u32 par = j.epoch & 1;
     const auto quiet = [&] { return STAMP ? false : j.quiet; };
     const auto plain = [&] { return STAMP ? true : j.plain; };
-    const u64 q0 = (u64)blk * TPB * RPT + threadIdx.x;
-    u64 k[RPT], s[RPT];
-    bool on[RPT];
+    const u32 lane = lane_id(), sub = lane & 3, quad = lane >> 2, qsh = lane & ~3u;
+    const u64 wbase = (u64)blk * TPB + (threadIdx.x & ~63u);  // the wave's first Get
+    if (wbase >= j.R) return;
+    u64 k[READ_PASSES], s[READ_PASSES], st[READ_PASSES];
+    u64x2 w[READ_PASSES];
 #pragma unroll
-    for (int r = 0; r < RPT; r++) {
-        const u64 q = q0 + (u64)r * TPB;
-        on[r] = q < j.R;
-        k[r] = on[r] ? j.keys[q] : EMPTY_KEY;
+    for (int p = 0; p < READ_PASSES; p++) {
+        const u64 q = wbase + p * 16 + quad;
+        k[p] = q < j.R ? j.keys[q] : EMPTY_KEY;  // (a Get past the end is not stored)
     }
-    // first probe of every key: {key, val} and the stamp, two loads of one line, all issued together
-    u64x2 w[RPT];
-    u64 st[RPT];
 #pragma unroll
-    for (int r = 0; r < RPT; r++) {
-        s[r] = table_home(k[r], shift);
-        const bool probe = on[r] && k[r] != EMPTY_KEY;
-        w[r].x = EMPTY_KEY;
-        w[r].y = 0;
-        st[r] = 0;
-        if (probe) {
+    for (int p = 0; p < READ_PASSES; p++) {
+        s[p] = ((table_home(k[p], shift) & ~3ull) | sub) & tmask;
+        w[p].x = EMPTY_KEY;
+        w[p].y = 0;
+        st[p] = 0;
+        if (k[p] != EMPTY_KEY) {
             // (round 6: with the streaming hint on these two loads, 34.04-34.13 -> 44.25-44.36 us per
             // B1 round; profiles/r06/b1_apply_nt.txt)
-            w[r] = *(const u64x2*)&table[s[r]];
-            if (!quiet()) st[r] = table[s[r]].st[par];
+            w[p] = *(const u64x2*)&table[s[p]];
+            if (!quiet()) st[p] = table[s[p]].st[par];
         }
     }
+    u64 rv[READ_PASSES], fb[READ_PASSES];
 #pragma unroll
-    for (int r = 0; r < RPT; r++) {
-        if (!on[r]) continue;
-        u64 v = 0;
-        bool f = false;
-        if (k[r] == EMPTY_KEY) {
-            if (ctl->sp_claim) {
+    for (int p = 0; p < READ_PASSES; p++) {
+        u64 kk = w[p].x, vv = w[p].y, stt = st[p], sl = s[p], v = 0;
+        // (without these the compiler sinks the stamp load below the loop, a second dependent trip)
+        asm volatile("" : "+v"(kk), "+v"(vv), "+v"(stt));
+        bool f = false, act = k[p] != EMPTY_KEY;
+        // at most one group per step and every group once: an absent key in a full table terminates
+        for (u64 g = 0;; g++) {
+            const bool hit = act && kk == k[p];
+            if (hit) {
                 if (quiet()) {
                     f = true;
-                    v = ctl->sp.val;
-                } else {
-                    f = resolve(ctl->sp.val, ctl->sp.st[par], j, &v);
-                }
-            }
-        } else if (quiet()) {
-            u64 kk = w[r].x, vv = w[r].y, sl = s[r];
-            for (u64 pr = 0; pr <= tmask; pr++) {
-                if (kk == k[r]) {
-                    f = true;
                     v = vv;
-                    break;
+                } else {
+                    f = resolve(vv, stt, j, &v);
                 }
-                if (kk == EMPTY_KEY) break;
-                sl = (sl + 1) & tmask;
+            }
+            // a match or an empty slot ends the quad's search (a lane that does not probe reads as empty)
+            const u64 done = __ballot(hit || !act || kk == EMPTY_KEY);
+            act = ((done >> qsh) & 15) == 0 && g < (tmask >> 2);
+            if (!__ballot(act)) break;
+            if (act) {
+                sl = (sl + 4) & tmask;
                 const u64x2 x = *(const u64x2*)&table[sl];
+                if (!quiet()) stt = table[sl].st[par];
                 kk = x.x;
                 vv = x.y;
             }
-        } else {
-            u64 kk = w[r].x, vv = w[r].y, stt = st[r], sl = s[r];
-            asm volatile("" : "+v"(kk), "+v"(vv), "+v"(stt));
-            for (u64 pr = 0; pr <= tmask; pr++) {
-                if (kk == k[r]) {
-                    f = resolve(vv, stt, j, &v);
-                    break;
-                }
-                if (kk == EMPTY_KEY) break;
-                sl = (sl + 1) & tmask;
-                const u64x2 x = *(const u64x2*)&table[sl];
-                stt = table[sl].st[par];
-                kk = x.x;
-                vv = x.y;
-                asm volatile("" : "+v"(kk), "+v"(vv), "+v"(stt));
+        }
+        if (k[p] == EMPTY_KEY && sub == 0 && ctl->sp_claim) {  // the side key, answered by the quad's first lane
+            if (quiet()) {
+                f = true;
+                v = ctl->sp.val;
+            } else {
+                f = resolve(ctl->sp.val, ctl->sp.st[par], j, &v);
             }
         }
         if (!f) v = 0;
-        const u64 q = q0 + (u64)r * TPB;
+        rv[p] = quad_or(v);
+        fb[p] = __ballot(f);
+    }
+    // back to one Get per lane: lane l keeps pass (l & 3)'s answer of its quad, and Get 16 p + g of
+    // the wave is then in lane 4 g + p; its found bit is any of the quad's four bits of pass p
+    u64 c = rv[0], b = fb[0];
+#pragma unroll
+    for (int p = 1; p < READ_PASSES; p++) {
+        if (sub == (u32)p) c = rv[p];
+        if ((lane >> 4) == (u32)p) b = fb[p];
+    }
+    const u64 v = __shfl(c, (int)(4 * (lane & 15) + (lane >> 4)), 64);
+    const u64 q = wbase + lane;
+    if (q < j.R) {
         st_out(&j.vals[q], v, plain());
-        st_out(&j.found[q], (uint8_t)(f ? 1 : 0), plain());
+        st_out(&j.found[q], (uint8_t)(((b >> (4 * (lane & 15))) & 15) != 0), plain());
     }
 }
 
@@ -690,7 +722,7 @@ template <int N, bool WANT_VAL>
 __device__ __forceinline__ void pa_resolve(Slot* table, u32 shift, u64 tmask, const u64* k, const bool* on,
                                            long long* slot, bool* fresh, u64* val) {
     u64 s[N], kk[N], vv[N];
-    u32 st[N];  // 0 done, 1 key loaded, 2 CAS needed
+    u32 st[N];  // 0 done, 1 key loaded, 2 CAS needed, 3 moved on to the chain's next slot
 #pragma unroll
     for (int r = 0; r < N; r++) {
         st[r] = on[r] ? 1u : 0u;
@@ -721,7 +753,7 @@ __device__ __forceinline__ void pa_resolve(Slot* table, u32 shift, u64 tmask, co
             } else if (kk[r] == EMPTY_KEY) {
                 st[r] = 2;
             } else {
-                s[r] = (s[r] + 1) & tmask;
+                s[r] = probe_next(s[r], pr, tmask);
                 st[r] = 3;
             }
             any = any || st[r] != 0;
@@ -748,7 +780,7 @@ __device__ __forceinline__ void pa_resolve(Slot* table, u32 shift, u64 tmask, co
                 if (WANT_VAL) val[r] = ld_relaxed(&table[s[r]].val);
                 st[r] = 0;
             } else {
-                s[r] = (s[r] + 1) & tmask;
+                s[r] = probe_next(s[r], pr, tmask);
                 st[r] = 3;
             }
         }
@@ -1253,7 +1285,7 @@ __device__ __forceinline__ void small_body(const SmallJob& j, Slot* table, u32 s
             f = sp_has;
             v = f ? sp_val : 0;
         } else {
-            u64 kk = w[q].x, vv = w[q].y, sl = s[q];
+            u64 kk = w[q].x, vv = w[q].y;
             for (u64 pr = 0; pr <= tmask; pr++) {
                 if (kk == k[q]) {
                     f = true;
@@ -1261,7 +1293,7 @@ __device__ __forceinline__ void small_body(const SmallJob& j, Slot* table, u32 s
                     break;
                 }
                 if (kk == EMPTY_KEY) break;
-                sl = (sl + 1) & tmask;
+                const u64 sl = probe_slot(s[q], pr + 1, tmask);
                 const u64x2 x = *(const u64x2*)&table[sl];
                 kk = x.x;
                 vv = x.y;
@@ -1492,7 +1524,9 @@ __global__ __launch_bounds__(TPB) void hm_init_table_kernel(Slot* table, u64 slo
 // either way).
 // The home slot is the TOP bits of mix64(key) (table_home), so growing by 2^d sends old home h to
 // (h << d) | the next d bits: the map is monotone, and a key found at old slot s lands near s << d
-// (it sat s - h >= 0 slots past its old home, h itself near s). So each workgroup takes a
+// (its old home h lies in s's group of four or, for the few keys that met a full group, in a group
+// shortly before it: probe_slot goes round the home group and then forward group by group, so s
+// may sit up to three slots before h but never a group before it). So each workgroup takes a
 // CONTIGUOUS run of RH_RUN old slots (128 KiB), not a grid-stride interleave: its claims, stamps and
 // values fall into one contiguous region of the new table (RH_RUN << d slots), the lines it
 // dirties are dirtied while they sit in its XCD's L2, and the pass streams through both tables
@@ -1554,7 +1588,7 @@ __global__ __launch_bounds__(RH_TPB) void hm_rehash_kernel(const Slot* __restric
                     moved++;
                     on[q] = false;
                 } else {
-                    s[q] = (s[q] + 1) & tmask;
+                    s[q] = probe_next(s[q], pr, tmask);
                     any = true;
                 }
             }
