@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void sy_read_kernel(const nrg_synth_rd* __rest
 
 // ---- bucket replay: no global sort ------------------------------------------------------
 // The default path for the reference's configurations (1 <= cold_writes <= 8, hot_reads <= 16,
-// <= 1024 buckets of 512 cold words, rounds <= 8M ops). Hot and cold words are disjoint, so:
+// cold word 0 plus <= 508 buckets of <= 512 cold words, rounds <= 8M ops). Hot and cold words are disjoint, so:
 //   hot   words: each 2048-op tile folds its hot touches into a summary per hot word
 //               {has SET, tid of the last SET, touches after it}; the summaries compose
 //               associatively in log order (sy_sum_kernel's block 0 folds them).
@@ -238,8 +238,9 @@ constexpr u32 SYA_OPS = SYA_WAVES * SYA_OROUNDS * 64;  // ops per tile (11 bits)
 constexpr u32 SY_MAX_NB = 512, SY_MAX_HOT = 16, SY_MAX_TILES = 4096, SY_MAX_CW = 8;
 // Cold word 0 (bucket 0) is replayed by SY_B0_PARTS workgroups when the chunk holds no WriteOnly:
 // its seen values are then its value plus the touch's rank, so each part takes a contiguous
-// range of the touches. The bucket pass launches SY_MAX_NB workgroups in all (two per CU), so
-// words 1.. go to SY_MAX_NB - SY_B0_PARTS buckets.
+// range of the touches. The bucket pass runs nblk = NB + SY_B0_PARTS - 1 workgroups (at most
+// SY_MAX_NB, two per CU), and the split is over nblk - NB + 1 of them, whatever NB is; words 1..
+// go to at most SY_MAX_NB - SY_B0_PARTS buckets.
 constexpr u32 SY_B0_PARTS = 4;
 // Rankings: the partition and the bucket pass's SET-free passes rank a wave's touches with one
 // returning LDS add per touch on a wave-private count. A returning LDS add hands the lanes of one
