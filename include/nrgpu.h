@@ -2,7 +2,7 @@
  * nrgpu.h — C ABI of the MI355X-native node-replication (NR) log-replay path.
  *
  * One `nrg_ctx` is one NR *replica* living on one GPU: it owns the replicated data
- * structure in HBM (NrHashMap / Stack / AbstractDataStructure / FIFO queue / VSpace), its copy of the shared
+ * structure in HBM (NrHashMap / Stack / AbstractDataStructure / FIFO queue / VSpace / skip list), its copy of the shared
  * operation log (an HBM ring of fixed-width records tagged by logical log index), the
  * per-replica replay epoch (`ltail`), scratch for the replay kernels, and a HIP stream.
  *
@@ -28,6 +28,8 @@
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
  *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
  *   nrg_vspace_*                  VSpace Dispatch (x86-64 page table) benches/vspace.rs:177-381, :436-467, :499-526
+ *   nrg_skiplist_*                SkipListWrapper Dispatch (SkipMap)  benches/lockfree.rs:73-97, :278-317,
+ *                                                                     benches/lockfree_partitioned.rs:86-118
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -78,9 +80,12 @@ extern "C" {
 #define NRG_DS_SYNTHETIC 3u /* AbstractDataStructure(n, 20, 5, 2, 1)                */
 #define NRG_DS_QUEUE 4u     /* FIFO queue of u64: Push/Pop, Len   benches/lockfree.rs:43-52 */
 #define NRG_DS_VSPACE 5u    /* four-level page table: Map/MapDevice, Identify  benches/vspace.rs:483-526 */
+#define NRG_DS_SKIPLIST 6u  /* ordered map u64 -> u64 (SkipMap): Push(k, v) / Get, seek, range
+                               benches/lockfree.rs:73-97, benches/lockfree_partitioned.rs:86-118 */
 
 /* ---- log record layouts (one WriteOperation each) --------------------------------- */
-/* NrHashMap WriteOperation::Put(key, val)               benches/hashmap.rs:52-56       */
+/* NrHashMap WriteOperation::Put(key, val)               benches/hashmap.rs:52-56;
+ * the skip list's OpWr::Push(key, val)                  benches/lockfree.rs:86-97      */
 typedef struct {
     uint64_t key;
     uint64_t val;
@@ -158,12 +163,15 @@ typedef struct {
                                  round stamps} (default 26: 2 GiB of HBM; < 2^30 slots);
                                  vspace (the field is reused): the pool holds 2^log2_slots page
                                  tables of 4 KiB (default 18: 1 GiB; 2 .. 22, else nrg_open
-                                 returns NRG_E_INVAL)                                         */
+                                 returns NRG_E_INVAL); skip list (reused again): the map holds
+                                 up to 2^log2_slots keys at open (default 24: 512 MiB for the two
+                                 buffers of keys and values; 4 .. 28, else NRG_E_INVAL)        */
     uint64_t log_bytes;       /* Log::new(bytes): ring entries = bytes/64 rounded as in the
                                  reference (min 2*GC_FROM_HEAD, power of two). 0 = 32 MiB   */
     uint64_t max_batch;       /* largest number of log records replayed per kernel pass;
                                  larger exec ranges are replayed in order, in chunks
-                                 (< 2^30; stack, queue: <= 2^24; vspace: <= 2^16, its default) */
+                                 (< 2^30; stack, queue, skip list: <= 2^24; vspace: <= 2^16, its
+                                 default) */
     uint64_t max_reads;       /* largest read batch per call                               */
     uint64_t stack_capacity;  /* stack: maximum number of elements (< 2^31) at nrg_open;
                                  nrg_stack_reserve and nrg_set_max_capacity raise it later     */
@@ -178,7 +186,7 @@ typedef struct {
                                  stack: the Pops answered from earlier tiles and the commit;
                                  synthetic: the per-op sums and the hot-word fold; queue: accepted,
                                  but nothing is deferred: a queue's outputs are always complete
-                                 in stream order; vspace: the same. Those outputs
+                                 in stream order; vspace, skip list: the same. Those outputs
                                  (and the buffers they read) are complete only after nrg_join(),
                                  the next round call on this context (an empty one included), or
                                  nrg_sync(); give back-to-back rounds distinct response buffers.
@@ -227,7 +235,7 @@ int nrg_sync(nrg_ctx* ctx);
  * blocking the host; a no-op when nothing is outstanding. */
 int nrg_join(nrg_ctx* ctx);
 
-/* Automatic growth of the stack and the queue, as Vec<u32> grows under push (benches/stack.rs:36-84)
+/* Automatic growth of the stack, the queue and the skip list, as Vec<u32> grows under push (benches/stack.rs:36-84)
  * and SegQueue never refuses one (benches/lockfree_comparisons.rs:75-101). max_items = 0, the state
  * after nrg_open, is a fixed capacity (config.stack_capacity / queue_capacity). With a bound, before
  * a replay chunk of n records could take the length past the capacity the structure is reallocated,
@@ -241,7 +249,10 @@ int nrg_join(nrg_ctx* ctx);
  * grow at the same record, and nothing observable depends on the capacity except where
  * NRG_E_CAPACITY would appear. With a bound, nrg_restore (and nrg_group_resync) accept an image of
  * up to max_items items and grow first. The config is not involved: nrg_config's size and offsets
- * are ABI. NRG_E_INVAL: a hashmap (it has config.hashmap_max_log2_slots), a synthetic or a vspace
+ * are ABI. The skip list (a SkipMap allocates a node per key) takes the bound in keys: the host keeps
+ * len_ub, the exact key count when last read plus every record replayed or prefilled since, and before
+ * a chunk could pass the capacity the exact count is read and the runs are reallocated, clipped to the
+ * bound (<= 2^28). NRG_E_INVAL: a hashmap (it has config.hashmap_max_log2_slots), a synthetic or a vspace
  * context; a nonzero bound below the current capacity or above the kind's nrg_open bound (stack
  * < 2^31, queue <= 2^32). NRG_E_NOMEM from a round call: the larger buffer could not be allocated;
  * nothing of the chunk was launched and the replica is unchanged. Synchronous; like every direct
@@ -258,6 +269,8 @@ int nrg_set_max_capacity(nrg_ctx* ctx, uint64_t max_items);
  *   synthetic  (word index, the word); count = synth_n
  *   vspace     (the leaf's first virtual address as nrg_vspace_dump reports it, the leaf entry),
  *              4 KiB and 2 MiB leaves alike; inner entries contribute nothing
+ *   skip list  (key, value), the hashmap's definition: a skip list and a hashmap that replayed the
+ *              same Puts hold equal triples
  * An empty structure gives {0, 0, 0}; the triple depends on the contents alone, not on the table's
  * size, the ring position or the order in which page tables were allocated. Two replicas that
  * replayed the same log hold equal triples; nrgpu/digest.py computes the triple from a host
@@ -292,6 +305,10 @@ int nrg_digest_async(nrg_ctx* ctx, uint64_t* d_out3);
  *   vspace     items = the tables allocated (nrg_vspace_tables), 4 KiB each: the pool image, inner
  *              entries as stored (table_index * 4096 | flags). The indices point into the image
  *              itself, so it restores into any pool of at least that many tables.
+ *   skip list  items records of nrg_put layout {key, value} in strictly ascending key order;
+ *              nrg_restore checks the order on the device (NRG_E_INVAL) before the digest
+ *              comparison, and accepts items up to the capacity, or up to the growth bound
+ *              (nrg_set_max_capacity), growing first; more is NRG_E_CAPACITY
  * Two replicas with equal state need not produce byte-equal images: the hashmap's record order and
  * the page table's table numbering depend on how the state came about. Their digest words are
  * equal. Like the dumps and every direct call, none of these calls is allowed while a combiner is
@@ -382,6 +399,8 @@ int nrg_log_append_segments_async(nrg_ctx* ctx, const void* d_base, uint32_t nse
  *   queue    : resp[u64] = pushed (Push -> Some(v)) or popped value, some[u8] = 0 for a Pop on
  *              an empty queue (benches/lockfree_comparisons.rs:94-98)
  *   vspace   : resp[nrg_vspace_resp] (16 B), some[u8] = 1 for Ok, 0 for Err (a = at)
+ *   skip list: resp[u64] = the key, some[u8] = 1 (Ok(Some(key)), benches/lockfree_partitioned.rs:108-111);
+ *              it does not depend on the state: SkipMap::insert replaces the value of a present key
  * `resp`/`some` may be NULL (no responses wanted, as benches/hashmap.rs:114-119 returns
  * Ok(None)); the hashmap then skips the previous-value pipeline entirely. */
 int nrg_log_exec(nrg_ctx* ctx, uint64_t resp_lo, uint64_t resp_hi, void* resp, uint8_t* some);
@@ -447,8 +466,8 @@ int nrg_hashmap_digest(nrg_ctx* ctx, uint64_t out[3]);
 /* ---- Flat combining on the host ---------------------------------------------------------- */
 /* Replica's flat combiner for many client threads (nr/src/context.rs:88-194,
  * nr/src/replica.rs:345-356, 404-433, 483-497, 508-595), for the hashmap, the stack, the synthetic
- * structure and the queue (not the page table: nrg_combiner_open on a vspace context returns
- * NRG_E_INVAL):
+ * structure and the queue (not the page table or the skip list: nrg_combiner_open on a vspace or
+ * skip-list context returns NRG_E_INVAL):
  * each registered thread posts up to 32 ops (MAX_PENDING_OPS) per call into the open batch and
  * parks; the combiner's own thread seals the batch into ONE GPU round of `ctx` (its writes
  * appended and replayed in batch order, then its reads answered against the post-round state)
@@ -594,6 +613,75 @@ int nrg_vspace_capacity(nrg_ctx* ctx, uint64_t* n_tables);
  * ascending vaddr, whatever order the tables were allocated in. `*n` receives their number; if it
  * exceeds `cap`, nothing is copied and NRG_E_CAPACITY is returned (as nrg_queue_dump). */
 int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_t* n);
+
+/* ---- Skip list: the replicated ordered map (SkipListWrapper over SkipMap<u64, u64>) -----------
+ * benches/lockfree.rs:278-317 runs it as skiplist-partinput / skiplist-mlnr: writes OpWr::Push(k, v)
+ * (:86-97), reads SkipListConcurrent::Get(k) (:73-84), a default of i -> i for i < INITIAL_CAPACITY
+ * (benches/lockfree_partitioned.rs:88-96). Through Dispatch it is observably the hashmap, but
+ * Replica::verify (nr/src/replica.rs:443-467) hands the caller the SkipMap itself, and what a SkipMap
+ * has and a HashMap has not is order: front, back, lower_bound, upper_bound, range, iteration in key
+ * order. The replica keeps two sorted runs with disjoint key sets; keys span all of u64.
+ * The map holds at most 2^config.log2_slots keys unless nrg_skiplist_reserve or automatic growth
+ * (nrg_set_max_capacity) raised that. Without a growth bound, a replay that would hold more distinct
+ * keys than the capacity latches NRG_E_CAPACITY once (reported by the next nrg_sync / synchronous
+ * call); the contents are unspecified from then on, but nrg_skiplist_len is at most the capacity:
+ * restore or close. Replica groups and the log calls take the kind as they take the others. Out of
+ * scope: there is no combiner (nrg_combiner_open returns NRG_E_INVAL, as for the page table), no
+ * partitioned mode (nrg_group_partitioned_round stays hashmap-only) and no removal of keys (the
+ * reference's wrapper has none). Every call below returns NRG_E_INVAL on a context of another kind. */
+/* Replica::combine for one batch of Push(k, v) records (nr/src/replica.rs:544-595): Log::append of the
+ * n records in d_ops (device) with `origin`, then Log::exec, with the log copy written by the
+ * replay's first pass. Responses (d_resp[i] = the key, d_some[i] = 1; nullable) as nrg_log_exec_async
+ * gives them. Same result as nrg_log_append_async + nrg_log_exec_async. */
+int nrg_skiplist_round_async(nrg_ctx* ctx, const nrg_put* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                             uint8_t* d_some);
+/* Dispatch::dispatch(Get(k)) for a batch (benches/lockfree.rs:73-84), after sync-to-tail
+ * (NRG_E_NOT_SYNCED while ltail < tail; n <= max_reads, else NRG_E_CAPACITY, as nrg_vspace_resolve):
+ * vals[i] = value or 0, found[i] = 1 iff present. */
+int nrg_skiplist_get(nrg_ctx* ctx, const uint64_t* keys, uint64_t n, uint64_t* vals, uint8_t* found);
+int nrg_skiplist_get_async(nrg_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint64_t* d_vals, uint8_t* d_found);
+/* SkipMap::lower_bound / upper_bound for a batch, same rules as the Gets: the entry with the smallest
+ * key >= k (GE: lower_bound(Included)) or > k (GT: lower_bound(Excluded)), or with the largest key
+ * <= k (LE: upper_bound(Included)) or < k (LT: upper_bound(Excluded)). out_keys[i] / out_vals[i] = the
+ * entry, found[i] = 1; none: 0, 0 and found[i] = 0. SkipMap::front is GE(0), back is LE(2^64 - 1);
+ * GT(2^64 - 1) and LT(0) find nothing, as does every seek on an empty map. Another mode: NRG_E_INVAL. */
+#define NRG_SEEK_GE 0u
+#define NRG_SEEK_GT 1u
+#define NRG_SEEK_LE 2u
+#define NRG_SEEK_LT 3u
+int nrg_skiplist_seek(nrg_ctx* ctx, const uint64_t* keys, uint64_t n, uint32_t mode, uint64_t* out_keys,
+                      uint64_t* out_vals, uint8_t* found);
+int nrg_skiplist_seek_async(nrg_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t mode, uint64_t* d_out_keys,
+                            uint64_t* d_out_vals, uint8_t* d_found);
+/* SkipMap::range(lo..=hi) into host buffers, ascending, both bounds inclusive (so the key 2^64 - 1 is
+ * reachable), after sync-to-tail. `*n` receives the count; if it exceeds `cap`, nothing is copied and
+ * NRG_E_CAPACITY is returned, as the dumps do. lo > hi gives *n = 0. */
+int nrg_skiplist_range(nrg_ctx* ctx, uint64_t lo, uint64_t hi, uint64_t* keys, uint64_t* vals, uint64_t cap,
+                       uint64_t* n);
+/* counts[i] = the number of keys in [los[i], his[i]] (0 where lo > hi); the Gets' rules. */
+int nrg_skiplist_range_count(nrg_ctx* ctx, const uint64_t* los, const uint64_t* his, uint64_t n, uint64_t* counts);
+int nrg_skiplist_range_count_async(nrg_ctx* ctx, const uint64_t* d_los, const uint64_t* d_his, uint64_t n,
+                                   uint64_t* d_counts);
+/* Replica::verify's view (nr/src/replica.rs:443-467): the whole map in ascending key order. `*n`
+ * receives the number of pairs; if it exceeds `cap`, nothing is copied and NRG_E_CAPACITY is returned. */
+int nrg_skiplist_dump(nrg_ctx* ctx, uint64_t* keys, uint64_t* vals, uint64_t cap, uint64_t* n);
+/* SkipMap::len: the number of keys. */
+int nrg_skiplist_len(nrg_ctx* ctx, uint64_t* n);
+/* SkipListWrapper::default with caller pairs: insert (keys[i], vals[i]) directly (host arrays, any
+ * order, no log traffic); of several records with one key the last wins. */
+int nrg_skiplist_prefill(nrg_ctx* ctx, const uint64_t* keys, const uint64_t* vals, uint64_t n);
+/* Generated on the device: keys k = 0..n-1 -> k + val_offset. SkipListWrapper::default
+ * (benches/lockfree_partitioned.rs:88-96) is n = INITIAL_CAPACITY, val_offset = 0. */
+int nrg_skiplist_prefill_range(nrg_ctx* ctx, uint64_t n, uint64_t val_offset);
+/* A SkipMap allocates a node per key; here, as Vec::reserve / Vec::capacity for the stack
+ * (nrg_stack_reserve): make room for `n_keys` keys in all, with automatic growth
+ * (nrg_set_max_capacity) on or off. It never shrinks: a request the map already satisfies returns
+ * NRG_OK and does nothing; a map reserved beyond its growth bound is a fixed one. NRG_E_INVAL: not a
+ * skip list, or n_keys > 2^28 (nrg_open's bound). NRG_E_NOMEM: the new buffers could not be
+ * allocated; the old ones are intact and the replica usable. Synchronous (one copy of the base run). */
+int nrg_skiplist_reserve(nrg_ctx* ctx, uint64_t n_keys);
+/* The current capacity in keys: 2^config.log2_slots, or what growth made of it. */
+int nrg_skiplist_capacity(nrg_ctx* ctx, uint64_t* n_keys);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's
@@ -775,7 +863,9 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
  * from its own dispatch (hipExtLaunchKernelGGL); multi-kernel pipelines ("hm_prev",
  * "st_replay", "sy_replay") with event records around them; a table growth's two passes are
  * "hm_grow_init" and "hm_rehash", a snapshot's table scan "hm_snapshot", a restore's two passes
- * "hm_restore_init" and "hm_restore". nrg_kernel_time reads (timed
+ * "hm_restore_init" and "hm_restore"; the skip list's chunk sort is "sl_sort" (event records around its
+ * launches), its chunk merge "sl_merge" and a compaction of the delta run into the base run
+ * "sl_compact" (one launch each: the launches counted are the compactions). nrg_kernel_time reads (timed
  * launches, their total milliseconds) after synchronising. */
 int nrg_kernel_timing(nrg_ctx* ctx, int enable);
 /* Restrict timing to one kernel name (NULL or "" = all). */

@@ -83,6 +83,10 @@ int nrg_test_vspace_table(nrg_ctx* ctx, uint64_t table, uint64_t out[512]);
                                    partition-round apply chunks, stack queries/table);
                                    2 (+1) = synthetic only, also drop the barrier that guards the
                                    bucket pass's tile map (diagnostic: results WRONG)            */
+#define NRG_KNOB_SL_DELTA_MAX 20 /* skip list: the delta run is merged into the base run when it holds
+                                   more keys than this after a chunk (1 .. capacity, else
+                                   NRG_E_INVAL; default min(capacity, 2^22)); only on an open, empty
+                                   context (NRG_E_INVAL otherwise, and on every other kind)      */
 int nrg_test_set_knob(nrg_ctx* ctx, int knob, uint64_t value);
 /* The combiner's round-server words and round counters: out = {posted, served, exited,
  * session, server running, rounds completed, rounds launched, open round}. */

@@ -27,6 +27,7 @@ struct SortScratch {
     u64 ctl_words = 0;
 };
 
+constexpr u32 SORT_TILE = 2048;  // keys per tile of a radix pass (radix_sort.hip)
 int sort_alloc(SortScratch& s, u64 cap);
 void sort_free(SortScratch& s);
 // Sort n pairs by the low `key_bits` bits of key (stable). vals_in == nullptr means
@@ -101,6 +102,13 @@ struct QuState {
 // The page table's device state (vspace.hip): tables allocated from the pool, the PML4 included.
 struct VsState {
     u64 ntables;
+};
+
+// The skip list's device state (skiplist.hip): keys in the base and in the delta run, and the delta
+// count before the chunk being replayed with that chunk's new keys (what its merge reads).
+struct SlState {
+    u64 nb, nd;
+    u64 nd_in, nnew;
 };
 
 struct HostRun {  // origin tags of appended log ranges (the Entry::replica field)
@@ -199,6 +207,27 @@ struct VsHost {  // page table (vspace.hip)
     uint64_t* d_tag = nullptr;  // the digest's tag per pool table, allocated by the first digest
 };
 
+struct SlHost {  // skip list / ordered map (skiplist.hip): two sorted runs with disjoint key sets
+    uint64_t* d_bk[2] = {nullptr, nullptr};  // base keys, two buffers (a compaction writes the other one)
+    uint64_t* d_bv[2] = {nullptr, nullptr};  // base values
+    uint64_t* d_dk[2] = {nullptr, nullptr};  // delta keys (a chunk's merge writes the other one)
+    uint64_t* d_dv[2] = {nullptr, nullptr};
+    uint32_t bcur = 0, dcur = 0;             // the current buffer of each run
+    uint64_t cap = 0;                        // keys the map holds (a base buffer's size)
+    uint64_t delta_max = 0;                  // compact when the delta run holds more (NRG_KNOB_SL_DELTA_MAX)
+    uint64_t dcap = 0;                       // a delta buffer's size: delta_max + max_batch
+    SlState* d_state = nullptr;
+    // scratch of one chunk
+    uint64_t *d_sk = nullptr, *d_nk = nullptr, *d_nv = nullptr;
+    uint32_t *d_sp = nullptr, *d_k32 = nullptr, *d_pv = nullptr, *d_tcnt = nullptr;
+    uint8_t* d_miss = nullptr;
+    // Growth (sl_room / sl_grow), as the stack's: the bound on the capacity (0: fixed) and the upper
+    // bound of the key count. nd_ub bounds the delta count the same way (the compaction policy).
+    uint64_t max_items = 0;
+    uint64_t len_ub = 0;
+    uint64_t nd_ub = 0;
+};
+
 struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*
     int32_t spin = -1;    // -1 = default
     uint32_t depth = 0;   // 0 = default
@@ -218,7 +247,7 @@ struct GenHost {  // workload generators (workload.hip): zeta(zipf_n, zipf_theta
 
 // What the runtime knows about a data structure: one table per kind, defined beside the
 // structure's launchers and entry points (hashmap.hip, stack.hip, synthetic.hip, queue.hip,
-// vspace.hip).
+// vspace.hip, skiplist.hip).
 struct DsOps {
     uint32_t rec_bytes;   // one log record
     uint32_t resp_bytes;  // one write response
@@ -263,7 +292,7 @@ struct DsOps {
     // The stream has been drained. nullptr: the kind has no such bound.
     int (*set_max)(nrg_ctx* c, u64 max_items);
 };
-const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops();
+const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops(), *sl_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
 
 }  // namespace nrg
@@ -297,6 +326,7 @@ struct nrg_ctx {
     nrg::SyHost sy;
     nrg::QuHost qu;
     nrg::VsHost vs;
+    nrg::SlHost sl;
     nrg::CombKnobs comb;
     nrg::PtHost pt;
     nrg::GenHost gen;

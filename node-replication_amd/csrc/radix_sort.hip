@@ -27,6 +27,7 @@ static inline int rs_items_for(u64 n) {
     (void)n;
     return 8;
 }
+static_assert(RS_TPB * 8 == SORT_TILE, "the tile size other files read (internal.hpp)");
 constexpr u32 ST_AGG = 1u << 30;
 constexpr u32 ST_INC = 2u << 30;
 constexpr u32 ST_MASK = 3u << 30;

@@ -1,0 +1,977 @@
+// skiplist.hip — replicated ordered map (SkipMap<u64, u64>) replay on gfx950
+// (benches/lockfree.rs:73-97 SkipListConcurrent::Get / OpWr::Push, :278-317 main;
+// benches/lockfree_partitioned.rs:86-118 SkipListWrapper, its default :88-96).
+//
+// What the reference's skip list has and a hash map has not is order: front, back, lower_bound,
+// upper_bound, range, iteration in key order (Replica::verify hands the caller the SkipMap itself,
+// nr/src/replica.rs:443-467). A pointer-chasing list would serialise a replay; here the map is two
+// sorted runs with DISJOINT key sets, each a pair of arrays (keys, values):
+//   base   up to `capacity` keys
+//   delta  up to delta_max + max_batch keys
+// Disjointness keeps everything else simple: len = nb + nd, a range count is two rank differences
+// per run, a seek is the better of two candidates, and the dump, the snapshot and the digest never
+// de-duplicate. Both runs are double-buffered: a merge reads one buffer and writes the other.
+//
+// Replay of a chunk of n records (Push(k, v) = SkipMap::insert, which replaces the value of a
+// present key; the response Ok(Some(k)) does not depend on the state), in stream order, no
+// workgroup waiting on another except inside the radix sort's look-back:
+//   sl_stream    the log copy of a fused round, the responses (key, 1), the keys' low words
+//   sort         stable sort of (key, position) by the full 64-bit key: n <= SL_SORT_WG in the LDS of
+//                one workgroup (bitonic on the pair, which is unique, so the order is the stable
+//                one); else two runs of the 32-bit pair sort (radix_sort.hip, tiles of
+//                SL_SORT_TILE), low word then high word. Timed as "sl_sort".
+//   sl_resolve   last-writer election (the last record of every run of equal keys survives) and a
+//                binary search of each survivor in base and in delta: a hit stores the value in
+//                place (survivors are distinct: no two lanes write one element), a miss is flagged
+//                and counted per tile of SL_RES_TILE
+//   sl_scan      one workgroup: the tiles' offsets, the number of new keys, the capacity check
+//   sl_scatter   the misses, still sorted, into the chunk's list of new keys
+//   sl_merge     merge path of delta and the new keys into the other delta buffer, partitions of
+//                SL_MERGE_PART outputs per workgroup, staged in LDS, and SL_MERGE_ITEMS per lane;
+//                diagonals are found by a binary search over index bounds (no padding key:
+//                2^64 - 1 is an ordinary key)
+//   sl_compact   only when nd > delta_max after the merge: the same merge of base and delta into
+//                the other base buffer; delta becomes empty
+// The host does not know nd exactly: it keeps an upper bound (nd when last read plus every record
+// replayed since) and reads the counts, one synchronise, only when the bound passes delta_max.
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "internal.hpp"
+#include "../../include/nrgpu_testing.h"
+
+namespace nrg {
+
+constexpr int SL_TPB = 256;
+constexpr u32 SL_SORT_WG = 1024;     // chunks up to here sort in one workgroup's LDS
+constexpr u32 SL_SORT_TILE = 2048;   // keys per tile of the radix sort's passes (radix_sort.hip)
+constexpr u32 SL_RES_TILE = 256;     // records per resolve / scatter workgroup
+constexpr u32 SL_MERGE_ITEMS = 8;    // outputs per lane of a merge
+constexpr u32 SL_MERGE_PART = 2048;  // outputs per merge workgroup: SL_TPB * SL_MERGE_ITEMS
+constexpr int SL_SCAN_TPB = 1024;
+constexpr u32 SL_MAX_GRID = 4096;    // merge workgroups launched at most; the rest by stride
+constexpr u32 SL_LOG2_MIN = 4, SL_LOG2_MAX = 28, SL_LOG2_DEFAULT = 24;
+// delta_max unless NRG_KNOB_SL_DELTA_MAX sets it (microbench/skiplist_round.py, DESIGN.md "Skip list replay")
+constexpr u64 SL_DELTA_DEFAULT = 1ull << 22;
+static_assert(SL_MERGE_PART == SL_TPB * SL_MERGE_ITEMS, "a merge workgroup's lanes cover its partition");
+static_assert(SL_SORT_TILE == SORT_TILE, "the radix sort's tile, mirrored for the tests' chunk sizes");
+static_assert(SL_RES_TILE == SL_TPB, "resolve and scatter take one record per lane");
+
+struct SlJob {
+    const nrg_put* src;  // the batch of a fused round or a prefill, or nullptr: read from the ring
+    nrg_put* ring;       // the log ring; written when src is a fused round's batch (wring)
+    u64 ring_mask;
+    u32 wring;
+    u64 lo, n;           // the chunk: log indices [lo, lo + n)
+    u64 rlo, rhi;        // response window
+    u64* resp;
+    uint8_t* some;
+    SlState* st;
+    DevCtl* ctl;
+    u64 *bk, *bv, *dk, *dv;  // the current base and delta buffers
+    u64 cap, dcap;           // keys the base and the delta buffers hold
+    u64* sk;                 // [n] sorted keys
+    u32* sp;                 // [n] their chunk positions
+    u32* k32;                // [n] low / high words (radix sort input)
+    u32* pv;                 // [n] permutation after the low-word sort
+    uint8_t* miss;           // [n] survivor found in neither run
+    u32* tcnt;               // [tiles] misses per tile, then their exclusive offsets
+    u64 *nk, *nv;            // the chunk's new keys, sorted
+};
+
+__device__ __forceinline__ nrg_put sl_load(const SlJob& j, u64 i) {
+    return j.src ? j.src[i] : j.ring[(j.lo + i) & j.ring_mask];
+}
+
+// first index with a[idx] >= k (lower) or > k (upper), in [0, n]
+__device__ __forceinline__ u64 sl_lower(const u64* __restrict__ a, u64 n, u64 k) {
+    u64 lo = 0, hi = n;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ u64 sl_upper(const u64* __restrict__ a, u64 n, u64 k) {
+    u64 lo = 0, hi = n;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (a[mid] <= k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(SL_TPB) void sl_stream_kernel(SlJob j) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= j.n) return;
+    const nrg_put r = sl_load(j, i);
+    if (j.wring) j.ring[(j.lo + i) & j.ring_mask] = r;  // Log::append of a fused round
+    const u64 g = j.lo + i;
+    if (j.resp && g >= j.rlo && g < j.rhi) {  // Ok(Some(key)) (benches/lockfree_partitioned.rs:108-111)
+        j.resp[g - j.rlo] = r.key;
+        j.some[g - j.rlo] = 1;
+    }
+    j.k32[i] = (u32)r.key;
+}
+
+// (key, position) pairs of a chunk of n <= SL_SORT_WG records, sorted in LDS: a bitonic network over
+// P = the power of two at or above n; the slots past n hold (2^64 - 1, 2^32 - 1), which no record
+// equals (positions are < n), so they sort last without any key being reserved.
+__global__ __launch_bounds__(SL_TPB) void sl_sort_wg_kernel(SlJob j, u32 P) {
+    __shared__ u64 s_k[SL_SORT_WG];
+    __shared__ u32 s_p[SL_SORT_WG];
+    const u32 t = threadIdx.x, n = (u32)j.n;
+    for (u32 i = t; i < P; i += SL_TPB) {
+        s_k[i] = i < n ? sl_load(j, i).key : ~0ull;
+        s_p[i] = i < n ? i : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    for (u32 k = 2; k <= P; k <<= 1)
+        for (u32 s = k >> 1; s > 0; s >>= 1) {
+            for (u32 q = t; q < P / 2; q += SL_TPB) {
+                const u32 a = ((q & ~(s - 1)) << 1) | (q & (s - 1)), b = a | s;
+                const bool up = (a & k) == 0;
+                const u64 ka = s_k[a], kb = s_k[b];
+                const u32 pa = s_p[a], pb = s_p[b];
+                const bool gt = ka > kb || (ka == kb && pa > pb);
+                if (gt == up) {
+                    s_k[a] = kb, s_k[b] = ka;
+                    s_p[a] = pb, s_p[b] = pa;
+                }
+            }
+            __syncthreads();
+        }
+    for (u32 i = t; i < n; i += SL_TPB) {
+        j.sk[i] = s_k[i];
+        j.sp[i] = s_p[i];
+    }
+}
+
+// after the low-word sort: the permutation, and the high word of each record in that order
+__global__ __launch_bounds__(SL_TPB) void sl_gather_hi_kernel(SlJob j, const u32* __restrict__ perm) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= j.n) return;
+    const u32 p = perm[i];
+    j.pv[i] = p;
+    j.k32[i] = (u32)(sl_load(j, p).key >> 32);
+}
+
+// after the high-word sort: the sorted keys and their positions
+__global__ __launch_bounds__(SL_TPB) void sl_gather_kernel(SlJob j, const u32* __restrict__ perm) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= j.n) return;
+    const u32 p = perm[i];
+    j.sp[i] = p;
+    j.sk[i] = sl_load(j, p).key;
+}
+
+__global__ __launch_bounds__(SL_TPB) void sl_resolve_kernel(SlJob j) {
+    __shared__ u32 s_cnt[SL_TPB / 64];
+    const u64 i = (u64)blockIdx.x * SL_RES_TILE + threadIdx.x;
+    bool miss = false;
+    if (i < j.n) {
+        const u64 k = j.sk[i];
+        // equal keys lie in ascending log position: the last one is the chunk's last writer
+        if (i + 1 == j.n || j.sk[i + 1] != k) {
+            const u64 v = sl_load(j, j.sp[i]).val;
+            const u64 nb = j.st->nb, nd = j.st->nd;
+            const u64 ib = sl_lower(j.bk, nb, k);
+            if (ib < nb && j.bk[ib] == k) {
+                j.bv[ib] = v;
+            } else {
+                const u64 id = sl_lower(j.dk, nd, k);
+                if (id < nd && j.dk[id] == k) j.dv[id] = v; else miss = true;
+            }
+        }
+        j.miss[i] = miss ? 1 : 0;
+    }
+    const u64 b = __ballot(miss);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (u32)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 c = 0;
+        for (int w = 0; w < SL_TPB / 64; w++) c += s_cnt[w];
+        j.tcnt[blockIdx.x] = c;
+    }
+}
+
+// One workgroup: tcnt becomes the tiles' exclusive offsets; the number of new keys is clipped to the
+// room left (nb + nd + nnew <= cap, and the delta buffer), ERR_CAPACITY latched when anything was
+// clipped: the chunk's largest new keys are then left out and len stays within the capacity.
+__global__ __launch_bounds__(SL_SCAN_TPB) void sl_scan_kernel(SlJob j, u32 tiles) {
+    __shared__ u32 s_scan[SL_SCAN_TPB];
+    const u32 t = threadIdx.x;
+    const u32 per = (tiles + SL_SCAN_TPB - 1) / SL_SCAN_TPB;
+    const u32 i0 = t * per < tiles ? t * per : tiles, i1 = i0 + per < tiles ? i0 + per : tiles;
+    u32 mine = 0;
+    for (u32 i = i0; i < i1; i++) mine += j.tcnt[i];
+    s_scan[t] = mine;
+    __syncthreads();
+    for (u32 s = 1; s < SL_SCAN_TPB; s <<= 1) {
+        const u32 o = t >= s ? s_scan[t - s] : 0;
+        __syncthreads();
+        s_scan[t] += o;
+        __syncthreads();
+    }
+    u32 run = s_scan[t] - mine;
+    for (u32 i = i0; i < i1; i++) {
+        const u32 c = j.tcnt[i];
+        j.tcnt[i] = run;
+        run += c;
+    }
+    if (t == 0) {
+        const u64 nb = j.st->nb, nd = j.st->nd;
+        u64 nnew = s_scan[SL_SCAN_TPB - 1];
+        u64 room = nb + nd < j.cap ? j.cap - (nb + nd) : 0;
+        const u64 droom = nd < j.dcap ? j.dcap - nd : 0;  // (never the smaller one under the host's policy)
+        if (droom < room) room = droom;
+        if (nnew > room) {
+            nnew = room;
+            atomicOr(&j.ctl->err, ERR_CAPACITY);
+        }
+        j.st->nd_in = nd;
+        j.st->nnew = nnew;
+        j.st->nd = nd + nnew;
+    }
+}
+
+__global__ __launch_bounds__(SL_TPB) void sl_scatter_kernel(SlJob j) {
+    __shared__ u32 s_cnt[SL_TPB / 64];
+    const u64 i = (u64)blockIdx.x * SL_RES_TILE + threadIdx.x;
+    const bool miss = i < j.n && j.miss[i];
+    const u64 b = __ballot(miss);
+    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) s_cnt[w] = (u32)__popcll(b);
+    __syncthreads();
+    if (!miss) return;
+    u32 pos = j.tcnt[blockIdx.x] + (u32)__popcll(b & ((1ull << lane) - 1));
+    for (u32 q = 0; q < w; q++) pos += s_cnt[q];
+    if (pos < j.st->nnew) {
+        j.nk[pos] = j.sk[i];
+        j.nv[pos] = sl_load(j, j.sp[i]).val;
+    }
+}
+
+// ---- merge path ----------------------------------------------------------------------------------
+struct SlMerge {
+    const u64 *ak, *av, *bk, *bv;  // two sorted runs
+    u64 na, nb;                    // their lengths, unless from_state
+    const SlState* st;             // from_state 1: na = st->nd_in, nb = st->nnew (a chunk's merge)
+    u32 from_state;
+    u64 *ok, *ov;                  // output arrays, or
+    nrg_put* orec;                 // output records
+};
+
+// The split of diagonal d of the merge of a[0, na) and b[0, nb): how many of the first d outputs come
+// from a, a first where keys are equal (they never are: the runs merged here hold disjoint key sets).
+// The search runs over the index range max(0, d - nb) <= i <= min(d, na): every element it reads exists.
+__device__ __forceinline__ u64 sl_split(const u64* a, u64 na, const u64* b, u64 nb, u64 d) {
+    u64 lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (a[mid] <= b[d - 1 - mid]) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The merge, a partition of SL_MERGE_PART outputs per workgroup and turn. The partition's two diagonals
+// are searched in global memory (every lane the same search: the loads broadcast); its stretch of a
+// and of b goes into LDS with coalesced loads; every lane finds the diagonal of its SL_MERGE_ITEMS
+// outputs in LDS and merges them into registers; the outputs go back through LDS so that the stores
+// are coalesced too. Workgroups of SL_TPB lanes.
+template <bool AOS>
+__device__ __forceinline__ void sl_merge_all(const SlMerge& m, u64 na, u64 nb) {
+    __shared__ u64 s_k[SL_MERGE_PART], s_v[SL_MERGE_PART];
+    const u32 t = threadIdx.x;
+    const u64 total = na + nb;
+    for (u64 part = blockIdx.x; part * SL_MERGE_PART < total; part += gridDim.x) {
+        const u64 D0 = part * SL_MERGE_PART, D1 = D0 + SL_MERGE_PART < total ? D0 + SL_MERGE_PART : total;
+        const u64 a0 = sl_split(m.ak, na, m.bk, nb, D0), a1 = sl_split(m.ak, na, m.bk, nb, D1);
+        const u64 b0 = D0 - a0;
+        const u32 cnt = (u32)(D1 - D0), la = (u32)(a1 - a0), lb = cnt - la;
+        __syncthreads();  // the previous partition's stores are done with the tile
+        for (u32 i = t; i < cnt; i += SL_TPB) {
+            s_k[i] = i < la ? m.ak[a0 + i] : m.bk[b0 + (i - la)];
+            s_v[i] = i < la ? m.av[a0 + i] : m.bv[b0 + (i - la)];
+        }
+        __syncthreads();
+        u64 k[SL_MERGE_ITEMS], v[SL_MERGE_ITEMS];
+        const u32 d0 = t * SL_MERGE_ITEMS;
+        const u32 c = d0 >= cnt ? 0 : (cnt - d0 < SL_MERGE_ITEMS ? cnt - d0 : SL_MERGE_ITEMS);
+        if (c) {
+            u32 i = (u32)sl_split(s_k, la, s_k + la, lb, d0), jx = d0 - i;
+#pragma unroll
+            for (u32 q = 0; q < SL_MERGE_ITEMS; q++)
+                if (q < c) {
+                    const u64 ka = i < la ? s_k[i] : 0, kb = jx < lb ? s_k[la + jx] : 0;
+                    const bool ta = jx >= lb || (i < la && ka <= kb);
+                    k[q] = ta ? ka : kb;
+                    v[q] = ta ? s_v[i] : s_v[la + jx];
+                    if (ta) i++; else jx++;
+                }
+        }
+        __syncthreads();  // every lane has read its inputs from the tile
+#pragma unroll
+        for (u32 q = 0; q < SL_MERGE_ITEMS; q++)
+            if (q < c) {
+                s_k[d0 + q] = k[q];
+                s_v[d0 + q] = v[q];
+            }
+        __syncthreads();
+        for (u32 i = t; i < cnt; i += SL_TPB) {
+            if (AOS) {
+                m.orec[D0 + i] = nrg_put{s_k[i], s_v[i]};
+            } else {
+                m.ok[D0 + i] = s_k[i];
+                m.ov[D0 + i] = s_v[i];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(SL_TPB) void sl_merge_kernel(SlMerge m) {
+    const u64 na = m.from_state ? m.st->nd_in : m.na, nb = m.from_state ? m.st->nnew : m.nb;
+    sl_merge_all<false>(m, na, nb);
+}
+
+__global__ void sl_set_state_kernel(SlState* st, u64 nb, u64 nd) { *st = SlState{nb, nd, nd, 0}; }
+
+// ---- reads: one lane per query, a binary search per run --------------------------------------------
+__global__ __launch_bounds__(SL_TPB) void sl_get_kernel(const u64* bk, const u64* bv, const u64* dk, const u64* dv,
+                                                        const SlState* st, const u64* keys, u64 n, u64* vals,
+                                                        uint8_t* found) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = keys[i], nb = st->nb, nd = st->nd;
+    u64 v = 0;
+    uint8_t f = 0;
+    const u64 ib = sl_lower(bk, nb, k);
+    if (ib < nb && bk[ib] == k) {
+        v = bv[ib], f = 1;
+    } else {
+        const u64 id = sl_lower(dk, nd, k);
+        if (id < nd && dk[id] == k) v = dv[id], f = 1;
+    }
+    vals[i] = v;
+    found[i] = f;
+}
+
+// the run's candidate for a seek: its index, or n where the run has none
+__device__ __forceinline__ u64 sl_seek_idx(const u64* a, u64 n, u64 k, u32 mode) {
+    if (mode == NRG_SEEK_GE) return sl_lower(a, n, k);
+    if (mode == NRG_SEEK_GT) return sl_upper(a, n, k);
+    const u64 i = mode == NRG_SEEK_LE ? sl_upper(a, n, k) : sl_lower(a, n, k);
+    return i ? i - 1 : n;
+}
+
+__global__ __launch_bounds__(SL_TPB) void sl_seek_kernel(const u64* bk, const u64* bv, const u64* dk, const u64* dv,
+                                                         const SlState* st, const u64* keys, u64 n, u32 mode,
+                                                         u64* okeys, u64* ovals, uint8_t* found) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = keys[i], nb = st->nb, nd = st->nd;
+    const u64 ib = sl_seek_idx(bk, nb, k, mode), id = sl_seek_idx(dk, nd, k, mode);
+    const bool hb = ib < nb, hd = id < nd;
+    u64 ok = 0, ov = 0;
+    if (hb || hd) {
+        const u64 kb = hb ? bk[ib] : 0, kd = hd ? dk[id] : 0;
+        const bool up = mode == NRG_SEEK_GE || mode == NRG_SEEK_GT;  // the smaller candidate, else the larger
+        const bool take_b = hb && (!hd || (up ? kb < kd : kb > kd));
+        ok = take_b ? kb : kd;
+        ov = take_b ? bv[ib] : dv[id];
+    }
+    okeys[i] = ok;
+    ovals[i] = ov;
+    found[i] = (hb || hd) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(SL_TPB) void sl_range_count_kernel(const u64* bk, const u64* dk, const SlState* st,
+                                                                const u64* los, const u64* his, u64 n, u64* counts) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= n) return;
+    const u64 lo = los[i], hi = his[i], nb = st->nb, nd = st->nd;
+    u64 c = 0;
+    if (lo <= hi) c = (sl_upper(bk, nb, hi) - sl_lower(bk, nb, lo)) + (sl_upper(dk, nd, hi) - sl_lower(dk, nd, lo));
+    counts[i] = c;
+}
+
+// the ranks of [lo, hi] in both runs: out = {b0, b1, d0, d1} (an empty window where lo > hi)
+__global__ void sl_rank_kernel(const u64* bk, const u64* dk, const SlState* st, u64 lo, u64 hi, u64* out) {
+    const u64 nb = st->nb, nd = st->nd;
+    const bool any = lo <= hi;
+    out[0] = any ? sl_lower(bk, nb, lo) : 0;
+    out[1] = any ? sl_upper(bk, nb, hi) : 0;
+    out[2] = any ? sl_lower(dk, nd, lo) : 0;
+    out[3] = any ? sl_upper(dk, nd, hi) : 0;
+}
+
+// SkipListWrapper::default's records (keys k0 .. k0 + n - 1 -> k + off) for the replay pipeline
+__global__ __launch_bounds__(SL_TPB) void sl_gen_kernel(nrg_put* out, u64 k0, u64 n, u64 off) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i < n) out[i] = nrg_put{k0 + i, k0 + i + off};
+}
+
+// ---- host side -------------------------------------------------------------------------------------
+static hipError_t sl_read_state(nrg_ctx* c, SlState* s) {
+    hipError_t e = hipMemcpyAsync(s, c->sl.d_state, sizeof(*s), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && s->nb + s->nd > c->sl.cap) e = hipErrorUnknown;  // (the scan never lets it)
+    return e;
+}
+
+static unsigned sl_merge_grid(u64 total) {
+    const u64 g = (total + SL_MERGE_PART - 1) / SL_MERGE_PART;
+    return g < 1 ? 1u : (g > SL_MAX_GRID ? SL_MAX_GRID : (unsigned)g);
+}
+
+static void sl_free_pair(u64* p[2]) {
+    for (int i = 0; i < 2; i++) {
+        if (p[i]) (void)hipFree(p[i]);
+        p[i] = nullptr;
+    }
+}
+
+// two buffers of `n` keys and two of `n` values; all or nothing
+static hipError_t sl_alloc_runs(u64* k[2], u64* v[2], u64 n) {
+    k[0] = k[1] = v[0] = v[1] = nullptr;
+    for (int i = 0; i < 2; i++)
+        if (hipMalloc(&k[i], n * 8) != hipSuccess || hipMalloc(&v[i], n * 8) != hipSuccess) {
+            (void)hipGetLastError();  // (the failure is reported by the return value alone)
+            sl_free_pair(k);
+            sl_free_pair(v);
+            return hipErrorOutOfMemory;
+        }
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(DG_TPB) void sl_grow_kernel(const u64* fk, const u64* fv, u64* tk, u64* tv,
+                                                         const SlState* st, u64 from_cap) {
+    const u64 n = st->nb < from_cap ? st->nb : from_cap;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        tk[i] = fk[i];
+        tv[i] = fv[i];
+    }
+}
+
+// Growth of the base run, as st_grow: the copy, then the stream is synchronised, the old buffers are
+// freed and the new ones installed. If the allocation fails nothing has been launched.
+static hipError_t sl_grow(nrg_ctx* c, u64 new_cap) {
+    SlHost& s = c->sl;
+    if (new_cap <= s.cap || new_cap > (1ull << SL_LOG2_MAX)) return hipErrorInvalidValue;
+    u64 *nk[2], *nv[2];
+    hipError_t e = sl_alloc_runs(nk, nv, new_cap);
+    if (e != hipSuccess) return e;
+    NRG_LAUNCH(c, "sl_grow", sl_grow_kernel, copy_grid(s.cap), DG_TPB, 0, c->stream, (const u64*)s.d_bk[s.bcur],
+               (const u64*)s.d_bv[s.bcur], nk[s.bcur], nv[s.bcur], (const SlState*)s.d_state, s.cap);
+    e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        sl_free_pair(nk);
+        sl_free_pair(nv);
+        return e;
+    }
+    sl_free_pair(s.d_bk);
+    sl_free_pair(s.d_bv);
+    for (int i = 0; i < 2; i++) s.d_bk[i] = nk[i], s.d_bv[i] = nv[i];
+    s.cap = new_cap;
+    return hipSuccess;
+}
+
+// the capacity automatic growth goes to for `need` keys: at least double, clipped to the bound
+static u64 sl_grown(const nrg_ctx* c, u64 need) {
+    u64 want = 2 * c->sl.cap;
+    if (want < need) want = need;
+    return want > c->sl.max_items ? c->sl.max_items : want;
+}
+
+// The growth policy, as st_room's: n records about to be replayed (or prefilled) are added to len_ub;
+// only when the bound passes the capacity is the exact count read, and only if exact + n still
+// passes it do the runs grow. A stream of updates re-reads its count now and then and never
+// reallocates.
+static hipError_t sl_room(nrg_ctx* c, u64 n) {
+    SlHost& s = c->sl;
+    if (!s.max_items || s.cap >= s.max_items) return hipSuccess;
+    if (s.len_ub + n <= s.cap) {
+        s.len_ub += n;
+        return hipSuccess;
+    }
+    SlState st{};
+    hipError_t e = sl_read_state(c, &st);
+    if (e != hipSuccess) return e;
+    const u64 exact = st.nb + st.nd;
+    if (exact + n > s.cap && (e = sl_grow(c, sl_grown(c, exact + n))) != hipSuccess) return e;
+    s.len_ub = exact + n;
+    return hipSuccess;
+}
+
+static hipError_t sl_compact(nrg_ctx* c, u64 nb, u64 nd) {
+    SlHost& s = c->sl;
+    SlMerge m{};
+    m.ak = s.d_bk[s.bcur], m.av = s.d_bv[s.bcur], m.na = nb;
+    m.bk = s.d_dk[s.dcur], m.bv = s.d_dv[s.dcur], m.nb = nd;
+    m.ok = s.d_bk[s.bcur ^ 1], m.ov = s.d_bv[s.bcur ^ 1];
+    NRG_LAUNCH(c, "sl_compact", sl_merge_kernel, sl_merge_grid(nb + nd), SL_TPB, 0, c->stream, m);
+    sl_set_state_kernel<<<1, 1, 0, c->stream>>>(s.d_state, nb + nd, 0);
+    s.bcur ^= 1;
+    s.nd_ub = 0;
+    return hipGetLastError();
+}
+
+// One chunk of n <= max_batch records through the pipeline. `wring`: src is a fused round's batch and
+// the log copy is written; a prefill passes its records as src with no log position behind them.
+static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u64 n, u64 resp_lo, u64 resp_hi,
+                           void* d_resp, uint8_t* d_some) {
+    if (n == 0) return hipSuccess;
+    SlHost& s = c->sl;
+    hipError_t e = sl_room(c, n);  // the runs grow first if they have to
+    if (e != hipSuccess) return e;
+    SlJob j{};
+    j.src = src;
+    j.ring = (nrg_put*)c->d_ring;
+    j.ring_mask = c->log_size - 1;
+    j.wring = wring ? 1 : 0;
+    j.lo = lo;
+    j.n = n;
+    const bool want = d_resp != nullptr && d_some != nullptr && resp_lo < resp_hi && resp_lo < lo + n && resp_hi > lo;
+    j.rlo = want ? resp_lo : 0;
+    j.rhi = want ? resp_hi : 0;
+    j.resp = want ? (u64*)d_resp : nullptr;
+    j.some = want ? d_some : nullptr;
+    j.st = s.d_state;
+    j.ctl = c->d_ctl;
+    j.bk = s.d_bk[s.bcur], j.bv = s.d_bv[s.bcur];
+    j.dk = s.d_dk[s.dcur], j.dv = s.d_dv[s.dcur];
+    j.cap = s.cap;
+    j.dcap = s.dcap;
+    j.sk = s.d_sk, j.sp = s.d_sp, j.k32 = s.d_k32, j.pv = s.d_pv, j.miss = s.d_miss, j.tcnt = s.d_tcnt;
+    j.nk = s.d_nk, j.nv = s.d_nv;
+    const unsigned g256 = (unsigned)((n + SL_TPB - 1) / SL_TPB);
+    NRG_LAUNCH(c, "sl_stream", sl_stream_kernel, g256, SL_TPB, 0, c->stream, j);
+    timer_begin(c, "sl_sort");
+    if (n <= SL_SORT_WG) {
+        u32 P = 2;
+        while (P < n) P <<= 1;
+        sl_sort_wg_kernel<<<1, SL_TPB, 0, c->stream>>>(j, P);
+    } else {
+        u32 *ok = nullptr, *ov = nullptr;
+        if ((e = sort_pairs(c->sort, j.k32, nullptr, n, 32, c->stream, &ok, &ov)) != hipSuccess) return e;
+        sl_gather_hi_kernel<<<g256, SL_TPB, 0, c->stream>>>(j, ov);
+        if ((e = sort_pairs(c->sort, j.k32, j.pv, n, 32, c->stream, &ok, &ov)) != hipSuccess) return e;
+        sl_gather_kernel<<<g256, SL_TPB, 0, c->stream>>>(j, ov);
+    }
+    timer_end(c, "sl_sort");
+    const u32 tiles = (u32)((n + SL_RES_TILE - 1) / SL_RES_TILE);
+    NRG_LAUNCH(c, "sl_resolve", sl_resolve_kernel, tiles, SL_TPB, 0, c->stream, j);
+    NRG_LAUNCH(c, "sl_scan", sl_scan_kernel, 1, SL_SCAN_TPB, 0, c->stream, j, tiles);
+    NRG_LAUNCH(c, "sl_scatter", sl_scatter_kernel, tiles, SL_TPB, 0, c->stream, j);
+    SlMerge m{};
+    m.ak = j.dk, m.av = j.dv, m.bk = j.nk, m.bv = j.nv;
+    m.st = s.d_state;
+    m.from_state = 1;
+    m.ok = s.d_dk[s.dcur ^ 1], m.ov = s.d_dv[s.dcur ^ 1];
+    NRG_LAUNCH(c, "sl_merge", sl_merge_kernel, sl_merge_grid(s.nd_ub + n), SL_TPB, 0, c->stream, m);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    s.dcur ^= 1;
+    s.nd_ub += n;
+    // compaction policy: compact when nd > delta_max after a chunk's merge
+    if (s.nd_ub > s.delta_max) {
+        SlState st{};
+        if ((e = sl_read_state(c, &st)) != hipSuccess) return e;
+        s.nd_ub = st.nd;
+        if (s.max_items) s.len_ub = st.nb + st.nd;
+        if (st.nd > s.delta_max) return sl_compact(c, st.nb, st.nd);
+    }
+    return hipSuccess;
+}
+
+static hipError_t sl_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                                  uint8_t* d_some) {
+    return sl_chunk(c, (const nrg_put*)src, src != nullptr, lo, n, resp_lo, resp_hi, d_resp, d_some);
+}
+
+static void sl_free_delta(SlHost& s) {
+    sl_free_pair(s.d_dk);
+    sl_free_pair(s.d_dv);
+}
+
+static int sl_open(nrg_ctx* c) {
+    const nrg_config& cf = c->cfg;
+    SlHost& s = c->sl;
+    const u64 mb = cf.max_batch;
+    // log2_slots: the map holds up to 2^log2_slots keys; max_batch <= 2^24: one workgroup scans a
+    // chunk's tile counts
+    if (cf.log2_slots < SL_LOG2_MIN || cf.log2_slots > SL_LOG2_MAX || mb > (1ull << 24)) return NRG_E_INVAL;
+    s.cap = 1ull << cf.log2_slots;
+    s.delta_max = std::min<u64>(s.cap, SL_DELTA_DEFAULT);
+    s.dcap = s.delta_max + mb;
+    HIPCHK(sl_alloc_runs(s.d_bk, s.d_bv, s.cap));
+    HIPCHK(sl_alloc_runs(s.d_dk, s.d_dv, s.dcap));
+    HIPCHK(hipMalloc(&s.d_state, sizeof(SlState)));
+    HIPCHK(hipMemsetAsync(s.d_state, 0, sizeof(SlState), c->stream));
+    HIPCHK(hipMalloc(&s.d_sk, mb * 8));
+    HIPCHK(hipMalloc(&s.d_nk, mb * 8));
+    HIPCHK(hipMalloc(&s.d_nv, mb * 8));
+    HIPCHK(hipMalloc(&s.d_sp, mb * 4));
+    HIPCHK(hipMalloc(&s.d_k32, mb * 4));
+    HIPCHK(hipMalloc(&s.d_pv, mb * 4));
+    HIPCHK(hipMalloc(&s.d_miss, mb));
+    HIPCHK(hipMalloc(&s.d_tcnt, ((mb + SL_RES_TILE - 1) / SL_RES_TILE) * 4));
+    if (mb > SL_SORT_WG && sort_alloc(c->sort, mb) != NRG_OK) return NRG_E_NOMEM;
+    c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
+    return NRG_OK;
+}
+
+static void sl_close(nrg_ctx* c) {
+    SlHost& s = c->sl;
+    sl_free_pair(s.d_bk);
+    sl_free_pair(s.d_bv);
+    sl_free_delta(s);
+    void* ptrs[] = {s.d_state, s.d_sk, s.d_nk, s.d_nv, s.d_sp, s.d_k32, s.d_pv, s.d_miss, s.d_tcnt};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+}
+
+static hipError_t sl_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
+
+// NRG_KNOB_SL_DELTA_MAX on an empty context: the delta buffers are sized by it
+static int sl_set_knob(nrg_ctx* c, int knob, uint64_t v) {
+    SlHost& s = c->sl;
+    if (knob != NRG_KNOB_SL_DELTA_MAX || v < 1 || v > s.cap) return NRG_E_INVAL;
+    SlState st{};
+    HIPCHK(sl_read_state(c, &st));
+    if (st.nb + st.nd) return NRG_E_INVAL;
+    u64 *nk[2], *nv[2];
+    HIPCHK(sl_alloc_runs(nk, nv, v + c->cfg.max_batch));
+    sl_free_delta(s);
+    for (int i = 0; i < 2; i++) s.d_dk[i] = nk[i], s.d_dv[i] = nv[i];
+    s.delta_max = v;
+    s.dcap = v + c->cfg.max_batch;
+    s.nd_ub = 0;
+    return NRG_OK;
+}
+
+static void sl_defaults(nrg_config* cfg) { cfg->log2_slots = SL_LOG2_DEFAULT; }
+
+// nrg_digest: items are (key, value), the hashmap's definition; a grid-stride over both runs
+__global__ __launch_bounds__(DG_TPB) void sl_digest_kernel(const u64* bk, const u64* bv, const u64* dk, const u64* dv,
+                                                           const SlState* st, u64* out3) {
+    const u64 nb = st->nb, n = nb + st->nd;
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 h = i < nb ? dg_item(bk[i], bv[i]) : dg_item(dk[i - nb], dv[i - nb]);
+        c++;
+        sm += h;
+        x ^= h;
+    }
+    dg_commit(c, sm, x, out3);
+}
+
+static hipError_t sl_digest(nrg_ctx* c, u64* d_out3) {
+    SlHost& s = c->sl;
+    hipError_t e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream);
+    if (e != hipSuccess) return e;
+    NRG_LAUNCH(c, "sl_digest", sl_digest_kernel, dg_grid(s.cap), DG_TPB, 0, c->stream, (const u64*)s.d_bk[s.bcur],
+               (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur], (const u64*)s.d_dv[s.dcur],
+               (const SlState*)s.d_state, d_out3);
+    return hipGetLastError();
+}
+
+static int sl_items(nrg_ctx* c, u64* n) {
+    SlState st{};
+    HIPCHK(sl_read_state(c, &st));
+    *n = st.nb + st.nd;
+    return NRG_OK;
+}
+
+// The snapshot payload: the merge of the two runs as nrg_put records in ascending key order. The
+// image must fit whole or nothing of the payload is stored.
+__global__ __launch_bounds__(SL_TPB) void sl_snapshot_kernel(SlMerge m, u64* buf, u64 cap, u64 log_idx, DevCtl* ctl) {
+    const u64 na = m.st->nb, nb = m.st->nd;
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_SKIPLIST, na + nb, (na + nb) * 16, log_idx, ctl);
+    if (snap_bytes((na + nb) * 16) > cap) return;
+    m.orec = (nrg_put*)(buf + SNAP_HDR / 8);
+    sl_merge_all<true>(m, na, nb);
+}
+
+static hipError_t sl_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    SlHost& s = c->sl;
+    SlMerge m{};
+    m.ak = s.d_bk[s.bcur], m.av = s.d_bv[s.bcur], m.bk = s.d_dk[s.dcur], m.bv = s.d_dv[s.dcur];
+    m.st = s.d_state;
+    NRG_LAUNCH(c, "sl_snapshot", sl_snapshot_kernel, sl_merge_grid(s.cap), SL_TPB, 0, c->stream, m, (u64*)d_buf, cap,
+               log_idx, c->d_ctl);
+    return hipGetLastError();
+}
+
+// The payload into base, delta empty; records out of strictly ascending key order latch ERR_INVAL
+// (the digest does not see the order).
+__global__ __launch_bounds__(DG_TPB) void sl_restore_kernel(u64* bk, u64* bv, const nrg_put* __restrict__ rec, u64 n,
+                                                            SlState* st, DevCtl* ctl) {
+    bool bad = false;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const nrg_put r = rec[i];
+        if (i + 1 < n && rec[i + 1].key <= r.key) bad = true;
+        bk[i] = r.key;
+        bv[i] = r.val;
+    }
+    if (bad) atomicOr(&ctl->err, ERR_INVAL);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *st = SlState{n, 0, 0, 0};
+}
+
+static int sl_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    SlHost& s = c->sl;
+    // with a growth bound the image may be as large as the bound: the runs grow first
+    if (check_only) return items <= std::max<u64>(s.cap, s.max_items) ? NRG_OK : NRG_E_CAPACITY;
+    if (!d_payload) items = 0;
+    if (items > s.cap) HIPCHK(sl_grow(c, sl_grown(c, items)));
+    NRG_LAUNCH(c, "sl_restore", sl_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, s.d_bk[s.bcur], s.d_bv[s.bcur],
+               (const nrg_put*)d_payload, items, s.d_state, c->d_ctl);
+    s.len_ub = items;
+    s.nd_ub = 0;
+    return hip_fail(hipGetLastError());
+}
+
+// nrg_set_max_capacity: the bound, and the count bound restarts from the exact count
+static int sl_set_max(nrg_ctx* c, u64 max_items) {
+    SlHost& s = c->sl;
+    if (max_items && (max_items < s.cap || max_items > (1ull << SL_LOG2_MAX))) return NRG_E_INVAL;
+    SlState st{};
+    HIPCHK(sl_read_state(c, &st));
+    s.max_items = max_items;
+    s.len_ub = st.nb + st.nd;
+    return NRG_OK;
+}
+
+const DsOps* sl_ops() {
+    static const DsOps ops = {sizeof(nrg_put), sizeof(uint64_t), sl_open, sl_close, sl_flush, sl_replay_chunk,
+                              floor_ltail, sl_set_knob, nullptr, sl_defaults, sl_digest,
+                              sl_items, sl_snapshot, sl_restore, sl_set_max};
+    return &ops;
+}
+
+// The keys of [lo, hi] in ascending order into host arrays: the ranks of the window in both runs (one
+// launch and a 32-byte copy), then the merge of the two sub-runs into staging.
+static int sl_extract(nrg_ctx* c, u64 lo, u64 hi, uint64_t* keys, uint64_t* vals, uint64_t cap, uint64_t* n) {
+    SlHost& s = c->sl;
+    Staging* g = c->stg;
+    int r;
+    if ((r = staging(g[3], 64))) return r;
+    u64 rk[4] = {0, 0, 0, 0};
+    sl_rank_kernel<<<1, 1, 0, c->stream>>>(s.d_bk[s.bcur], s.d_dk[s.dcur], s.d_state, lo, hi, (u64*)g[3].p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rk, g[3].p, sizeof rk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    const u64 na = rk[1] - rk[0], nb = rk[3] - rk[2];
+    *n = na + nb;
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (*n == 0) return NRG_OK;
+    if (!keys || !vals) return NRG_E_INVAL;
+    if ((r = staging(g[0], *n * 8)) || (r = staging(g[1], *n * 8))) return r;
+    SlMerge m{};
+    m.ak = s.d_bk[s.bcur] + rk[0], m.av = s.d_bv[s.bcur] + rk[0], m.na = na;
+    m.bk = s.d_dk[s.dcur] + rk[2], m.bv = s.d_dv[s.dcur] + rk[2], m.nb = nb;
+    m.ok = (u64*)g[0].p, m.ov = (u64*)g[1].p;
+    NRG_LAUNCH(c, "sl_range", sl_merge_kernel, sl_merge_grid(*n), SL_TPB, 0, c->stream, m);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(keys, g[0].p, *n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(vals, g[1].p, *n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+}  // namespace nrg
+
+// ---- the skip list's entry points (include/nrgpu.h) ------------------------------------------------
+using namespace nrg;
+
+extern "C" {
+
+int nrg_skiplist_round_async(nrg_ctx* c, const nrg_put* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                             uint8_t* d_some) {
+    return round_common(c, NRG_DS_SKIPLIST, d_ops, n, origin, d_resp, d_some);
+}
+
+// the checks every read shares (nrg_vspace_resolve's)
+static int sl_read_check(nrg_ctx* c, uint64_t n) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n > c->cfg.max_reads) return NRG_E_CAPACITY;
+    return NRG_OK;
+}
+
+int nrg_skiplist_get_async(nrg_ctx* c, const uint64_t* d_keys, uint64_t n, uint64_t* d_vals, uint8_t* d_found) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (n == 0) return NRG_OK;
+    if (!d_keys || !d_vals || !d_found) return NRG_E_INVAL;
+    SlHost& s = c->sl;
+    NRG_LAUNCH(c, "sl_get", sl_get_kernel, (unsigned)((n + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur],
+               (const u64*)s.d_dv[s.dcur], (const SlState*)s.d_state, d_keys, n, d_vals, d_found);
+    return hip_fail(hipGetLastError());
+}
+
+int nrg_skiplist_get(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint64_t* vals, uint8_t* found) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (n == 0) return NRG_OK;
+    if (!keys || !vals || !found) return NRG_E_INVAL;
+    Staging* g = c->stg;
+    if ((r = staging(g[0], n * 8)) || (r = staging(g[1], n * 8)) || (r = staging(g[2], n))) return r;
+    HIPCHK(hipMemcpyAsync(g[0].p, keys, n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((r = nrg_skiplist_get_async(c, (u64*)g[0].p, n, (u64*)g[1].p, (uint8_t*)g[2].p))) return r;
+    HIPCHK(hipMemcpyAsync(vals, g[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(found, g[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_skiplist_seek_async(nrg_ctx* c, const uint64_t* d_keys, uint64_t n, uint32_t mode, uint64_t* d_out_keys,
+                            uint64_t* d_out_vals, uint8_t* d_found) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (mode > NRG_SEEK_LT) return NRG_E_INVAL;
+    if (n == 0) return NRG_OK;
+    if (!d_keys || !d_out_keys || !d_out_vals || !d_found) return NRG_E_INVAL;
+    SlHost& s = c->sl;
+    NRG_LAUNCH(c, "sl_seek", sl_seek_kernel, (unsigned)((n + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur],
+               (const u64*)s.d_dv[s.dcur], (const SlState*)s.d_state, d_keys, n, mode, d_out_keys, d_out_vals,
+               d_found);
+    return hip_fail(hipGetLastError());
+}
+
+int nrg_skiplist_seek(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint32_t mode, uint64_t* out_keys,
+                      uint64_t* out_vals, uint8_t* found) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (mode > NRG_SEEK_LT) return NRG_E_INVAL;
+    if (n == 0) return NRG_OK;
+    if (!keys || !out_keys || !out_vals || !found) return NRG_E_INVAL;
+    Staging* g = c->stg;
+    // keys, then out_keys behind them in one slot; values; found
+    if ((r = staging(g[0], 2 * n * 8)) || (r = staging(g[1], n * 8)) || (r = staging(g[2], n))) return r;
+    u64* dk = (u64*)g[0].p;
+    HIPCHK(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((r = nrg_skiplist_seek_async(c, dk, n, mode, dk + n, (u64*)g[1].p, (uint8_t*)g[2].p))) return r;
+    HIPCHK(hipMemcpyAsync(out_keys, dk + n, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_vals, g[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(found, g[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_skiplist_range_count_async(nrg_ctx* c, const uint64_t* d_los, const uint64_t* d_his, uint64_t n,
+                                   uint64_t* d_counts) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (n == 0) return NRG_OK;
+    if (!d_los || !d_his || !d_counts) return NRG_E_INVAL;
+    SlHost& s = c->sl;
+    NRG_LAUNCH(c, "sl_range_count", sl_range_count_kernel, (unsigned)((n + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_dk[s.dcur], (const SlState*)s.d_state, d_los, d_his, n,
+               d_counts);
+    return hip_fail(hipGetLastError());
+}
+
+int nrg_skiplist_range_count(nrg_ctx* c, const uint64_t* los, const uint64_t* his, uint64_t n, uint64_t* counts) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (n == 0) return NRG_OK;
+    if (!los || !his || !counts) return NRG_E_INVAL;
+    Staging* g = c->stg;
+    if ((r = staging(g[0], n * 8)) || (r = staging(g[1], n * 8)) || (r = staging(g[2], n * 8))) return r;
+    HIPCHK(hipMemcpyAsync(g[0].p, los, n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g[1].p, his, n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((r = nrg_skiplist_range_count_async(c, (u64*)g[0].p, (u64*)g[1].p, n, (u64*)g[2].p))) return r;
+    HIPCHK(hipMemcpyAsync(counts, g[2].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_skiplist_range(nrg_ctx* c, uint64_t lo, uint64_t hi, uint64_t* keys, uint64_t* vals, uint64_t cap,
+                       uint64_t* n) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    return sl_extract(c, lo, hi, keys, vals, cap, n);
+}
+
+int nrg_skiplist_dump(nrg_ctx* c, uint64_t* keys, uint64_t* vals, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    return sl_extract(c, 0, ~0ull, keys, vals, cap, n);
+}
+
+int nrg_skiplist_len(nrg_ctx* c, uint64_t* n) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    SlState st{};
+    HIPCHK(sl_read_state(c, &st));
+    *n = st.nb + st.nd;
+    return check_err(c);
+}
+
+int nrg_skiplist_prefill(nrg_ctx* c, const uint64_t* keys, const uint64_t* vals, uint64_t n) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (n && (!keys || !vals)) return NRG_E_INVAL;
+    const uint64_t mb = c->cfg.max_batch;
+    std::vector<nrg_put> recs;
+    try {
+        recs.resize(n < mb ? n : mb);
+    } catch (const std::bad_alloc&) {
+        return NRG_E_NOMEM;
+    }
+    // the replay pipeline without a log position: later records win, as in a replay
+    for (uint64_t at = 0; at < n; at += mb) {
+        const uint64_t m = n - at < mb ? n - at : mb;
+        for (uint64_t i = 0; i < m; i++) recs[i] = nrg_put{keys[at + i], vals[at + i]};
+        if ((r = staging(c->stg[0], m * sizeof(nrg_put)))) return r;
+        HIPCHK(hipMemcpyAsync(c->stg[0].p, recs.data(), m * sizeof(nrg_put), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));  // (recs is filled again)
+        HIPCHK(sl_chunk(c, (const nrg_put*)c->stg[0].p, false, 0, m, 0, 0, nullptr, nullptr));
+    }
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_skiplist_prefill_range(nrg_ctx* c, uint64_t n, uint64_t val_offset) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    const uint64_t mb = c->cfg.max_batch;
+    for (uint64_t at = 0; at < n; at += mb) {
+        const uint64_t m = n - at < mb ? n - at : mb;
+        if ((r = staging(c->stg[0], m * sizeof(nrg_put)))) return r;
+        sl_gen_kernel<<<(unsigned)((m + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream>>>((nrg_put*)c->stg[0].p, at, m,
+                                                                                      val_offset);
+        HIPCHK(hipGetLastError());
+        HIPCHK(sl_chunk(c, (const nrg_put*)c->stg[0].p, false, 0, m, 0, 0, nullptr, nullptr));
+    }
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_skiplist_reserve(nrg_ctx* c, uint64_t n_keys) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (n_keys > (1ull << SL_LOG2_MAX)) return NRG_E_INVAL;  // nrg_open's bound
+    if (n_keys <= c->sl.cap) return NRG_OK;
+    HIPCHK(sl_grow(c, n_keys));
+    return NRG_OK;
+}
+
+int nrg_skiplist_capacity(nrg_ctx* c, uint64_t* n) {
+    if (!c || !n || c->cfg.ds_kind != NRG_DS_SKIPLIST) return NRG_E_INVAL;
+    *n = c->sl.cap;
+    return NRG_OK;
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@ uint64_t item_bytes(uint32_t kind) {
         case NRG_DS_SYNTHETIC: return sizeof(uint64_t);
         case NRG_DS_QUEUE: return sizeof(uint64_t);
         case NRG_DS_VSPACE: return 4096;
+        case NRG_DS_SKIPLIST: return sizeof(nrg_put);
         default: return 0;
     }
 }

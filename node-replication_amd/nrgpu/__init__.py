@@ -33,6 +33,9 @@ from .replica import (
     ReadWrite,
     Replica,
     ReplicaToken,
+    Seek,
+    SkipList,
+    SlPush,
     Stack,
     VSpace,
     WriteOnly,
@@ -43,6 +46,7 @@ __all__ = [
     "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
+    "Seek", "SkipList", "SlPush",
 ]
 
 

@@ -41,6 +41,7 @@ NRG_DS_STACK = 2
 NRG_DS_SYNTHETIC = 3
 NRG_DS_QUEUE = 4
 NRG_DS_VSPACE = 5
+NRG_DS_SKIPLIST = 6
 
 NRG_STACK_POP = 0
 NRG_STACK_PUSH = 1
@@ -50,6 +51,11 @@ NRG_SYNTH_WRITE_ONLY = 0
 NRG_SYNTH_READ_WRITE = 1
 NRG_VSPACE_MAP = 0
 NRG_VSPACE_MAP_DEVICE = 1
+# nrg_skiplist_seek modes: SkipMap::lower_bound (GE, GT) / upper_bound (LE, LT)
+NRG_SEEK_GE = 0
+NRG_SEEK_GT = 1
+NRG_SEEK_LE = 2
+NRG_SEEK_LT = 3
 
 # nrg_vspace_op (32 B), nrg_vspace_resp (16 B) and nrg_vspace_leaf (16 B)
 VSPACE_OP_DTYPE = np.dtype([("vbase", "<u8"), ("pbase", "<u8"), ("len", "<u8"), ("op", "<u4"), ("rights", "<u4")])
@@ -193,6 +199,20 @@ SIGNATURES = {
     "nrg_vspace_dump": (C.c_int, [vp, vp, u64, u64p]),
     "nrg_vspace_reserve": (C.c_int, [vp, u64]),
     "nrg_vspace_capacity": (C.c_int, [vp, u64p]),
+    "nrg_skiplist_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
+    "nrg_skiplist_get": (C.c_int, [vp, vp, u64, vp, vp]),
+    "nrg_skiplist_get_async": (C.c_int, [vp, vp, u64, vp, vp]),
+    "nrg_skiplist_seek": (C.c_int, [vp, vp, u64, u32, vp, vp, vp]),
+    "nrg_skiplist_seek_async": (C.c_int, [vp, vp, u64, u32, vp, vp, vp]),
+    "nrg_skiplist_range": (C.c_int, [vp, u64, u64, vp, vp, u64, u64p]),
+    "nrg_skiplist_range_count": (C.c_int, [vp, vp, vp, u64, vp]),
+    "nrg_skiplist_range_count_async": (C.c_int, [vp, vp, vp, u64, vp]),
+    "nrg_skiplist_dump": (C.c_int, [vp, vp, vp, u64, u64p]),
+    "nrg_skiplist_len": (C.c_int, [vp, u64p]),
+    "nrg_skiplist_prefill": (C.c_int, [vp, vp, vp, u64]),
+    "nrg_skiplist_prefill_range": (C.c_int, [vp, u64, u64]),
+    "nrg_skiplist_reserve": (C.c_int, [vp, u64]),
+    "nrg_skiplist_capacity": (C.c_int, [vp, u64p]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),
@@ -254,7 +274,8 @@ TEST_SIGNATURES = {
 # nrg_test_set_knob knobs (include/nrgpu_testing.h): tuning and diagnostics of an open context
 KNOBS = {"STAMP_MAX": 1, "SKEW_EVERY": 2, "EPOCH_LIMIT": 3, "K1": 4, "EXP": 6, "SY_SORT": 7,
          "PIPELINE": 8, "COMB_SPIN": 10, "COMB_DEPTH": 11,
-         "SMALL_MAX": 12, "PART": 13, "STALL": 14, "COMB_GATHER": 15, "PA_TPB": 16, "COMB_SERVE": 17, "SY_FUSED": 18}
+         "SMALL_MAX": 12, "PART": 13, "STALL": 14, "COMB_GATHER": 15, "PA_TPB": 16, "COMB_SERVE": 17, "SY_FUSED": 18,
+         "SL_DELTA_MAX": 20}
 
 _lib = None
 

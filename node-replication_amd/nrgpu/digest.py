@@ -8,6 +8,7 @@ h = mix64(k ^ mix64(v)), the sum wrapping in u64. What (k, v) is depends on the 
   queue      (index from the front, element)
   synthetic  (word index, word)
   vspace     (the leaf's first virtual address, the leaf entry)
+  skip list  (key, value), the hashmap's definition
 
 With these a caller that holds a host snapshot or a CPU model of the structure computes the triple
 the device must report, without the device's state ever leaving the GPU.
@@ -66,6 +67,11 @@ def vspace(vaddrs, entries):
     """A page table's leaves: each leaf's first virtual address (raw, bits 48..63 clear) and its
     entry, in any order."""
     return pairs(vaddrs, entries)
+
+
+def skiplist(keys, vals):
+    """An ordered map's (key, value) pairs, in any order: the hashmap's triple for the same pairs."""
+    return pairs(keys, vals)
 
 
 def combine(triples):

@@ -7,9 +7,10 @@
                                    sync / verify, with flat combining of the registered
                                    threads' pending ops into one log append + one replay
   ReplicaToken    nr::ReplicaToken
-  NrHashMap, Stack, AbstractDataStructure, Queue, VSpace — the Dispatch plug-ins of the reference
-                                   (benches/hashmap.rs, benches/stack.rs, benches/synthetic.rs,
-                                   benches/lockfree_comparisons.rs, benches/vspace.rs)
+  NrHashMap, Stack, AbstractDataStructure, Queue, VSpace, SkipList — the Dispatch plug-ins of the
+                                   reference (benches/hashmap.rs, benches/stack.rs,
+                                   benches/synthetic.rs, benches/lockfree_comparisons.rs,
+                                   benches/vspace.rs, benches/lockfree_partitioned.rs)
 """
 from __future__ import annotations
 
@@ -259,6 +260,15 @@ class DeviceReplica:
         L.check(self._lib.nrg_vspace_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
                 "vspace_round")
 
+    @_stream_ordered
+    def sl_round_device(self, d_ops, n: int, origin: int, d_resp=None, d_some=None):
+        """Replica::combine for one skip-list batch of Push(k, v) records on device buffers: append +
+        exec, the log copy written by the replay (nrg_skiplist_round_async); responses (the key,
+        some = 1) for these ops into d_resp / d_some.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_skiplist_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
+                "skiplist_round")
+
     def log_reset(self):
         L.check(self._lib.nrg_log_reset(self._h))
 
@@ -492,7 +502,7 @@ class DeviceReplica:
         return n.value
 
     def set_max_capacity(self, max_items: int):
-        """Automatic growth of a stack or queue replica up to `max_items` elements; 0 (the state after
+        """Automatic growth of a stack, queue or skip-list replica up to `max_items` elements; 0 (the state after
         open) is a fixed capacity (nrg_set_max_capacity). Synchronous."""
         max_items = int(max_items)
         if max_items < 0 or max_items >= 2**64:
@@ -578,6 +588,91 @@ class DeviceReplica:
         m = C.c_uint64()
         L.check(self._lib.nrg_vspace_dump(self._h, _ptr(out), n.value, C.byref(m)), "vspace_dump")
         return out[: m.value]
+
+    # -- skip list -----------------------------------------------------------------
+    def sl_get(self, keys):
+        """Get for a batch of keys: (vals, found); 0 where the key is absent."""
+        keys = np.ascontiguousarray(np.asarray(keys, np.uint64))
+        n = len(keys)
+        vals = np.zeros(max(n, 1), np.uint64)
+        found = np.zeros(max(n, 1), np.uint8)
+        L.check(self._lib.nrg_skiplist_get(self._h, _ptr(keys), n, _ptr(vals), _ptr(found)), "skiplist_get")
+        return vals[:n], found[:n]
+
+    @_stream_ordered
+    def sl_get_device(self, d_keys, n: int, d_vals, d_found):
+        """Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_skiplist_get_async(self._h, _dptr(d_keys), n, _dptr(d_vals), _dptr(d_found)),
+                "skiplist_get")
+
+    def sl_seek(self, keys, mode: int):
+        """SkipMap::lower_bound / upper_bound for a batch (mode: L.NRG_SEEK_GE / GT / LE / LT):
+        (out_keys, out_vals, found)."""
+        keys = np.ascontiguousarray(np.asarray(keys, np.uint64))
+        n = len(keys)
+        ok = np.zeros(max(n, 1), np.uint64)
+        ov = np.zeros(max(n, 1), np.uint64)
+        found = np.zeros(max(n, 1), np.uint8)
+        L.check(self._lib.nrg_skiplist_seek(self._h, _ptr(keys), n, mode, _ptr(ok), _ptr(ov), _ptr(found)),
+                "skiplist_seek")
+        return ok[:n], ov[:n], found[:n]
+
+    def sl_range_count(self, los, his) -> np.ndarray:
+        """The number of keys in each [lo, hi], both bounds inclusive."""
+        los = np.ascontiguousarray(np.asarray(los, np.uint64))
+        his = np.ascontiguousarray(np.asarray(his, np.uint64))
+        if los.shape != his.shape:
+            raise ValueError("los and his differ in length")
+        n = len(los)
+        out = np.zeros(max(n, 1), np.uint64)
+        L.check(self._lib.nrg_skiplist_range_count(self._h, _ptr(los), _ptr(his), n, _ptr(out)), "skiplist_range_count")
+        return out[:n]
+
+    def _sl_pairs(self, call, what: str):
+        n = C.c_uint64()
+        rc = call(None, None, 0, C.byref(n))  # the count: nothing fits in 0
+        if rc != L.NRG_E_CAPACITY:
+            L.check(rc, what)
+        k = np.zeros(max(n.value, 1), np.uint64)
+        v = np.zeros(max(n.value, 1), np.uint64)
+        m = C.c_uint64()
+        L.check(call(_ptr(k), _ptr(v), n.value, C.byref(m)), what)
+        return k[: m.value], v[: m.value]
+
+    def sl_range(self, lo: int, hi: int):
+        """SkipMap::range(lo..=hi): (keys, vals) in ascending key order."""
+        return self._sl_pairs(lambda k, v, cap, n: self._lib.nrg_skiplist_range(self._h, lo, hi, k, v, cap, n),
+                              "skiplist_range")
+
+    def sl_dump(self):
+        """The whole map, (keys, vals) in ascending key order: Replica::verify's view."""
+        return self._sl_pairs(lambda k, v, cap, n: self._lib.nrg_skiplist_dump(self._h, k, v, cap, n),
+                              "skiplist_dump")
+
+    def sl_len(self) -> int:
+        n = C.c_uint64()
+        L.check(self._lib.nrg_skiplist_len(self._h, C.byref(n)), "skiplist_len")
+        return n.value
+
+    def sl_prefill(self, keys, vals):
+        """Insert the pairs directly (any order, no log traffic); of equal keys the last wins."""
+        keys = np.ascontiguousarray(np.asarray(keys, np.uint64))
+        vals = np.ascontiguousarray(np.asarray(vals, np.uint64))
+        if keys.shape != vals.shape:
+            raise ValueError("keys and vals differ in length")
+        L.check(self._lib.nrg_skiplist_prefill(self._h, _ptr(keys), _ptr(vals), len(keys)), "skiplist_prefill")
+
+    def sl_prefill_range(self, n: int, off: int = 0):
+        """SkipListWrapper::default: keys 0..n-1 -> k + off."""
+        L.check(self._lib.nrg_skiplist_prefill_range(self._h, n, off), "skiplist_prefill_range")
+
+    def sl_reserve(self, n_keys: int):
+        """Room for `n_keys` keys in all; never shrinks (nrg_skiplist_reserve)."""
+        self._reserve(self._lib.nrg_skiplist_reserve, L.NRG_DS_SKIPLIST, "sl_reserve", n_keys)
+
+    def sl_capacity(self) -> int:
+        """The keys the map has room for (nrg_skiplist_capacity)."""
+        return self._capacity(self._lib.nrg_skiplist_capacity, L.NRG_DS_SKIPLIST, "sl_capacity")
 
     # -- synthetic -----------------------------------------------------------------
     def sy_read(self, ops: np.ndarray) -> np.ndarray:
@@ -683,6 +778,18 @@ class MapDevice:  # benches/vspace.rs:486 OpcodeWr::MapDevice(vbase, pbase, len)
 @dataclass(frozen=True)
 class Identify:  # benches/vspace.rs:491 OpcodeRd::Identify(vaddr)
     vaddr: int
+
+
+@dataclass(frozen=True)
+class SlPush:  # benches/lockfree.rs:86-97 OpWr::Push(key, val) on the skip list
+    key: int
+    val: int
+
+
+@dataclass(frozen=True)
+class Seek:  # SkipMap::lower_bound / upper_bound; mode: L.NRG_SEEK_GE / GT / LE / LT
+    key: int
+    mode: int
 
 
 @dataclass(frozen=True)
@@ -820,6 +927,45 @@ class VSpace:
     def snapshot(dev: DeviceReplica):
         d = dev.vs_dump()
         return list(zip(d["vaddr"].tolist(), d["entry"].tolist()))
+
+
+class SkipList:
+    """SkipListWrapper (benches/lockfree_partitioned.rs:86-118): an ordered map u64 -> u64. SlPush ->
+    the key (Ok(Some(key))); Get -> the value or None; Seek -> (key, value) or None."""
+
+    kind = L.NRG_DS_SKIPLIST
+    rec_dtype = PUT_DTYPE
+
+    @staticmethod
+    def encode(ops) -> np.ndarray:
+        r = np.zeros(len(ops), PUT_DTYPE)
+        r["key"] = [o.key for o in ops]
+        r["val"] = [o.val for o in ops]
+        return r
+
+    @staticmethod
+    def decode(resp, some) -> list:
+        return [int(v) if s else None for v, s in zip(resp, some)]
+
+    @staticmethod
+    def read_batch(dev: DeviceReplica, ops) -> list:
+        out = [None] * len(ops)
+        gets = [i for i, o in enumerate(ops) if isinstance(o, Get)]
+        if gets:
+            v, f = dev.sl_get(np.array([ops[i].key for i in gets], np.uint64))
+            for i, a, b in zip(gets, v, f):
+                out[i] = int(a) if b else None
+        for mode in sorted({o.mode for o in ops if isinstance(o, Seek)}):
+            idx = [i for i, o in enumerate(ops) if isinstance(o, Seek) and o.mode == mode]
+            k, v, f = dev.sl_seek(np.array([ops[i].key for i in idx], np.uint64), mode)
+            for i, a, b, c in zip(idx, k, v, f):
+                out[i] = (int(a), int(b)) if c else None
+        return out
+
+    @staticmethod
+    def snapshot(dev: DeviceReplica):
+        k, v = dev.sl_dump()
+        return list(zip(k.tolist(), v.tolist()))
 
 
 class AbstractDataStructure:

@@ -12,7 +12,8 @@ little-endian u64 words
 
 and the payload: hashmap `items` {key, value} records in any order; stack `items` u32, bottom
 first; queue `items` u64, front first; synthetic synth_n u64 words; vspace the `items` allocated
-pool tables of 512 u64, inner entries as stored (table_index * 4096 | flags).
+pool tables of 512 u64, inner entries as stored (table_index * 4096 | flags); skip list `items`
+{key, value} records in strictly ascending key order.
 
 unpack() reads an image of any kind; pack() builds one for the four flat kinds from a host model,
 its digest words from nrgpu.digest, so that a model can seed a GPU replica (DeviceReplica.restore).
@@ -34,7 +35,7 @@ HEADER_BYTES = 64
 Info = namedtuple("Info", "ds_kind version items bytes log_idx digest")
 
 _ITEM_BYTES = {L.NRG_DS_HASHMAP: 16, L.NRG_DS_STACK: 4, L.NRG_DS_SYNTHETIC: 8, L.NRG_DS_QUEUE: 8,
-               L.NRG_DS_VSPACE: 4096}
+               L.NRG_DS_VSPACE: 4096, L.NRG_DS_SKIPLIST: 16}
 _ADDR = 0x000FFFFFFFFFF000  # x86 ADDRESS_MASK: bits 12..51
 
 
@@ -79,7 +80,7 @@ def unpack(buf):
     b = as_u8(buf)
     pay = b[HEADER_BYTES:HEADER_BYTES + info.items * _ITEM_BYTES[info.ds_kind]]
     k = info.ds_kind
-    if k == L.NRG_DS_HASHMAP:
+    if k in (L.NRG_DS_HASHMAP, L.NRG_DS_SKIPLIST):  # (the skip list's in ascending key order)
         r = pay.view("<u8").reshape(-1, 2)
         return info, (r[:, 0].copy(), r[:, 1].copy())
     if k == L.NRG_DS_STACK:
@@ -116,8 +117,9 @@ def leaves(tables) -> np.ndarray:
 def pack(kind: int, state, log_idx: int) -> np.ndarray:
     """The image (u8 array) of a host model's state after replaying [0, log_idx): hashmap a
     (keys, vals) pair or a dict; stack the elements, bottom first; queue the elements, front first;
-    synthetic the words. The digest words are nrgpu.digest's."""
-    if kind == L.NRG_DS_HASHMAP:
+    synthetic the words; skip list as the hashmap (the records are written in ascending key order).
+    The digest words are nrgpu.digest's."""
+    if kind in (L.NRG_DS_HASHMAP, L.NRG_DS_SKIPLIST):
         if isinstance(state, dict):
             keys, vals = list(state.keys()), list(state.values())
         else:
@@ -128,6 +130,9 @@ def pack(kind: int, state, log_idx: int) -> np.ndarray:
             raise ValueError("keys and vals differ in length")
         if np.unique(keys).size != keys.size:
             raise ValueError("a key appears twice")
+        if kind == L.NRG_DS_SKIPLIST:
+            order = np.argsort(keys, kind="stable")
+            keys, vals = keys[order], vals[order]
         pay = np.stack([keys, vals], 1).astype("<u8").view(np.uint8).reshape(-1)
         items, dg = keys.size, _digest.pairs(keys, vals)
     elif kind == L.NRG_DS_STACK:
