@@ -625,9 +625,14 @@ int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_
  * (nrg_set_max_capacity) raised that. Without a growth bound, a replay that would hold more distinct
  * keys than the capacity latches NRG_E_CAPACITY once (reported by the next nrg_sync / synchronous
  * call); the contents are unspecified from then on, but nrg_skiplist_len is at most the capacity:
- * restore or close. Replica groups and the log calls take the kind as they take the others. Out of
- * scope: there is no combiner (nrg_combiner_open returns NRG_E_INVAL, as for the page table), no
- * partitioned mode (nrg_group_partitioned_round stays hashmap-only) and no removal of keys (the
+ * restore or close. Replica groups and the log calls take the kind as they take the others; a
+ * replicated group's round (nrg_group_round_async) answers a skip-list member's get_keys after its
+ * replay, as it does a hashmap member's. The reference itself runs the skip list key-partitioned
+ * (skiplist-mlnr, a cnr::Replica with several logs, benches/lockfree.rs:228-317, LogMapper::hash
+ * :73-97): that is nrg_group_partitioned_round on a group of skip-list replicas, with
+ * nrg_skiplist_prefill_partition and the group-wide ordered reads nrg_group_skiplist_seek /
+ * nrg_group_skiplist_range_count (the cnr section below). Out of scope: there is no combiner
+ * (nrg_combiner_open returns NRG_E_INVAL, as for the page table) and no removal of keys (the
  * reference's wrapper has none). Every call below returns NRG_E_INVAL on a context of another kind. */
 /* Replica::combine for one batch of Push(k, v) records (nr/src/replica.rs:544-595): Log::append of the
  * n records in d_ops (device) with `origin`, then Log::exec, with the log copy written by the
@@ -673,6 +678,12 @@ int nrg_skiplist_prefill(nrg_ctx* ctx, const uint64_t* keys, const uint64_t* val
 /* Generated on the device: keys k = 0..n-1 -> k + val_offset. SkipListWrapper::default
  * (benches/lockfree_partitioned.rs:88-96) is n = INITIAL_CAPACITY, val_offset = 0. */
 int nrg_skiplist_prefill_range(nrg_ctx* ctx, uint64_t n, uint64_t val_offset);
+/* SkipListWrapper::default restricted to one partition: the keys k < n with
+ * nrg_key_owner(k, parts) == part, values k + val_offset, generated on the device with no log
+ * traffic (a member of a partitioned skip-list group: part = its rank, parts = the group's size).
+ * NRG_E_INVAL: parts == 0, parts > NRG_MAX_PARTS or part >= parts. Synchronous; the keys count
+ * towards automatic growth as nrg_skiplist_prefill_range's do. */
+int nrg_skiplist_prefill_partition(nrg_ctx* ctx, uint64_t n, uint64_t val_offset, uint32_t part, uint32_t parts);
 /* A SkipMap allocates a node per key; here, as Vec::reserve / Vec::capacity for the stack
  * (nrg_stack_reserve): make room for `n_keys` keys in all, with automatic growth
  * (nrg_set_max_capacity) on or off. It never shrinks: a request the map already satisfies returns
@@ -707,7 +718,7 @@ typedef struct {
     uint64_t n;                /* records in it                                                  */
     void* resp;                /* nullable: responses to its own writes (as nrg_log_exec_async)  */
     uint8_t* some;
-    const uint64_t* get_keys;  /* hashmap: reads answered against the post-round state          */
+    const uint64_t* get_keys;  /* hashmap, skip list: reads answered against the post-round state */
     uint64_t n_gets;
     uint64_t* get_vals;
     uint8_t* get_found;
@@ -787,7 +798,7 @@ int nrg_group_set_timeout(nrg_group* g, uint32_t ms);
 /* The sticky failure's description ("nrg_group rank R of N, round E: ..."), "" if none. */
 const char* nrg_group_last_error(const nrg_group* g);
 
-/* ---- cnr-style key-partitioned NrHashMap ---------------------------------
+/* ---- cnr-style key-partitioned NrHashMap and skip list --------------------
  * cnr maps each operation to one of several logs with LogMapper::hash() (cnr/src/lib.rs:134-167);
  * the operations of one key share a log, so the logs replay independently
  * (cnr/src/replica.rs:430-445 hash -> log, :673-736 combine(hashidx)). Across GPUs, partition p's
@@ -795,7 +806,11 @@ const char* nrg_group_last_error(const nrg_group* g);
  * Gets travel to their owners, each owner replays the Puts it received in rank order -- for every
  * key the same order as the NR global log W_0 || W_1 || ... -- and answers the Gets it received,
  * and answers and previous values travel back in the caller's order. The answers are identical
- * to NR's; the replicas are not (each holds one partition). */
+ * to NR's; the replicas are not (each holds one partition).
+ * The reference runs its skip list only this way (skiplist-mlnr{logs}, benches/lockfree.rs:228-317:
+ * OpWr::Push(k, v) and SkipListConcurrent::Get(k) both mapped to a log by key, :73-97), so a group
+ * of NRG_DS_SKIPLIST replicas takes partitioned rounds too: records are Push(k, v) (nrg_put), the
+ * Gets are Get(k). Every member of a group must be of the same kind. */
 #define NRG_MAX_PARTS 64
 /* Owner partition of a key: (low 32 bits of splitmix64(key)) * parts >> 32. */
 uint32_t nrg_key_owner(uint64_t key, uint32_t parts);
@@ -811,10 +826,15 @@ int nrg_route_back_async(nrg_ctx* ctx, const uint64_t* d_src, const uint8_t* d_s
                          uint64_t* d_dst, uint8_t* d_dst8);
 /* NrHashMap::default restricted to a partition: keys k < n with nrg_key_owner(k, parts) == part. */
 int nrg_hashmap_prefill_partition(nrg_ctx* ctx, uint64_t n, uint64_t off, uint32_t part, uint32_t parts);
-/* One partitioned round on every local member (group of hashmap replicas, one partition each,
- * rank = partition): rounds[i].recs / n = the member's Puts (nrg_put), get_keys / n_gets its Gets;
- * get_vals / get_found and (nullable) resp / some = the Gets' answers and the Puts' previous values,
- * in the member's order. A round is one fused partition launch (owner regions, no global scan), an
+/* One partitioned round on every local member (group of hashmap or of skip-list replicas, one
+ * partition each, rank = partition; another kind: NRG_E_INVAL): rounds[i].recs / n = the member's
+ * Puts (nrg_put), get_keys / n_gets its Gets; get_vals / get_found and (nullable) resp / some = the
+ * Gets' answers and the Puts' previous values, in the member's order. A skip list's Push responses
+ * are Ok(Some(key)) whatever the state (benches/lockfree_partitioned.rs:108-111): they never travel;
+ * resp[i] = recs[i].key and some[i] = 1 are written on the asker's GPU when the round's Get answers
+ * arrive, and a dropped round writes none. An owner replays the Puts it received in slices of at
+ * most max_batch and then answers the Gets it received in slices of at most max_reads. Ranks whose
+ * kinds differ make the round return NRG_E_INVAL on every rank before any payload moves. A round is one fused partition launch (owner regions, no global scan), an
  * all-gather of every rank's per-owner counts, ncclSend / ncclRecv of the Puts and Get keys to
  * their owners (a rank's own part stays on its GPU), the owner's replay, the answers back and one
  * route-back launch. Everything is on the replica's stream. Returns once the round is queued,
@@ -833,6 +853,46 @@ int nrg_group_partitioned_round(nrg_group* g, const nrg_round* rounds);
 int nrg_group_partitioned_round_async(nrg_group* g, const nrg_round* rounds);
 /* Complete the round posted by nrg_group_partitioned_round_async, if any (its result). */
 int nrg_group_partitioned_flush(nrg_group* g);
+
+/* Group-wide ordered reads of a partitioned skip-list group. A skip list exists for its order, and
+ * under hash partitioning no member alone can answer lower_bound or a range count: every member
+ * answers every query against its own partition (the kernels of nrg_skiplist_seek_async /
+ * nrg_skiplist_range_count_async) and each asker reduces the candidates of the G partitions. Both
+ * calls are collectives, shaped like nrg_group_verify: every rank calls them (seek: with the same
+ * mode), with one entry per local member; all pointers are device pointers on the member's GPU.
+ * They complete queued group work as nrg_group_sync does (a posted partitioned round included, a
+ * latched device error reported at the end), exchange the members' n and argument errors (one
+ * 8-byte-per-rank all-gather read back under the group's deadline), all-gather the queries padded
+ * to the longest n, answer, return each asker's candidates with ncclSend / ncclRecv (a rank's own:
+ * a device copy) and reduce them in one launch; they return when the answers are in the caller's
+ * buffers. The members' n may differ; n = 0 on every rank returns NRG_OK after the exchange. A
+ * one-rank group's only candidate is the answer: after the exchange its read kernel answers straight
+ * into the caller's buffers.
+ *   seek         out_keys[i] / out_vals[i] / found[i] as nrg_skiplist_seek's over the whole map: among
+ *                the partitions that found a candidate the smallest key (GE, GT) or the largest (LE,
+ *                LT); partitions hold disjoint key sets, and 0 and 2^64 - 1 are ordinary keys.
+ *   range count  counts[i] = keys of the whole map in [los[i], his[i]] (0 where lo > hi): the sum.
+ * NRG_E_INVAL on every rank, before any data moves: the group's replicas are not skip lists, a mode
+ * above NRG_SEEK_LT, ranks that passed different modes, or any rank with n > 0 and a NULL buffer
+ * (n >= 2^32 counts as that). NRG_E_COMM / NRG_E_TIMEOUT as nrg_group_verify. The scratch belongs to
+ * the group and grows on demand. There is no nrg_group_skiplist_len: the count words (word 0 of each
+ * rank's triple) of nrg_group_verify add up to it. A partitioned range / dump is the caller's merge
+ * of the members' nrg_skiplist_range results. */
+typedef struct {
+    const uint64_t* keys;
+    uint64_t n;
+    uint64_t* out_keys;
+    uint64_t* out_vals;
+    uint8_t* found;
+} nrg_seek;
+int nrg_group_skiplist_seek(nrg_group* g, const nrg_seek* seeks, uint32_t mode);
+typedef struct {
+    const uint64_t* los;
+    const uint64_t* his;
+    uint64_t n;
+    uint64_t* counts;
+} nrg_count;
+int nrg_group_skiplist_range_count(nrg_group* g, const nrg_count* counts);
 
 /* ---- device memory helpers (for callers without their own allocator) ----------------- */
 int nrg_dev_alloc(nrg_ctx* ctx, uint64_t bytes, void** d_ptr);

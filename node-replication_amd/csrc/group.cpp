@@ -89,6 +89,10 @@ struct DBuf {
 enum PtBuf { PB_AVAL, PB_AFOUND, PB_APREV, PB_APREVF, PB_ST, PB_ALLST, PB_DESC, PB_N };
 enum PtPar { PP_POUT, PP_PPOS, PP_KOUT, PP_GPOS, PP_CNT, PP_ALLCNT, PP_N };
 enum PtRecv { PR_RPUT, PR_RKEY, PR_RVAL, PR_RFOUND, PR_RPREV, PR_RPREVF, PR_N };
+// Group-wide ordered reads of a partitioned skip-list group (nrg_group_skiplist_seek / _range_count):
+// the padded send copy of this member's queries, every rank's queries, this partition's candidates
+// for all of them (keys or counts, values, found) and the candidates that came back for its own.
+enum SkBuf { SK_SEND, SK_QALL, SK_CK, SK_CV, SK_CF, SK_BK, SK_BV, SK_BF, SK_N };
 constexpr int PT_DEPTH = 3;
 
 // A round's send/recv plan (stage A), kept for its answers (stage B).
@@ -117,6 +121,7 @@ struct Member {
     DBuf pt[PB_N];                  // partitioned rounds
     DBuf pp[PT_DEPTH][PP_N];        // ... by round slot (round % PT_DEPTH)
     DBuf rv[2][PR_N];               // ... by round parity
+    DBuf sk[SK_N];                  // group-wide skip-list reads
     uint64_t* h_cnt[PT_DEPTH] = {};  // pinned: [nranks][2 * nranks + XW_N] counts, capacities, flags
     hipEvent_t cnt_ev[PT_DEPTH] = {};  // the counts of that slot are in h_cnt
     nrg_round pr[PT_DEPTH] = {};       // the caller's part of the round of that slot
@@ -188,7 +193,8 @@ enum : uint64_t {
     XW_RP_CAP = 1,  // received Puts its buffers hold now
     XW_RK_CAP = 2,  // received Get keys its buffers hold now
     XW_ERR = 3,     // -NRG_E_* of a local failure before the exchange, else 0
-    XW_N = 4,
+    XW_KIND = 4,    // the member's data structure (NRG_DS_*): every rank's must be the same
+    XW_N = 5,
 };
 
 int member_init(Member& m, int nranks) {
@@ -244,6 +250,59 @@ __global__ void grp_put2_kernel(uint64_t* dst, uint64_t a, uint64_t b) {
     if (threadIdx.x < 2) dst[threadIdx.x] = threadIdx.x ? b : a;
 }
 
+constexpr int GRP_TPB = 256;
+inline unsigned grp_grid(uint64_t n) {
+    const uint64_t b = (n + GRP_TPB - 1) / GRP_TPB;
+    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
+// A partitioned skip-list round's Push responses, Ok(Some(key)) (benches/lockfree_partitioned.rs:
+// 108-111): they do not depend on the state, so the asker writes them from its own records.
+__global__ __launch_bounds__(GRP_TPB) void grp_push_resp_kernel(const nrg_put* __restrict__ recs, uint64_t n,
+                                                                uint64_t* __restrict__ resp, uint8_t* __restrict__ some) {
+    for (uint64_t i = blockIdx.x * (uint64_t)GRP_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * GRP_TPB) {
+        resp[i] = recs[i].key;
+        some[i] = 1;
+    }
+}
+
+// nrg_group_skiplist_seek's reduction: query i has one candidate per partition, ck / cv / cf[o * n + i]
+// (found = 0: that partition has none). Partitions hold disjoint key sets, so among the found ones
+// the smallest key (GE, GT) or the largest (LE, LT) is the answer of the whole map; no key value
+// stands for "none".
+__global__ __launch_bounds__(GRP_TPB) void grp_seek_reduce_kernel(const uint64_t* __restrict__ ck,
+                                                                  const uint64_t* __restrict__ cv,
+                                                                  const uint8_t* __restrict__ cf, uint32_t G, uint64_t n,
+                                                                  uint32_t mode, uint64_t* __restrict__ okeys,
+                                                                  uint64_t* __restrict__ ovals, uint8_t* __restrict__ found) {
+    const bool up = mode == NRG_SEEK_GE || mode == NRG_SEEK_GT;
+    for (uint64_t i = blockIdx.x * (uint64_t)GRP_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * GRP_TPB) {
+        uint64_t bk = 0, bv = 0;
+        bool any = false;
+        for (uint32_t o = 0; o < G; o++) {
+            const uint64_t at = (uint64_t)o * n + i;
+            if (!cf[at]) continue;
+            const uint64_t k = ck[at];
+            if (!any || (up ? k < bk : k > bk)) bk = k, bv = cv[at];
+            any = true;
+        }
+        okeys[i] = bk;
+        ovals[i] = bv;
+        found[i] = any ? 1 : 0;
+    }
+}
+
+// nrg_group_skiplist_range_count's: the sum of the partitions' counts (at most 2^64 keys exist, and
+// 2^64 only for [0, 2^64 - 1] on a full key space, which no capacity allows: the sum cannot wrap)
+__global__ __launch_bounds__(GRP_TPB) void grp_count_reduce_kernel(const uint64_t* __restrict__ cc, uint32_t G,
+                                                                   uint64_t n, uint64_t* __restrict__ counts) {
+    for (uint64_t i = blockIdx.x * (uint64_t)GRP_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * GRP_TPB) {
+        uint64_t c = 0;
+        for (uint32_t o = 0; o < G; o++) c += cc[(uint64_t)o * n + i];
+        counts[i] = c;
+    }
+}
+
 // fingerprint of a round's segment lengths (every rank must pass the same ones)
 uint64_t lens_fp(const std::vector<uint64_t>& lens) {
     uint64_t h = 0x9E3779B97F4A7C15ull ^ lens.size();
@@ -267,6 +326,8 @@ void member_free(Member& m, const Rccl* R) {
     if (m.h_glx) (void)hipHostFree(m.h_glx);
     if (m.h_gdg) (void)hipHostFree(m.h_gdg);
     for (DBuf& d : m.pt)
+        if (d.p) (void)hipFree(d.p);
+    for (DBuf& d : m.sk)
         if (d.p) (void)hipFree(d.p);
     for (int q = 0; q < PT_DEPTH; q++) {
         for (DBuf& d : m.pp[q])
@@ -486,14 +547,15 @@ int nrg_group_set_input_stream(nrg_group* g, int member, void* s) {
 // process): each rank all-gathers {n, local error} and the host reads them back (one host round
 // trip). A rank whose own part is bad makes every rank return NRG_E_INVAL, so no rank is left
 // inside a collective its peers never post.
-static int exchange_lengths(nrg_group* g, const nrg_round* rounds, const std::vector<int>& bad,
-                            std::vector<uint64_t>& lens) {
+// Two words per rank, all-gathered on the comm streams and read back under the group's deadline:
+// g->m[0].h_glx then holds {a, b} of every rank, in rank order (identical on every rank).
+static int exchange_pairs(nrg_group* g, const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) {
     const Rccl* R = g->R;
     const int nl = (int)g->m.size(), G = g->nranks;
     for (int i = 0; i < nl; i++) {
         Member& m = g->m[i];
         RCHK(nrg::ctx_use_device(m.ctx));
-        grp_put2_kernel<<<1, 64, 0, m.cstream>>>(m.lx, rounds[i].n, bad[i] ? 1 : 0);
+        grp_put2_kernel<<<1, 64, 0, m.cstream>>>(m.lx, a[i], b[i]);
         GCHK(hipGetLastError());
     }
     if (R->group_start() != ncclSuccess) return NRG_E_COMM;
@@ -508,6 +570,15 @@ static int exchange_lengths(nrg_group* g, const nrg_round* rounds, const std::ve
         GCHK(hipMemcpyAsync(m.h_glx, m.glx, 2 * (uint64_t)G * 8, hipMemcpyDeviceToHost, m.cstream));
         RCHK(wait_stream(g, m.cstream, "length exchange"));
     }
+    return NRG_OK;
+}
+
+static int exchange_lengths(nrg_group* g, const nrg_round* rounds, const std::vector<int>& bad,
+                            std::vector<uint64_t>& lens) {
+    const int nl = (int)g->m.size(), G = g->nranks;
+    std::vector<uint64_t> a(nl), b(nl);
+    for (int i = 0; i < nl; i++) a[i] = rounds[i].n, b[i] = bad[i] ? 1 : 0;
+    RCHK(exchange_pairs(g, a, b));
     const uint64_t* H = g->m[0].h_glx;  // identical on every rank
     bool any_bad = false;
     for (int r = 0; r < G; r++) {
@@ -515,6 +586,15 @@ static int exchange_lengths(nrg_group* g, const nrg_round* rounds, const std::ve
         any_bad |= H[2 * r + 1] != 0;
     }
     return any_bad ? NRG_E_INVAL : NRG_OK;
+}
+
+// n Gets of a skip-list replica in slices of at most max_reads (nrg_skiplist_get_async takes no more
+// in one call; a skewed partitioned round can hand one owner G times a member's Gets)
+static int sl_gets(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint64_t* vals, uint8_t* found) {
+    const uint64_t step = std::max<uint64_t>(1, c->cfg.max_reads);
+    for (uint64_t at = 0; at < n; at += step)
+        RCHK(nrg_skiplist_get_async(c, keys + at, std::min(step, n - at), vals + at, found + at));
+    return NRG_OK;
 }
 
 int nrg_group_round_async(nrg_group* g, const nrg_round* rounds, const uint64_t* seg_lens) {
@@ -529,7 +609,9 @@ int nrg_group_round_async(nrg_group* g, const nrg_round* rounds, const uint64_t*
     std::vector<uint64_t> lens(G);
     std::vector<int> bad(nl, 0);
     for (int i = 0; i < nl; i++)
-        bad[i] = g->m[i].ctx->cfg.ds_kind != kind || (rounds[i].n && !rounds[i].recs);
+        bad[i] = g->m[i].ctx->cfg.ds_kind != kind || (rounds[i].n && !rounds[i].recs) ||
+                 (kind == NRG_DS_SKIPLIST && rounds[i].n_gets &&
+                  (!rounds[i].get_keys || !rounds[i].get_vals || !rounds[i].get_found));
     // Three ways to know them:
     //   whole   this process drives every rank: the members' n (or seg_lens, checked against them)
     //   given   seg_lens from the caller, who promises every rank passes the same array: a header
@@ -626,7 +708,7 @@ int nrg_group_round_async(nrg_group* g, const nrg_round* rounds, const uint64_t*
         if (bad[i]) {  // took part in the collectives, replays nothing
             // Its peers replay the round (with this rank's segment as zeros) and latch ERR_GROUP;
             // the replicas now differ, so the group is over for every rank (sticky error).
-            rc = group_fail(g, NRG_E_INVAL, "this rank's segment disagreed with seg_lens: replicas diverged");
+            rc = group_fail(g, NRG_E_INVAL, "this rank's segment disagreed with seg_lens (or its buffers were missing): replicas diverged");
             continue;
         }
         if (stride) {
@@ -649,6 +731,9 @@ int nrg_group_round_async(nrg_group* g, const nrg_round* rounds, const uint64_t*
             if (r == NRG_OK)
                 r = nrg_log_exec_async(c, firsts[m.rank], firsts[m.rank] + lens[m.rank], x.resp, x.some);
         }
+        // a skip list's reads (SkipListConcurrent::Get, benches/lockfree.rs:73-84) against the
+        // post-round state, as the hashmap's round answers its own
+        if (r == NRG_OK && kind == NRG_DS_SKIPLIST) r = sl_gets(c, x.get_keys, x.n_gets, x.get_vals, x.get_found);
         if (r) return r;
         if (stride) {
             GCHK(hipEventRecord(m.freed[b], c->stream));
@@ -679,6 +764,10 @@ int nrg_group_round_async(nrg_group* g, const nrg_round* rounds, const uint64_t*
 // Everything runs on the replica's stream. Every failure before a round's first send/recv is
 // agreed on by all ranks (the same exchanged words): the round is dropped everywhere and the call
 // that ran its stage A returns the error.
+// A group of skip-list replicas (the reference's skiplist-mlnr, benches/lockfree.rs:228-317) takes
+// the same rounds: the records are Push(k, v), the owner's replay is nrg_skiplist_round_async per
+// slice and nrg_skiplist_get_async for the Gets, nothing is deferred, and the Push responses
+// Ok(Some(key)) are written on the asker's side in stage B (they never travel: XW_PREV = 0).
 // A one-rank group owns every key, so its partition is the identity and so is the route-back:
 // the owner's replay reads the caller's records and Get keys and answers straight into the
 // caller's buffers -- no data moves, as a cnr replica with one log appends and replays in place
@@ -696,7 +785,8 @@ static int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
         const nrg_round& x = rounds[i];
         nrg_ctx* c = m.ctx;
         int err = NRG_OK;
-        if (c->cfg.ds_kind != NRG_DS_HASHMAP || (x.n && !x.recs) ||
+        const uint32_t kind = c->cfg.ds_kind;
+        if ((kind != NRG_DS_HASHMAP && kind != NRG_DS_SKIPLIST) || (x.n && !x.recs) ||
             (x.n_gets && (!x.get_keys || !x.get_vals || !x.get_found)))
             err = NRG_E_INVAL;
         else if (x.n >= (1ull << 32) || x.n_gets >= (1ull << 32) || (uint64_t)G * x.n >= (1ull << 32) ||
@@ -719,7 +809,9 @@ static int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
             }
         }
         uint64_t* w = m.xwords;
-        w[XW_PREV] = (x.resp && x.some) ? 1 : 0;
+        // (a skip list's Push responses are its own keys: they never travel, see pt_stage_b)
+        w[XW_PREV] = (kind == NRG_DS_HASHMAP && x.resp && x.some) ? 1 : 0;
+        w[XW_KIND] = kind;
         // receive capacities of the round's parity (one rank replays straight from its partition
         // output: no RPUT / RKEY)
         const DBuf* rv = m.rv[par];
@@ -810,6 +902,9 @@ static int pt_stage_a(nrg_group* g, uint64_t e) {
     auto word = [&](int s, uint64_t k) { return H[(size_t)s * CW + 2 * G + k]; };
     for (int s = 0; s < G; s++)
         if (word(s, XW_ERR)) return -(int)word(s, XW_ERR);  // the same answer on every rank
+    for (int s = 1; s < G; s++)
+        if (word(s, XW_KIND) != word(0, XW_KIND)) return NRG_E_INVAL;  // hashmap and skip-list ranks in one group
+    const bool skiplist = word(0, XW_KIND) == NRG_DS_SKIPLIST;
     bool any_prev = false, any_grow = false;
     for (int s = 0; s < G; s++) {
         any_prev |= word(s, XW_PREV) != 0;
@@ -947,6 +1042,22 @@ static int pt_stage_a(nrg_group* g, uint64_t e) {
         uint64_t* rval = ident ? x.get_vals : (uint64_t*)m.rv[par][PR_RVAL].p;
         uint8_t* rfound = ident ? x.get_found : (uint8_t*)m.rv[par][PR_RFOUND].p;
         uint64_t off = 0;
+        if (skiplist) {
+            // Push(k, v) slices in rank order, then the Gets against the post-round state. The skip
+            // list defers nothing; its chunk replay synchronises this stream now and then (the counts
+            // behind the compaction policy and growth), which every send and recv it waits for
+            // allows: they were all enqueued above, before any member's replay.
+            // Identity form: the responses Ok(Some(key)) come from the replay itself.
+            uint64_t* presp = ident && x.resp && x.some ? (uint64_t*)x.resp : nullptr;
+            uint8_t* psome = presp ? x.some : nullptr;
+            for (; off < P.rp; off += chunk) {
+                const uint64_t n = std::min(chunk, P.rp - off);
+                RCHK(nrg_skiplist_round_async(c, rput + off, n, (uint32_t)m.rank + 1, presp ? presp + off : nullptr,
+                                              psome ? psome + off : nullptr));
+            }
+            RCHK(sl_gets(c, (const uint64_t*)rkey_of(i), P.rk, rval, rfound));
+            continue;
+        }
         do {
             const uint64_t n = std::min(chunk, P.rp - off);
             const bool last = off + n == P.rp;
@@ -971,6 +1082,8 @@ static int pt_stage_b(nrg_group* g, uint64_t e) {
     const int G = g->nranks, nl = (int)g->m.size();
     const int sl = (int)(e % PT_DEPTH), par = (int)(e & 1);
     if (g->pt_drop[sl]) return NRG_OK;  // dropped in stage A (its error was returned there)
+    // (the kind every rank agreed on in stage A: a skip list's Push responses never travel)
+    const bool skiplist = g->m[0].ctx->cfg.ds_kind == NRG_DS_SKIPLIST;
     const uint64_t CW = 2 * (uint64_t)G + XW_N;
     const uint64_t* H = g->m[0].h_cnt[sl];
     auto word = [&](int s, uint64_t k) { return H[(size_t)s * CW + 2 * G + k]; };
@@ -980,7 +1093,7 @@ static int pt_stage_b(nrg_group* g, uint64_t e) {
         for (int i = 0; i < nl && res == ncclSuccess; i++) {
             Member& m = g->m[i];
             const PtPlan& P = m.plan[sl];
-            const bool mine = m.pr[sl].resp && m.pr[sl].some;
+            const bool mine = !skiplist && m.pr[sl].resp && m.pr[sl].some;
             const uint64_t cp = m.cap_p[sl], ck = m.cap_k[sl];
             const DBuf* rv = m.rv[par];
             hipStream_t s = m.ctx->stream;
@@ -1019,7 +1132,7 @@ static int pt_stage_b(nrg_group* g, uint64_t e) {
         const int r = m.rank;
         if (pt_ident(g, m)) continue;  // the replay answered into the caller's buffers
         RCHK(nrg::ctx_use_device(c));
-        const bool mine = x.resp && x.some;
+        const bool mine = !skiplist && x.resp && x.some;
         const uint64_t cp = m.cap_p[sl], ck = m.cap_k[sl];
         const DBuf* rv = m.rv[par];
         void *aval = m.pt[PB_AVAL].p, *afound = m.pt[PB_AFOUND].p, *aprev = m.pt[PB_APREV].p, *aprevf = m.pt[PB_APREVF].p;
@@ -1045,6 +1158,11 @@ static int pt_stage_b(nrg_group* g, uint64_t e) {
             x.get_vals, x.get_found, (const uint64_t*)aprev, (const uint8_t*)aprevf,
             (const uint32_t*)m.pp[sl][PP_PPOS].p, mine ? x.n : 0, mine ? (uint64_t*)x.resp : nullptr, mine ? x.some : nullptr);
         if (he != hipSuccess) return hip_rc(he);
+        if (skiplist && x.n && x.resp && x.some) {  // Ok(Some(key)) from the asker's own records
+            grp_push_resp_kernel<<<grp_grid(x.n), GRP_TPB, 0, c->stream>>>((const nrg_put*)x.recs, x.n,
+                                                                          (uint64_t*)x.resp, x.some);
+            GCHK(hipGetLastError());
+        }
     }
     g->round++;
     return NRG_OK;
@@ -1187,6 +1305,226 @@ int nrg_group_verify(nrg_group* g, uint64_t* digests, int* identical) {
     if (digests) std::memcpy(digests, H, 3 * (uint64_t)G * 8);
     *identical = same;
     return rc;
+}
+
+// ---- group-wide ordered reads of a partitioned skip-list group ------------------------------------
+// Under hash partitioning no member alone can answer lower_bound or a range count: every member
+// answers every query against its own partition and the asker reduces the G candidates.
+//   1. {n, flags} of every rank (exchange_pairs): the flags carry a rank's bad arguments, its kind
+//      and the seek mode, so that every rank returns the same code before any data moves;
+//   2. the queries, padded to the longest n, all-gathered (a range count's los and his travel as one
+//      block: the los of every slot, then the his);
+//   3. the existing skip-list read kernels over all G * nmax of them (skiplist.hip);
+//   4. each asker's candidates back with send / recv in one group (a rank's own: a device copy);
+//   5. one reduction launch into the caller's buffers.
+// Everything after step 1 runs on the replica's stream, which the call then waits for. A one-rank
+// group (pt_ident) stops after step 1 and runs step 3 straight into the caller's buffers.
+struct SkQuery {
+    const uint64_t *a, *b;  // keys, or los and his
+    uint64_t n;
+    bool bad;
+};
+
+static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, uint32_t mode, uint64_t* nmax_out,
+                      std::vector<uint64_t>& lens, bool* ident) {
+    const Rccl* R = g->R;
+    const int nl = (int)g->m.size(), G = g->nranks;
+    std::vector<uint64_t> a(nl), b(nl);
+    for (int i = 0; i < nl; i++) {
+        const nrg_ctx* c = g->m[i].ctx;
+        const bool bad = q[i].bad || c->cfg.ds_kind != NRG_DS_SKIPLIST || c->ltail != c->tail ||
+                         (!count && mode > NRG_SEEK_LT) || q[i].n >= (1ull << 32);
+        a[i] = q[i].n;
+        b[i] = (bad ? 1 : 0) | ((uint64_t)(count ? 0 : mode) << 8) | ((uint64_t)c->cfg.ds_kind << 40);
+    }
+    RCHK(exchange_pairs(g, a, b));
+    const uint64_t* H = g->m[0].h_glx;
+    uint64_t nmax = 0;
+    for (int r = 0; r < G; r++) {
+        if ((H[2 * r + 1] & 1) || H[2 * r + 1] != H[1]) return NRG_E_INVAL;  // the same on every rank
+        lens[r] = H[2 * r];
+        nmax = std::max(nmax, lens[r]);
+    }
+    *nmax_out = nmax;
+    if (nmax == 0) return NRG_OK;
+    // One rank owns every key: its only candidate is the answer, so the read kernel answers straight
+    // into the caller's buffers and nothing moves (as a one-rank group's rounds; NRG_KNOB_EXP bit 16
+    // keeps the general path selectable for it).
+    *ident = pt_ident(g, g->m[0]);
+    if (*ident) {
+        Member& m = g->m[0];
+        if (m.in_set && m.in_stream != m.ctx->stream) RCHK(order(m, m.in_stream, m.ctx->stream));
+        return NRG_OK;
+    }
+    const uint64_t words = count ? 2 : 1;  // u64 words per query
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        nrg_ctx* c = m.ctx;
+        RCHK(nrg::ctx_use_device(c));
+        int r = grow_buf(m, m.sk[SK_SEND], words * nmax * 8);
+        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_QALL], (uint64_t)G * words * nmax * 8);
+        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_CK], (uint64_t)G * nmax * 8);
+        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BK], (uint64_t)G * q[i].n * 8);
+        if (r == NRG_OK && !count) {
+            r = grow_buf(m, m.sk[SK_CV], (uint64_t)G * nmax * 8);
+            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_CF], (uint64_t)G * nmax);
+            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BV], (uint64_t)G * q[i].n * 8);
+            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BF], (uint64_t)G * q[i].n);
+        }
+        // (its peers are already inside the collectives below: the group cannot go on)
+        if (r) return group_fail(g, r, "group-wide skip-list read: scratch allocation failed");
+        hipStream_t s = c->stream;
+        if (m.in_set && m.in_stream != s) RCHK(order(m, m.in_stream, s));
+        // the padded send copy (padding queries are zeros: answered, never returned)
+        char* send = (char*)m.sk[SK_SEND].p;
+        GCHK(hipMemsetAsync(send, 0, words * nmax * 8, s));
+        if (q[i].n) {
+            GCHK(hipMemcpyAsync(send, q[i].a, q[i].n * 8, hipMemcpyDeviceToDevice, s));
+            if (count) GCHK(hipMemcpyAsync(send + nmax * 8, q[i].b, q[i].n * 8, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (R->group_start() != ncclSuccess) return NRG_E_COMM;
+    ncclResult_t res = ncclSuccess;
+    for (int i = 0; i < nl && res == ncclSuccess; i++)
+        res = R->all_gather(g->m[i].sk[SK_SEND].p, g->m[i].sk[SK_QALL].p, words * nmax, ncclUint64, g->m[i].comm,
+                            g->m[i].ctx->stream);
+    RCHK(group_end(g, "group-wide skip-list read: queries"));
+    if (res != ncclSuccess) return group_fail(g, NRG_E_COMM, "group-wide skip-list read: all-gather refused");
+    // every member answers every rank's block against its own partition
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        nrg_ctx* c = m.ctx;
+        RCHK(nrg::ctx_use_device(c));
+        const uint64_t* qall = (const uint64_t*)m.sk[SK_QALL].p;
+        for (int s = 0; s < G; s++) {
+            if (!lens[s]) continue;
+            const uint64_t* blk = qall + (uint64_t)s * words * nmax;
+            const hipError_t he =
+                count ? nrg::sl_count_launch(c, blk, blk + nmax, lens[s], (uint64_t*)m.sk[SK_CK].p + (uint64_t)s * nmax)
+                      : nrg::sl_seek_launch(c, blk, lens[s], mode, (uint64_t*)m.sk[SK_CK].p + (uint64_t)s * nmax,
+                                            (uint64_t*)m.sk[SK_CV].p + (uint64_t)s * nmax,
+                                            (uint8_t*)m.sk[SK_CF].p + (uint64_t)s * nmax);
+            if (he != hipSuccess) return hip_rc(he);
+        }
+    }
+    // the candidates back to their askers: rank r's block for asker s lands at s's slot r
+    if (G > 1) {
+        if (R->group_start() != ncclSuccess) return NRG_E_COMM;
+        for (int i = 0; i < nl && res == ncclSuccess; i++) {
+            Member& m = g->m[i];
+            const uint64_t n = q[i].n;
+            hipStream_t s = m.ctx->stream;
+            for (int o = 0; o < G && res == ncclSuccess; o++) {
+                if (o == m.rank) continue;
+                if (lens[o]) {
+                    res = R->send(at(m.sk[SK_CK].p, o * nmax * 8), lens[o], ncclUint64, o, m.comm, s);
+                    if (res == ncclSuccess && !count)
+                        res = R->send(at(m.sk[SK_CV].p, o * nmax * 8), lens[o], ncclUint64, o, m.comm, s);
+                    if (res == ncclSuccess && !count)
+                        res = R->send(at(m.sk[SK_CF].p, o * nmax), lens[o], ncclUint8, o, m.comm, s);
+                }
+                if (res == ncclSuccess && n) {
+                    res = R->recv(at(m.sk[SK_BK].p, o * n * 8), n, ncclUint64, o, m.comm, s);
+                    if (res == ncclSuccess && !count) res = R->recv(at(m.sk[SK_BV].p, o * n * 8), n, ncclUint64, o, m.comm, s);
+                    if (res == ncclSuccess && !count) res = R->recv(at(m.sk[SK_BF].p, o * n), n, ncclUint8, o, m.comm, s);
+                }
+            }
+        }
+        RCHK(group_end(g, "group-wide skip-list read: candidates back"));
+        if (res != ncclSuccess) return group_fail(g, NRG_E_COMM, "group-wide skip-list read: send/recv refused");
+    }
+    for (int i = 0; i < nl; i++) {  // a rank's own candidates: a device copy
+        Member& m = g->m[i];
+        const uint64_t n = q[i].n, r = (uint64_t)m.rank;
+        if (!n) continue;
+        RCHK(nrg::ctx_use_device(m.ctx));
+        hipStream_t s = m.ctx->stream;
+        GCHK(hipMemcpyAsync(at(m.sk[SK_BK].p, r * n * 8), at(m.sk[SK_CK].p, r * nmax * 8), n * 8, hipMemcpyDeviceToDevice, s));
+        if (count) continue;
+        GCHK(hipMemcpyAsync(at(m.sk[SK_BV].p, r * n * 8), at(m.sk[SK_CV].p, r * nmax * 8), n * 8, hipMemcpyDeviceToDevice, s));
+        GCHK(hipMemcpyAsync(at(m.sk[SK_BF].p, r * n), at(m.sk[SK_CF].p, r * nmax), n, hipMemcpyDeviceToDevice, s));
+    }
+    return NRG_OK;
+}
+
+// the calls' common end: wait for every local member's stream under the group's deadline
+static int sk_finish(nrg_group* g, int rc) {
+    for (Member& m : g->m) {
+        RCHK(nrg::ctx_use_device(m.ctx));
+        RCHK(wait_stream(g, m.ctx->stream, "group-wide skip-list read"));
+    }
+    return rc;
+}
+
+int nrg_group_skiplist_seek(nrg_group* g, const nrg_seek* seeks, uint32_t mode) {
+    int r = pt_check(g);
+    if (r) return r;
+    if (!seeks) return NRG_E_INVAL;
+    const int nl = (int)g->m.size(), G = g->nranks;
+    // queued group work first; a latched device error of this rank is reported at the end, after it
+    // has taken its part in the collectives (as nrg_group_verify)
+    const int rc = nrg_group_sync(g);
+    if (g->broken) return g->broken;
+    std::vector<SkQuery> q(nl);
+    for (int i = 0; i < nl; i++) {
+        const nrg_seek& x = seeks[i];
+        q[i] = SkQuery{x.keys, nullptr, x.n, x.n && (!x.keys || !x.out_keys || !x.out_vals || !x.found)};
+    }
+    std::vector<uint64_t> lens(G);
+    uint64_t nmax = 0;
+    bool ident = false;
+    RCHK(sk_collect(g, q, false, mode, &nmax, lens, &ident));
+    if (nmax == 0) return rc;
+    if (ident) {
+        const nrg_seek& x = seeks[0];
+        const hipError_t he = nrg::sl_seek_launch(g->m[0].ctx, x.keys, x.n, mode, x.out_keys, x.out_vals, x.found);
+        return he != hipSuccess ? hip_rc(he) : sk_finish(g, rc);
+    }
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        const nrg_seek& x = seeks[i];
+        if (!x.n) continue;
+        RCHK(nrg::ctx_use_device(m.ctx));
+        grp_seek_reduce_kernel<<<grp_grid(x.n), GRP_TPB, 0, m.ctx->stream>>>(
+            (const uint64_t*)m.sk[SK_BK].p, (const uint64_t*)m.sk[SK_BV].p, (const uint8_t*)m.sk[SK_BF].p, (uint32_t)G, x.n,
+            mode, x.out_keys, x.out_vals, x.found);
+        GCHK(hipGetLastError());
+    }
+    return sk_finish(g, rc);
+}
+
+int nrg_group_skiplist_range_count(nrg_group* g, const nrg_count* counts) {
+    int r = pt_check(g);
+    if (r) return r;
+    if (!counts) return NRG_E_INVAL;
+    const int nl = (int)g->m.size(), G = g->nranks;
+    const int rc = nrg_group_sync(g);
+    if (g->broken) return g->broken;
+    std::vector<SkQuery> q(nl);
+    for (int i = 0; i < nl; i++) {
+        const nrg_count& x = counts[i];
+        q[i] = SkQuery{x.los, x.his, x.n, x.n && (!x.los || !x.his || !x.counts)};
+    }
+    std::vector<uint64_t> lens(G);
+    uint64_t nmax = 0;
+    bool ident = false;
+    RCHK(sk_collect(g, q, true, 0, &nmax, lens, &ident));
+    if (nmax == 0) return rc;
+    if (ident) {
+        const nrg_count& x = counts[0];
+        const hipError_t he = nrg::sl_count_launch(g->m[0].ctx, x.los, x.his, x.n, x.counts);
+        return he != hipSuccess ? hip_rc(he) : sk_finish(g, rc);
+    }
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        const nrg_count& x = counts[i];
+        if (!x.n) continue;
+        RCHK(nrg::ctx_use_device(m.ctx));
+        grp_count_reduce_kernel<<<grp_grid(x.n), GRP_TPB, 0, m.ctx->stream>>>((const uint64_t*)m.sk[SK_BK].p, (uint32_t)G,
+                                                                              x.n, x.counts);
+        GCHK(hipGetLastError());
+    }
+    return sk_finish(g, rc);
 }
 
 // Replica::new from the root's state (include/nrgpu.h): the root's snapshot to every other rank,

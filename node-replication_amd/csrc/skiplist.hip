@@ -782,6 +782,45 @@ static int sl_extract(nrg_ctx* c, u64 lo, u64 hi, uint64_t* keys, uint64_t* vals
     return NRG_OK;
 }
 
+// The read kernels for the replica group's group-wide reads (group.cpp): the queries and the answers
+// live in the group's scratch, so max_reads (the bound of the entry points' staging) does not apply.
+hipError_t sl_seek_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u64* d_okeys, u64* d_ovals, uint8_t* d_found) {
+    if (n == 0) return hipSuccess;
+    if (c->cfg.ds_kind != NRG_DS_SKIPLIST || mode > NRG_SEEK_LT || n >= (1ull << 32)) return hipErrorInvalidValue;
+    SlHost& s = c->sl;
+    NRG_LAUNCH(c, "sl_seek", sl_seek_kernel, (unsigned)((n + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur],
+               (const u64*)s.d_dv[s.dcur], (const SlState*)s.d_state, d_keys, n, mode, d_okeys, d_ovals, d_found);
+    return hipGetLastError();
+}
+
+hipError_t sl_count_launch(nrg_ctx* c, const u64* d_los, const u64* d_his, u64 n, u64* d_counts) {
+    if (n == 0) return hipSuccess;
+    if (c->cfg.ds_kind != NRG_DS_SKIPLIST || n >= (1ull << 32)) return hipErrorInvalidValue;
+    SlHost& s = c->sl;
+    NRG_LAUNCH(c, "sl_range_count", sl_range_count_kernel, (unsigned)((n + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_dk[s.dcur], (const SlState*)s.d_state, d_los, d_his, n,
+               d_counts);
+    return hipGetLastError();
+}
+
+// SkipListWrapper::default restricted to a partition: of the keys k0 .. k0 + n - 1, the records of
+// those `part` owns (nrg_key_owner), compacted into `out` in no particular order (the keys are
+// distinct and the chunk sorts them); *cnt, zero before the launch, receives their number. One
+// atomic per wave: the lanes that own their key take consecutive places from the wave's base.
+__global__ __launch_bounds__(SL_TPB) void sl_gen_part_kernel(nrg_put* out, u64 k0, u64 n, u64 off, u32 part, u32 parts,
+                                                             u32* cnt) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    const bool mine = i < n && key_owner(k0 + i, parts) == part;
+    const u64 b = __ballot(mine);
+    if (b == 0) return;
+    const u32 lane = threadIdx.x & 63;
+    u32 base = 0;
+    if (lane == (u32)__ffsll((unsigned long long)b) - 1) base = atomicAdd(cnt, (u32)__popcll(b));
+    base = __shfl(base, __ffsll((unsigned long long)b) - 1);
+    if (mine) out[base + (u32)__popcll(b & ((1ull << lane) - 1))] = nrg_put{k0 + i, k0 + i + off};
+}
+
 }  // namespace nrg
 
 // ---- the skip list's entry points (include/nrgpu.h) ------------------------------------------------
@@ -954,6 +993,33 @@ int nrg_skiplist_prefill_range(nrg_ctx* c, uint64_t n, uint64_t val_offset) {
                                                                                       val_offset);
         HIPCHK(hipGetLastError());
         HIPCHK(sl_chunk(c, (const nrg_put*)c->stg[0].p, false, 0, m, 0, 0, nullptr, nullptr));
+    }
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_skiplist_prefill_partition(nrg_ctx* c, uint64_t n, uint64_t val_offset, uint32_t part, uint32_t parts) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (parts == 0 || parts > NRG_MAX_PARTS || part >= parts) return NRG_E_INVAL;
+    const uint64_t mb = c->cfg.max_batch;
+    if ((r = staging(c->stg[3], 64))) return r;
+    u32* d_cnt = (u32*)c->stg[3].p;
+    // a slice of max_batch keys at a time: its owned records compacted on the device, their number
+    // read back (the call is synchronous anyway), and that many handed to the chunk path, which
+    // accounts them for growth as any prefill's
+    for (uint64_t at = 0; at < n; at += mb) {
+        const uint64_t m = n - at < mb ? n - at : mb;
+        if ((r = staging(c->stg[0], m * sizeof(nrg_put)))) return r;
+        HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(u32), c->stream));
+        sl_gen_part_kernel<<<(unsigned)((m + SL_TPB - 1) / SL_TPB), SL_TPB, 0, c->stream>>>((nrg_put*)c->stg[0].p, at, m,
+                                                                                           val_offset, part, parts, d_cnt);
+        HIPCHK(hipGetLastError());
+        u32 owned = 0;
+        HIPCHK(hipMemcpyAsync(&owned, d_cnt, sizeof owned, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (owned > m) return NRG_E_HIP;  // (cannot happen: a slice owns at most its keys)
+        HIPCHK(sl_chunk(c, (const nrg_put*)c->stg[0].p, false, 0, owned, 0, 0, nullptr, nullptr));
     }
     HIPCHK(sync_all(c));
     return check_err(c);

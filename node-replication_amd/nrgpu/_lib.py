@@ -131,6 +131,29 @@ class Round(C.Structure):
     ]
 
 
+class Seek(C.Structure):
+    """nrg_seek: one group member's queries of nrg_group_skiplist_seek (device pointers on its GPU)."""
+
+    _fields_ = [
+        ("keys", C.c_void_p),
+        ("n", C.c_uint64),
+        ("out_keys", C.c_void_p),
+        ("out_vals", C.c_void_p),
+        ("found", C.c_void_p),
+    ]
+
+
+class Count(C.Structure):
+    """nrg_count: one group member's queries of nrg_group_skiplist_range_count."""
+
+    _fields_ = [
+        ("los", C.c_void_p),
+        ("his", C.c_void_p),
+        ("n", C.c_uint64),
+        ("counts", C.c_void_p),
+    ]
+
+
 vp = C.c_void_p
 u64 = C.c_uint64
 u32 = C.c_uint32
@@ -211,6 +234,7 @@ SIGNATURES = {
     "nrg_skiplist_len": (C.c_int, [vp, u64p]),
     "nrg_skiplist_prefill": (C.c_int, [vp, vp, vp, u64]),
     "nrg_skiplist_prefill_range": (C.c_int, [vp, u64, u64]),
+    "nrg_skiplist_prefill_partition": (C.c_int, [vp, u64, u64, C.c_uint32, C.c_uint32]),
     "nrg_skiplist_reserve": (C.c_int, [vp, u64]),
     "nrg_skiplist_capacity": (C.c_int, [vp, u64p]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
@@ -254,6 +278,8 @@ SIGNATURES = {
     "nrg_group_partitioned_round": (C.c_int, [vp, C.POINTER(Round)]),
     "nrg_group_partitioned_round_async": (C.c_int, [vp, C.POINTER(Round)]),
     "nrg_group_partitioned_flush": (C.c_int, [vp]),
+    "nrg_group_skiplist_seek": (C.c_int, [vp, C.POINTER(Seek), C.c_uint32]),
+    "nrg_group_skiplist_range_count": (C.c_int, [vp, C.POINTER(Count)]),
 }
 
 # include/nrgpu_testing.h (kernel unit-test hooks)

@@ -96,7 +96,8 @@ class ReplicaGroup:
 
     def round_async(self, recs, n: int, resp=None, some=None, get_keys=None, n_gets: int = 0, get_vals=None,
                     get_found=None, seg_lens: Optional[Sequence[int]] = None):
-        """One NR round (device tensors or raw pointers): all-gather + replay + local reads.
+        """One NR round (device tensors or raw pointers): all-gather + replay + local reads
+        (get_keys: a hashmap's or a skip list's Gets, answered against the post-round state).
 
         seg_lens: every rank's segment length, the same list on every rank (the stream-ordered
         path; a header checks it on every rank). None: the lengths are exchanged first, which
@@ -246,13 +247,16 @@ class ReplicatedHashMap(ReplicatedLog):
         return g.buf.view(-1, 2)
 
 
-# ---- cnr-style key-partitioned NrHashMap ----------------------------------
+# ---- cnr-style key-partitioned NrHashMap and skip list ---------------------
 # cnr maps every operation to one of several logs with LogMapper::hash (cnr/src/lib.rs:134-167,
 # cnr/src/replica.rs:430-445) and each log replays on its own (:673-736). Here partition p's log
 # lives on rank p, which holds only the keys it owns: a round routes Puts and Gets to their
 # owners, every owner replays what it received in rank order (for each key the NR global-log
 # order) and answers its Gets, and the answers come back in the caller's order. Answers equal
 # NR's; the replicas hold one partition each (their digests add up to the NR replica's).
+# The reference runs its skip list only this way (skiplist-mlnr, benches/lockfree.rs:73-97, :228-317):
+# a PartitionedGroup of skip-list replicas takes the same rounds (Push(k, v) records, Get(k) reads)
+# and adds the group-wide ordered reads no single partition can answer.
 
 _M1, _M2 = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
 
@@ -270,8 +274,9 @@ def key_owner(keys, parts: int):
 
 
 class PartitionedGroup(ReplicaGroup):
-    """This rank's replica as partition `rank` of a key-partitioned group (libnrgpu.so, RCCL
-    send/recv): nrg_group_partitioned_round."""
+    """This rank's replica (a hashmap or a skip list; every rank the same kind) as partition `rank`
+    of a key-partitioned group (libnrgpu.so, RCCL send/recv): nrg_group_partitioned_round. For a
+    skip list prev / prev_found receive the Push responses (the key, 1)."""
 
     def round(self, puts, n: int, get_keys, n_gets: int, get_vals, get_found, prev=None, prev_found=None):
         """One round, queued once its counts are exchanged (nrg_group_partitioned_round)."""
@@ -298,6 +303,40 @@ class PartitionedGroup(ReplicaGroup):
         rc = self._lib.nrg_group_partitioned_flush(self._h)
         if rc:
             self._check(rc, "nrg_group_partitioned_flush")
+
+    def seek(self, keys, mode: int):
+        """nrg_group_skiplist_seek (a collective: every rank calls it with the same mode, its own
+        keys and any number of them): SkipMap::lower_bound / upper_bound over the whole partitioned
+        map for a 1-D int64 device tensor of keys (u64 bit patterns). Returns (out_keys, out_vals,
+        found) device tensors; synchronous (torch's current stream is drained first, so the keys
+        may have been produced on it)."""
+        keys = keys.contiguous()
+        n = keys.numel()
+        ok = torch.zeros(max(n, 1), dtype=torch.int64, device=keys.device)
+        ov = torch.zeros_like(ok)
+        found = torch.zeros(max(n, 1), dtype=torch.uint8, device=keys.device)
+        torch.cuda.current_stream(keys.device).synchronize()  # the buffers exist before the library writes them
+        q = L.Seek(_ptr(keys) if n else 0, n, _ptr(ok), _ptr(ov), _ptr(found))
+        rc = self._lib.nrg_group_skiplist_seek(self._h, C.byref(q), int(mode))
+        if rc:
+            self._check(rc, "nrg_group_skiplist_seek")
+        return ok[:n], ov[:n], found[:n]
+
+    def range_count(self, los, his):
+        """nrg_group_skiplist_range_count (a collective): the number of keys of the whole
+        partitioned map in each [lo, hi], both inclusive (0 where lo > hi), for two 1-D int64 device
+        tensors of equal length. Returns a device tensor; synchronous."""
+        los, his = los.contiguous(), his.contiguous()
+        if los.shape != his.shape:
+            raise ValueError("los and his differ in length")
+        n = los.numel()
+        out = torch.zeros(max(n, 1), dtype=torch.int64, device=los.device)
+        torch.cuda.current_stream(los.device).synchronize()  # the buffers exist before the library writes them
+        q = L.Count(_ptr(los) if n else 0, _ptr(his) if n else 0, n, _ptr(out))
+        rc = self._lib.nrg_group_skiplist_range_count(self._h, C.byref(q))
+        if rc:
+            self._check(rc, "nrg_group_skiplist_range_count")
+        return out[:n]
 
 
 class PartitionedHashMap:

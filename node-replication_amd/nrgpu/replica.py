@@ -666,6 +666,11 @@ class DeviceReplica:
         """SkipListWrapper::default: keys 0..n-1 -> k + off."""
         L.check(self._lib.nrg_skiplist_prefill_range(self._h, n, off), "skiplist_prefill_range")
 
+    def sl_prefill_partition(self, n: int, off: int, part: int, parts: int):
+        """SkipListWrapper::default restricted to partition `part` of `parts`: the keys k < n that
+        nrg_key_owner gives to it, values k + off (a member of a partitioned skip-list group)."""
+        L.check(self._lib.nrg_skiplist_prefill_partition(self._h, n, off, part, parts), "skiplist_prefill_partition")
+
     def sl_reserve(self, n_keys: int):
         """Room for `n_keys` keys in all; never shrinks (nrg_skiplist_reserve)."""
         self._reserve(self._lib.nrg_skiplist_reserve, L.NRG_DS_SKIPLIST, "sl_reserve", n_keys)
