@@ -631,7 +631,7 @@ int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_
  * (skiplist-mlnr, a cnr::Replica with several logs, benches/lockfree.rs:228-317, LogMapper::hash
  * :73-97): that is nrg_group_partitioned_round on a group of skip-list replicas, with
  * nrg_skiplist_prefill_partition and the group-wide ordered reads nrg_group_skiplist_seek /
- * nrg_group_skiplist_range_count (the cnr section below). Out of scope: there is no combiner
+ * nrg_group_skiplist_range_count / nrg_group_skiplist_scan (the cnr section below). Out of scope: there is no combiner
  * (nrg_combiner_open returns NRG_E_INVAL, as for the page table) and no removal of keys (the
  * reference's wrapper has none). Every call below returns NRG_E_INVAL on a context of another kind. */
 /* Replica::combine for one batch of Push(k, v) records (nr/src/replica.rs:544-595): Log::append of the
@@ -658,6 +658,26 @@ int nrg_skiplist_seek(nrg_ctx* ctx, const uint64_t* keys, uint64_t n, uint32_t m
                       uint64_t* out_vals, uint8_t* found);
 int nrg_skiplist_seek_async(nrg_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t mode, uint64_t* d_out_keys,
                             uint64_t* d_out_vals, uint8_t* d_found);
+/* SkipMap::range from a bound, the first `limit` entries, for a batch: range(k..).take(limit) or
+ * range(..=k).rev().take(limit), what a caller does with the SkipMap Replica::verify hands it
+ * (nr/src/replica.rs:443-467); YCSB's SCAN. Same rules as the Gets (after sync-to-tail, else
+ * NRG_E_NOT_SYNCED; n <= max_reads, else NRG_E_CAPACITY). mode is NRG_SEEK_*:
+ *   GE / GT: ascending keys >= k / > k.
+ *   LE / LT: DESCENDING keys <= k / < k.
+ * Entry j of query i goes to out_keys[i*limit + j] / out_vals[i*limit + j], for j < counts[i];
+ * counts[i] (u32) is the number of entries written, 0..limit: min(limit, the entries the map has in
+ * the direction). Slots j >= counts[i] are NOT written. With limit = 1 the entry and counts[i] are
+ * nrg_skiplist_seek's entry and found[i]. Paging: GT(the last key of a page) continues an ascending
+ * walk, LT a descending one. NRG_E_INVAL: mode > NRG_SEEK_LT, limit = 0 or limit >
+ * NRG_SCAN_MAX_LIMIT, or a NULL buffer with n > 0; n = 0 returns NRG_OK with nothing written. The
+ * host-pointer form stages its answers on the device and returns NRG_E_CAPACITY when n * limit >
+ * 2^24; it is synchronous, as the other host forms. One launch per batch ("sl_walk"): a group of
+ * lanes per query, DESIGN.md "Skip list replay". */
+#define NRG_SCAN_MAX_LIMIT 1024u
+int nrg_skiplist_scan(nrg_ctx* ctx, const uint64_t* keys, uint64_t n, uint32_t mode, uint32_t limit,
+                      uint64_t* out_keys, uint64_t* out_vals, uint32_t* counts);
+int nrg_skiplist_scan_async(nrg_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t mode, uint32_t limit,
+                            uint64_t* d_out_keys, uint64_t* d_out_vals, uint32_t* d_counts);
 /* SkipMap::range(lo..=hi) into host buffers, ascending, both bounds inclusive (so the key 2^64 - 1 is
  * reachable), after sync-to-tail. `*n` receives the count; if it exceeds `cap`, nothing is copied and
  * NRG_E_CAPACITY is returned, as the dumps do. lo > hi gives *n = 0. */
@@ -877,7 +897,8 @@ int nrg_group_partitioned_flush(nrg_group* g);
  * (n >= 2^32 counts as that). NRG_E_COMM / NRG_E_TIMEOUT as nrg_group_verify. The scratch belongs to
  * the group and grows on demand. There is no nrg_group_skiplist_len: the count words (word 0 of each
  * rank's triple) of nrg_group_verify add up to it. A partitioned range / dump is the caller's merge
- * of the members' nrg_skiplist_range results. */
+ * of the members' nrg_skiplist_range results, or, page by page and in key order over the whole map,
+ * nrg_group_skiplist_scan below. */
 typedef struct {
     const uint64_t* keys;
     uint64_t n;
@@ -893,6 +914,32 @@ typedef struct {
     uint64_t* counts;
 } nrg_count;
 int nrg_group_skiplist_range_count(nrg_group* g, const nrg_count* counts);
+/* nrg_skiplist_scan over the whole partitioned map (SkipMap::range from a bound, the first `limit`
+ * entries; nr/src/replica.rs:443-467): a collective shaped exactly like nrg_group_skiplist_seek, on
+ * the same data path. Every rank calls it with the same mode and the same limit, one entry per local
+ * member; n may differ, n = 0 on every rank returns NRG_OK after the exchange. Every member answers
+ * every rank's queries against its own partition (the kernel of nrg_skiplist_scan_async: up to
+ * `limit` candidates per query and partition), the candidate blocks (keys, values, u32 counts) go
+ * back to their askers, and one launch per member merges each query's G sorted lists: partitions
+ * hold disjoint key sets, so a candidate's place is its place in its own list plus the number of
+ * candidates of the other lists that precede it, and the first `limit` places are stored. The
+ * answers are nrg_skiplist_scan's over the whole map, slots j >= counts[i] not written. The
+ * candidate traffic is G times the answer's size, as the seek's: under hash partitioning every
+ * partition may hold the next key. A one-rank group's kernel answers straight into the caller's
+ * buffers. Paging with GT(the last key of a page) walks the whole map in key order.
+ * NRG_E_INVAL on every rank, before any data moves: not skip lists, mode > NRG_SEEK_LT, limit = 0 or
+ * limit > NRG_SCAN_MAX_LIMIT, ranks that passed different modes or limits, or any rank with n > 0 and
+ * a NULL buffer. NRG_E_CAPACITY on every rank, before any data moves: G * nmax * limit > 2^27
+ * entries, nmax the longest n of the ranks (the candidate scratch of one member: 2 GiB of keys and
+ * values at the bound). */
+typedef struct {
+    const uint64_t* keys;
+    uint64_t n;
+    uint64_t* out_keys;
+    uint64_t* out_vals;
+    uint32_t* counts;
+} nrg_scan;
+int nrg_group_skiplist_scan(nrg_group* g, const nrg_scan* scans, uint32_t mode, uint32_t limit);
 
 /* ---- device memory helpers (for callers without their own allocator) ----------------- */
 int nrg_dev_alloc(nrg_ctx* ctx, uint64_t bytes, void** d_ptr);
@@ -925,7 +972,9 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
  * "hm_grow_init" and "hm_rehash", a snapshot's table scan "hm_snapshot", a restore's two passes
  * "hm_restore_init" and "hm_restore"; the skip list's chunk sort is "sl_sort" (event records around its
  * launches), its chunk merge "sl_merge" and a compaction of the delta run into the base run
- * "sl_compact" (one launch each: the launches counted are the compactions). nrg_kernel_time reads (timed
+ * "sl_compact" (one launch each: the launches counted are the compactions); its batched reads are
+ * "sl_get", "sl_seek", "sl_range_count" and "sl_walk" (nrg_skiplist_scan: "sl_scan" is the chunk
+ * replay's prefix scan). nrg_kernel_time reads (timed
  * launches, their total milliseconds) after synchronising. */
 int nrg_kernel_timing(nrg_ctx* ctx, int enable);
 /* Restrict timing to one kernel name (NULL or "" = all). */

@@ -89,9 +89,10 @@ struct DBuf {
 enum PtBuf { PB_AVAL, PB_AFOUND, PB_APREV, PB_APREVF, PB_ST, PB_ALLST, PB_DESC, PB_N };
 enum PtPar { PP_POUT, PP_PPOS, PP_KOUT, PP_GPOS, PP_CNT, PP_ALLCNT, PP_N };
 enum PtRecv { PR_RPUT, PR_RKEY, PR_RVAL, PR_RFOUND, PR_RPREV, PR_RPREVF, PR_N };
-// Group-wide ordered reads of a partitioned skip-list group (nrg_group_skiplist_seek / _range_count):
-// the padded send copy of this member's queries, every rank's queries, this partition's candidates
-// for all of them (keys or counts, values, found) and the candidates that came back for its own.
+// Group-wide ordered reads of a partitioned skip-list group (nrg_group_skiplist_seek / _range_count /
+// _scan): the padded send copy of this member's queries, every rank's queries, this partition's
+// candidates for all of them (keys or counts, values, found; a scan: `limit` keys and values per
+// query and a u32 count) and the candidates that came back for its own.
 enum SkBuf { SK_SEND, SK_QALL, SK_CK, SK_CV, SK_CF, SK_BK, SK_BV, SK_BF, SK_N };
 constexpr int PT_DEPTH = 3;
 
@@ -300,6 +301,52 @@ __global__ __launch_bounds__(GRP_TPB) void grp_count_reduce_kernel(const uint64_
         uint64_t c = 0;
         for (uint32_t o = 0; o < G; o++) c += cc[(uint64_t)o * n + i];
         counts[i] = c;
+    }
+}
+
+// nrg_group_skiplist_scan's reduction: query i has one sorted candidate list per partition,
+// ck / cv[(o * n + i) * limit + t] for t < cc[o * n + i], ascending (GE, GT) or descending (LE, LT).
+// Partitions hold disjoint key sets, so keys never tie and a candidate's place in the merge of the G
+// lists is t plus, for every other list, the number of its candidates that precede the key (smaller
+// when ascending, greater when descending): a binary search per list. The places below `limit` are
+// stored; the places are a permutation, so no slot is written twice and none at or past the count.
+// A group of 2^lw lanes per query strides over the G * limit candidate slots.
+__global__ __launch_bounds__(GRP_TPB) void grp_scan_reduce_kernel(const uint64_t* __restrict__ ck,
+                                                                  const uint64_t* __restrict__ cv,
+                                                                  const uint32_t* __restrict__ cc, uint32_t G, uint64_t n,
+                                                                  uint32_t mode, uint32_t limit, uint32_t lw,
+                                                                  uint64_t* __restrict__ okeys,
+                                                                  uint64_t* __restrict__ ovals, uint32_t* __restrict__ counts) {
+    const uint64_t gt = blockIdx.x * (uint64_t)GRP_TPB + threadIdx.x;
+    const uint64_t i = gt >> lw;
+    if (i >= n) return;
+    const uint32_t W = 1u << lw, lane = (uint32_t)gt & (W - 1);
+    const bool up = mode == NRG_SEEK_GE || mode == NRG_SEEK_GT;
+    for (uint32_t s = lane; s < G * limit; s += W) {
+        const uint32_t o = s / limit, t = s - o * limit;
+        if (t >= cc[(uint64_t)o * n + i]) continue;
+        const uint64_t at = ((uint64_t)o * n + i) * limit + t;
+        const uint64_t k = ck[at];
+        uint32_t place = t;
+        for (uint32_t p = 0; p < G && place < limit; p++) {
+            if (p == o) continue;
+            const uint64_t* l = ck + ((uint64_t)p * n + i) * limit;
+            uint32_t lo = 0, hi = cc[(uint64_t)p * n + i];
+            while (lo < hi) {  // the candidates of list p that precede k
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (up ? l[mid] < k : l[mid] > k) lo = mid + 1; else hi = mid;
+            }
+            place += lo;
+        }
+        if (place < limit) {
+            okeys[i * limit + place] = k;
+            ovals[i * limit + place] = cv[at];
+        }
+    }
+    if (lane == 0) {
+        uint64_t c = 0;
+        for (uint32_t o = 0; o < G; o++) c += cc[(uint64_t)o * n + i];
+        counts[i] = c < limit ? (uint32_t)c : limit;
     }
 }
 
@@ -1310,12 +1357,14 @@ int nrg_group_verify(nrg_group* g, uint64_t* digests, int* identical) {
 // ---- group-wide ordered reads of a partitioned skip-list group ------------------------------------
 // Under hash partitioning no member alone can answer lower_bound or a range count: every member
 // answers every query against its own partition and the asker reduces the G candidates.
-//   1. {n, flags} of every rank (exchange_pairs): the flags carry a rank's bad arguments, its kind
-//      and the seek mode, so that every rank returns the same code before any data moves;
+//   1. {n, flags} of every rank (exchange_pairs): the flags carry a rank's bad arguments, its kind,
+//      the seek mode and a scan's limit, so that every rank returns the same code before any data
+//      moves (a scan also bounds G * nmax * limit, which every rank derives from the same lengths);
 //   2. the queries, padded to the longest n, all-gathered (a range count's los and his travel as one
 //      block: the los of every slot, then the his);
-//   3. the existing skip-list read kernels over all G * nmax of them (skiplist.hip);
-//   4. each asker's candidates back with send / recv in one group (a rank's own: a device copy);
+//   3. the skip-list read kernels over all G * nmax of them (skiplist.hip);
+//   4. each asker's candidates back with send / recv in one group (a rank's own: a device copy; a
+//      scan's block is lens * limit keys, as many values and lens counts);
 //   5. one reduction launch into the caller's buffers.
 // Everything after step 1 runs on the replica's stream, which the call then waits for. A one-rank
 // group (pt_ident) stops after step 1 and runs step 3 straight into the caller's buffers.
@@ -1325,17 +1374,22 @@ struct SkQuery {
     bool bad;
 };
 
-static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, uint32_t mode, uint64_t* nmax_out,
-                      std::vector<uint64_t>& lens, bool* ident) {
+constexpr uint64_t SK_SCAN_MAX_SLOTS = 1ull << 27;  // G * nmax * limit of a scan (include/nrgpu.h)
+
+static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, uint32_t mode, uint32_t limit, bool scan,
+                      uint64_t* nmax_out, std::vector<uint64_t>& lens, bool* ident) {
     const Rccl* R = g->R;
     const int nl = (int)g->m.size(), G = g->nranks;
     std::vector<uint64_t> a(nl), b(nl);
     for (int i = 0; i < nl; i++) {
         const nrg_ctx* c = g->m[i].ctx;
         const bool bad = q[i].bad || c->cfg.ds_kind != NRG_DS_SKIPLIST || c->ltail != c->tail ||
-                         (!count && mode > NRG_SEEK_LT) || q[i].n >= (1ull << 32);
+                         (!count && mode > NRG_SEEK_LT) || q[i].n >= (1ull << 32) ||
+                         (scan && (limit == 0 || limit > NRG_SCAN_MAX_LIMIT));
         a[i] = q[i].n;
-        b[i] = (bad ? 1 : 0) | ((uint64_t)(count ? 0 : mode) << 8) | ((uint64_t)c->cfg.ds_kind << 40);
+        // a scan's limit (1 .. 1024) in bits 16..26; a seek and a range count leave them zero
+        b[i] = (bad ? 1 : 0) | ((uint64_t)(count ? 0 : mode) << 8) | ((uint64_t)(scan ? limit & 0x7FFu : 0) << 16) |
+               ((uint64_t)c->cfg.ds_kind << 40);
     }
     RCHK(exchange_pairs(g, a, b));
     const uint64_t* H = g->m[0].h_glx;
@@ -1346,6 +1400,8 @@ static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, u
         nmax = std::max(nmax, lens[r]);
     }
     *nmax_out = nmax;
+    // a scan's candidate scratch: the bound follows from the exchanged lengths, the same on every rank
+    if (scan && (uint64_t)G * nmax * limit > SK_SCAN_MAX_SLOTS) return NRG_E_CAPACITY;
     if (nmax == 0) return NRG_OK;
     // One rank owns every key: its only candidate is the answer, so the read kernel answers straight
     // into the caller's buffers and nothing moves (as a one-rank group's rounds; NRG_KNOB_EXP bit 16
@@ -1357,19 +1413,23 @@ static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, u
         return NRG_OK;
     }
     const uint64_t words = count ? 2 : 1;  // u64 words per query
+    // per query and partition: `per` candidate keys and values, and one flag of `fb` bytes (a seek's
+    // found byte, a scan's u32 count)
+    const uint64_t per = scan ? limit : 1, fb = scan ? 4 : 1;
+    const ncclDataType_t ft = scan ? ncclUint32 : ncclUint8;
     for (int i = 0; i < nl; i++) {
         Member& m = g->m[i];
         nrg_ctx* c = m.ctx;
         RCHK(nrg::ctx_use_device(c));
         int r = grow_buf(m, m.sk[SK_SEND], words * nmax * 8);
         if (r == NRG_OK) r = grow_buf(m, m.sk[SK_QALL], (uint64_t)G * words * nmax * 8);
-        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_CK], (uint64_t)G * nmax * 8);
-        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BK], (uint64_t)G * q[i].n * 8);
+        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_CK], (uint64_t)G * nmax * per * 8);
+        if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BK], (uint64_t)G * q[i].n * per * 8);
         if (r == NRG_OK && !count) {
-            r = grow_buf(m, m.sk[SK_CV], (uint64_t)G * nmax * 8);
-            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_CF], (uint64_t)G * nmax);
-            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BV], (uint64_t)G * q[i].n * 8);
-            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BF], (uint64_t)G * q[i].n);
+            r = grow_buf(m, m.sk[SK_CV], (uint64_t)G * nmax * per * 8);
+            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_CF], (uint64_t)G * nmax * fb);
+            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BV], (uint64_t)G * q[i].n * per * 8);
+            if (r == NRG_OK) r = grow_buf(m, m.sk[SK_BF], (uint64_t)G * q[i].n * fb);
         }
         // (its peers are already inside the collectives below: the group cannot go on)
         if (r) return group_fail(g, r, "group-wide skip-list read: scratch allocation failed");
@@ -1399,11 +1459,12 @@ static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, u
         for (int s = 0; s < G; s++) {
             if (!lens[s]) continue;
             const uint64_t* blk = qall + (uint64_t)s * words * nmax;
-            const hipError_t he =
-                count ? nrg::sl_count_launch(c, blk, blk + nmax, lens[s], (uint64_t*)m.sk[SK_CK].p + (uint64_t)s * nmax)
-                      : nrg::sl_seek_launch(c, blk, lens[s], mode, (uint64_t*)m.sk[SK_CK].p + (uint64_t)s * nmax,
-                                            (uint64_t*)m.sk[SK_CV].p + (uint64_t)s * nmax,
-                                            (uint8_t*)m.sk[SK_CF].p + (uint64_t)s * nmax);
+            uint64_t* ck = (uint64_t*)m.sk[SK_CK].p + (uint64_t)s * nmax * per;
+            uint64_t* cv = (uint64_t*)m.sk[SK_CV].p + (uint64_t)s * nmax * per;
+            void* cf = at(m.sk[SK_CF].p, (uint64_t)s * nmax * fb);
+            const hipError_t he = count  ? nrg::sl_count_launch(c, blk, blk + nmax, lens[s], ck)
+                                  : scan ? nrg::sl_walk_launch(c, blk, lens[s], mode, limit, ck, cv, (uint32_t*)cf)
+                                         : nrg::sl_seek_launch(c, blk, lens[s], mode, ck, cv, (uint8_t*)cf);
             if (he != hipSuccess) return hip_rc(he);
         }
     }
@@ -1417,16 +1478,17 @@ static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, u
             for (int o = 0; o < G && res == ncclSuccess; o++) {
                 if (o == m.rank) continue;
                 if (lens[o]) {
-                    res = R->send(at(m.sk[SK_CK].p, o * nmax * 8), lens[o], ncclUint64, o, m.comm, s);
+                    res = R->send(at(m.sk[SK_CK].p, o * nmax * per * 8), lens[o] * per, ncclUint64, o, m.comm, s);
                     if (res == ncclSuccess && !count)
-                        res = R->send(at(m.sk[SK_CV].p, o * nmax * 8), lens[o], ncclUint64, o, m.comm, s);
+                        res = R->send(at(m.sk[SK_CV].p, o * nmax * per * 8), lens[o] * per, ncclUint64, o, m.comm, s);
                     if (res == ncclSuccess && !count)
-                        res = R->send(at(m.sk[SK_CF].p, o * nmax), lens[o], ncclUint8, o, m.comm, s);
+                        res = R->send(at(m.sk[SK_CF].p, o * nmax * fb), lens[o], ft, o, m.comm, s);
                 }
                 if (res == ncclSuccess && n) {
-                    res = R->recv(at(m.sk[SK_BK].p, o * n * 8), n, ncclUint64, o, m.comm, s);
-                    if (res == ncclSuccess && !count) res = R->recv(at(m.sk[SK_BV].p, o * n * 8), n, ncclUint64, o, m.comm, s);
-                    if (res == ncclSuccess && !count) res = R->recv(at(m.sk[SK_BF].p, o * n), n, ncclUint8, o, m.comm, s);
+                    res = R->recv(at(m.sk[SK_BK].p, o * n * per * 8), n * per, ncclUint64, o, m.comm, s);
+                    if (res == ncclSuccess && !count)
+                        res = R->recv(at(m.sk[SK_BV].p, o * n * per * 8), n * per, ncclUint64, o, m.comm, s);
+                    if (res == ncclSuccess && !count) res = R->recv(at(m.sk[SK_BF].p, o * n * fb), n, ft, o, m.comm, s);
                 }
             }
         }
@@ -1439,10 +1501,11 @@ static int sk_collect(nrg_group* g, const std::vector<SkQuery>& q, bool count, u
         if (!n) continue;
         RCHK(nrg::ctx_use_device(m.ctx));
         hipStream_t s = m.ctx->stream;
-        GCHK(hipMemcpyAsync(at(m.sk[SK_BK].p, r * n * 8), at(m.sk[SK_CK].p, r * nmax * 8), n * 8, hipMemcpyDeviceToDevice, s));
+        const uint64_t kb = n * per * 8;  // the block's keys (and values) in bytes
+        GCHK(hipMemcpyAsync(at(m.sk[SK_BK].p, r * kb), at(m.sk[SK_CK].p, r * nmax * per * 8), kb, hipMemcpyDeviceToDevice, s));
         if (count) continue;
-        GCHK(hipMemcpyAsync(at(m.sk[SK_BV].p, r * n * 8), at(m.sk[SK_CV].p, r * nmax * 8), n * 8, hipMemcpyDeviceToDevice, s));
-        GCHK(hipMemcpyAsync(at(m.sk[SK_BF].p, r * n), at(m.sk[SK_CF].p, r * nmax), n, hipMemcpyDeviceToDevice, s));
+        GCHK(hipMemcpyAsync(at(m.sk[SK_BV].p, r * kb), at(m.sk[SK_CV].p, r * nmax * per * 8), kb, hipMemcpyDeviceToDevice, s));
+        GCHK(hipMemcpyAsync(at(m.sk[SK_BF].p, r * n * fb), at(m.sk[SK_CF].p, r * nmax * fb), n * fb, hipMemcpyDeviceToDevice, s));
     }
     return NRG_OK;
 }
@@ -1473,7 +1536,7 @@ int nrg_group_skiplist_seek(nrg_group* g, const nrg_seek* seeks, uint32_t mode) 
     std::vector<uint64_t> lens(G);
     uint64_t nmax = 0;
     bool ident = false;
-    RCHK(sk_collect(g, q, false, mode, &nmax, lens, &ident));
+    RCHK(sk_collect(g, q, false, mode, 0, false, &nmax, lens, &ident));
     if (nmax == 0) return rc;
     if (ident) {
         const nrg_seek& x = seeks[0];
@@ -1508,7 +1571,7 @@ int nrg_group_skiplist_range_count(nrg_group* g, const nrg_count* counts) {
     std::vector<uint64_t> lens(G);
     uint64_t nmax = 0;
     bool ident = false;
-    RCHK(sk_collect(g, q, true, 0, &nmax, lens, &ident));
+    RCHK(sk_collect(g, q, true, 0, 0, false, &nmax, lens, &ident));
     if (nmax == 0) return rc;
     if (ident) {
         const nrg_count& x = counts[0];
@@ -1522,6 +1585,45 @@ int nrg_group_skiplist_range_count(nrg_group* g, const nrg_count* counts) {
         RCHK(nrg::ctx_use_device(m.ctx));
         grp_count_reduce_kernel<<<grp_grid(x.n), GRP_TPB, 0, m.ctx->stream>>>((const uint64_t*)m.sk[SK_BK].p, (uint32_t)G,
                                                                               x.n, x.counts);
+        GCHK(hipGetLastError());
+    }
+    return sk_finish(g, rc);
+}
+
+int nrg_group_skiplist_scan(nrg_group* g, const nrg_scan* scans, uint32_t mode, uint32_t limit) {
+    int r = pt_check(g);
+    if (r) return r;
+    if (!scans) return NRG_E_INVAL;
+    const int nl = (int)g->m.size(), G = g->nranks;
+    const int rc = nrg_group_sync(g);
+    if (g->broken) return g->broken;
+    std::vector<SkQuery> q(nl);
+    for (int i = 0; i < nl; i++) {
+        const nrg_scan& x = scans[i];
+        q[i] = SkQuery{x.keys, nullptr, x.n, x.n && (!x.keys || !x.out_keys || !x.out_vals || !x.counts)};
+    }
+    std::vector<uint64_t> lens(G);
+    uint64_t nmax = 0;
+    bool ident = false;
+    RCHK(sk_collect(g, q, false, mode, limit, true, &nmax, lens, &ident));
+    if (nmax == 0) return rc;
+    if (ident) {
+        const nrg_scan& x = scans[0];
+        const hipError_t he = nrg::sl_walk_launch(g->m[0].ctx, x.keys, x.n, mode, limit, x.out_keys, x.out_vals, x.counts);
+        return he != hipSuccess ? hip_rc(he) : sk_finish(g, rc);
+    }
+    // the lane group of a query: the power of two at or above its G * limit candidate slots, up to a wave
+    uint32_t lw = 0;
+    while (lw < 6 && (1ull << lw) < (uint64_t)G * limit) lw++;
+    const uint64_t per_wg = (uint64_t)GRP_TPB >> lw;
+    for (int i = 0; i < nl; i++) {
+        Member& m = g->m[i];
+        const nrg_scan& x = scans[i];
+        if (!x.n) continue;
+        RCHK(nrg::ctx_use_device(m.ctx));
+        grp_scan_reduce_kernel<<<(unsigned)((x.n + per_wg - 1) / per_wg), GRP_TPB, 0, m.ctx->stream>>>(
+            (const uint64_t*)m.sk[SK_BK].p, (const uint64_t*)m.sk[SK_BV].p, (const uint32_t*)m.sk[SK_BF].p, (uint32_t)G, x.n,
+            mode, limit, lw, x.out_keys, x.out_vals, x.counts);
         GCHK(hipGetLastError());
     }
     return sk_finish(g, rc);

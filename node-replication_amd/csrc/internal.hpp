@@ -453,10 +453,12 @@ void pt_close(nrg_ctx* c);  // partition.hip: free the partition scratch (the ha
 // hashmap.hip: the log's segment copy (nrg_log_append_segments_async)
 hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_stride, const u64* lens,
                          u64 dst_lo);
-// skiplist.hip: the seek and range-count kernels over n < 2^32 queries in the caller's device
+// skiplist.hip: the seek, range-count and scan kernels over n < 2^32 queries in the caller's device
 // buffers, on the context's stream (the replica group's group-wide reads; no max_reads bound)
 hipError_t sl_seek_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u64* d_okeys, u64* d_ovals, uint8_t* d_found);
 hipError_t sl_count_launch(nrg_ctx* c, const u64* d_los, const u64* d_his, u64 n, u64* d_counts);
+hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 limit, u64* d_okeys, u64* d_ovals,
+                          u32* d_counts);
 // queue.hip
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads (the combiner)
 }  // namespace nrg

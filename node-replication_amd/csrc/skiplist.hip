@@ -387,6 +387,46 @@ __global__ __launch_bounds__(SL_TPB) void sl_seek_kernel(const u64* bk, const u6
     found[i] = (hb || hd) ? 1 : 0;
 }
 
+// SkipMap::range from a bound, the first `limit` entries (nrg_skiplist_scan): a group of W = 2^lw
+// lanes per query, SL_TPB / W queries per workgroup. The answer is the head of the merge of two
+// windows of at most `limit` keys, one per run, found by the seek's searches (every lane of the group
+// runs them with the same addresses: the loads broadcast). Both directions are one ascending merge:
+//   GE / GT  windows base[ib, ib + la), delta[id, id + lb); output t is merge position t
+//   LE / LT  windows base[eb - la, eb), delta[ed - lb, ed) ending at the seek; output t is merge
+//            position la + lb - 1 - t (the first `limit` in descending order are the last `limit` of
+//            the merge, and those lie in the last `limit` keys of each run's stretch)
+// Lane j takes outputs j, j + W, ...: its merge-path split (sl_split: index bounds, no padding key)
+// says how many keys before its position come from base, and the smaller of the two keys there is
+// its entry. Consecutive lanes store consecutive slots. No lane waits for another.
+__global__ __launch_bounds__(SL_TPB) void sl_walk_kernel(const u64* bk, const u64* bv, const u64* dk, const u64* dv,
+                                                         const SlState* st, const u64* keys, u64 n, u32 mode, u32 limit,
+                                                         u32 lw, u64* okeys, u64* ovals, u32* counts) {
+    const u64 gt = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    const u64 q = gt >> lw;
+    if (q >= n) return;
+    const u32 W = 1u << lw, lane = (u32)gt & (W - 1);
+    const u64 k = keys[q], nb = st->nb, nd = st->nd;
+    const bool up = mode == NRG_SEEK_GE || mode == NRG_SEEK_GT;
+    const u64 ib = sl_seek_idx(bk, nb, k, mode), id = sl_seek_idx(dk, nd, k, mode);
+    // the keys of each run in the direction: from the seek index on, or up to and including it
+    const u64 rb = up ? nb - ib : (ib < nb ? ib + 1 : 0), rd = up ? nd - id : (id < nd ? id + 1 : 0);
+    const u32 la = rb < limit ? (u32)rb : limit, lb = rd < limit ? (u32)rd : limit;
+    const u32 total = la + lb < limit ? la + lb : limit;
+    const u64 a0 = up ? ib : rb - la, b0 = up ? id : rd - lb;
+    const u64 *ak = bk + a0, *ck = dk + b0;
+    u64* ok = okeys + q * limit;
+    u64* ov = ovals + q * limit;
+    for (u32 t = lane; t < total; t += W) {
+        const u32 p = up ? t : la + lb - 1 - t;
+        const u32 i = (u32)sl_split(ak, la, ck, lb, p), jx = p - i;  // (i < la or jx < lb: p < la + lb)
+        const u64 ka = i < la ? ak[i] : 0, kc = jx < lb ? ck[jx] : 0;
+        const bool ta = jx >= lb || (i < la && ka < kc);
+        ok[t] = ta ? ka : kc;
+        ov[t] = ta ? bv[a0 + i] : dv[b0 + jx];
+    }
+    if (lane == 0) counts[q] = total;
+}
+
 __global__ __launch_bounds__(SL_TPB) void sl_range_count_kernel(const u64* bk, const u64* dk, const SlState* st,
                                                                 const u64* los, const u64* his, u64 n, u64* counts) {
     const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
@@ -804,6 +844,31 @@ hipError_t sl_count_launch(nrg_ctx* c, const u64* d_los, const u64* d_his, u64 n
     return hipGetLastError();
 }
 
+// The lane group of a scan: the power of two at or above `limit`, up to a wave. A group covers
+// `limit` outputs in ceil(limit / width) steps; a narrower group for a small limit leaves no lane
+// without an output, and SL_TPB / width queries share a workgroup.
+static u32 sl_walk_log2_width(u32 limit) {
+    u32 lw = 0;
+    while (lw < 6 && (1u << lw) < limit) lw++;
+    return lw;
+}
+
+hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 limit, u64* d_okeys, u64* d_ovals,
+                          u32* d_counts) {
+    if (n == 0) return hipSuccess;
+    if (c->cfg.ds_kind != NRG_DS_SKIPLIST || mode > NRG_SEEK_LT || limit == 0 || limit > NRG_SCAN_MAX_LIMIT ||
+        n >= (1ull << 32))
+        return hipErrorInvalidValue;
+    SlHost& s = c->sl;
+    const u32 lw = sl_walk_log2_width(limit);
+    const u64 per_wg = (u64)SL_TPB >> lw;  // queries per workgroup
+    NRG_LAUNCH(c, "sl_walk", sl_walk_kernel, (unsigned)((n + per_wg - 1) / per_wg), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur],
+               (const u64*)s.d_dv[s.dcur], (const SlState*)s.d_state, d_keys, n, mode, limit, lw, d_okeys, d_ovals,
+               d_counts);
+    return hipGetLastError();
+}
+
 // SkipListWrapper::default restricted to a partition: of the keys k0 .. k0 + n - 1, the records of
 // those `part` owns (nrg_key_owner), compacted into `out` in no particular order (the keys are
 // distinct and the chunk sorts them); *cnt, zero before the launch, receives their number. One
@@ -902,6 +967,53 @@ int nrg_skiplist_seek(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint32_t mod
     HIPCHK(hipMemcpyAsync(found, g[2].p, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
     return check_err(c);
+}
+
+int nrg_skiplist_scan_async(nrg_ctx* c, const uint64_t* d_keys, uint64_t n, uint32_t mode, uint32_t limit,
+                            uint64_t* d_out_keys, uint64_t* d_out_vals, uint32_t* d_counts) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (mode > NRG_SEEK_LT || limit == 0 || limit > NRG_SCAN_MAX_LIMIT) return NRG_E_INVAL;
+    if (n == 0) return NRG_OK;
+    if (!d_keys || !d_out_keys || !d_out_vals || !d_counts) return NRG_E_INVAL;
+    return hip_fail(sl_walk_launch(c, d_keys, n, mode, limit, d_out_keys, d_out_vals, d_counts));
+}
+
+int nrg_skiplist_scan(nrg_ctx* c, const uint64_t* keys, uint64_t n, uint32_t mode, uint32_t limit, uint64_t* out_keys,
+                      uint64_t* out_vals, uint32_t* counts) {
+    int r = sl_read_check(c, n);
+    if (r) return r;
+    if (mode > NRG_SEEK_LT || limit == 0 || limit > NRG_SCAN_MAX_LIMIT) return NRG_E_INVAL;
+    if (n == 0) return NRG_OK;
+    if (!keys || !out_keys || !out_vals || !counts) return NRG_E_INVAL;
+    const uint64_t slots = n * limit;  // (n <= max_reads < 2^54: no wrap)
+    if (slots > (1ull << 24)) return NRG_E_CAPACITY;  // the staging's size
+    // the device writes only the slots below each count, and so does this call: the entries come
+    // back through host copies of the staging and only the written ones reach the caller's arrays
+    std::vector<uint64_t> hk, hv;
+    try {
+        hk.resize(slots);
+        hv.resize(slots);
+    } catch (const std::bad_alloc&) {
+        return NRG_E_NOMEM;
+    }
+    Staging* g = c->stg;
+    // keys, then out_keys behind them in one slot; values; counts
+    if ((r = staging(g[0], (n + slots) * 8)) || (r = staging(g[1], slots * 8)) || (r = staging(g[2], n * 4))) return r;
+    u64* dk = (u64*)g[0].p;
+    HIPCHK(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, c->stream));
+    if ((r = nrg_skiplist_scan_async(c, dk, n, mode, limit, dk + n, (u64*)g[1].p, (u32*)g[2].p))) return r;
+    HIPCHK(hipMemcpyAsync(hk.data(), dk + n, slots * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hv.data(), g[1].p, slots * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(counts, g[2].p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    if ((r = check_err(c))) return r;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t cnt = counts[i] < limit ? counts[i] : limit;
+        std::memcpy(out_keys + i * limit, hk.data() + i * limit, cnt * 8);
+        std::memcpy(out_vals + i * limit, hv.data() + i * limit, cnt * 8);
+    }
+    return NRG_OK;
 }
 
 int nrg_skiplist_range_count_async(nrg_ctx* c, const uint64_t* d_los, const uint64_t* d_his, uint64_t n,

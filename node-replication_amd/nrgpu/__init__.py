@@ -33,6 +33,7 @@ from .replica import (
     ReadWrite,
     Replica,
     ReplicaToken,
+    Scan,
     Seek,
     SkipList,
     SlPush,
@@ -46,7 +47,7 @@ __all__ = [
     "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
-    "Seek", "SkipList", "SlPush",
+    "Scan", "Seek", "SkipList", "SlPush",
 ]
 
 

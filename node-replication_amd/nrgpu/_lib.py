@@ -56,6 +56,7 @@ NRG_SEEK_GE = 0
 NRG_SEEK_GT = 1
 NRG_SEEK_LE = 2
 NRG_SEEK_LT = 3
+NRG_SCAN_MAX_LIMIT = 1024  # nrg_skiplist_scan: entries per query at most
 
 # nrg_vspace_op (32 B), nrg_vspace_resp (16 B) and nrg_vspace_leaf (16 B)
 VSPACE_OP_DTYPE = np.dtype([("vbase", "<u8"), ("pbase", "<u8"), ("len", "<u8"), ("op", "<u4"), ("rights", "<u4")])
@@ -143,6 +144,18 @@ class Seek(C.Structure):
     ]
 
 
+class Scan(C.Structure):
+    """nrg_scan: one group member's queries of nrg_group_skiplist_scan (device pointers on its GPU)."""
+
+    _fields_ = [
+        ("keys", C.c_void_p),
+        ("n", C.c_uint64),
+        ("out_keys", C.c_void_p),
+        ("out_vals", C.c_void_p),
+        ("counts", C.c_void_p),
+    ]
+
+
 class Count(C.Structure):
     """nrg_count: one group member's queries of nrg_group_skiplist_range_count."""
 
@@ -227,6 +240,8 @@ SIGNATURES = {
     "nrg_skiplist_get_async": (C.c_int, [vp, vp, u64, vp, vp]),
     "nrg_skiplist_seek": (C.c_int, [vp, vp, u64, u32, vp, vp, vp]),
     "nrg_skiplist_seek_async": (C.c_int, [vp, vp, u64, u32, vp, vp, vp]),
+    "nrg_skiplist_scan": (C.c_int, [vp, vp, u64, u32, u32, vp, vp, vp]),
+    "nrg_skiplist_scan_async": (C.c_int, [vp, vp, u64, u32, u32, vp, vp, vp]),
     "nrg_skiplist_range": (C.c_int, [vp, u64, u64, vp, vp, u64, u64p]),
     "nrg_skiplist_range_count": (C.c_int, [vp, vp, vp, u64, vp]),
     "nrg_skiplist_range_count_async": (C.c_int, [vp, vp, vp, u64, vp]),
@@ -280,6 +295,7 @@ SIGNATURES = {
     "nrg_group_partitioned_flush": (C.c_int, [vp]),
     "nrg_group_skiplist_seek": (C.c_int, [vp, C.POINTER(Seek), C.c_uint32]),
     "nrg_group_skiplist_range_count": (C.c_int, [vp, C.POINTER(Count)]),
+    "nrg_group_skiplist_scan": (C.c_int, [vp, C.POINTER(Scan), C.c_uint32, C.c_uint32]),
 }
 
 # include/nrgpu_testing.h (kernel unit-test hooks)

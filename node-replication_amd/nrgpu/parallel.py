@@ -322,6 +322,42 @@ class PartitionedGroup(ReplicaGroup):
             self._check(rc, "nrg_group_skiplist_seek")
         return ok[:n], ov[:n], found[:n]
 
+    def scan(self, keys, mode: int, limit: int):
+        """nrg_group_skiplist_scan (a collective: every rank calls it with the same mode and limit, its
+        own keys and any number of them): SkipMap::range from a bound, the first `limit` entries over
+        the whole partitioned map (GE / GT ascending, LE / LT descending), for a 1-D int64 device
+        tensor of keys (u64 bit patterns). Returns (out_keys [n, limit], out_vals [n, limit],
+        counts [n] int32) device tensors, row i valid in columns 0 .. counts[i] - 1; synchronous."""
+        keys = keys.contiguous()
+        n, limit = keys.numel(), int(limit)
+        ok = torch.zeros(max(n, 1) * max(limit, 1), dtype=torch.int64, device=keys.device)
+        ov = torch.zeros_like(ok)
+        cnt = torch.zeros(max(n, 1), dtype=torch.int32, device=keys.device)
+        torch.cuda.current_stream(keys.device).synchronize()  # the buffers exist before the library writes them
+        q = L.Scan(_ptr(keys) if n else 0, n, _ptr(ok), _ptr(ov), _ptr(cnt))
+        rc = self._lib.nrg_group_skiplist_scan(self._h, C.byref(q), int(mode), limit)
+        if rc:
+            self._check(rc, "nrg_group_skiplist_scan")
+        return ok[: n * limit].view(n, limit), ov[: n * limit].view(n, limit), cnt[:n]
+
+    def items(self, page: int = 1024):
+        """The whole partitioned map in ascending key order, as (key, value) pairs of Python ints
+        (u64): pages of `page` entries by scan, GE(0) first, then GT(the last key seen). The
+        library's partitioned dump. A generator over a collective: every rank iterates it in step,
+        with the same page, to its end."""
+        dev = torch.device("cuda", self.replica.device)
+        key, mode = 0, L.NRG_SEEK_GE
+        while True:
+            q = torch.tensor([key - (1 << 64) if key >= (1 << 63) else key], dtype=torch.int64, device=dev)
+            k, v, c = self.scan(q, mode, page)
+            m = int(c[0].item())
+            ks = k[0, :m].cpu().numpy().view("uint64").tolist()
+            vs = v[0, :m].cpu().numpy().view("uint64").tolist()
+            yield from zip(ks, vs)
+            if m < page:
+                return
+            key, mode = ks[-1], L.NRG_SEEK_GT
+
     def range_count(self, los, his):
         """nrg_group_skiplist_range_count (a collective): the number of keys of the whole
         partitioned map in each [lo, hi], both inclusive (0 where lo > hi), for two 1-D int64 device

@@ -617,6 +617,27 @@ class DeviceReplica:
                 "skiplist_seek")
         return ok[:n], ov[:n], found[:n]
 
+    def sl_scan(self, keys, mode: int, limit: int):
+        """SkipMap::range from a bound, the first `limit` entries, for a batch (mode: L.NRG_SEEK_GE / GT
+        ascending, LE / LT descending): (keys[n, limit], vals[n, limit], counts[n]); row i holds its
+        entries in columns 0 .. counts[i] - 1 and zeros behind them."""
+        keys = np.ascontiguousarray(np.asarray(keys, np.uint64))
+        n = len(keys)
+        rows = max(n, 1) * max(int(limit), 1)
+        ok = np.zeros(rows, np.uint64)
+        ov = np.zeros(rows, np.uint64)
+        cnt = np.zeros(max(n, 1), np.uint32)
+        L.check(self._lib.nrg_skiplist_scan(self._h, _ptr(keys), n, mode, limit, _ptr(ok), _ptr(ov), _ptr(cnt)),
+                "skiplist_scan")
+        return ok[: n * limit].reshape(n, limit), ov[: n * limit].reshape(n, limit), cnt[:n]
+
+    @_stream_ordered
+    def sl_scan_device(self, d_keys, n: int, mode: int, limit: int, d_out_keys, d_out_vals, d_counts):
+        """nrg_skiplist_scan_async: d_out_keys / d_out_vals hold n * limit u64, d_counts n u32 (int32
+        tensors); slots at or past a query's count are not written. Stream-ordered as sl_get_device."""
+        L.check(self._lib.nrg_skiplist_scan_async(self._h, _dptr(d_keys), n, mode, limit, _dptr(d_out_keys),
+                                                  _dptr(d_out_vals), _dptr(d_counts)), "skiplist_scan")
+
     def sl_range_count(self, los, his) -> np.ndarray:
         """The number of keys in each [lo, hi], both bounds inclusive."""
         los = np.ascontiguousarray(np.asarray(los, np.uint64))
@@ -798,6 +819,13 @@ class Seek:  # SkipMap::lower_bound / upper_bound; mode: L.NRG_SEEK_GE / GT / LE
 
 
 @dataclass(frozen=True)
+class Scan:  # SkipMap::range from a bound, .take(limit); mode: GE / GT ascending, LE / LT descending
+    key: int
+    mode: int
+    limit: int
+
+
+@dataclass(frozen=True)
 class WriteOnly:  # benches/synthetic.rs:33-39
     tid: int
     r1: int
@@ -936,7 +964,8 @@ class VSpace:
 
 class SkipList:
     """SkipListWrapper (benches/lockfree_partitioned.rs:86-118): an ordered map u64 -> u64. SlPush ->
-    the key (Ok(Some(key))); Get -> the value or None; Seek -> (key, value) or None."""
+    the key (Ok(Some(key))); Get -> the value or None; Seek -> (key, value) or None; Scan -> a list of
+    (key, value) in the scan's order."""
 
     kind = L.NRG_DS_SKIPLIST
     rec_dtype = PUT_DTYPE
@@ -965,6 +994,11 @@ class SkipList:
             k, v, f = dev.sl_seek(np.array([ops[i].key for i in idx], np.uint64), mode)
             for i, a, b, c in zip(idx, k, v, f):
                 out[i] = (int(a), int(b)) if c else None
+        for mode, limit in sorted({(o.mode, o.limit) for o in ops if isinstance(o, Scan)}):
+            idx = [i for i, o in enumerate(ops) if isinstance(o, Scan) and (o.mode, o.limit) == (mode, limit)]
+            k, v, c = dev.sl_scan(np.array([ops[i].key for i in idx], np.uint64), mode, limit)
+            for i, kr, vr, m in zip(idx, k, v, c):
+                out[i] = list(zip(kr[:m].tolist(), vr[:m].tolist()))
         return out
 
     @staticmethod
