@@ -30,6 +30,8 @@
  *   nrg_vspace_*                  VSpace Dispatch (x86-64 page table) benches/vspace.rs:177-381, :436-467, :499-526
  *   nrg_skiplist_*                SkipListWrapper Dispatch (SkipMap)  benches/lockfree.rs:73-97, :278-317,
  *                                                                     benches/lockfree_partitioned.rs:86-118
+ *   nrg_memfs_*                   NrMemFilesystem Dispatch (Write /   benches/memfs.rs:24-85, :112-121, :194-292
+ *                                 Read / GetAttr, all through the log)
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -82,6 +84,8 @@ extern "C" {
 #define NRG_DS_VSPACE 5u    /* four-level page table: Map/MapDevice, Identify  benches/vspace.rs:483-526 */
 #define NRG_DS_SKIPLIST 6u  /* ordered map u64 -> u64 (SkipMap): Push(k, v) / Get, seek, range
                                benches/lockfree.rs:73-97, benches/lockfree_partitioned.rs:86-118 */
+#define NRG_DS_MEMFS 7u     /* file store: Write / Read / GetAttr on files of fixed size, reads through
+                               the log   benches/memfs.rs:24-85, :194-292 */
 
 /* ---- log record layouts (one WriteOperation each) --------------------------------- */
 /* NrHashMap WriteOperation::Put(key, val)               benches/hashmap.rs:52-56;
@@ -149,6 +153,45 @@ typedef struct {
     uint64_t entry;
 } nrg_vspace_leaf;
 
+/* File store WriteOperation (OperationWr, benches/memfs.rs:24-85). In memfs.rs ReadOperation = ()
+ * and dispatch is unreachable!() (:194-201): Read is a WRITE operation, logged like Write, and its
+ * answer is the file as every earlier record of the log left it. A record carries at most 128 data
+ * bytes ([3; 128] in generate_fs_operations, :294-322). The reference shows the op set, the initial
+ * file, Written(len) and Data(bytes); everything else is defined here as POSIX pwrite / pread on
+ * files of fixed size (the file system behind memfs.rs, btfs, is not part of the reference checkout).
+ * A replica holds F files of B bytes, inodes NRG_MEMFS_FIRST_INO .. NRG_MEMFS_FIRST_INO + F - 1.
+ *   WRITE    offset + len <= B: bytes [offset, offset + len) take data; some = 1, n = len
+ *            (Written(len), :88-98); len = 0 is a valid no-op. Else nothing changes; some = 0,
+ *            n = NRG_MEMFS_EFBIG.
+ *   READ     some = 1, n = min(len, B - offset), or 0 where offset >= B; data[0, n) are the file's
+ *            bytes (Data(bytes)), data[n, 128) zero.
+ *   GETATTR  some = 1, n = B (Attr: the size); data zero.
+ * A record is checked in this order: len > 128 or an unknown op: some = 0, n = NRG_MEMFS_EINVAL,
+ * nothing changes and NRG_E_INVAL is latched once (the page table's rule for a record outside its
+ * domain); an ino outside the range: some = 0, n = NRG_MEMFS_ENOENT; then the Write's range. Every
+ * error response has data all zero.
+ * Out of scope: directories, names, inode creation and removal, rename; file growth and truncate
+ * (SetAttr; the size is fixed at open, all either benchmark exercises); benches/nrfs.rs's whole-file
+ * 4096-byte ops; the combiner, partitioned groups and growth (NRG_E_INVAL from their entry points). */
+#define NRG_MEMFS_WRITE 0u   /* OperationWr::Write{ino, offset, data[0..len)}  memfs.rs:66-72  */
+#define NRG_MEMFS_READ 1u    /* OperationWr::Read{ino, offset, size = len}      memfs.rs:73-78  */
+#define NRG_MEMFS_GETATTR 2u /* OperationWr::GetAttr{ino}: n = B                memfs.rs:27-29  */
+#define NRG_MEMFS_FIRST_INO 5u /* the ino of the benchmark's file                memfs.rs:117-119 */
+#define NRG_MEMFS_ENOENT 1u
+#define NRG_MEMFS_EFBIG 2u
+#define NRG_MEMFS_EINVAL 3u
+typedef struct {
+    uint64_t ino;
+    uint64_t offset;
+    uint32_t op;
+    uint32_t len;
+    uint8_t data[128];
+} nrg_memfs_op; /* 152 B */
+typedef struct {
+    uint64_t n;
+    uint8_t data[128];
+} nrg_memfs_resp; /* 136 B */
+
 /* Synthetic ReadOperation::ReadOnly(tid, rnd1, rnd2)     benches/synthetic.rs:28-31       */
 typedef struct {
     uint64_t tid;
@@ -165,7 +208,10 @@ typedef struct {
                                  tables of 4 KiB (default 18: 1 GiB; 2 .. 22, else nrg_open
                                  returns NRG_E_INVAL); skip list (reused again): the map holds
                                  up to 2^log2_slots keys at open (default 24: 512 MiB for the two
-                                 buffers of keys and values; 4 .. 28, else NRG_E_INVAL)        */
+                                 buffers of keys and values; 4 .. 28, else NRG_E_INVAL); file
+                                 store (reused again): log2 of a file's bytes B (default 12, the
+                                 4096-byte file of benches/memfs.rs:112-121; 7 .. 26, else
+                                 NRG_E_INVAL) */
     uint64_t log_bytes;       /* Log::new(bytes): ring entries = bytes/64 rounded as in the
                                  reference (min 2*GC_FROM_HEAD, power of two). 0 = 32 MiB   */
     uint64_t max_batch;       /* largest number of log records replayed per kernel pass;
@@ -207,7 +253,9 @@ typedef struct {
                                  struct's size changed, and nrg_config_default always zeroed it.) */
     uint64_t queue_capacity;  /* queue: maximum number of elements (default 2^24; 1 .. 2^32,
                                  else nrg_open returns NRG_E_INVAL; the queue's ring holds a
-                                 power of two >= queue_capacity + max_batch u64) */
+                                 power of two >= queue_capacity + max_batch u64); file store (the
+                                 field is reused): the number of files F (default 1; 1 .. 2^16
+                                 and F * B <= 2^29, else NRG_E_INVAL; its max_batch <= 2^20) */
 } nrg_config;
 
 /* Fill `cfg` with the defaults of the reference benches for `ds_kind`. */
@@ -271,6 +319,8 @@ int nrg_set_max_capacity(nrg_ctx* ctx, uint64_t max_items);
  *              4 KiB and 2 MiB leaves alike; inner entries contribute nothing
  *   skip list  (key, value), the hashmap's definition: a skip list and a hashmap that replayed the
  *              same Puts hold equal triples
+ *   file store (file index << 32 | word index, the word) for every aligned 8-byte little-endian
+ *              word of every file; count = F * B / 8
  * An empty structure gives {0, 0, 0}; the triple depends on the contents alone, not on the table's
  * size, the ring position or the order in which page tables were allocated. Two replicas that
  * replayed the same log hold equal triples; nrgpu/digest.py computes the triple from a host
@@ -309,6 +359,10 @@ int nrg_digest_async(nrg_ctx* ctx, uint64_t* d_out3);
  *              nrg_restore checks the order on the device (NRG_E_INVAL) before the digest
  *              comparison, and accepts items up to the capacity, or up to the growth bound
  *              (nrg_set_max_capacity), growing first; more is NRG_E_CAPACITY
+ *   file store items = F * B / 8 words: the files' bytes in inode order. nrg_restore takes an image
+ *              only into a context of the same F and B, NRG_E_INVAL otherwise: another total is
+ *              refused with nothing touched; an equal total cut into other files fails the digest
+ *              comparison (the items' keys carry the file) and leaves the files as at open
  * Two replicas with equal state need not produce byte-equal images: the hashmap's record order and
  * the page table's table numbering depend on how the state came about. Their digest words are
  * equal. Like the dumps and every direct call, none of these calls is allowed while a combiner is
@@ -466,8 +520,8 @@ int nrg_hashmap_digest(nrg_ctx* ctx, uint64_t out[3]);
 /* ---- Flat combining on the host ---------------------------------------------------------- */
 /* Replica's flat combiner for many client threads (nr/src/context.rs:88-194,
  * nr/src/replica.rs:345-356, 404-433, 483-497, 508-595), for the hashmap, the stack, the synthetic
- * structure and the queue (not the page table or the skip list: nrg_combiner_open on a vspace or
- * skip-list context returns NRG_E_INVAL):
+ * structure and the queue (not the page table, the skip list or the file store: nrg_combiner_open
+ * on a vspace, skip-list or memfs context returns NRG_E_INVAL):
  * each registered thread posts up to 32 ops (MAX_PENDING_OPS) per call into the open batch and
  * parks; the combiner's own thread seals the batch into ONE GPU round of `ctx` (its writes
  * appended and replayed in batch order, then its reads answered against the post-round state)
@@ -713,6 +767,35 @@ int nrg_skiplist_prefill_partition(nrg_ctx* ctx, uint64_t n, uint64_t val_offset
 int nrg_skiplist_reserve(nrg_ctx* ctx, uint64_t n_keys);
 /* The current capacity in keys: 2^config.log2_slots, or what growth made of it. */
 int nrg_skiplist_capacity(nrg_ctx* ctx, uint64_t* n_keys);
+
+/* ---- file store (kind NRG_DS_MEMFS; benches/memfs.rs) ---------------------------------------
+ * NrMemFilesystem (benches/memfs.rs:106-192) behind Dispatch (:194-292) with ReadOperation = (): every
+ * op, Read included, is a log record (nrg_memfs_op above), so the generic log calls carry the whole
+ * structure: nrg_log_append* / nrg_log_exec* with records of 152 B and responses of 136 B, and
+ * replicated group rounds (nrg_group_round_async). At nrg_open every byte of every file is 0x01
+ * (memfs.rs:118). Every call below returns NRG_E_INVAL on a context of another kind, and every
+ * other kind's calls return NRG_E_INVAL on this one; nrg_set_max_capacity, the partitioned rounds
+ * and nrg_combiner_open return NRG_E_INVAL. */
+/* Replica::combine for one batch (memfs.rs:194-292 dispatch_mut per record, in order): append + exec
+ * in one replay pass that also writes the log copy; responses of these n ops into d_resp / d_some
+ * (both NULL: none wanted). d_ops and d_resp 8-byte aligned. n <= config.max_batch. */
+int nrg_memfs_round_async(nrg_ctx* ctx, const nrg_memfs_op* d_ops, uint64_t n, uint32_t origin,
+                          nrg_memfs_resp* d_resp, uint8_t* d_some);
+/* NrMemFilesystem::default's memfs.write(ino, 0, 0, &[1; 4096], 0) (memfs.rs:112-121) with the
+ * caller's bytes: set the first `len` bytes of file `ino` directly, no log traffic, before any
+ * replay (replicas of one log must be given the same bytes). NRG_E_INVAL: an ino outside the range or
+ * len > B. Synchronous. */
+int nrg_memfs_init(nrg_ctx* ctx, uint64_t ino, const uint8_t* bytes, uint64_t len);
+/* pread in the style of Replica::verify (nr/src/replica.rs:443-467; the benchmark's own Reads are log
+ * records, memfs.rs:73-78): *n = min(len, B - offset) bytes of file `ino` from `offset` into buf (any
+ * len; 0 where offset >= B). NRG_E_NOT_SYNCED while ltail < tail; NRG_E_INVAL: an ino outside the
+ * range. Synchronous. */
+int nrg_memfs_read(nrg_ctx* ctx, uint64_t ino, uint64_t offset, uint64_t len, uint8_t* buf, uint64_t* n);
+/* Replica::verify's view of one file: *n = B, and its B bytes into buf when cap >= B
+ * (NRG_E_CAPACITY otherwise). What has been replayed so far; does not need ltail == tail. */
+int nrg_memfs_dump(nrg_ctx* ctx, uint64_t ino, uint8_t* buf, uint64_t cap, uint64_t* n);
+/* F and B of the context (either pointer may be NULL). */
+int nrg_memfs_geometry(nrg_ctx* ctx, uint64_t* files, uint64_t* file_bytes);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's
@@ -974,7 +1057,8 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
  * launches), its chunk merge "sl_merge" and a compaction of the delta run into the base run
  * "sl_compact" (one launch each: the launches counted are the compactions); its batched reads are
  * "sl_get", "sl_seek", "sl_range_count" and "sl_walk" (nrg_skiplist_scan: "sl_scan" is the chunk
- * replay's prefix scan). nrg_kernel_time reads (timed
+ * replay's prefix scan); the file store's chunk is "mf_expand", "mf_sort" (event records around the
+ * slot sort's launches) and "mf_lines". nrg_kernel_time reads (timed
  * launches, their total milliseconds) after synchronising. */
 int nrg_kernel_timing(nrg_ctx* ctx, int enable);
 /* Restrict timing to one kernel name (NULL or "" = all). */

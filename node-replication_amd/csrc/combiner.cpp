@@ -557,8 +557,8 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
     if (!ctx || !out || !max_threads || max_threads > 4096) return NRG_E_INVAL;
     const uint32_t kind = ctx->cfg.ds_kind;
     if (!nrg::ds_ops(kind)) return NRG_E_INVAL;
-    // the page table and the skip list have no combiner (include/nrgpu.h)
-    if (kind == NRG_DS_VSPACE || kind == NRG_DS_SKIPLIST) return NRG_E_INVAL;
+    // the page table, the skip list and the file store have no combiner (include/nrgpu.h)
+    if (kind == NRG_DS_VSPACE || kind == NRG_DS_SKIPLIST || kind == NRG_DS_MEMFS) return NRG_E_INVAL;
     const uint64_t cap = (uint64_t)max_threads * MAX_PENDING;
     if (cap > ctx->cfg.max_batch || (kind == NRG_DS_HASHMAP && cap > ctx->cfg.max_reads)) return NRG_E_CAPACITY;
     int r = nrg::ctx_use_device(ctx);

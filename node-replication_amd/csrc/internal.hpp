@@ -228,6 +228,17 @@ struct SlHost {  // skip list / ordered map (skiplist.hip): two sorted runs with
     uint64_t nd_ub = 0;
 };
 
+struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, contiguous in inode order
+    uint8_t* d_files = nullptr;
+    uint64_t files = 0;
+    uint32_t log2_b = 0;
+    uint32_t nlines = 0;    // F * B / 128: the 128-byte lines of the store; as a slot key, the sentinel
+    uint32_t key_bits = 0;  // ceil(log2(nlines + 1)): what the slot sort sorts by
+    // scratch of one chunk
+    uint32_t* d_keys = nullptr;  // [2 * max_batch] slot keys
+    uint64_t* d_desc = nullptr;  // [max_batch] record descriptors
+};
+
 struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*
     int32_t spin = -1;    // -1 = default
     uint32_t depth = 0;   // 0 = default
@@ -247,7 +258,7 @@ struct GenHost {  // workload generators (workload.hip): zeta(zipf_n, zipf_theta
 
 // What the runtime knows about a data structure: one table per kind, defined beside the
 // structure's launchers and entry points (hashmap.hip, stack.hip, synthetic.hip, queue.hip,
-// vspace.hip, skiplist.hip).
+// vspace.hip, skiplist.hip, memfs.hip).
 struct DsOps {
     uint32_t rec_bytes;   // one log record
     uint32_t resp_bytes;  // one write response
@@ -292,7 +303,7 @@ struct DsOps {
     // The stream has been drained. nullptr: the kind has no such bound.
     int (*set_max)(nrg_ctx* c, u64 max_items);
 };
-const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops(), *sl_ops();
+const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops(), *sl_ops(), *mf_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
 
 }  // namespace nrg
@@ -327,6 +338,7 @@ struct nrg_ctx {
     nrg::QuHost qu;
     nrg::VsHost vs;
     nrg::SlHost sl;
+    nrg::MfHost mf;
     nrg::CombKnobs comb;
     nrg::PtHost pt;
     nrg::GenHost gen;

@@ -1,0 +1,426 @@
+// memfs.hip — replicated file store (memfs Write / Read / GetAttr) replay on gfx950
+// (benches/memfs.rs:24-85 OperationWr, :88-98 Response, :112-121 the initial file, :194-292 Dispatch,
+// :294-322 generate_fs_operations).
+//
+// What this structure has and the six others have not: READS GO THROUGH THE LOG. In memfs.rs
+// ReadOperation = () and dispatch is unreachable!() (:194-201); OperationWr::Read is a write
+// operation (:73-78, :267-282), so a Read's answer is the file's bytes as every earlier record of the
+// log left them. And the payload is bytes (data: &[u8], [3; 128] in generate_fs_operations), not a u64.
+//
+// What the reference pins: the op set (Write / Read / GetAttr of :24-85), the initial file (ino 5,
+// 4096 bytes of 1, :112-121), the responses Written(len) and Data(bytes) (:88-98), and that both ops
+// are logged. The file system itself (btfs) is a crates.io dependency and is not part of the
+// reference checkout, so everything else is DEFINED HERE as POSIX pwrite / pread on files of fixed
+// size: a replica holds F files of B bytes, inodes NRG_MEMFS_FIRST_INO .. +F-1, every byte 0x01 at
+// open; a Write past the end fails whole (EFBIG), a Read is clipped at the end. A record is checked
+// in this order: len > 128 or an unknown op (EINVAL, latched), then the ino (ENOENT), then the
+// Write's range (EFBIG).
+// Out of scope: directories, names, inode creation and removal, rename.
+// Out of scope: file growth and truncate (SetAttr): the size is fixed at open.
+// Out of scope: benches/nrfs.rs's whole-file 4096-byte ops (a record carries at most 128 bytes).
+// Out of scope: the combiner, partitioned groups and growth (nrg_set_max_capacity).
+//
+// A file is cut into aligned 128-byte LINES; an op of at most 128 bytes touches at most two. Lines
+// are independent of each other; within a line log order decides. A chunk of n records, in stream
+// order, no workgroup waiting on another except inside the radix sort's look-back:
+//   mf_expand  one lane per record: the log copy of a fused round, the validation, the whole
+//              response inside the response window (n, some, 128 data bytes zeroed; 8-byte coalesced
+//              stores), a descriptor per record {first byte, count, is-write}, and exactly two slots
+//              2i and 2i + 1 keyed by the global line id (file * B/128 + line) of each line the op
+//              touches; the sentinel F*B/128, which sorts last and is no line, for an unused slot, a
+//              failed op, an op of no bytes and GetAttr. ERR_INVAL latched for len > 128 / unknown op.
+//   sort       radix_sort.hip sort_pairs of the 2n (key, slot) pairs, stable: slot order is log order,
+//              so every line's run is in log order. Timed as "mf_sort".
+//   mf_lines   one wave per line of the store. The wave finds its run by a lower-bound search of the
+//              sorted keys (uniform: scalar loads); an empty run exits without touching the line. Else
+//              lane l holds bytes 2l and 2l + 1 of the line and the wave walks the run in batches of 64
+//              slots: lane j fetches slot t0 + j and its record's descriptor, the batch loop broadcasts
+//              each descriptor (v_readlane: the values are uniform, so are the branches on them) and
+//              applies it: a Write's covered lanes take data[x - offset], a Read's covered lanes store
+//              their byte to resp[i].data[x - offset] (records inside the response window only). The
+//              only serial dependence is the line register: the data loads of MF_AHEAD ops are issued
+//              before the first of them is applied, and the next batch's slots and descriptors are
+//              fetched before this batch is walked. The line is stored back once. No LDS, no atomics,
+//              no spinning.
+// Known limit: memfs.rs's own shape, one 4 KiB file, is 32 lines and so 32 waves (DESIGN.md "File
+// store replay"; the next step is a segmented reduce-then-scan over tiles of a line's run).
+#include <cstring>
+
+#include "internal.hpp"
+
+namespace nrg {
+
+constexpr int MF_TPB = 256;
+constexpr u32 MF_LINE = 128;      // bytes of a line; also the most bytes a record carries
+constexpr u32 MF_REC_WORDS = 19;  // nrg_memfs_op in u64 words
+constexpr u32 MF_RESP_WORDS = 17; // nrg_memfs_resp in u64 words
+constexpr u32 MF_AHEAD = 8;       // ops whose data loads are in flight together (divides 64)
+constexpr u32 MF_LOG2_MIN = 7, MF_LOG2_MAX = 26, MF_LOG2_DEFAULT = 12;
+constexpr u64 MF_MAX_FILES = 1ull << 16, MF_MAX_BYTES = 1ull << 29, MF_MAX_BATCH = 1ull << 20;
+static_assert(sizeof(nrg_memfs_op) == MF_REC_WORDS * 8 && sizeof(nrg_memfs_resp) == MF_RESP_WORDS * 8, "ABI");
+static_assert(64 % MF_AHEAD == 0, "a batch of 64 slots is walked in whole groups");
+
+struct MfJob {
+    const u64* src;  // the batch of a fused round in u64 words, or nullptr: read from the ring
+    u64* ring;       // the log ring; written when src is given
+    u64 ring_mask;
+    u64 lo, n;       // the chunk: log indices [lo, lo + n)
+    u64 rlo, rhi;    // response window
+    u64* resp;       // responses in u64 words (nullptr: none wanted)
+    uint8_t* some;
+    DevCtl* ctl;
+    uint8_t* files;  // F files of B bytes, inode order
+    u32 log2_b, nfiles;
+    u32 nlines;      // F * B / 128: the sentinel key
+    u32* keys;       // [2n] slot keys
+    u64* desc;       // [n] first byte in the store | count << 32 | is-write << 48; 0: touches nothing
+};
+
+__device__ __forceinline__ const u64* mf_rec(const MfJob& j, u64 i) {
+    return j.src ? j.src + i * MF_REC_WORDS : j.ring + ((j.lo + i) & j.ring_mask) * MF_REC_WORDS;
+}
+
+__global__ __launch_bounds__(MF_TPB) void mf_expand_kernel(MfJob j) {
+    __shared__ u64 s_n[MF_TPB];
+    const u32 t = threadIdx.x;
+    const u64 base = (u64)blockIdx.x * MF_TPB;
+    const u32 cnt = j.n - base < MF_TPB ? (u32)(j.n - base) : MF_TPB;
+    bool inval = false;
+    if (t < cnt) {
+        const u64 i = base + t;
+        const u64* r = mf_rec(j, i);
+        const u64 ino = r[0], off = r[1], w2 = r[2];
+        const u32 op = (u32)w2, len = (u32)(w2 >> 32);
+        const u64 B = 1ull << j.log2_b;
+        u64 nresp;
+        u32 cover = 0;
+        uint8_t sm = 0;
+        bool wr = false;
+        if (op > NRG_MEMFS_GETATTR || len > MF_LINE) {
+            nresp = NRG_MEMFS_EINVAL;
+            inval = true;
+        } else if (ino < NRG_MEMFS_FIRST_INO || ino - NRG_MEMFS_FIRST_INO >= j.nfiles) {
+            nresp = NRG_MEMFS_ENOENT;
+        } else if (op == NRG_MEMFS_GETATTR) {  // Attr(FileAttr): the size
+            nresp = B, sm = 1;
+        } else if (op == NRG_MEMFS_WRITE) {
+            if (off <= B && len <= B - off) nresp = len, cover = len, sm = 1, wr = true;  // Written(len)
+            else nresp = NRG_MEMFS_EFBIG;
+        } else {  // Data(bytes), clipped at the end of the file
+            nresp = off >= B ? 0 : (len < B - off ? len : B - off);
+            cover = (u32)nresp, sm = 1;
+        }
+        u32 k0 = j.nlines, k1 = j.nlines;
+        u64 d = 0;
+        if (cover) {
+            const u64 start = ((ino - NRG_MEMFS_FIRST_INO) << j.log2_b) + off;  // < 2^29
+            k0 = (u32)(start >> 7);
+            const u32 kl = (u32)((start + cover - 1) >> 7);
+            if (kl != k0) k1 = kl;
+            d = start | ((u64)cover << 32) | ((u64)(wr ? 1 : 0) << 48);
+        }
+        *(uint2*)(j.keys + 2 * i) = make_uint2(k0, k1);
+        j.desc[i] = d;
+        s_n[t] = nresp;
+        const u64 g = j.lo + i;
+        if (j.resp && g >= j.rlo && g < j.rhi) j.some[g - j.rlo] = sm;
+    }
+    if (__any(inval) && (t & 63) == 0) atomicOr(&j.ctl->err, ERR_INVAL);
+    __syncthreads();
+    if (j.src)  // Log::append of a fused round
+        for (u32 w = t; w < cnt * MF_REC_WORDS; w += MF_TPB) {
+            const u32 rec = w / MF_REC_WORDS, q = w - rec * MF_REC_WORDS;
+            j.ring[((j.lo + base + rec) & j.ring_mask) * MF_REC_WORDS + q] = j.src[(base + rec) * MF_REC_WORDS + q];
+        }
+    if (j.resp)
+        for (u32 w = t; w < cnt * MF_RESP_WORDS; w += MF_TPB) {
+            const u32 rec = w / MF_RESP_WORDS, q = w - rec * MF_RESP_WORDS;
+            const u64 g = j.lo + base + rec;
+            if (g >= j.rlo && g < j.rhi) j.resp[(g - j.rlo) * MF_RESP_WORDS + q] = q ? 0 : s_n[rec];
+        }
+}
+
+// One wave per line. sk / sv: the m = 2n sorted (key, slot) pairs.
+__global__ __launch_bounds__(MF_TPB) void mf_lines_kernel(MfJob j, const u32* __restrict__ sk,
+                                                          const u32* __restrict__ sv, u32 m) {
+    const u32 lane = threadIdx.x & 63;
+    const u32 X = __builtin_amdgcn_readfirstlane(blockIdx.x * (MF_TPB / 64) + (threadIdx.x >> 6));
+    if (X >= j.nlines) return;
+    u32 lo = 0, hi = m;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (sk[mid] < X) lo = mid + 1; else hi = mid;
+    }
+    const u32 r0 = lo;
+    if (r0 >= m || sk[r0] != X) return;  // no op of the chunk touches the line
+    lo = r0 + 1, hi = m;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (sk[mid] <= X) lo = mid + 1; else hi = mid;
+    }
+    const u32 r1 = lo;
+    unsigned short* lp = (unsigned short*)(j.files + (u64)X * MF_LINE) + lane;
+    const u32 w = *lp;
+    u32 b0 = w & 0xFF, b1 = w >> 8;
+    const u32 gx0 = X * MF_LINE + 2 * lane;  // this lane's first byte in the store
+    uint8_t* const rbytes = (uint8_t*)j.resp;
+    u32 myrec = 0;
+    u64 mydesc = 0;
+    if (r0 + lane < r1) {
+        myrec = sv[r0 + lane] >> 1;
+        mydesc = j.desc[myrec];
+    }
+    for (u32 t0 = r0; t0 < r1; t0 += 64) {
+        const u32 cnt = r1 - t0 < 64 ? r1 - t0 : 64;
+        u32 nrec = 0;  // the next batch, fetched before this one is walked
+        u64 ndesc = 0;
+        if (t0 + 64 + lane < r1) {
+            nrec = sv[t0 + 64 + lane] >> 1;
+            ndesc = j.desc[nrec];
+        }
+        const u32 dlo = (u32)mydesc, dhi = (u32)(mydesc >> 32);  // (lanes at or past cnt hold 0: no bytes)
+        for (u32 k = 0; k < cnt; k += MF_AHEAD) {
+            u32 rec[MF_AHEAD], rel[MF_AHEAD], cn[MF_AHEAD], d0[MF_AHEAD], d1[MF_AHEAD];
+            bool wr[MF_AHEAD];
+#pragma unroll
+            for (u32 u = 0; u < MF_AHEAD; u++) {
+                const u32 st = __builtin_amdgcn_readlane(dlo, k + u), h = __builtin_amdgcn_readlane(dhi, k + u);
+                rec[u] = __builtin_amdgcn_readlane(myrec, k + u);
+                cn[u] = h & 0xFFFF;
+                wr[u] = (h >> 16) != 0;
+                rel[u] = gx0 - st;  // byte 0's offset into the op (wraps where the op starts later)
+                d0[u] = d1[u] = 0;
+                if (wr[u]) {
+                    const uint8_t* p = (const uint8_t*)(mf_rec(j, rec[u]) + 3);
+                    if (rel[u] < cn[u]) d0[u] = p[rel[u]];
+                    if (rel[u] + 1 < cn[u]) d1[u] = p[rel[u] + 1];
+                }
+            }
+#pragma unroll
+            for (u32 u = 0; u < MF_AHEAD; u++) {
+                const bool c0 = rel[u] < cn[u], c1 = rel[u] + 1 < cn[u];
+                if (wr[u]) {
+                    b0 = c0 ? d0[u] : b0;
+                    b1 = c1 ? d1[u] : b1;
+                } else if (cn[u]) {
+                    const u64 g = j.lo + rec[u];
+                    if (rbytes && g >= j.rlo && g < j.rhi) {
+                        uint8_t* o = rbytes + (g - j.rlo) * sizeof(nrg_memfs_resp) + 8;
+                        if (c0) o[rel[u]] = (uint8_t)b0;
+                        if (c1) o[rel[u] + 1] = (uint8_t)b1;
+                    }
+                }
+            }
+        }
+        myrec = nrec, mydesc = ndesc;
+    }
+    *lp = (unsigned short)(b0 | (b1 << 8));
+}
+
+// every byte of every file 0x01 (benches/memfs.rs:118), 8 bytes per lane
+__global__ __launch_bounds__(DG_TPB) void mf_fill_kernel(u64* words, u64 n) {
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB)
+        words[i] = 0x0101010101010101ull;
+}
+
+// ---- host side -------------------------------------------------------------------------------------
+static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                                  uint8_t* d_some) {
+    if (n == 0) return hipSuccess;
+    MfHost& s = c->mf;
+    MfJob j{};
+    j.src = (const u64*)src;
+    j.ring = (u64*)c->d_ring;
+    j.ring_mask = c->log_size - 1;
+    j.lo = lo;
+    j.n = n;
+    const bool want = d_resp != nullptr && d_some != nullptr && resp_lo < resp_hi && resp_lo < lo + n && resp_hi > lo;
+    j.rlo = want ? resp_lo : 0;
+    j.rhi = want ? resp_hi : 0;
+    j.resp = want ? (u64*)d_resp : nullptr;
+    j.some = want ? d_some : nullptr;
+    j.ctl = c->d_ctl;
+    j.files = s.d_files;
+    j.log2_b = s.log2_b;
+    j.nfiles = (u32)s.files;
+    j.nlines = s.nlines;
+    j.keys = s.d_keys;
+    j.desc = s.d_desc;
+    NRG_LAUNCH(c, "mf_expand", mf_expand_kernel, (unsigned)((n + MF_TPB - 1) / MF_TPB), MF_TPB, 0, c->stream, j);
+    u32 *sk = nullptr, *sv = nullptr;
+    timer_begin(c, "mf_sort");
+    const hipError_t e = sort_pairs(c->sort, s.d_keys, nullptr, 2 * n, (int)s.key_bits, c->stream, &sk, &sv);
+    timer_end(c, "mf_sort");
+    if (e != hipSuccess) return e;
+    const u32 per = MF_TPB / 64;
+    NRG_LAUNCH(c, "mf_lines", mf_lines_kernel, (s.nlines + per - 1) / per, MF_TPB, 0, c->stream, j, (const u32*)sk,
+               (const u32*)sv, (u32)(2 * n));
+    return hipGetLastError();
+}
+
+static hipError_t mf_fill(nrg_ctx* c) {
+    const u64 words = c->mf.files * (1ull << c->mf.log2_b) / 8;
+    mf_fill_kernel<<<copy_grid(words), DG_TPB, 0, c->stream>>>((u64*)c->mf.d_files, words);
+    return hipGetLastError();
+}
+
+static int mf_open(nrg_ctx* c) {
+    const nrg_config& cf = c->cfg;
+    MfHost& s = c->mf;
+    // log2_slots: log2 of a file's bytes; queue_capacity: the number of files (include/nrgpu.h)
+    if (cf.log2_slots < MF_LOG2_MIN || cf.log2_slots > MF_LOG2_MAX || cf.queue_capacity < 1 ||
+        cf.queue_capacity > MF_MAX_FILES || (cf.queue_capacity << cf.log2_slots) > MF_MAX_BYTES ||
+        cf.max_batch > MF_MAX_BATCH)
+        return NRG_E_INVAL;
+    s.log2_b = cf.log2_slots;
+    s.files = cf.queue_capacity;
+    s.nlines = (u32)((s.files << s.log2_b) / MF_LINE);
+    s.key_bits = 1;  // ceil(log2(nlines + 1)): the sentinel is a key too
+    while ((1ull << s.key_bits) <= s.nlines) s.key_bits++;
+    HIPCHK(hipMalloc(&s.d_files, s.files << s.log2_b));
+    HIPCHK(hipMalloc(&s.d_keys, 2 * cf.max_batch * sizeof(u32)));
+    HIPCHK(hipMalloc(&s.d_desc, cf.max_batch * sizeof(u64)));
+    if (sort_alloc(c->sort, 2 * cf.max_batch) != NRG_OK) return NRG_E_NOMEM;
+    HIPCHK(mf_fill(c));
+    c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
+    return NRG_OK;
+}
+
+static void mf_close(nrg_ctx* c) {
+    MfHost& s = c->mf;
+    void* ptrs[] = {s.d_files, s.d_keys, s.d_desc};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+}
+
+static hipError_t mf_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
+
+static void mf_defaults(nrg_config* cfg) {
+    cfg->log2_slots = MF_LOG2_DEFAULT;  // one 4096-byte file (benches/memfs.rs:112-121)
+    cfg->queue_capacity = 1;
+}
+
+// nrg_digest: items are the aligned 8-byte words of every file, (file << 32 | word index, the word)
+__global__ __launch_bounds__(DG_TPB) void mf_digest_kernel(const u64* words, u64 n, u32 log2_wpf, u64* out3) {
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 h = dg_item(((i >> log2_wpf) << 32) | (i & ((1ull << log2_wpf) - 1)), words[i]);
+        c++;
+        sm += h;
+        x ^= h;
+    }
+    dg_commit(c, sm, x, out3);
+}
+
+static u64 mf_words(const nrg_ctx* c) { return (c->mf.files << c->mf.log2_b) / 8; }
+
+static hipError_t mf_digest(nrg_ctx* c, u64* d_out3) {
+    hipError_t e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream);
+    if (e != hipSuccess) return e;
+    NRG_LAUNCH(c, "mf_digest", mf_digest_kernel, dg_grid(mf_words(c)), DG_TPB, 0, c->stream, (const u64*)c->mf.d_files,
+               mf_words(c), c->mf.log2_b - 3, d_out3);
+    return hipGetLastError();
+}
+
+static int mf_items(nrg_ctx* c, u64* n) {
+    *n = mf_words(c);
+    return NRG_OK;
+}
+
+// The snapshot payload: the files' bytes in inode order (items: their 8-byte words).
+__global__ __launch_bounds__(DG_TPB) void mf_snapshot_kernel(const u64* words, u64 n, u64* buf, u64 cap, u64 log_idx,
+                                                             DevCtl* ctl) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_MEMFS, n, n * 8, log_idx, ctl);
+    if (snap_bytes(n * 8) > cap) return;
+    u64* out = buf + SNAP_HDR / 8;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) out[i] = words[i];
+}
+
+static hipError_t mf_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
+    NRG_LAUNCH(c, "mf_snapshot", mf_snapshot_kernel, copy_grid(mf_words(c)), DG_TPB, 0, c->stream,
+               (const u64*)c->mf.d_files, mf_words(c), (u64*)d_buf, cap, log_idx, c->d_ctl);
+    return hipGetLastError();
+}
+
+// An image goes only into a context of the same geometry. The header carries the item count alone:
+// another total is refused by check_only with nothing touched; the same total cut into other files
+// has another digest (the items' keys carry the file), which nrg_restore's comparison refuses.
+static int mf_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
+    if (check_only) return items == mf_words(c) ? NRG_OK : NRG_E_INVAL;
+    if (!d_payload) return hip_fail(mf_fill(c));
+    return hip_fail(hipMemcpyAsync(c->mf.d_files, d_payload, mf_words(c) * 8, hipMemcpyDeviceToDevice, c->stream));
+}
+
+const DsOps* mf_ops() {
+    static const DsOps ops = {sizeof(nrg_memfs_op), sizeof(nrg_memfs_resp), mf_open, mf_close, mf_flush,
+                              mf_replay_chunk, floor_ltail, nullptr, nullptr, mf_defaults, mf_digest,
+                              mf_items, mf_snapshot, mf_restore, nullptr};
+    return &ops;
+}
+
+}  // namespace nrg
+
+// ---- the file store's entry points (include/nrgpu.h) ------------------------------------------------
+using namespace nrg;
+
+// the file of `ino` in a memfs context's store; nullptr for an ino outside the range
+static uint8_t* mf_file(nrg_ctx* c, uint64_t ino) {
+    if (ino < NRG_MEMFS_FIRST_INO || ino - NRG_MEMFS_FIRST_INO >= c->mf.files) return nullptr;
+    return c->mf.d_files + ((ino - NRG_MEMFS_FIRST_INO) << c->mf.log2_b);
+}
+
+extern "C" {
+
+int nrg_memfs_round_async(nrg_ctx* c, const nrg_memfs_op* d_ops, uint64_t n, uint32_t origin, nrg_memfs_resp* d_resp,
+                          uint8_t* d_some) {
+    if (((uintptr_t)d_ops | (uintptr_t)d_resp) & 7) return NRG_E_INVAL;  // (records and responses move as u64 words)
+    return round_common(c, NRG_DS_MEMFS, d_ops, n, origin, d_resp, d_some);
+}
+
+int nrg_memfs_init(nrg_ctx* c, uint64_t ino, const uint8_t* bytes, uint64_t len) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    uint8_t* f = mf_file(c, ino);
+    if (!f || len > (1ull << c->mf.log2_b) || (len && !bytes)) return NRG_E_INVAL;
+    if (len) HIPCHK(hipMemcpyAsync(f, bytes, len, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_memfs_read(nrg_ctx* c, uint64_t ino, uint64_t offset, uint64_t len, uint8_t* buf, uint64_t* n) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    const uint8_t* f = mf_file(c, ino);
+    if (!f) return NRG_E_INVAL;
+    const uint64_t B = 1ull << c->mf.log2_b;
+    *n = offset >= B ? 0 : (len < B - offset ? len : B - offset);
+    if (*n && !buf) return NRG_E_INVAL;
+    if (*n) HIPCHK(hipMemcpyAsync(buf, f + offset, *n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_memfs_dump(nrg_ctx* c, uint64_t ino, uint8_t* buf, uint64_t cap, uint64_t* n) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (!n) return NRG_E_INVAL;
+    const uint8_t* f = mf_file(c, ino);
+    if (!f) return NRG_E_INVAL;
+    *n = 1ull << c->mf.log2_b;
+    if (*n > cap) return NRG_E_CAPACITY;
+    if (!buf) return NRG_E_INVAL;
+    HIPCHK(hipMemcpyAsync(buf, f, *n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_memfs_geometry(nrg_ctx* c, uint64_t* files, uint64_t* file_bytes) {
+    if (!c || c->cfg.ds_kind != NRG_DS_MEMFS) return NRG_E_INVAL;
+    if (files) *files = c->mf.files;
+    if (file_bytes) *file_bytes = 1ull << c->mf.log2_b;
+    return NRG_OK;
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 // ring with the reference's head/tail/ctail/ltail bookkeeping (the nrg_log_* calls), dispatch of
 // the replay pipelines through each structure's ops table, timing and the device-memory helpers.
 // Everything about one data structure, its entry points included, is in its own file
-// (hashmap.hip, stack.hip, synthetic.hip, queue.hip, vspace.hip, skiplist.hip); nothing here names a kind
+// (hashmap.hip, stack.hip, synthetic.hip, queue.hip, vspace.hip, skiplist.hip, memfs.hip); nothing here names a kind
 // except ds_ops and one open-time check.
 //
 // Log bookkeeping follows nr/src/log.rs: Log::new sizing (:179-242), append with GC when
@@ -157,7 +157,7 @@ int staging(Staging& st, uint64_t bytes) {
     return NRG_OK;
 }
 
-// Replica::combine for one batch of a stack, synthetic, queue, page-table or skip-list replica: one replay pass that
+// Replica::combine for one batch of a stack, synthetic, queue, page-table, skip-list or file-store replica: one replay pass that
 // also writes the log copy (Log::append + Log::exec of this batch)
 int round_common(nrg_ctx* c, uint32_t kind, const void* d_ops, uint64_t n, uint32_t origin, void* d_resp,
                  uint8_t* d_some) {
@@ -184,6 +184,7 @@ const DsOps* ds_ops(uint32_t kind) {
         case NRG_DS_QUEUE: return qu_ops();
         case NRG_DS_VSPACE: return vs_ops();
         case NRG_DS_SKIPLIST: return sl_ops();
+        case NRG_DS_MEMFS: return mf_ops();
         default: return nullptr;
     }
 }

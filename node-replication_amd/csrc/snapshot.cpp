@@ -25,6 +25,7 @@ uint64_t item_bytes(uint32_t kind) {
         case NRG_DS_QUEUE: return sizeof(uint64_t);
         case NRG_DS_VSPACE: return 4096;
         case NRG_DS_SKIPLIST: return sizeof(nrg_put);
+        case NRG_DS_MEMFS: return sizeof(uint64_t);  // an aligned 8-byte word of a file
         default: return 0;
     }
 }

@@ -7,6 +7,8 @@ from . import _lib, digest, snapshot
 from ._lib import NrgError, load
 from .combiner import Combiner
 from .replica import (
+    MEMFS_OP_DTYPE,
+    MEMFS_RESP_DTYPE,
     PUT_DTYPE,
     QUEUE_OP_DTYPE,
     STACK_OP_DTYPE,
@@ -23,6 +25,10 @@ from .replica import (
     Log,
     Map,
     MapDevice,
+    MemFs,
+    MfGetAttr,
+    MfRead,
+    MfWrite,
     NrHashMap,
     Peek,
     Pop,
@@ -48,6 +54,7 @@ __all__ = [
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
     "Scan", "Seek", "SkipList", "SlPush",
+    "MEMFS_OP_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfRead", "MfWrite",
 ]
 
 

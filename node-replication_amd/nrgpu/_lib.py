@@ -42,6 +42,7 @@ NRG_DS_SYNTHETIC = 3
 NRG_DS_QUEUE = 4
 NRG_DS_VSPACE = 5
 NRG_DS_SKIPLIST = 6
+NRG_DS_MEMFS = 7
 
 NRG_STACK_POP = 0
 NRG_STACK_PUSH = 1
@@ -57,11 +58,23 @@ NRG_SEEK_GT = 1
 NRG_SEEK_LE = 2
 NRG_SEEK_LT = 3
 NRG_SCAN_MAX_LIMIT = 1024  # nrg_skiplist_scan: entries per query at most
+# file store ops (benches/memfs.rs:24-85 OperationWr), its first inode (:117-119) and error answers
+NRG_MEMFS_WRITE = 0
+NRG_MEMFS_READ = 1
+NRG_MEMFS_GETATTR = 2
+NRG_MEMFS_FIRST_INO = 5
+NRG_MEMFS_ENOENT = 1
+NRG_MEMFS_EFBIG = 2
+NRG_MEMFS_EINVAL = 3
+NRG_MEMFS_MAX_DATA = 128  # data bytes a record carries at most
 
 # nrg_vspace_op (32 B), nrg_vspace_resp (16 B) and nrg_vspace_leaf (16 B)
 VSPACE_OP_DTYPE = np.dtype([("vbase", "<u8"), ("pbase", "<u8"), ("len", "<u8"), ("op", "<u4"), ("rights", "<u4")])
 VSPACE_RESP_DTYPE = np.dtype([("a", "<u8"), ("b", "<u8")])
 VSPACE_LEAF_DTYPE = np.dtype([("vaddr", "<u8"), ("entry", "<u8")])
+# nrg_memfs_op (152 B) and nrg_memfs_resp (136 B)
+MEMFS_OP_DTYPE = np.dtype([("ino", "<u8"), ("offset", "<u8"), ("op", "<u4"), ("len", "<u4"), ("data", "u1", (128,))])
+MEMFS_RESP_DTYPE = np.dtype([("n", "<u8"), ("data", "u1", (128,))])
 
 
 class NrgError(RuntimeError):
@@ -252,6 +265,11 @@ SIGNATURES = {
     "nrg_skiplist_prefill_partition": (C.c_int, [vp, u64, u64, C.c_uint32, C.c_uint32]),
     "nrg_skiplist_reserve": (C.c_int, [vp, u64]),
     "nrg_skiplist_capacity": (C.c_int, [vp, u64p]),
+    "nrg_memfs_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
+    "nrg_memfs_init": (C.c_int, [vp, u64, vp, u64]),
+    "nrg_memfs_read": (C.c_int, [vp, u64, u64, u64, vp, u64p]),
+    "nrg_memfs_dump": (C.c_int, [vp, u64, vp, u64, u64p]),
+    "nrg_memfs_geometry": (C.c_int, [vp, u64p, u64p]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

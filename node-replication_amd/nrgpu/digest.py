@@ -9,6 +9,7 @@ h = mix64(k ^ mix64(v)), the sum wrapping in u64. What (k, v) is depends on the 
   synthetic  (word index, word)
   vspace     (the leaf's first virtual address, the leaf entry)
   skip list  (key, value), the hashmap's definition
+  file store (file index << 32 | word index, the word) over every aligned 8-byte word of every file
 
 With these a caller that holds a host snapshot or a CPU model of the structure computes the triple
 the device must report, without the device's state ever leaving the GPU.
@@ -72,6 +73,19 @@ def vspace(vaddrs, entries):
 def skiplist(keys, vals):
     """An ordered map's (key, value) pairs, in any order: the hashmap's triple for the same pairs."""
     return pairs(keys, vals)
+
+
+def memfs(files):
+    """A file store's files in inode order, each a bytes-like of the same length B (a multiple of
+    8): the items are the aligned little-endian 8-byte words, keyed (file index << 32 | word index)."""
+    keys, vals = [], []
+    for f, data in enumerate(files):
+        w = np.frombuffer(bytes(data), dtype="<u8")
+        keys.append((_U64(f) << _U64(32)) | np.arange(w.size, dtype=_U64))
+        vals.append(w)
+    if not keys:
+        return (0, 0, 0)
+    return pairs(np.concatenate(keys), np.concatenate(vals))
 
 
 def combine(triples):

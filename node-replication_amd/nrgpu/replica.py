@@ -7,10 +7,10 @@
                                    sync / verify, with flat combining of the registered
                                    threads' pending ops into one log append + one replay
   ReplicaToken    nr::ReplicaToken
-  NrHashMap, Stack, AbstractDataStructure, Queue, VSpace, SkipList — the Dispatch plug-ins of the
-                                   reference (benches/hashmap.rs, benches/stack.rs,
+  NrHashMap, Stack, AbstractDataStructure, Queue, VSpace, SkipList, MemFs — the Dispatch plug-ins
+                                   of the reference (benches/hashmap.rs, benches/stack.rs,
                                    benches/synthetic.rs, benches/lockfree_comparisons.rs,
-                                   benches/vspace.rs, benches/lockfree_partitioned.rs)
+                                   benches/vspace.rs, benches/lockfree_partitioned.rs, benches/memfs.rs)
 """
 from __future__ import annotations
 
@@ -33,6 +33,8 @@ SYNTH_RD_DTYPE = np.dtype([("tid", "<u8"), ("r1", "<u8"), ("r2", "<u8")])
 VSPACE_OP_DTYPE = L.VSPACE_OP_DTYPE
 VSPACE_RESP_DTYPE = L.VSPACE_RESP_DTYPE
 VSPACE_LEAF_DTYPE = L.VSPACE_LEAF_DTYPE
+MEMFS_OP_DTYPE = L.MEMFS_OP_DTYPE
+MEMFS_RESP_DTYPE = L.MEMFS_RESP_DTYPE
 
 # nr/src/log.rs:22,26,36 ; nr/src/context.rs:12 ; nr/src/replica.rs:56
 DEFAULT_LOG_BYTES = 32 * 1024 * 1024
@@ -209,6 +211,8 @@ class DeviceReplica:
             return np.uint32
         if self.kind == L.NRG_DS_VSPACE:
             return VSPACE_RESP_DTYPE  # (a, b): Ok((a, b)), or Err(at = a) where some = 0
+        if self.kind == L.NRG_DS_MEMFS:
+            return MEMFS_RESP_DTYPE  # (n, data[128]): Written(n) / Data(data[:n]) / the size, or the error n
         # hashmap previous values, synthetic sums, queue pushed / popped values
         return np.uint64
 
@@ -268,6 +272,15 @@ class DeviceReplica:
         Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
         L.check(self._lib.nrg_skiplist_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
                 "skiplist_round")
+
+    @_stream_ordered
+    def mf_round(self, d_ops, n: int, origin: int, d_resp=None, d_some=None):
+        """Replica::combine for one file-store batch of Write / Read / GetAttr records (152 B each) on
+        device buffers: append + exec, the log copy written by the replay (nrg_memfs_round_async);
+        responses (136 B {n, data[128]} each) for these ops into d_resp / d_some.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_memfs_round_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some)),
+                "memfs_round")
 
     def log_reset(self):
         L.check(self._lib.nrg_log_reset(self._h))
@@ -700,6 +713,33 @@ class DeviceReplica:
         """The keys the map has room for (nrg_skiplist_capacity)."""
         return self._capacity(self._lib.nrg_skiplist_capacity, L.NRG_DS_SKIPLIST, "sl_capacity")
 
+    # -- file store ----------------------------------------------------------------
+    def mf_geometry(self):
+        """(F, B): the number of files and a file's bytes (nrg_memfs_geometry)."""
+        f, b = C.c_uint64(), C.c_uint64()
+        L.check(self._lib.nrg_memfs_geometry(self._h, C.byref(f), C.byref(b)), "memfs_geometry")
+        return f.value, b.value
+
+    def mf_init(self, ino: int, data):
+        """Set the first len(data) bytes of file `ino` directly, before any replay (nrg_memfs_init)."""
+        b = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
+        L.check(self._lib.nrg_memfs_init(self._h, ino, _ptr(b) if b.size else None, b.size), "memfs_init")
+
+    def mf_read(self, ino: int, offset: int, size: int) -> bytes:
+        """pread of a synced replica (nrg_memfs_read): up to `size` bytes of file `ino` from `offset`."""
+        out = np.zeros(max(size, 1), np.uint8)
+        n = C.c_uint64()
+        L.check(self._lib.nrg_memfs_read(self._h, ino, offset, size, _ptr(out), C.byref(n)), "memfs_read")
+        return out[: n.value].tobytes()
+
+    def mf_dump(self, ino: int) -> bytes:
+        """The whole file `ino`: Replica::verify's view (nrg_memfs_dump)."""
+        _, b = self.mf_geometry()
+        out = np.zeros(b, np.uint8)
+        n = C.c_uint64()
+        L.check(self._lib.nrg_memfs_dump(self._h, ino, _ptr(out), b, C.byref(n)), "memfs_dump")
+        return out[: n.value].tobytes()
+
     # -- synthetic -----------------------------------------------------------------
     def sy_read(self, ops: np.ndarray) -> np.ndarray:
         ops = np.ascontiguousarray(ops, SYNTH_RD_DTYPE)
@@ -823,6 +863,25 @@ class Scan:  # SkipMap::range from a bound, .take(limit); mode: GE / GT ascendin
     key: int
     mode: int
     limit: int
+
+
+@dataclass(frozen=True)
+class MfWrite:  # benches/memfs.rs:66-72 OperationWr::Write{ino, offset, data}; at most 128 bytes
+    ino: int
+    offset: int
+    data: bytes
+
+
+@dataclass(frozen=True)
+class MfRead:  # benches/memfs.rs:73-78 OperationWr::Read{ino, offset, size}: a write operation, logged
+    ino: int
+    offset: int
+    size: int
+
+
+@dataclass(frozen=True)
+class MfGetAttr:  # benches/memfs.rs:27-29 OperationWr::GetAttr{ino}
+    ino: int
 
 
 @dataclass(frozen=True)
@@ -1005,6 +1064,66 @@ class SkipList:
     def snapshot(dev: DeviceReplica):
         k, v = dev.sl_dump()
         return list(zip(k.tolist(), v.tolist()))
+
+
+class MemFs:
+    """NrMemFilesystem (benches/memfs.rs:106-292): files of fixed size, every op a log record
+    (ReadOperation = (), :194-201). MfWrite -> ("written", len); MfRead -> ("data", bytes), the file
+    as every earlier record of the log left it; MfGetAttr -> ("attr", size); any of them ->
+    ("err", code) with code L.NRG_MEMFS_ENOENT / EFBIG / EINVAL. An MfWrite of more than 128 bytes is
+    encoded with its length and no data: the replay answers EINVAL."""
+
+    kind = L.NRG_DS_MEMFS
+    rec_dtype = MEMFS_OP_DTYPE
+    _TAGS = {MfWrite: "written", MfRead: "data", MfGetAttr: "attr"}
+
+    @staticmethod
+    def encode(ops) -> np.ndarray:
+        r = np.zeros(len(ops), MEMFS_OP_DTYPE)
+        for i, o in enumerate(ops):
+            if not isinstance(o, (MfWrite, MfRead, MfGetAttr)):
+                raise TypeError(f"not a file-store op: {o!r}")
+            r["ino"][i] = o.ino
+            if isinstance(o, MfWrite):
+                r["offset"][i], r["op"][i], r["len"][i] = o.offset, L.NRG_MEMFS_WRITE, len(o.data)
+                if len(o.data) <= L.NRG_MEMFS_MAX_DATA:
+                    r["data"][i, : len(o.data)] = np.frombuffer(bytes(o.data), np.uint8)
+            elif isinstance(o, MfRead):
+                r["offset"][i], r["op"][i], r["len"][i] = o.offset, L.NRG_MEMFS_READ, o.size
+            else:
+                r["op"][i] = L.NRG_MEMFS_GETATTR
+        return r
+
+    @staticmethod
+    def decode_ops(ops, resp, some) -> list:
+        """The responses of `ops` (a response does not say which op it answers; Replica._combine
+        passes the batch)."""
+        out = []
+        for o, r, s in zip(ops, resp, some):
+            n = int(r["n"])
+            if not s:
+                out.append(("err", n))
+            elif isinstance(o, MfRead):
+                out.append(("data", r["data"][:n].tobytes()))
+            else:
+                out.append((MemFs._TAGS[type(o)], n))
+        return out
+
+    @staticmethod
+    def decode(resp, some) -> list:
+        """Without the ops: (n, the 128 data bytes) where some, ("err", code) otherwise."""
+        return [(int(r["n"]), r["data"].tobytes()) if s else ("err", int(r["n"])) for r, s in zip(resp, some)]
+
+    @staticmethod
+    def read_batch(dev: DeviceReplica, ops) -> list:
+        if ops:
+            raise TypeError("the file store has no read operations (ReadOperation = ()): MfRead is an execute_mut op")
+        return []
+
+    @staticmethod
+    def snapshot(dev: DeviceReplica):
+        files, _ = dev.mf_geometry()
+        return [dev.mf_dump(L.NRG_MEMFS_FIRST_INO + f) for f in range(files)]
 
 
 class AbstractDataStructure:
@@ -1243,7 +1362,9 @@ class Replica:
             if batch:
                 first = self.log.append(self.ds.encode(batch), self.idx)
                 resp, some = self.dev.log_exec(first, first + len(batch))
-                out = self.ds.decode(resp, some)
+                # a plug-in whose responses need their ops to be read (MemFs) decodes with the batch
+                with_ops = getattr(self.ds, "decode_ops", None)
+                out = with_ops(batch, resp, some) if with_ops else self.ds.decode(resp, some)
                 s = 0
                 for t, n in order:
                     self._resp[t].extend(out[s:s + n])

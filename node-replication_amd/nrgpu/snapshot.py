@@ -13,7 +13,8 @@ little-endian u64 words
 and the payload: hashmap `items` {key, value} records in any order; stack `items` u32, bottom
 first; queue `items` u64, front first; synthetic synth_n u64 words; vspace the `items` allocated
 pool tables of 512 u64, inner entries as stored (table_index * 4096 | flags); skip list `items`
-{key, value} records in strictly ascending key order.
+{key, value} records in strictly ascending key order; file store `items` = F * B / 8 u64 words, the
+files' bytes in inode order.
 
 unpack() reads an image of any kind; pack() builds one for the four flat kinds from a host model,
 its digest words from nrgpu.digest, so that a model can seed a GPU replica (DeviceReplica.restore).
@@ -35,7 +36,7 @@ HEADER_BYTES = 64
 Info = namedtuple("Info", "ds_kind version items bytes log_idx digest")
 
 _ITEM_BYTES = {L.NRG_DS_HASHMAP: 16, L.NRG_DS_STACK: 4, L.NRG_DS_SYNTHETIC: 8, L.NRG_DS_QUEUE: 8,
-               L.NRG_DS_VSPACE: 4096, L.NRG_DS_SKIPLIST: 16}
+               L.NRG_DS_VSPACE: 4096, L.NRG_DS_SKIPLIST: 16, L.NRG_DS_MEMFS: 8}
 _ADDR = 0x000FFFFFFFFFF000  # x86 ADDRESS_MASK: bits 12..51
 
 
@@ -75,7 +76,8 @@ def header(buf) -> Info:
 def unpack(buf):
     """(info, state) of an image: hashmap (keys, vals) u64 arrays in the image's order; stack a u32
     array, bottom first; queue a u64 array, front first; synthetic the u64 words; vspace the pool
-    tables, a u64 array [items, 512] (leaves() walks it)."""
+    tables, a u64 array [items, 512] (leaves() walks it); file store the files' bytes in inode order
+    as one u8 array (the image does not carry the geometry: reshape it to [F, B])."""
     info = header(buf)
     b = as_u8(buf)
     pay = b[HEADER_BYTES:HEADER_BYTES + info.items * _ITEM_BYTES[info.ds_kind]]
@@ -87,6 +89,8 @@ def unpack(buf):
         return info, pay.view("<u4").copy()
     if k == L.NRG_DS_VSPACE:
         return info, pay.view("<u8").reshape(-1, 512).copy()
+    if k == L.NRG_DS_MEMFS:
+        return info, pay.copy()
     return info, pay.view("<u8").copy()  # queue, synthetic
 
 
@@ -117,7 +121,8 @@ def leaves(tables) -> np.ndarray:
 def pack(kind: int, state, log_idx: int) -> np.ndarray:
     """The image (u8 array) of a host model's state after replaying [0, log_idx): hashmap a
     (keys, vals) pair or a dict; stack the elements, bottom first; queue the elements, front first;
-    synthetic the words; skip list as the hashmap (the records are written in ascending key order).
+    synthetic the words; skip list as the hashmap (the records are written in ascending key order);
+    file store the files in inode order, each a bytes-like of the same length.
     The digest words are nrgpu.digest's."""
     if kind in (L.NRG_DS_HASHMAP, L.NRG_DS_SKIPLIST):
         if isinstance(state, dict):
@@ -142,6 +147,12 @@ def pack(kind: int, state, log_idx: int) -> np.ndarray:
         v = np.asarray(state, dtype=np.uint64).reshape(-1)
         pay, items = v.astype("<u8").view(np.uint8), v.size
         dg = _digest.queue(v) if kind == L.NRG_DS_QUEUE else _digest.synthetic(v)
+    elif kind == L.NRG_DS_MEMFS:
+        files = [bytes(f) for f in state]
+        if not files or len({len(f) for f in files}) != 1 or len(files[0]) % 8:
+            raise ValueError("files of one length, a multiple of 8")
+        pay = np.frombuffer(b"".join(files), np.uint8)
+        items, dg = pay.size // 8, _digest.memfs(files)
     else:
         raise ValueError(f"pack: kind {kind} has no flat state")
     nbytes = image_bytes(kind, items)
