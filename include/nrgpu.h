@@ -32,6 +32,8 @@
  *                                                                     benches/lockfree_partitioned.rs:86-118
  *   nrg_memfs_*                   NrMemFilesystem Dispatch (Write /   benches/memfs.rs:24-85, :112-121, :194-292
  *                                 Read / GetAttr, all through the log)
+ *   nrg_memfs_pread*              Replica::execute -> read_only of    nr/src/replica.rs:404-410, :483-497;
+ *                                 OpRd::FileRead, any length          benches/nrfs.rs:16-18, :88-101
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -796,6 +798,29 @@ int nrg_memfs_read(nrg_ctx* ctx, uint64_t ino, uint64_t offset, uint64_t len, ui
 int nrg_memfs_dump(nrg_ctx* ctx, uint64_t ino, uint8_t* buf, uint64_t cap, uint64_t* n);
 /* F and B of the context (either pointer may be NULL). */
 int nrg_memfs_geometry(nrg_ctx* ctx, uint64_t* files, uint64_t* file_bytes);
+/* Replica::execute -> read_only (nr/src/replica.rs:404-410, :483-497) for a batch of reads: the
+ * read-only file op of benches/nrfs.rs:16-18, :88-101 (OpRd::FileRead, a true ReadOperation that
+ * copies the whole 4096-byte file), here POSIX pread of any length. Nothing is logged and nothing is
+ * latched; the replica is not changed (digest and dumps are the same before and after). The reads
+ * see everything already enqueued on the context's stream, as nrg_hashmap_get_async's do.
+ *   request i: an ino outside the range gives some[i] = 0 and count_i = 0; otherwise some[i] = 1 and
+ *              count_i = offset >= B ? 0 : min(len, B - offset). Any len up to 2^64 - 1 is legal.
+ *   offs:      n + 1 words, offs[0] = 0, offs[i + 1] = offs[i] + count_i.
+ *   data:      packed in request order: request i's bytes are data[offs[i] .. offs[i + 1]). A byte
+ *              whose packed position is at or past cap is not written, and no byte of data at or
+ *              past min(cap, offs[n]) is ever written.
+ * The async call cannot know the total: the caller compares offs[n] with cap. The synchronous call
+ * returns NRG_E_CAPACITY when offs[n] > cap, with offs and some complete and the first cap bytes
+ * valid. n == 0 is NRG_OK and writes offs[0] = 0. NRG_E_NOT_SYNCED while ltail < tail;
+ * n > config.max_reads: NRG_E_CAPACITY; NRG_E_INVAL: a reqs or offs pointer that is not 8-byte
+ * aligned, or with n > 0 a NULL reqs, offs or some, or a NULL data with cap > 0. */
+typedef struct {
+    uint64_t ino, offset, len;
+} nrg_memfs_rd; /* 24 B */
+int nrg_memfs_pread_async(nrg_ctx* ctx, const nrg_memfs_rd* d_reqs, uint64_t n, uint8_t* d_data, uint64_t cap,
+                          uint64_t* d_offs /* n + 1 */, uint8_t* d_some /* n */);
+int nrg_memfs_pread(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, uint8_t* data, uint64_t cap,
+                    uint64_t* offs /* n + 1 */, uint8_t* some /* n */);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's

@@ -35,6 +35,9 @@ int nrg_test_debug_read(nrg_ctx* ctx, uint64_t* out, uint64_t words);
  * memory `out`, inner entries as stored; syncs first. Lets tests see that two replicas whose leaves
  * agree allocated their tables in different orders. */
 int nrg_test_vspace_table(nrg_ctx* ctx, uint64_t table, uint64_t out[512]);
+/* Bytes of packed output one workgroup of nrg_memfs_pread's copy kernel takes (memfs.hip
+ * MF_PREAD_TILE): tests place requests on both sides of its multiples. */
+#define NRG_MF_PREAD_TILE 16384u
 
 /* Tuning and diagnostic knobs of an OPEN context. The product never reads the environment:
  * these setters are the only way to change them, so a stray variable in a caller's environment

@@ -237,6 +237,8 @@ struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, conti
     // scratch of one chunk
     uint32_t* d_keys = nullptr;  // [2 * max_batch] slot keys
     uint64_t* d_desc = nullptr;  // [max_batch] record descriptors
+    // scratch of one nrg_memfs_pread_async: [ceil(max_reads / 1024)] scan-tile aggregates
+    uint64_t* d_pagg = nullptr;
 };
 
 struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*

@@ -17,7 +17,8 @@
 // Write's range (EFBIG).
 // Out of scope: directories, names, inode creation and removal, rename.
 // Out of scope: file growth and truncate (SetAttr): the size is fixed at open.
-// Out of scope: benches/nrfs.rs's whole-file 4096-byte ops (a record carries at most 128 bytes).
+// Out of scope: benches/nrfs.rs's whole-file 4096-byte FileWrite (a record carries at most 128 bytes);
+// its read-only FileRead is nrg_memfs_pread* below, which goes through no log record.
 // Out of scope: the combiner, partitioned groups and growth (nrg_set_max_capacity).
 //
 // A file is cut into aligned 128-byte LINES; an op of at most 128 bytes touches at most two. Lines
@@ -46,6 +47,7 @@
 // store replay"; the next step is a segmented reduce-then-scan over tiles of a line's run).
 #include <cstring>
 
+#include "../../include/nrgpu_testing.h"
 #include "internal.hpp"
 
 namespace nrg {
@@ -223,6 +225,213 @@ __global__ __launch_bounds__(DG_TPB) void mf_fill_kernel(u64* words, u64 n) {
         words[i] = 0x0101010101010101ull;
 }
 
+// ---- read-only reads (nrg_memfs_pread*): Replica::execute -> read_only of nr/src/replica.rs:483-497
+// ---- for benches/nrfs.rs:88-101 OpRd::FileRead, here pread of any length ---------------------------
+// n requests {ino, offset, len} against the store as it stands; the answers packed in request order.
+// A request may be of 0 bytes or of a whole 64-MiB file, so no lane, wave or workgroup is given a
+// request: the clipped lengths are scanned into d_offs, then the OUTPUT is cut into tiles.
+//   mf_pread_reduce / _aggscan / _scan   the exclusive u64 scan of the clipped lengths in tiles of
+//              MF_PR_SCAN requests, three launches in stream order, no workgroup waiting on another;
+//              n <= MF_PR_SCAN is the one launch of _scan. _scan also writes some and offs[n].
+//   mf_pread_copy   one workgroup per MF_PREAD_TILE bytes of output (grid-stride over the tiles that
+//              exist: the grid is sized from the host's bound, the total is read from offs[n]). The
+//              workgroup finds the first and last request of its tile by upper-bound searches of
+//              d_offs (an upper bound: a run of empty requests at a position is skipped whole). The
+//              tile is cut into the destination's aligned 16-byte chunks, lane after lane; a lane
+//              finds its chunk's request by the same search inside the tile's range. A chunk that lies
+//              inside one request is two aligned 16-byte loads around the source, a byte shift and
+//              one 16-byte store; any other chunk (a request boundary inside it, the head or tail of
+//              the output) is gathered byte by byte, stepping to the next request, or searching for it
+//              where the next is empty, and stored whole when all 16 bytes are output bytes.
+//              Plain loads and stores; no LDS, no atomics, no spinning.
+constexpr u32 MF_PR_ITEMS = 4;                      // requests per lane of the scan
+constexpr u32 MF_PR_SCAN = MF_TPB * MF_PR_ITEMS;    // requests per scan tile
+constexpr u32 MF_PREAD_TILE = 16384;                // output bytes per copy workgroup (measured)
+constexpr u32 MF_PR_MAX_GRID = 1u << 20;            // copy workgroups at most; the tiles are strided over
+static_assert(MF_PREAD_TILE == NRG_MF_PREAD_TILE, "the tests place requests around this tile");
+static_assert(MF_PREAD_TILE % (16 * MF_TPB) == 0, "every lane takes the same number of 16-byte chunks");
+static_assert(sizeof(nrg_memfs_rd) == 24, "ABI");
+
+struct MfRdJob {
+    const u64* rq;   // the requests in u64 words: ino, offset, len
+    u64 n;
+    u64* offs;       // [n + 1]
+    uint8_t* some;   // [n]
+    uint8_t* data;   // the packed output
+    u64 cap;
+    const uint8_t* files;
+    u32 log2_b, nfiles;
+};
+
+// request i's clipped length; ok: its ino names a file
+__device__ __forceinline__ u64 mf_rd_count(const MfRdJob& j, u64 i, bool* ok) {
+    const u64 ino = j.rq[3 * i], off = j.rq[3 * i + 1], len = j.rq[3 * i + 2];
+    const u64 B = 1ull << j.log2_b;
+    *ok = ino >= NRG_MEMFS_FIRST_INO && ino - NRG_MEMFS_FIRST_INO < j.nfiles;
+    return !*ok || off >= B ? 0 : (len < B - off ? len : B - off);
+}
+
+// exclusive scan of v over the workgroup's threads, and the workgroup's total. s_w: MF_TPB / 64 words;
+// a caller that calls again puts a barrier between the calls.
+__device__ __forceinline__ u64 mf_block_excl(u64 v, u64* s_w, u64* total) {
+    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    u64 inc = v;
+#pragma unroll
+    for (u32 d = 1; d < 64; d <<= 1) {
+        const u64 o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    u64 base = 0, tot = 0;
+#pragma unroll
+    for (u32 k = 0; k < MF_TPB / 64; k++) {
+        const u64 x = s_w[k];
+        if (k < w) base += x;
+        tot += x;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+
+// agg[tile] = the sum of the tile's clipped lengths
+__global__ __launch_bounds__(MF_TPB) void mf_pread_reduce_kernel(MfRdJob j, u64* agg) {
+    __shared__ u64 s_w[MF_TPB / 64];
+    const u64 first = (u64)blockIdx.x * MF_PR_SCAN + threadIdx.x * MF_PR_ITEMS;
+    u64 sum = 0;
+#pragma unroll
+    for (u32 k = 0; k < MF_PR_ITEMS; k++) {
+        bool ok;
+        if (first + k < j.n) sum += mf_rd_count(j, first + k, &ok);
+    }
+    u64 tot;
+    (void)mf_block_excl(sum, s_w, &tot);
+    if (threadIdx.x == 0) agg[blockIdx.x] = tot;
+}
+
+// agg[tile] = the sum of the tiles before it; one workgroup
+__global__ __launch_bounds__(MF_TPB) void mf_pread_aggscan_kernel(u64* agg, u32 tiles) {
+    __shared__ u64 s_w[MF_TPB / 64];
+    u64 carry = 0;
+    for (u32 b = 0; b < tiles; b += MF_TPB) {
+        const u32 i = b + threadIdx.x;
+        u64 tot;
+        const u64 ex = mf_block_excl(i < tiles ? agg[i] : 0, s_w, &tot);
+        if (i < tiles) agg[i] = carry + ex;
+        carry += tot;
+        __syncthreads();
+    }
+}
+
+// some[i], offs[i] and offs[n]; agg: the scanned aggregates, or nullptr for a single tile
+__global__ __launch_bounds__(MF_TPB) void mf_pread_scan_kernel(MfRdJob j, const u64* agg) {
+    __shared__ u64 s_w[MF_TPB / 64];
+    const u64 first = (u64)blockIdx.x * MF_PR_SCAN + threadIdx.x * MF_PR_ITEMS;
+    u64 c[MF_PR_ITEMS], sum = 0;
+#pragma unroll
+    for (u32 k = 0; k < MF_PR_ITEMS; k++) {
+        c[k] = 0;
+        if (first + k < j.n) {
+            bool ok;
+            c[k] = mf_rd_count(j, first + k, &ok);
+            j.some[first + k] = ok ? 1 : 0;
+        }
+        sum += c[k];
+    }
+    u64 tot;
+    u64 run = mf_block_excl(sum, s_w, &tot) + (agg ? agg[blockIdx.x] : 0);
+#pragma unroll
+    for (u32 k = 0; k < MF_PR_ITEMS; k++)
+        if (first + k < j.n) {
+            j.offs[first + k] = run;
+            run += c[k];
+            if (first + k == j.n - 1) j.offs[j.n] = run;
+        }
+}
+
+// the first index i of [lo, hi] with offs[i] > p; offs[hi] > p holds
+__device__ __forceinline__ u64 mf_upper(const u64* offs, u64 lo, u64 hi, u64 p) {
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (offs[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the store's address of packed byte `lo` of request r, whose bytes begin at packed position lo
+__device__ __forceinline__ const uint8_t* mf_rd_src(const MfRdJob& j, u64 r) {
+    return j.files + ((j.rq[3 * r] - NRG_MEMFS_FIRST_INO) << j.log2_b) + j.rq[3 * r + 1];
+}
+
+// Positions below are packed positions plus mis = data & 15, so that a multiple of 16 is an aligned
+// address of the output: the output bytes are [mis, aend).
+__global__ __launch_bounds__(MF_TPB) void mf_pread_copy_kernel(MfRdJob j) {
+    const u64* __restrict__ offs = j.offs;
+    const u64 total = offs[j.n];
+    const u64 end = total < j.cap ? total : j.cap;
+    if (end == 0) return;
+    const u64 mis = (uintptr_t)j.data & 15;
+    uint8_t* const out = j.data - mis;
+    const u64 aend = end + mis;
+    const u64 ntiles = (aend + MF_PREAD_TILE - 1) / MF_PREAD_TILE;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u64 a0 = tile * MF_PREAD_TILE;
+        const u64 a1 = a0 + MF_PREAD_TILE < aend ? a0 + MF_PREAD_TILE : aend;
+        const u64 v0 = a0 > mis ? a0 : mis;  // the tile's output bytes are [v0, a1), not empty
+        // requests r_first .. r_last - 1 hold them (the same in every lane)
+        const u64 r_first = mf_upper(offs, 1, j.n, v0 - mis) - 1;
+        const u64 r_last = mf_upper(offs, r_first + 1, j.n, a1 - 1 - mis);
+        for (u64 a = a0 + 16 * threadIdx.x; a < a1; a += 16 * MF_TPB) {
+            const u64 lo = a > v0 ? a : v0, hi = a + 16 < a1 ? a + 16 : a1;  // the chunk's output bytes
+            u64 r = mf_upper(offs, r_first + 1, r_last, lo - mis) - 1;
+            u64 rl = offs[r] + mis, rh = offs[r + 1] + mis;  // request r's bytes: rl <= lo < rh
+            const uint8_t* src = mf_rd_src(j, r);
+            const bool whole = hi - lo == 16;
+            if (whole && a + 16 <= rh) {  // inside one request
+                const uint8_t* s = src + (a - rl);
+                const u32 sh = (u32)((uintptr_t)s & 15);
+                const ulonglong2 x = *(const ulonglong2*)(s - sh);
+                u64 w0 = x.x, w1 = x.y;
+                if (sh) {  // (the chunk's last byte lies in the second 16 bytes: inside the file)
+                    const ulonglong2 y = *(const ulonglong2*)(s - sh + 16);
+                    u64 w2 = y.x;
+                    if (sh >= 8) w0 = w1, w1 = y.x, w2 = y.y;
+                    const u32 b = (sh & 7) * 8;
+                    if (b) {
+                        w0 = (w0 >> b) | (w1 << (64 - b));
+                        w1 = (w1 >> b) | (w2 << (64 - b));
+                    }
+                }
+                *(ulonglong2*)(out + a) = make_ulonglong2(w0, w1);
+                continue;
+            }
+            u64 w0 = 0, w1 = 0;
+            for (u64 q = lo; q < hi; q++) {
+                if (q >= rh) {  // the next request that has bytes
+                    r++;
+                    rl = rh, rh = offs[r + 1] + mis;
+                    if (rh <= q) {  // an empty one: search past the run
+                        r = mf_upper(offs, r + 1, r_last, q - mis) - 1;
+                        rl = offs[r] + mis, rh = offs[r + 1] + mis;
+                    }
+                    src = mf_rd_src(j, r);
+                }
+                const u64 byte = src[q - rl];
+                const u32 k = (u32)(q - a);
+                if (k < 8) w0 |= byte << (8 * k); else w1 |= byte << (8 * (k - 8));
+            }
+            if (whole) {
+                *(ulonglong2*)(out + a) = make_ulonglong2(w0, w1);
+            } else {
+                for (u64 q = lo; q < hi; q++) {
+                    const u32 k = (u32)(q - a);
+                    out[q] = (uint8_t)(k < 8 ? w0 >> (8 * k) : w1 >> (8 * (k - 8)));
+                }
+            }
+        }
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------
 static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
@@ -280,6 +489,7 @@ static int mf_open(nrg_ctx* c) {
     HIPCHK(hipMalloc(&s.d_files, s.files << s.log2_b));
     HIPCHK(hipMalloc(&s.d_keys, 2 * cf.max_batch * sizeof(u32)));
     HIPCHK(hipMalloc(&s.d_desc, cf.max_batch * sizeof(u64)));
+    HIPCHK(hipMalloc(&s.d_pagg, (cf.max_reads / MF_PR_SCAN + 1) * sizeof(u64)));
     if (sort_alloc(c->sort, 2 * cf.max_batch) != NRG_OK) return NRG_E_NOMEM;
     HIPCHK(mf_fill(c));
     c->pipeline = false;  // config.pipeline is accepted: nothing is deferred
@@ -288,7 +498,7 @@ static int mf_open(nrg_ctx* c) {
 
 static void mf_close(nrg_ctx* c) {
     MfHost& s = c->mf;
-    void* ptrs[] = {s.d_files, s.d_keys, s.d_desc};
+    void* ptrs[] = {s.d_files, s.d_keys, s.d_desc, s.d_pagg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
@@ -421,6 +631,89 @@ int nrg_memfs_geometry(nrg_ctx* c, uint64_t* files, uint64_t* file_bytes) {
     if (files) *files = c->mf.files;
     if (file_bytes) *file_bytes = 1ull << c->mf.log2_b;
     return NRG_OK;
+}
+
+// the checks both preads share, in nrg_skiplist_get's order
+static int mf_pread_check(nrg_ctx* c, const void* reqs, uint64_t n, const void* data, uint64_t cap, const void* offs,
+                          const void* some) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (n > c->cfg.max_reads) return NRG_E_CAPACITY;
+    if (((uintptr_t)reqs | (uintptr_t)offs) & 7) return NRG_E_INVAL;
+    if (n && (!reqs || !offs || !some || (cap && !data))) return NRG_E_INVAL;
+    return NRG_OK;
+}
+
+// the most bytes n requests can answer, or cap if that is less
+static uint64_t mf_pread_bound(const nrg_ctx* c, uint64_t n, uint64_t cap) {
+    const uint32_t lb = c->mf.log2_b;
+    return n > (~0ull >> lb) || (n << lb) > cap ? cap : n << lb;
+}
+
+int nrg_memfs_pread_async(nrg_ctx* c, const nrg_memfs_rd* d_reqs, uint64_t n, uint8_t* d_data, uint64_t cap,
+                          uint64_t* d_offs, uint8_t* d_some) {
+    int r = mf_pread_check(c, d_reqs, n, d_data, cap, d_offs, d_some);
+    if (r) return r;
+    if (n == 0) {
+        if (d_offs) HIPCHK(hipMemsetAsync(d_offs, 0, sizeof(uint64_t), c->stream));
+        return NRG_OK;
+    }
+    MfHost& s = c->mf;
+    MfRdJob j{};
+    j.rq = (const u64*)d_reqs;
+    j.n = n;
+    j.offs = d_offs;
+    j.some = d_some;
+    j.data = d_data;
+    j.cap = cap;
+    j.files = s.d_files;
+    j.log2_b = s.log2_b;
+    j.nfiles = (u32)s.files;
+    const unsigned tiles = (unsigned)((n + MF_PR_SCAN - 1) / MF_PR_SCAN);
+    if (tiles > 1) {
+        NRG_LAUNCH(c, "mf_pread_reduce", mf_pread_reduce_kernel, tiles, MF_TPB, 0, c->stream, j, s.d_pagg);
+        NRG_LAUNCH(c, "mf_pread_aggscan", mf_pread_aggscan_kernel, 1, MF_TPB, 0, c->stream, s.d_pagg, (u32)tiles);
+    }
+    NRG_LAUNCH(c, "mf_pread_scan", mf_pread_scan_kernel, tiles, MF_TPB, 0, c->stream, j,
+               tiles > 1 ? (const u64*)s.d_pagg : (const u64*)nullptr);
+    // the total is on the device: the grid comes from the host's bound, surplus workgroups exit
+    const uint64_t bound = mf_pread_bound(c, n, cap);
+    if (bound) {
+        const uint64_t ct = (bound + 15 + MF_PREAD_TILE - 1) / MF_PREAD_TILE;
+        NRG_LAUNCH(c, "mf_pread_copy", mf_pread_copy_kernel, (unsigned)(ct < MF_PR_MAX_GRID ? ct : MF_PR_MAX_GRID), MF_TPB,
+                   0, c->stream, j);
+    }
+    return hip_fail(hipGetLastError());
+}
+
+int nrg_memfs_pread(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, uint8_t* data, uint64_t cap, uint64_t* offs,
+                    uint8_t* some) {
+    int r = mf_pread_check(c, reqs, n, data, cap, offs, some);
+    if (r) return r;
+    if (n == 0) {
+        if (offs) offs[0] = 0;
+        return NRG_OK;
+    }
+    const uint64_t room = mf_pread_bound(c, n, cap);  // what the device buffer has to hold
+    Staging* g = c->stg;
+    if ((r = staging(g[0], n * sizeof(nrg_memfs_rd))) || (r = staging(g[1], (n + 1) * 8)) || (r = staging(g[2], n)) ||
+        (r = staging(g[3], room)))
+        return r;
+    HIPCHK(hipMemcpyAsync(g[0].p, reqs, n * sizeof(nrg_memfs_rd), hipMemcpyHostToDevice, c->stream));
+    if ((r = nrg_memfs_pread_async(c, (const nrg_memfs_rd*)g[0].p, n, (uint8_t*)g[3].p, room, (uint64_t*)g[1].p,
+                                   (uint8_t*)g[2].p)))
+        return r;
+    HIPCHK(hipMemcpyAsync(offs, g[1].p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(some, g[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    const uint64_t got = offs[n] < cap ? offs[n] : cap;
+    if (got) {
+        HIPCHK(hipMemcpyAsync(data, g[3].p, got, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    if ((r = check_err(c))) return r;
+    return offs[n] > cap ? NRG_E_CAPACITY : NRG_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ from ._lib import NrgError, load
 from .combiner import Combiner
 from .replica import (
     MEMFS_OP_DTYPE,
+    MEMFS_RD_DTYPE,
     MEMFS_RESP_DTYPE,
     PUT_DTYPE,
     QUEUE_OP_DTYPE,
@@ -27,6 +28,7 @@ from .replica import (
     MapDevice,
     MemFs,
     MfGetAttr,
+    MfPread,
     MfRead,
     MfWrite,
     NrHashMap,
@@ -54,7 +56,7 @@ __all__ = [
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
     "Scan", "Seek", "SkipList", "SlPush",
-    "MEMFS_OP_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfRead", "MfWrite",
+    "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfWrite",
 ]
 
 

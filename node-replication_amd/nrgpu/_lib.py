@@ -75,6 +75,8 @@ VSPACE_LEAF_DTYPE = np.dtype([("vaddr", "<u8"), ("entry", "<u8")])
 # nrg_memfs_op (152 B) and nrg_memfs_resp (136 B)
 MEMFS_OP_DTYPE = np.dtype([("ino", "<u8"), ("offset", "<u8"), ("op", "<u4"), ("len", "<u4"), ("data", "u1", (128,))])
 MEMFS_RESP_DTYPE = np.dtype([("n", "<u8"), ("data", "u1", (128,))])
+# nrg_memfs_rd (24 B): one request of nrg_memfs_pread
+MEMFS_RD_DTYPE = np.dtype([("ino", "<u8"), ("offset", "<u8"), ("len", "<u8")])
 
 
 class NrgError(RuntimeError):
@@ -270,6 +272,8 @@ SIGNATURES = {
     "nrg_memfs_read": (C.c_int, [vp, u64, u64, u64, vp, u64p]),
     "nrg_memfs_dump": (C.c_int, [vp, u64, vp, u64, u64p]),
     "nrg_memfs_geometry": (C.c_int, [vp, u64p, u64p]),
+    "nrg_memfs_pread": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
+    "nrg_memfs_pread_async": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

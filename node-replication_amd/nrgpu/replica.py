@@ -35,6 +35,7 @@ VSPACE_RESP_DTYPE = L.VSPACE_RESP_DTYPE
 VSPACE_LEAF_DTYPE = L.VSPACE_LEAF_DTYPE
 MEMFS_OP_DTYPE = L.MEMFS_OP_DTYPE
 MEMFS_RESP_DTYPE = L.MEMFS_RESP_DTYPE
+MEMFS_RD_DTYPE = L.MEMFS_RD_DTYPE
 
 # nr/src/log.rs:22,26,36 ; nr/src/context.rs:12 ; nr/src/replica.rs:56
 DEFAULT_LOG_BYTES = 32 * 1024 * 1024
@@ -732,6 +733,50 @@ class DeviceReplica:
         L.check(self._lib.nrg_memfs_read(self._h, ino, offset, size, _ptr(out), C.byref(n)), "memfs_read")
         return out[: n.value].tobytes()
 
+    @_stream_ordered
+    def mf_pread_device(self, d_reqs, n: int, d_data, cap: int, d_offs, d_some):
+        """Replica::execute for n read-only reads {ino, offset, len} (24 B each) on device buffers
+        (nrg_memfs_pread_async): the clipped lengths scanned into d_offs[0..n], the bytes packed into
+        d_data below cap, d_some[i] = 0 for an unknown ino. The caller compares d_offs[n] with cap.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_memfs_pread_async(self._h, _dptr(d_reqs), n, _dptr(d_data), cap, _dptr(d_offs),
+                                                _dptr(d_some)), "memfs_pread")
+
+    def mf_pread(self, reqs, cap: Optional[int] = None):
+        """A batch of read-only reads: (data, offs, some), torch tensors on this replica's GPU (uint8
+        [cap], int64 [n + 1], uint8 [n]); request i's bytes are data[offs[i]:offs[i + 1]]. `reqs`: a
+        numpy array of MEMFS_RD_DTYPE (or [n, 3] u64: ino, offset, len), or a torch tensor on the GPU
+        holding those records. cap=None sizes data from the requests on the host (a device tensor is
+        copied back for that), so that offs[n] == cap; with a cap of the caller's, bytes at or past
+        cap are not written and offs[n] > cap says so."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        host = None
+        if hasattr(reqs, "data_ptr"):
+            d_reqs = reqs.contiguous()
+            n = d_reqs.numel() * d_reqs.element_size() // L.MEMFS_RD_DTYPE.itemsize
+        else:
+            host = np.asarray(reqs)
+            if host.dtype != L.MEMFS_RD_DTYPE:
+                host = np.ascontiguousarray(host, np.uint64).reshape(-1, 3).view(L.MEMFS_RD_DTYPE)
+            host = np.ascontiguousarray(host.reshape(-1))
+            n = len(host)
+            d_reqs = torch.from_numpy(host.view(np.uint8).copy()).to(dev)
+        if cap is None:
+            if host is None:
+                host = d_reqs.cpu().numpy().reshape(-1).view(np.uint8).view(L.MEMFS_RD_DTYPE)
+            files, b = self.mf_geometry()
+            first = np.uint64(L.NRG_MEMFS_FIRST_INO)
+            ok = (host["ino"] >= first) & (host["ino"] < first + np.uint64(files)) & (host["offset"] < np.uint64(b))
+            left = np.uint64(b) - np.minimum(host["offset"], np.uint64(b))
+            cap = int(np.where(ok, np.minimum(host["len"], left), np.uint64(0)).sum(dtype=np.uint64))
+        data = torch.empty(cap, dtype=torch.uint8, device=dev)
+        offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        some = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.mf_pread_device(d_reqs if n else None, n, data if cap else None, cap, offs, some if n else None)
+        return data, offs, some
+
     def mf_dump(self, ino: int) -> bytes:
         """The whole file `ino`: Replica::verify's view (nrg_memfs_dump)."""
         _, b = self.mf_geometry()
@@ -882,6 +927,13 @@ class MfRead:  # benches/memfs.rs:73-78 OperationWr::Read{ino, offset, size}: a 
 @dataclass(frozen=True)
 class MfGetAttr:  # benches/memfs.rs:27-29 OperationWr::GetAttr{ino}
     ino: int
+
+
+@dataclass(frozen=True)
+class MfPread:  # benches/nrfs.rs:16-18, :88-101 OpRd::FileRead: a read operation, not logged; any size
+    ino: int
+    offset: int
+    size: int
 
 
 @dataclass(frozen=True)
@@ -1116,9 +1168,24 @@ class MemFs:
 
     @staticmethod
     def read_batch(dev: DeviceReplica, ops) -> list:
-        if ops:
-            raise TypeError("the file store has no read operations (ReadOperation = ()): MfRead is an execute_mut op")
-        return []
+        """MfPread -> ("data", bytes), clipped at the end of the file, or ("err", ENOENT): one
+        nrg_memfs_pread_async for the batch. memfs.rs itself has no read operations (ReadOperation =
+        ()): its MfRead is an execute_mut op and is refused here."""
+        for o in ops:
+            if isinstance(o, MfRead):
+                raise TypeError("MfRead is an execute_mut op (memfs.rs: ReadOperation = ()); the read-only read is MfPread")
+            if not isinstance(o, MfPread):
+                raise TypeError(f"not a file-store read: {o!r}")
+        if not ops:
+            return []
+        reqs = np.zeros(len(ops), L.MEMFS_RD_DTYPE)
+        reqs["ino"] = [o.ino for o in ops]
+        reqs["offset"] = [o.offset for o in ops]
+        reqs["len"] = [o.size for o in ops]
+        data, offs, some = dev.mf_pread(reqs)
+        data, offs, some = data.cpu().numpy(), offs.cpu().numpy(), some.cpu().numpy()
+        return [("data", data[offs[i]:offs[i + 1]].tobytes()) if some[i] else ("err", L.NRG_MEMFS_ENOENT)
+                for i in range(len(ops))]
 
     @staticmethod
     def snapshot(dev: DeviceReplica):
