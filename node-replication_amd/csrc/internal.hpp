@@ -1,7 +1,7 @@
 // internal.hpp — what the host-side files share: the context (nrg_ctx: the log and what every kind
-// uses, plus one state struct per owner, each touched by its owner's file alone), each kind's ops
-// table (DsOps), the runtime helpers the structures' entry points use, and the few functions one
-// structure's file uses of another's.
+// uses, the growth state (capacity.hpp), plus one state struct per owner, each touched by its owner's
+// file alone), each kind's ops table (DsOps), the runtime helpers the structures' entry points use,
+// and the few functions one structure's file uses of another's.
 #pragma once
 
 #include <hip/hip_ext.h>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/nrgpu.h"
+#include "capacity.hpp"
 #include "common.hpp"
 
 namespace nrg {
@@ -117,7 +118,9 @@ struct HostRun {  // origin tags of appended log ranges (the Entry::replica fiel
 };
 
 // ---- Host state of each owner, embedded in nrg_ctx. Only the owner's file touches its struct
-// ---- (and allocates and frees its buffers); the runtime touches none of them.
+// ---- (and allocates and frees its buffers); the runtime touches none of them. The growth state
+// ---- (nrg_ctx::growth) is the runtime's: a kind's file runs the inline fast path on it before a
+// ---- chunk and sets len_ub where it learns the exact count (init, restore, a compaction's re-read).
 
 struct HmHost {  // NrHashMap (hashmap.hip)
     uint32_t slot_shift = 0;  // 64 - log2_slots
@@ -168,10 +171,6 @@ struct StHost {  // stack (stack.hip)
     uint32_t par = 0;            // buffer parity of the next chunk
     uint32_t* d_desc = nullptr;  // look-back descriptors of both parities (st_desc_words)
     uint64_t desc_words = 0;
-    // Growth (st_room / st_grow): the buffer may grow to max_items elements (0: fixed); len_ub bounds
-    // the length from above: the exact length when it was last read plus every record replayed since.
-    uint64_t max_items = 0;
-    uint64_t len_ub = 0;
 };
 
 struct SyHost {  // synthetic (synthetic.hip)
@@ -193,10 +192,6 @@ struct QuHost {  // FIFO queue (queue.hip)
     uint64_t size = 0;
     QuState* d_state = nullptr;
     void* d_aux = nullptr;  // per-tile aggregates and scanned starts
-    // Growth (qu_room / qu_grow), as the stack's: the bound on the capacity (0: fixed) and the upper
-    // bound of the length.
-    uint64_t max_items = 0;
-    uint64_t len_ub = 0;
 };
 
 struct VsHost {  // page table (vspace.hip)
@@ -221,10 +216,8 @@ struct SlHost {  // skip list / ordered map (skiplist.hip): two sorted runs with
     uint64_t *d_sk = nullptr, *d_nk = nullptr, *d_nv = nullptr;
     uint32_t *d_sp = nullptr, *d_k32 = nullptr, *d_pv = nullptr, *d_tcnt = nullptr;
     uint8_t* d_miss = nullptr;
-    // Growth (sl_room / sl_grow), as the stack's: the bound on the capacity (0: fixed) and the upper
-    // bound of the key count. nd_ub bounds the delta count the same way (the compaction policy).
-    uint64_t max_items = 0;
-    uint64_t len_ub = 0;
+    // The compaction policy: nd_ub bounds the delta count from above, as Growth::len_ub bounds the key
+    // count: the exact count when it was last read plus every record replayed since.
     uint64_t nd_ub = 0;
 };
 
@@ -269,7 +262,7 @@ struct DsOps {
     int (*open)(nrg_ctx* c);
     // free what open, and growth since, allocated; the context may be half-opened
     void (*close)(nrg_ctx* c);
-    // launch the work the last replayed chunk deferred, if any
+    // launch the work the last replayed chunk deferred, if any (nullptr: a chunk defers nothing)
     hipError_t (*flush)(nrg_ctx* c);
     // replay the n records at log positions [lo, lo + n) (n <= max_batch): from the ring, or from
     // `src` if given, and then the ring copy is written too; write responses of [resp_lo, resp_hi)
@@ -301,9 +294,14 @@ struct DsOps {
     // payload (the stream has been drained, nothing is deferred). d_payload == nullptr: the empty
     // structure of a fresh context instead (after a restore whose digest did not match).
     int (*restore)(nrg_ctx* c, const void* d_payload, u64 items, bool check_only);
-    // nrg_set_max_capacity: the bound automatic growth stops at (0: fixed capacity); an NRG_* code.
-    // The stream has been drained. nullptr: the kind has no such bound.
-    int (*set_max)(nrg_ctx* c, u64 max_items);
+    // Capacity (capacity.hpp; null or zero: the kind has none the runtime drives). The exact item count
+    // the policy reads is `items`.
+    u64 cap_limit;                        // the largest capacity nrg_open accepts, inclusive
+    u64 (*capacity)(const nrg_ctx* c);    // the current capacity, in items
+    // reallocate to new_cap items (capacity < new_cap <= cap_limit), synchronously; if the allocation
+    // fails nothing of it has been launched and the replica is as it was
+    hipError_t (*grow)(nrg_ctx* c, u64 new_cap);
+    bool auto_grow;  // grows under replay up to nrg_set_max_capacity's bound (else: nrg_*_reserve only)
 };
 const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops(), *sl_ops(), *mf_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
@@ -326,6 +324,8 @@ struct nrg_ctx {
     std::vector<nrg::HostRun> origins;
 
     nrg::DevCtl* d_ctl = nullptr;
+
+    nrg::Growth growth;  // of the context's kind (stack, queue, skip list)
 
     uint64_t rounds = 0;  // replay rounds launched (statistics)
     // set only through nrg_test_set_knob (include/nrgpu_testing.h)
@@ -396,6 +396,17 @@ void commit_round(nrg_ctx* c, uint64_t lo, uint64_t n);  // [lo, lo + n) appende
 int round_common(nrg_ctx* c, uint32_t kind, const void* d_ops, uint64_t n, uint32_t origin, void* d_resp,
                  uint8_t* d_some);
 inline u64 floor_ltail(const nrg_ctx* c) { return c->ltail; }  // DsOps::floor of a kind that defers no ring reads
+// The slow half of the growth policy, for a chunk of n records that growth_fits (capacity.hpp) did
+// not pass: the exact count (DsOps::items: what the chunk deferred, a copy and a stream synchronise,
+// timed as `timer` so that nrg_kernel_time counts the re-reads), the grow if exact + n does not fit,
+// then len_ub = exact + n. On an error the growth state is untouched.
+hipError_t room(nrg_ctx* c, u64 n, const char* timer);
+// nrg_*_reserve and nrg_*_capacity of `kind`
+int reserve_common(nrg_ctx* c, uint32_t kind, uint64_t n);
+int capacity_common(nrg_ctx* c, uint32_t kind, uint64_t* out);
+// The head of a growing kind's DsOps::restore. True: *r answers the call (check_only's answer, or a
+// grow that failed). False: the structure holds *items items (0 without a payload): load them.
+bool restore_room(nrg_ctx* c, const void* d_payload, u64* items, bool check_only, int* r);
 
 inline int hip_fail(hipError_t e) {
     if (e == hipSuccess) return NRG_OK;

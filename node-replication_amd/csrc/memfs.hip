@@ -503,8 +503,6 @@ static void mf_close(nrg_ctx* c) {
         if (p) (void)hipFree(p);
 }
 
-static hipError_t mf_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
-
 static void mf_defaults(nrg_config* cfg) {
     cfg->log2_slots = MF_LOG2_DEFAULT;  // one 4096-byte file (benches/memfs.rs:112-121)
     cfg->queue_capacity = 1;
@@ -562,9 +560,9 @@ static int mf_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_o
 }
 
 const DsOps* mf_ops() {
-    static const DsOps ops = {sizeof(nrg_memfs_op), sizeof(nrg_memfs_resp), mf_open, mf_close, mf_flush,
+    static const DsOps ops = {sizeof(nrg_memfs_op), sizeof(nrg_memfs_resp), mf_open, mf_close, nullptr,
                               mf_replay_chunk, floor_ltail, nullptr, nullptr, mf_defaults, mf_digest,
-                              mf_items, mf_snapshot, mf_restore, nullptr};
+                              mf_items, mf_snapshot, mf_restore};
     return &ops;
 }
 

@@ -365,16 +365,6 @@ __global__ __launch_bounds__(DG_TPB) void qu_grow_kernel(const u64* __restrict__
         to[(head + i) & to_mask] = from[(head + i) & from_mask];
 }
 
-// The exact length, clamped as nrg_queue_len clamps it. Drains the stream.
-static hipError_t qu_exact_len(nrg_ctx* c, u64* n) {
-    u64 len = 0;
-    hipError_t e = hipMemcpyAsync(&len, &c->qu.d_state->len, sizeof(len), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return e;
-    *n = len > c->cfg.queue_capacity ? c->cfg.queue_capacity : len;
-    return hipSuccess;
-}
-
 // The ring is reallocated to the power of two at or above new_cap + max_batch (qu_open's invariant);
 // where that is the ring it has, only the capacity changes. The re-layout, then the stream is
 // synchronised (there is no stream-ordered free), the old ring freed and the new one installed with
@@ -407,40 +397,16 @@ static hipError_t qu_grow(nrg_ctx* c, u64 new_cap) {
     return hipSuccess;
 }
 
-// the capacity automatic growth goes to for `need` elements: at least double, clipped to the bound
-static u64 qu_grown(const nrg_ctx* c, u64 need) {
-    u64 want = 2 * c->cfg.queue_capacity;
-    if (want < need) want = need;
-    return want > c->qu.max_items ? c->qu.max_items : want;
-}
-
-// The growth policy, the stack's (st_room): the n records about to be replayed are added to the
-// upper bound len_ub; only when the bound passes the capacity is QuState::len read, and only if
-// exact + n still passes it does the queue grow. At the bound the queue is a fixed one.
-static hipError_t qu_room(nrg_ctx* c, u64 n) {
-    QuHost& q = c->qu;
-    if (!q.max_items || c->cfg.queue_capacity >= q.max_items) return hipSuccess;
-    if (q.len_ub + n <= c->cfg.queue_capacity) {
-        q.len_ub += n;
-        return hipSuccess;
-    }
-    u64 exact = 0;
-    timer_begin(c, "qu_room");  // (nrg_kernel_time counts the re-reads)
-    hipError_t e = qu_exact_len(c, &exact);
-    timer_end(c, "qu_room");
-    if (e != hipSuccess) return e;
-    if (exact + n > c->cfg.queue_capacity && (e = qu_grow(c, qu_grown(c, exact + n))) != hipSuccess) return e;
-    q.len_ub = exact + n;
-    return hipSuccess;
-}
-
 // One chunk of at most max_batch records: log indices [lo, lo + n), read from the ring or, for a
 // fused round, from `src` (the log copy is then written by the aggregate pass).
 static hipError_t qu_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
     if (n == 0) return hipSuccess;
-    const hipError_t eg = qu_room(c, n);  // the ring grows first if it has to (one comparison if not)
-    if (eg != hipSuccess) return eg;
+    // the ring grows first if it has to (one comparison if not)
+    if (!growth_fits(c->growth, c->cfg.queue_capacity, n)) {
+        const hipError_t eg = room(c, n, "qu_room");
+        if (eg != hipSuccess) return eg;
+    }
     QuJob j{};
     j.src = (const nrg_queue_op*)src;
     j.ring = (nrg_queue_op*)c->d_ring;
@@ -506,8 +472,6 @@ static void qu_close(nrg_ctx* c) {
     (void)hipFree(c->qu.d_aux);
 }
 
-static hipError_t qu_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
-
 // nrg_digest: item i from the front is (i, q[(head + i) & mask]): the logical position, whatever
 // ring slot holds it; head and the length are read here, the length clamped as nrg_queue_len clamps it
 __global__ __launch_bounds__(DG_TPB) void qu_digest_kernel(const u64* __restrict__ q, u64 qmask, const QuState* st,
@@ -534,11 +498,20 @@ static hipError_t qu_digest(nrg_ctx* c, u64* d_out3) {
 }
 
 // ---- nrg_snapshot_async / nrg_restore: the elements, front first ---------------------------------
+// The one reader of QuState (the snapshot's item count, the growth policy's exact length,
+// nrg_queue_len and nrg_queue_dump): the length never more than the capacity. Drains the stream.
+static int qu_read_state(nrg_ctx* c, QuState* s) {
+    HIPCHK(hipMemcpyAsync(s, c->qu.d_state, sizeof(*s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (s->len > c->cfg.queue_capacity) s->len = c->cfg.queue_capacity;
+    return NRG_OK;
+}
+
 static int qu_items(nrg_ctx* c, u64* n) {
     QuState s{};
-    HIPCHK(hipMemcpyAsync(&s, c->qu.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *n = s.len > c->cfg.queue_capacity ? c->cfg.queue_capacity : s.len;  // clamped as nrg_queue_len clamps it
+    int r = qu_read_state(c, &s);
+    if (r) return r;
+    *n = s.len;
     return NRG_OK;
 }
 
@@ -574,31 +547,20 @@ __global__ __launch_bounds__(DG_TPB) void qu_restore_kernel(u64* q, const u64* _
 }
 
 static int qu_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
-    // with a growth bound the image may be as large as the bound: the ring grows first
-    if (check_only)
-        return items <= std::max<u64>(c->cfg.queue_capacity, c->qu.max_items) ? NRG_OK : NRG_E_CAPACITY;
-    if (!d_payload) items = 0;
-    if (items > c->cfg.queue_capacity) HIPCHK(qu_grow(c, qu_grown(c, items)));
+    int r;
+    if (restore_room(c, d_payload, &items, check_only, &r)) return r;
     NRG_LAUNCH(c, "qu_restore", qu_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->qu.d_queue,
                (const u64*)d_payload, items, c->qu.d_state);
-    c->qu.len_ub = items;
+    c->growth.len_ub = items;
     return hip_fail(hipGetLastError());
 }
 
-// nrg_set_max_capacity: the bound, and the length bound restarts from the exact length
-static int qu_set_max(nrg_ctx* c, u64 max_items) {
-    if (max_items && (max_items < c->cfg.queue_capacity || max_items > (1ull << 32))) return NRG_E_INVAL;
-    u64 exact = 0;
-    HIPCHK(qu_exact_len(c, &exact));
-    c->qu.max_items = max_items;
-    c->qu.len_ub = exact;
-    return NRG_OK;
-}
+static u64 qu_capacity(const nrg_ctx* c) { return c->cfg.queue_capacity; }
 
 const DsOps* qu_ops() {
-    static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, qu_flush, qu_replay_chunk,
+    static const DsOps ops = {sizeof(nrg_queue_op), sizeof(u64), qu_open, qu_close, nullptr, qu_replay_chunk,
                               floor_ltail, nullptr, nullptr, nullptr, qu_digest,
-                              qu_items, qu_snapshot, qu_restore, qu_set_max};
+                              qu_items, qu_snapshot, qu_restore, 1ull << 32, qu_capacity, qu_grow, true};
     return &ops;
 }
 
@@ -630,7 +592,7 @@ int nrg_queue_init(nrg_ctx* c, const uint64_t* vals, uint64_t n) {
     // head = 0: the n values sit at the start of the ring (capacity <= its size)
     if (n) HIPCHK(hipMemcpyAsync(c->qu.d_queue, vals, n * 8, hipMemcpyHostToDevice, c->stream));
     if ((r = qu_set_state(c, n))) return r;
-    c->qu.len_ub = n;
+    c->growth.len_ub = n;
     return NRG_OK;
 }
 
@@ -640,32 +602,21 @@ int nrg_queue_init_range(nrg_ctx* c, uint64_t n) {
     if (n > c->cfg.queue_capacity) return NRG_E_CAPACITY;
     HIPCHK(qu_init_range(c, n));
     HIPCHK(sync_all(c));
-    c->qu.len_ub = n;
+    c->growth.len_ub = n;
     return NRG_OK;
 }
 
-int nrg_queue_reserve(nrg_ctx* c, uint64_t n_elems) {
-    int r = need(c, NRG_DS_QUEUE);
-    if (r) return r;
-    if (n_elems > (1ull << 32)) return NRG_E_INVAL;  // nrg_open's bound
-    if (n_elems <= c->cfg.queue_capacity) return NRG_OK;
-    HIPCHK(qu_grow(c, n_elems));
-    return NRG_OK;
-}
+int nrg_queue_reserve(nrg_ctx* c, uint64_t n_elems) { return reserve_common(c, NRG_DS_QUEUE, n_elems); }
 
-int nrg_queue_capacity(nrg_ctx* c, uint64_t* n) {
-    if (!c || !n || c->cfg.ds_kind != NRG_DS_QUEUE) return NRG_E_INVAL;
-    *n = c->cfg.queue_capacity;
-    return NRG_OK;
-}
+int nrg_queue_capacity(nrg_ctx* c, uint64_t* n) { return capacity_common(c, NRG_DS_QUEUE, n); }
 
-// the front's monotonic position and the length, never more than the capacity
+// the front's monotonic position and the length, then the error latch
 static int qu_get_state(nrg_ctx* c, uint64_t* head, uint64_t* len) {
     QuState s{};
-    HIPCHK(hipMemcpyAsync(&s, c->qu.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_all(c));
+    int r = qu_read_state(c, &s);
+    if (r) return r;
     *head = s.head;
-    *len = s.len > c->cfg.queue_capacity ? c->cfg.queue_capacity : s.len;
+    *len = s.len;
     return check_err(c);
 }
 

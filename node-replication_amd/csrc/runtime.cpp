@@ -56,7 +56,7 @@ int need(nrg_ctx* c, uint32_t kind) {
 
 // what the last replayed chunk deferred (a round's reads, a chunk's finish or sums), launched now
 // if there is any
-hipError_t flush_deferred(nrg_ctx* c) { return c->ops->flush(c); }
+hipError_t flush_deferred(nrg_ctx* c) { return c->ops->flush ? c->ops->flush(c) : hipSuccess; }
 
 // wait for everything queued on this replica, including what the last chunk deferred
 hipError_t sync_all(nrg_ctx* c) {
@@ -174,6 +174,59 @@ int round_common(nrg_ctx* c, uint32_t kind, const void* d_ops, uint64_t n, uint3
     if (n) note_origin(c, lo, n, origin);
     commit_round(c, lo, n);
     return NRG_OK;
+}
+
+// ---- capacity and growth (capacity.hpp), driven through the kind's DsOps ------------------------
+hipError_t room(nrg_ctx* c, u64 n, const char* timer) {
+    const DsOps* o = c->ops;
+    u64 exact = 0;
+    timer_begin(c, timer);
+    const int r = o->items(c, &exact);
+    timer_end(c, timer);
+    if (r != NRG_OK) return r == NRG_E_NOMEM ? hipErrorOutOfMemory : hipErrorUnknown;
+    const u64 cap = o->capacity(c), to = growth_target(c->growth, cap, exact + n);
+    hipError_t e;
+    if (to != cap && (e = o->grow(c, to)) != hipSuccess) return e;
+    c->growth.len_ub = exact + n;
+    return hipSuccess;
+}
+
+// nrg_set_max_capacity of a kind that grows under replay: the bound, and the count bound restarts
+// from the exact count. The stream has been drained.
+static int set_max(nrg_ctx* c, u64 max_items) {
+    if (!growth_bound_ok(max_items, c->ops->capacity(c), c->ops->cap_limit)) return NRG_E_INVAL;
+    u64 exact = 0;
+    int r = c->ops->items(c, &exact);
+    if (r) return r;
+    c->growth = Growth{max_items, exact};
+    return NRG_OK;
+}
+
+int reserve_common(nrg_ctx* c, uint32_t kind, uint64_t n) {
+    int r = need(c, kind);
+    if (r) return r;
+    if (n > c->ops->cap_limit) return NRG_E_INVAL;  // nrg_open's bound
+    if (n <= c->ops->capacity(c)) return NRG_OK;    // never shrinks
+    HIPCHK(c->ops->grow(c, n));
+    return NRG_OK;
+}
+
+int capacity_common(nrg_ctx* c, uint32_t kind, uint64_t* out) {  // no device is touched
+    if (!c || !out || c->cfg.ds_kind != kind) return NRG_E_INVAL;
+    *out = c->ops->capacity(c);
+    return NRG_OK;
+}
+
+bool restore_room(nrg_ctx* c, const void* d_payload, u64* items, bool check_only, int* r) {
+    const u64 cap = c->ops->capacity(c);
+    *r = NRG_OK;
+    if (check_only) {
+        if (!growth_admits(c->growth, cap, *items)) *r = NRG_E_CAPACITY;
+        return true;
+    }
+    if (!d_payload) *items = 0;
+    if (*items > cap) *r = hip_fail(c->ops->grow(c, growth_target(c->growth, cap, *items)));
+    return *r != NRG_OK;
 }
 
 const DsOps* ds_ops(uint32_t kind) {
@@ -400,14 +453,14 @@ int nrg_sync(nrg_ctx* c) {
     return check_err(c);
 }
 
-// The bound of a kind that grows under replay as its reference structure does (Vec, SegQueue);
-// what it means is the kind's (DsOps::set_max).
+// The bound of a kind that grows under replay as its reference structure does (Vec, SegQueue), in
+// the kind's items (DsOps::auto_grow).
 int nrg_set_max_capacity(nrg_ctx* c, uint64_t max_items) {
-    if (!c || !c->ops->set_max) return NRG_E_INVAL;
+    if (!c || !c->ops->auto_grow) return NRG_E_INVAL;
     int r = use_device(c);
     if (r) return r;
     HIPCHK(sync_all(c));
-    return c->ops->set_max(c, max_items);
+    return set_max(c, max_items);
 }
 
 int nrg_join(nrg_ctx* c) {

@@ -520,33 +520,6 @@ static hipError_t sl_grow(nrg_ctx* c, u64 new_cap) {
     return hipSuccess;
 }
 
-// the capacity automatic growth goes to for `need` keys: at least double, clipped to the bound
-static u64 sl_grown(const nrg_ctx* c, u64 need) {
-    u64 want = 2 * c->sl.cap;
-    if (want < need) want = need;
-    return want > c->sl.max_items ? c->sl.max_items : want;
-}
-
-// The growth policy, as st_room's: n records about to be replayed (or prefilled) are added to len_ub;
-// only when the bound passes the capacity is the exact count read, and only if exact + n still
-// passes it do the runs grow. A stream of updates re-reads its count now and then and never
-// reallocates.
-static hipError_t sl_room(nrg_ctx* c, u64 n) {
-    SlHost& s = c->sl;
-    if (!s.max_items || s.cap >= s.max_items) return hipSuccess;
-    if (s.len_ub + n <= s.cap) {
-        s.len_ub += n;
-        return hipSuccess;
-    }
-    SlState st{};
-    hipError_t e = sl_read_state(c, &st);
-    if (e != hipSuccess) return e;
-    const u64 exact = st.nb + st.nd;
-    if (exact + n > s.cap && (e = sl_grow(c, sl_grown(c, exact + n))) != hipSuccess) return e;
-    s.len_ub = exact + n;
-    return hipSuccess;
-}
-
 static hipError_t sl_compact(nrg_ctx* c, u64 nb, u64 nd) {
     SlHost& s = c->sl;
     SlMerge m{};
@@ -566,8 +539,9 @@ static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u
                            void* d_resp, uint8_t* d_some) {
     if (n == 0) return hipSuccess;
     SlHost& s = c->sl;
-    hipError_t e = sl_room(c, n);  // the runs grow first if they have to
-    if (e != hipSuccess) return e;
+    hipError_t e;
+    // the runs grow first if they have to (one comparison if not)
+    if (!growth_fits(c->growth, s.cap, n) && (e = room(c, n, "sl_room")) != hipSuccess) return e;
     SlJob j{};
     j.src = src;
     j.ring = (nrg_put*)c->d_ring;
@@ -621,7 +595,7 @@ static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u
         SlState st{};
         if ((e = sl_read_state(c, &st)) != hipSuccess) return e;
         s.nd_ub = st.nd;
-        if (s.max_items) s.len_ub = st.nb + st.nd;
+        if (c->growth.max_items) c->growth.len_ub = st.nb + st.nd;
         if (st.nd > s.delta_max) return sl_compact(c, st.nb, st.nd);
     }
     return hipSuccess;
@@ -673,8 +647,6 @@ static void sl_close(nrg_ctx* c) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
-
-static hipError_t sl_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
 
 // NRG_KNOB_SL_DELTA_MAX on an empty context: the delta buffers are sized by it
 static int sl_set_knob(nrg_ctx* c, int knob, uint64_t v) {
@@ -763,32 +735,21 @@ __global__ __launch_bounds__(DG_TPB) void sl_restore_kernel(u64* bk, u64* bv, co
 
 static int sl_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
     SlHost& s = c->sl;
-    // with a growth bound the image may be as large as the bound: the runs grow first
-    if (check_only) return items <= std::max<u64>(s.cap, s.max_items) ? NRG_OK : NRG_E_CAPACITY;
-    if (!d_payload) items = 0;
-    if (items > s.cap) HIPCHK(sl_grow(c, sl_grown(c, items)));
+    int r;
+    if (restore_room(c, d_payload, &items, check_only, &r)) return r;
     NRG_LAUNCH(c, "sl_restore", sl_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, s.d_bk[s.bcur], s.d_bv[s.bcur],
                (const nrg_put*)d_payload, items, s.d_state, c->d_ctl);
-    s.len_ub = items;
+    c->growth.len_ub = items;
     s.nd_ub = 0;
     return hip_fail(hipGetLastError());
 }
 
-// nrg_set_max_capacity: the bound, and the count bound restarts from the exact count
-static int sl_set_max(nrg_ctx* c, u64 max_items) {
-    SlHost& s = c->sl;
-    if (max_items && (max_items < s.cap || max_items > (1ull << SL_LOG2_MAX))) return NRG_E_INVAL;
-    SlState st{};
-    HIPCHK(sl_read_state(c, &st));
-    s.max_items = max_items;
-    s.len_ub = st.nb + st.nd;
-    return NRG_OK;
-}
+static u64 sl_capacity(const nrg_ctx* c) { return c->sl.cap; }
 
 const DsOps* sl_ops() {
-    static const DsOps ops = {sizeof(nrg_put), sizeof(uint64_t), sl_open, sl_close, sl_flush, sl_replay_chunk,
+    static const DsOps ops = {sizeof(nrg_put), sizeof(uint64_t), sl_open, sl_close, nullptr, sl_replay_chunk,
                               floor_ltail, sl_set_knob, nullptr, sl_defaults, sl_digest,
-                              sl_items, sl_snapshot, sl_restore, sl_set_max};
+                              sl_items, sl_snapshot, sl_restore, 1ull << SL_LOG2_MAX, sl_capacity, sl_grow, true};
     return &ops;
 }
 
@@ -1137,19 +1098,8 @@ int nrg_skiplist_prefill_partition(nrg_ctx* c, uint64_t n, uint64_t val_offset, 
     return check_err(c);
 }
 
-int nrg_skiplist_reserve(nrg_ctx* c, uint64_t n_keys) {
-    int r = need(c, NRG_DS_SKIPLIST);
-    if (r) return r;
-    if (n_keys > (1ull << SL_LOG2_MAX)) return NRG_E_INVAL;  // nrg_open's bound
-    if (n_keys <= c->sl.cap) return NRG_OK;
-    HIPCHK(sl_grow(c, n_keys));
-    return NRG_OK;
-}
+int nrg_skiplist_reserve(nrg_ctx* c, uint64_t n_keys) { return reserve_common(c, NRG_DS_SKIPLIST, n_keys); }
 
-int nrg_skiplist_capacity(nrg_ctx* c, uint64_t* n) {
-    if (!c || !n || c->cfg.ds_kind != NRG_DS_SKIPLIST) return NRG_E_INVAL;
-    *n = c->sl.cap;
-    return NRG_OK;
-}
+int nrg_skiplist_capacity(nrg_ctx* c, uint64_t* n) { return capacity_common(c, NRG_DS_SKIPLIST, n); }
 
 }  // extern "C"

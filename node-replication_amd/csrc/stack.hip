@@ -919,19 +919,6 @@ __global__ __launch_bounds__(DG_TPB) void st_grow_kernel(const u32* __restrict__
     if (r < n) to[r] = from[r];
 }
 
-// The stack's exact length (the deferred finish publishes it), clamped as nrg_stack_len clamps it.
-// Drains the stream.
-static hipError_t st_exact_len(nrg_ctx* c, u64* n) {
-    long long d = 0;
-    hipError_t e = st_flush(c);
-    if (e == hipSuccess) e = hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return e;
-    if (d < 0) d = 0;
-    *n = (u64)d > c->cfg.stack_capacity ? c->cfg.stack_capacity : (u64)d;
-    return hipSuccess;
-}
-
 // Steps, in stream order: the deferred finish of the last chunk commits into the old buffer; the
 // copy; then the stream is synchronised (there is no stream-ordered free), the old buffer freed and
 // the new one installed, with the capacity every launch and clamp reads (cfg.stack_capacity). If the
@@ -961,45 +948,17 @@ static hipError_t st_grow(nrg_ctx* c, u64 new_cap) {
     return hipSuccess;
 }
 
-// the capacity automatic growth goes to for `need` elements: at least double, clipped to the bound
-static u64 st_grown(const nrg_ctx* c, u64 need) {
-    u64 want = 2 * c->cfg.stack_capacity;
-    if (want < need) want = need;
-    return want > c->st.max_items ? c->st.max_items : want;
-}
-
-// The growth policy, as hm_room's. The n records about to be replayed are added to the upper bound
-// len_ub; only when the bound passes the capacity is the exact length read (the deferred finish, an
-// 8-B copy and a stream synchronise), and only if exact + n still passes it does the buffer grow.
-// A balanced Push/Pop stream re-reads its length now and then and never reallocates. At the bound
-// the stack is a fixed one: nothing is read, and a chunk that overflows latches ERR_CAPACITY as it
-// always did. The decision depends on the log prefix, the chunking and the bound alone, so replicas
-// that replay the same log in the same chunks grow at the same record.
-static hipError_t st_room(nrg_ctx* c, u64 n) {
-    StHost& s = c->st;
-    if (!s.max_items || c->cfg.stack_capacity >= s.max_items) return hipSuccess;
-    if (s.len_ub + n <= c->cfg.stack_capacity) {
-        s.len_ub += n;
-        return hipSuccess;
-    }
-    u64 exact = 0;
-    timer_begin(c, "st_room");  // (nrg_kernel_time counts the re-reads)
-    hipError_t e = st_exact_len(c, &exact);
-    timer_end(c, "st_room");
-    if (e != hipSuccess) return e;
-    if (exact + n > c->cfg.stack_capacity && (e = st_grow(c, st_grown(c, exact + n))) != hipSuccess) return e;
-    s.len_ub = exact + n;
-    return hipSuccess;
-}
-
 // One chunk: its tile pass, fused with the previous chunk's finish in one launch. The chunk's
 // own finish runs in the next chunk's launch (config.pipeline = 1, until nrg_join or a sync)
 // or right away.
 static hipError_t st_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
     if (n == 0) return st_flush(c);  // an empty round still completes the last round's deferred finish
-    const hipError_t eg = st_room(c, n);  // the buffer grows first if it has to (one comparison if not)
-    if (eg != hipSuccess) return eg;
+    // the buffer grows first if it has to (one comparison if not)
+    if (!growth_fits(c->growth, c->cfg.stack_capacity, n)) {
+        const hipError_t eg = room(c, n, "st_room");
+        if (eg != hipSuccess) return eg;
+    }
     StPass A = st_pass(c, c->st.par);
     A.src = (const nrg_stack_op*)src;
     A.lo = lo;
@@ -1087,12 +1046,16 @@ static hipError_t st_digest(nrg_ctx* c, u64* d_out3) {
 }
 
 // ---- nrg_snapshot_async / nrg_restore: the elements, bottom first --------------------------------
+// The one reader of the length (the snapshot's item count, the growth policy's exact length,
+// nrg_stack_len). Drains the stream.
 static int st_items(nrg_ctx* c, u64* n) {
     long long d = 0;
     HIPCHK(st_flush(c));  // a deferred chunk finish publishes the length
     HIPCHK(hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (d < 0) d = 0;  // clamped as nrg_stack_len clamps it
+    // an overflowing chunk latches ERR_CAPACITY once but keeps counting: never report (or let
+    // dump/peek copy) more elements than the allocation holds
+    if (d < 0) d = 0;
     *n = (u64)d > c->cfg.stack_capacity ? c->cfg.stack_capacity : (u64)d;
     return NRG_OK;
 }
@@ -1126,32 +1089,21 @@ __global__ __launch_bounds__(DG_TPB) void st_restore_kernel(u32* stack, const u3
 }
 
 static int st_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
-    // with a growth bound the image may be as large as the bound: the buffer grows first
-    if (check_only)
-        return items <= std::max<u64>(c->cfg.stack_capacity, c->st.max_items) ? NRG_OK : NRG_E_CAPACITY;
-    if (!d_payload) items = 0;
-    if (items > c->cfg.stack_capacity) HIPCHK(st_grow(c, st_grown(c, items)));
+    int r;
+    if (restore_room(c, d_payload, &items, check_only, &r)) return r;
     c->st.pend.valid = false;
     NRG_LAUNCH(c, "st_restore", st_restore_kernel, dg_grid(items), DG_TPB, 0, c->stream, c->st.d_stack,
                (const u32*)d_payload, items, c->d_ctl);
-    c->st.len_ub = items;
+    c->growth.len_ub = items;
     return hip_fail(hipGetLastError());
 }
 
-// nrg_set_max_capacity: the bound, and the length bound restarts from the exact length
-static int st_set_max(nrg_ctx* c, u64 max_items) {
-    if (max_items && (max_items < c->cfg.stack_capacity || max_items >= (1ull << 31))) return NRG_E_INVAL;
-    u64 exact = 0;
-    HIPCHK(st_exact_len(c, &exact));
-    c->st.max_items = max_items;
-    c->st.len_ub = exact;
-    return NRG_OK;
-}
+static u64 st_capacity(const nrg_ctx* c) { return c->cfg.stack_capacity; }
 
 const DsOps* st_ops() {
     static const DsOps ops = {sizeof(nrg_stack_op), sizeof(uint32_t), st_open, st_close, st_flush, st_replay_chunk,
                               floor_ltail, nullptr, st_dbg_words, nullptr, st_digest,
-                              st_items, st_snapshot, st_restore, st_set_max};
+                              st_items, st_snapshot, st_restore, (1ull << 31) - 1, st_capacity, st_grow, true};
     return &ops;
 }
 
@@ -1178,37 +1130,18 @@ int nrg_stack_init(nrg_ctx* c, const uint32_t* vals, uint64_t n) {
     // the depth slot the next chunk starts from (a chunk of parity p reads slot p ^ 1)
     HIPCHK(hipMemcpyAsync(&c->d_ctl->depth0 + (c->st.par ^ 1), &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
     HIPCHK(sync_all(c));
-    c->st.len_ub = n;
+    c->growth.len_ub = n;
     return NRG_OK;
 }
 
-int nrg_stack_reserve(nrg_ctx* c, uint64_t n_elems) {
-    int r = need(c, NRG_DS_STACK);
-    if (r) return r;
-    if (n_elems >= (1ull << 31)) return NRG_E_INVAL;  // nrg_open's bound
-    if (n_elems <= c->cfg.stack_capacity) return NRG_OK;
-    HIPCHK(st_grow(c, n_elems));
-    return NRG_OK;
-}
+int nrg_stack_reserve(nrg_ctx* c, uint64_t n_elems) { return reserve_common(c, NRG_DS_STACK, n_elems); }
 
-int nrg_stack_capacity(nrg_ctx* c, uint64_t* n) {
-    if (!c || !n || c->cfg.ds_kind != NRG_DS_STACK) return NRG_E_INVAL;
-    *n = c->cfg.stack_capacity;
-    return NRG_OK;
-}
+int nrg_stack_capacity(nrg_ctx* c, uint64_t* n) { return capacity_common(c, NRG_DS_STACK, n); }
 
 int nrg_stack_len(nrg_ctx* c, uint64_t* n) {
     int r = need(c, NRG_DS_STACK);
     if (r) return r;
-    long long d = 0;
-    HIPCHK(flush_deferred(c));  // a deferred chunk finish publishes the length
-    HIPCHK(hipMemcpyAsync(&d, &c->d_ctl->depth, sizeof(d), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_all(c));
-    // an overflowing chunk latches ERR_CAPACITY once but keeps counting: never report (or
-    // let dump/peek copy) more elements than the allocation holds
-    if (d < 0) d = 0;
-    if ((uint64_t)d > c->cfg.stack_capacity) d = (long long)c->cfg.stack_capacity;
-    *n = (uint64_t)d;
+    if ((r = st_items(c, n))) return r;
     return check_err(c);
 }
 

@@ -597,8 +597,6 @@ static void vs_close(nrg_ctx* c) {
     (void)hipFree(c->vs.d_tag);
 }
 
-static hipError_t vs_flush(nrg_ctx*) { return hipSuccess; }  // a chunk defers nothing
-
 // ---- nrg_digest: {count, sum, xor} of dg_item(leaf's first vaddr, leaf entry) over the leaves ----
 // A pool table knows neither its level nor the addresses it maps, so the digest goes top-down, a
 // launch per level, none of which waits on another workgroup. tag[t] = base vaddr of table t |
@@ -693,10 +691,18 @@ static void vs_defaults(nrg_config* cfg) {
 // ---- nrg_snapshot_async / nrg_restore: the pool image [0, ntables) ---------------------------------
 typedef u64 vs_u64x2 __attribute__((ext_vector_type(2)));  // 16 B moved by one lane
 
+// The one reader of VsState (the snapshot's item count, nrg_vspace_tables and nrg_vspace_dump).
+// Drains the stream.
+static int vs_read_state(nrg_ctx* c, VsState* s) {
+    HIPCHK(hipMemcpyAsync(s, c->vs.d_state, sizeof(*s), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return NRG_OK;
+}
+
 static int vs_items(nrg_ctx* c, u64* n) {
     VsState s{};
-    HIPCHK(hipMemcpyAsync(&s, c->vs.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    int r = vs_read_state(c, &s);
+    if (r) return r;
     *n = s.ntables < c->vs.cap ? s.ntables : c->vs.cap;
     return NRG_OK;
 }
@@ -796,10 +802,12 @@ static hipError_t vs_grow(nrg_ctx* c, u64 new_cap) {
     return hipSuccess;
 }
 
-const DsOps* vs_ops() {
-    static const DsOps ops = {sizeof(nrg_vspace_op), sizeof(nrg_vspace_resp), vs_open, vs_close, vs_flush,
+static u64 vs_capacity(const nrg_ctx* c) { return c->vs.cap; }
+
+const DsOps* vs_ops() {  // (reserve only: the tables a chunk needs are known on the device alone)
+    static const DsOps ops = {sizeof(nrg_vspace_op), sizeof(nrg_vspace_resp), vs_open, vs_close, nullptr,
                               vs_replay_chunk, floor_ltail, nullptr, nullptr, vs_defaults, vs_digest,
-                              vs_items, vs_snapshot, vs_restore};
+                              vs_items, vs_snapshot, vs_restore, 1ull << 22, vs_capacity, vs_grow, false};
     return &ops;
 }
 
@@ -844,8 +852,8 @@ int nrg_vspace_resolve(nrg_ctx* c, const uint64_t* vaddrs, uint64_t n, uint64_t*
 // tables allocated from the pool
 static int vs_get_tables(nrg_ctx* c, uint64_t* n) {
     VsState s{};
-    HIPCHK(hipMemcpyAsync(&s, c->vs.d_state, sizeof(s), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(sync_all(c));
+    int r = vs_read_state(c, &s);
+    if (r) return r;
     *n = s.ntables;
     if (s.ntables > c->vs.cap) return NRG_E_HIP;  // (the allocation passes never hand out more than the pool holds)
     return check_err(c);
@@ -858,20 +866,9 @@ int nrg_vspace_tables(nrg_ctx* c, uint64_t* n) {
     return vs_get_tables(c, n);
 }
 
-int nrg_vspace_reserve(nrg_ctx* c, uint64_t n_tables) {
-    int r = need(c, NRG_DS_VSPACE);
-    if (r) return r;
-    if (n_tables > (1ull << 22)) return NRG_E_INVAL;  // nrg_open's bound
-    if (n_tables <= c->vs.cap) return NRG_OK;
-    HIPCHK(vs_grow(c, n_tables));
-    return NRG_OK;
-}
+int nrg_vspace_reserve(nrg_ctx* c, uint64_t n_tables) { return reserve_common(c, NRG_DS_VSPACE, n_tables); }
 
-int nrg_vspace_capacity(nrg_ctx* c, uint64_t* n) {
-    if (!c || !n || c->cfg.ds_kind != NRG_DS_VSPACE) return NRG_E_INVAL;
-    *n = c->vs.cap;
-    return NRG_OK;
-}
+int nrg_vspace_capacity(nrg_ctx* c, uint64_t* n) { return capacity_common(c, NRG_DS_VSPACE, n); }
 
 int nrg_test_vspace_table(nrg_ctx* c, uint64_t table, uint64_t out[512]) {
     int r = need(c, NRG_DS_VSPACE);
