@@ -4,7 +4,7 @@ it is made of, and one group-wide seek.
 Three ways through the same ops, alternating window by window so that drift hits all of them alike:
   direct    nrg_skiplist_round_async + nrg_skiplist_get_async on a plain replica
   identity  nrg_group_partitioned_round on a one-rank group: the owner's replay reads the caller's
-            records and answers into the caller's buffers (group.cpp pt_ident)
+            records and answers into the caller's buffers (group.hpp pt_ident)
   moving    the same with NRG_KNOB_EXP bit 16: partition copy on the side stream, route-back launch
 Shapes are microbench/skiplist_round.py's (generate_sops_concurrent, benches/lockfree.rs:128-154): N ops
 per round, 10 % and 100 % Push(random u64, random u64), the rest Get(random u64), on a map prefilled

@@ -1,0 +1,159 @@
+// group_plan.hpp — what a replica group decides from the words its ranks exchanged, as pure host
+// arithmetic: no HIP header and no RCCL header, so tests/group_plan.cpp checks it without a GPU.
+// Every rank runs these on the same exchanged words and so reaches the same code, the same plan and
+// the same byte offsets before any payload moves; group.cpp, group_partitioned.cpp and
+// group_reads.cpp do the waiting, the collectives and the launches around them.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/nrgpu.h"
+
+namespace nrg {
+namespace grp {
+
+// ---- replicated rounds (group.cpp) ----------------------------------------------------------------
+
+// the splitmix64 finaliser (common.hpp mix64, which needs the HIP header for its qualifiers)
+inline uint64_t plan_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// fingerprint of a round's segment lengths (every rank must pass the same ones)
+inline uint64_t lens_fp(const std::vector<uint64_t>& lens) {
+    uint64_t h = 0x9E3779B97F4A7C15ull ^ lens.size();
+    for (uint64_t l : lens) h = plan_mix64(h ^ l) + 0x632BE59BD9B4E019ull;
+    return h;
+}
+
+// the common stride of a round's segments: the longest
+inline uint64_t lens_stride(const std::vector<uint64_t>& lens) {
+    uint64_t stride = 0;
+    for (uint64_t l : lens) stride = l > stride ? l : stride;
+    return stride;
+}
+
+// ---- partitioned rounds (group_partitioned.cpp) ---------------------------------------------------
+
+// Exchange words per rank (u64) of a partitioned round: [0, G) Puts per owner, [G, 2G) Gets per
+// owner, then
+enum : uint64_t {
+    XW_PREV = 0,    // 1 when this rank wants its Puts' previous values
+    XW_RP_CAP = 1,  // received Puts its buffers hold now
+    XW_RK_CAP = 2,  // received Get keys its buffers hold now
+    XW_ERR = 3,     // -NRG_E_* of a local failure before the exchange, else 0
+    XW_KIND = 4,    // the member's data structure (NRG_DS_*): every rank's must be the same
+    XW_N = 5,
+};
+
+// The exchanged matrix H holds G rows of xw_cw(G) words, in rank order.
+inline uint64_t xw_cw(int G) { return 2 * (uint64_t)G + XW_N; }
+inline uint64_t xw_puts(const uint64_t* H, int G, int s, int o) { return H[(size_t)s * xw_cw(G) + o]; }      // s -> owner o
+inline uint64_t xw_gets(const uint64_t* H, int G, int s, int o) { return H[(size_t)s * xw_cw(G) + G + o]; }
+inline uint64_t xw_word(const uint64_t* H, int G, int s, uint64_t k) { return H[(size_t)s * xw_cw(G) + 2 * G + k]; }
+
+// What every rank concludes from H before any payload moves.
+struct PlanAgree {
+    int rc = NRG_OK;     // the code every rank returns: the first XW_ERR in rank order, or mixed kinds
+    uint64_t kind = 0;   // the group's kind (rc == NRG_OK)
+    bool any_prev = false;  // some rank wants previous values
+    bool any_grow = false;  // some rank receives more than its buffers hold: all confirm the growth
+};
+
+inline PlanAgree plan_agree(const uint64_t* H, int G) {
+    PlanAgree A;
+    for (int s = 0; s < G; s++)
+        if (xw_word(H, G, s, XW_ERR)) {
+            A.rc = -(int)xw_word(H, G, s, XW_ERR);  // the same answer on every rank
+            return A;
+        }
+    for (int s = 1; s < G; s++)
+        if (xw_word(H, G, s, XW_KIND) != xw_word(H, G, 0, XW_KIND)) {
+            A.rc = NRG_E_INVAL;  // hashmap and skip-list ranks in one group
+            return A;
+        }
+    A.kind = xw_word(H, G, 0, XW_KIND);
+    for (int s = 0; s < G; s++) {
+        A.any_prev |= xw_word(H, G, s, XW_PREV) != 0;
+        uint64_t rp = 0, rk = 0;  // what rank s receives
+        for (int o = 0; o < G; o++) {
+            rp += xw_puts(H, G, o, s);
+            rk += xw_gets(H, G, o, s);
+        }
+        A.any_grow |= rp > xw_word(H, G, s, XW_RP_CAP) || rk > xw_word(H, G, s, XW_RK_CAP);
+    }
+    return A;
+}
+
+// A round's send/recv plan of one rank (stage A), kept for its answers (stage B): the rank sends its
+// owner-o region to o and receives rank s's group for it at offset sum_{s' < s} (rank order = the
+// global log order).
+struct PtPlan {
+    std::vector<uint64_t> pto, gto, pfrom, gfrom, pfrom_off, gfrom_off;
+    uint64_t rp = 0, rk = 0;  // received Puts and Get keys in all
+    uint64_t sp = 0, sk = 0;  // sent in all: the rank's own n and n_gets, if its partition agrees
+};
+
+inline void plan_for(const uint64_t* H, int G, int r, PtPlan& P) {
+    P.pto.assign(G, 0), P.gto.assign(G, 0), P.pfrom.assign(G, 0), P.gfrom.assign(G, 0);
+    P.pfrom_off.assign(G, 0), P.gfrom_off.assign(G, 0);
+    uint64_t a = 0, b = 0, cq = 0, d = 0;
+    for (int o = 0; o < G; o++) {
+        P.pto[o] = xw_puts(H, G, r, o);
+        P.gto[o] = xw_gets(H, G, r, o);
+        P.pfrom[o] = xw_puts(H, G, o, r);
+        P.gfrom[o] = xw_gets(H, G, o, r);
+        a += P.pto[o], b += P.gto[o];
+        P.pfrom_off[o] = cq, cq += P.pfrom[o];
+        P.gfrom_off[o] = d, d += P.gfrom[o];
+    }
+    P.sp = a;
+    P.sk = b;
+    P.rp = cq;
+    P.rk = d;
+}
+
+constexpr uint64_t GC_FROM_HEAD = 32 * 256;  // nr/src/log.rs:36 (the ring keeps this much free)
+
+// The most Puts an owner replays in one call: its max_batch, within what the log's ring takes.
+inline uint64_t replay_chunk(uint64_t log_size, uint64_t max_batch) {
+    const uint64_t ring_room = log_size > 2 * GC_FROM_HEAD ? log_size - GC_FROM_HEAD : GC_FROM_HEAD;
+    return std::max<uint64_t>(1, std::min<uint64_t>(max_batch, ring_room));
+}
+
+// ---- group-wide skip-list reads (group_reads.cpp) -------------------------------------------------
+
+constexpr uint64_t SK_SCAN_MAX_SLOTS = 1ull << 27;  // G * nmax * limit of a scan (include/nrgpu.h)
+
+// A rank's flags word of the {n, flags} exchange: its bad arguments, the seek mode, a scan's limit
+// (1 .. 1024) in bits 16..26 (a seek and a range count leave them zero) and its kind.
+inline uint64_t sk_flags(bool bad, bool count, uint32_t mode, bool scan, uint32_t limit, uint32_t kind) {
+    return (bad ? 1 : 0) | ((uint64_t)(count ? 0 : mode) << 8) | ((uint64_t)(scan ? limit & 0x7FFu : 0) << 16) |
+           ((uint64_t)kind << 40);
+}
+
+// H: {n, flags} of every rank. No rank's arguments are bad and every rank's flags are the same.
+inline int sk_flags_agree(const uint64_t* H, int G) {
+    for (int r = 0; r < G; r++)
+        if ((H[2 * r + 1] & 1) || H[2 * r + 1] != H[1]) return NRG_E_INVAL;
+    return NRG_OK;
+}
+
+// a scan's candidate scratch (nmax < 2^32, G <= 64 and limit <= 1024: the product cannot wrap)
+inline bool sk_scan_fits(int G, uint64_t nmax, uint32_t limit) { return (uint64_t)G * nmax * limit <= SK_SCAN_MAX_SLOTS; }
+
+// the lane group of a scan's query: the power of two at or above its G * limit candidate slots, up to a wave
+inline uint32_t scan_lane_log2(int G, uint32_t limit) {
+    uint32_t lw = 0;
+    while (lw < 6 && (1ull << lw) < (uint64_t)G * limit) lw++;
+    return lw;
+}
+
+}  // namespace grp
+}  // namespace nrg

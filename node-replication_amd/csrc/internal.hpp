@@ -329,7 +329,7 @@ struct nrg_ctx {
 
     uint64_t rounds = 0;  // replay rounds launched (statistics)
     // set only through nrg_test_set_knob (include/nrgpu_testing.h)
-    uint32_t exp = 0;       // NRG_KNOB_EXP: 2 phase timestamps, 0x10000 group.cpp pt_ident
+    uint32_t exp = 0;       // NRG_KNOB_EXP: 2 phase timestamps, 0x10000 group.hpp pt_ident
     bool pipeline = false;  // a chunk's deferred work waits for the next launch, nrg_join or a sync
     uint32_t stall = 0;     // NRG_KNOB_STALL (tests): 1 odd waves sleep at LDS reuse points, 2 (synthetic,
                             // diagnostic: wrong results) without the bucket pass's tile-map barrier

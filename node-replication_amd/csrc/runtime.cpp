@@ -707,7 +707,7 @@ extern "C" int nrg_test_set_knob(nrg_ctx* c, int knob, uint64_t v) {
     HIPCHK(sync_all(c));  // deferred work of the old setting completes first
     switch (knob) {
         case NRG_KNOB_EXP: {
-            if (v & ~0x10002ull) return NRG_E_INVAL;  // 2: phase timestamps, 0x10000: group.cpp pt_ident
+            if (v & ~0x10002ull) return NRG_E_INVAL;  // 2: phase timestamps, 0x10000: group.hpp pt_ident
             c->exp = (uint32_t)v;
             // the kind's timestamp buffer
             const uint64_t words = (c->exp & 2) && c->ops->dbg_words ? c->ops->dbg_words(c) : 0;

@@ -783,7 +783,7 @@ static int sl_extract(nrg_ctx* c, u64 lo, u64 hi, uint64_t* keys, uint64_t* vals
     return NRG_OK;
 }
 
-// The read kernels for the replica group's group-wide reads (group.cpp): the queries and the answers
+// The read kernels for the replica group's group-wide reads (group_reads.cpp): the queries and the answers
 // live in the group's scratch, so max_reads (the bound of the entry points' staging) does not apply.
 hipError_t sl_seek_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u64* d_okeys, u64* d_ovals, uint8_t* d_found) {
     if (n == 0) return hipSuccess;
