@@ -86,8 +86,8 @@ extern "C" {
 #define NRG_DS_VSPACE 5u    /* four-level page table: Map/MapDevice, Identify  benches/vspace.rs:483-526 */
 #define NRG_DS_SKIPLIST 6u  /* ordered map u64 -> u64 (SkipMap): Push(k, v) / Get, seek, range
                                benches/lockfree.rs:73-97, benches/lockfree_partitioned.rs:86-118 */
-#define NRG_DS_MEMFS 7u     /* file store: Write / Read / GetAttr on files of fixed size, reads through
-                               the log   benches/memfs.rs:24-85, :194-292 */
+#define NRG_DS_MEMFS 7u     /* file store: Write / Read / GetAttr / SetAttr on files of fixed capacity, reads
+                               through the log   benches/memfs.rs:24-85, :194-292 */
 
 /* ---- log record layouts (one WriteOperation each) --------------------------------- */
 /* NrHashMap WriteOperation::Put(key, val)               benches/hashmap.rs:52-56;
@@ -172,12 +172,26 @@ typedef struct {
  * nothing changes and NRG_E_INVAL is latched once (the page table's rule for a record outside its
  * domain); an ino outside the range: some = 0, n = NRG_MEMFS_ENOENT; then the Write's range. Every
  * error response has data all zero.
- * Out of scope: directories, names, inode creation and removal, rename; file growth and truncate
- * (SetAttr; the size is fixed at open, all either benchmark exercises); benches/nrfs.rs's whole-file
- * 4096-byte ops; the combiner, partitioned groups and growth (NRG_E_INVAL from their entry points). */
+ * SIZES (OperationWr::SetAttr{ino, new_attrs}, memfs.rs:26-85, dispatched at :210-213; the file system
+ * behind it grows a file when a Write ends past its end). Off unless nrg_memfs_enable_sizes was called:
+ * without it everything above holds byte for byte and op 3 is the unknown op it always was. With it a
+ * file has a CAPACITY B and a SIZE 0 .. B (B when sizes are enabled), defined as POSIX pwrite / pread /
+ * ftruncate, every op evaluated at its own log position:
+ *   WRITE    valid exactly when offset + len <= B, as above; with len > 0, size = max(size, offset + len),
+ *            and a gap between the old size and offset reads as zero.
+ *   READ     n = offset >= size ? 0 : min(len, size - offset).
+ *   GETATTR  n = size.
+ *   SETATTR  offset carries the new size s; len and data are ignored (but len > 128 is EINVAL, first).
+ *            After the EINVAL and ENOENT checks: s > B: some = 0, n = NRG_MEMFS_EFBIG, nothing changes.
+ *            Else some = 1, n = s (Attr: the size), data zero; size = s. Bytes [s, old size) are gone;
+ *            where s is above the old size the new bytes read as zero.
+ * Out of scope: directories, names, inode creation and removal, rename; capacity growth past B; the
+ * SetAttrRequest fields other than the size; benches/nrfs.rs's whole-file 4096-byte ops; the combiner,
+ * partitioned groups and nrg_set_max_capacity for this kind (NRG_E_INVAL from their entry points). */
 #define NRG_MEMFS_WRITE 0u   /* OperationWr::Write{ino, offset, data[0..len)}  memfs.rs:66-72  */
 #define NRG_MEMFS_READ 1u    /* OperationWr::Read{ino, offset, size = len}      memfs.rs:73-78  */
-#define NRG_MEMFS_GETATTR 2u /* OperationWr::GetAttr{ino}: n = B                memfs.rs:27-29  */
+#define NRG_MEMFS_GETATTR 2u /* OperationWr::GetAttr{ino}: n = B, or the size    memfs.rs:27-29  */
+#define NRG_MEMFS_SETATTR 3u /* OperationWr::SetAttr{ino, size = offset}; sized contexts only  memfs.rs:30-33 */
 #define NRG_MEMFS_FIRST_INO 5u /* the ino of the benchmark's file                memfs.rs:117-119 */
 #define NRG_MEMFS_ENOENT 1u
 #define NRG_MEMFS_EFBIG 2u
@@ -821,6 +835,32 @@ int nrg_memfs_pread_async(nrg_ctx* ctx, const nrg_memfs_rd* d_reqs, uint64_t n, 
                           uint64_t* d_offs /* n + 1 */, uint8_t* d_some /* n */);
 int nrg_memfs_pread(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, uint8_t* data, uint64_t cap,
                     uint64_t* offs /* n + 1 */, uint8_t* some /* n */);
+/* Sizes (see nrg_memfs_op above): from here on the context's files have sizes, NRG_MEMFS_SETATTR is an
+ * op, Writes grow and Reads / GetAttr see the size. Every size starts as B, so the state described is
+ * the one found. Synchronous, idempotent, no way back. NRG_E_NOT_SYNCED while ltail < tail. Replicas of
+ * one log must enable sizes at the same log index (nrg_memfs_init's rule). With sizes enabled:
+ *   nrg_memfs_init   additionally sets size = max(size, len).
+ *   nrg_memfs_read, nrg_memfs_pread*   clip at the size instead of B.
+ *   nrg_memfs_dump   *n = size, and that many bytes.
+ *   nrg_digest       today's items plus one per file: key file << 32 | 0xFFFFFFFF (no word index reaches
+ *                    it), value the size.
+ *   snapshots        the payload is followed by the F sizes as u64: items = F * B / 8 + F
+ *                    (nrg_snapshot_size and nrg_snapshot_info_read say so). nrg_restore takes an image of
+ *                    F * B / 8 items as before (a sized context stays sized, every size B) and one of
+ *                    F * B / 8 + F items as a sized image: the context becomes sized; NRG_E_INVAL, the
+ *                    files as at open, if a size is above B or a byte at or past a file's size is not
+ *                    zero (checked on the device before the digests are compared).
+ *   groups           nrg_group_resync carries the sizes in the image; a replicated round replays the
+ *                    SetAttr records like any others. Enable sizes on every member (nrg_group_replica)
+ *                    at the same log index. */
+int nrg_memfs_enable_sizes(nrg_ctx* ctx);
+/* *size = the size of file `ino` as replayed so far (does not need ltail == tail). NRG_E_INVAL: sizes not
+ * enabled, or an ino outside the range. Synchronous. */
+int nrg_memfs_size(nrg_ctx* ctx, uint64_t ino, uint64_t* size);
+/* What a logged SetAttr{ino, size} does, directly and with no log traffic, for seeding short or empty
+ * files as nrg_memfs_init seeds bytes (replicas of one log must be given the same). NRG_E_INVAL: sizes
+ * not enabled, an ino outside the range or size > B; NRG_E_NOT_SYNCED while ltail < tail. Synchronous. */
+int nrg_memfs_truncate(nrg_ctx* ctx, uint64_t ino, uint64_t size);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's

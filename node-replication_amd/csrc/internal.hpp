@@ -232,6 +232,20 @@ struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, conti
     uint64_t* d_desc = nullptr;  // [max_batch] record descriptors
     // scratch of one nrg_memfs_pread_async: [ceil(max_reads / 1024)] scan-tile aggregates
     uint64_t* d_pagg = nullptr;
+    // Sizes (nrg_memfs_enable_sizes; nullptr: the context is unsized and none of the below exists)
+    uint64_t* d_size = nullptr;  // [F] every file's size; stored bytes at or past it are zero
+    uint32_t file_bits = 0;      // ceil(log2 F): what a sized chunk's file sort sorts by
+    uint32_t epoch = 0;          // sized chunks replayed: stamps d_fm's entries
+    bool unsized_image = false;  // nrg_restore loaded an unsized image: its digest comparison, the next
+                                 // digest taken, leaves the size items out
+    // scratch of one sized chunk
+    uint32_t* d_fkey = nullptr;  // [max_batch] a record's file
+    uint32_t* d_el = nullptr;    // [max_batch] a record's function on the size
+    void* d_sc = nullptr;        // [max_batch] {size before the record, shrinks of its file before it}
+    uint32_t* d_ev = nullptr;    // [max_batch] shrink targets, per file in log order
+    void* d_fm = nullptr;        // [F] {first grouped position, shrinks, smallest target, new size}
+    uint32_t* d_fep = nullptr;   // [F] the epoch of the chunk that wrote d_fm's entry
+    void* d_sagg = nullptr;      // [max_batch / 1024 + 1] scan-tile aggregates
 };
 
 struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*

@@ -16,7 +16,8 @@
 // in this order: len > 128 or an unknown op (EINVAL, latched), then the ino (ENOENT), then the
 // Write's range (EFBIG).
 // Out of scope: directories, names, inode creation and removal, rename.
-// Out of scope: file growth and truncate (SetAttr): the size is fixed at open.
+// Sizes (SetAttr as ftruncate, Writes that grow a file) are off unless nrg_memfs_enable_sizes was called:
+// the section "Sizes" below. Out of scope: capacity growth past B, the other SetAttrRequest fields.
 // Out of scope: benches/nrfs.rs's whole-file 4096-byte FileWrite (a record carries at most 128 bytes);
 // its read-only FileRead is nrg_memfs_pread* below, which goes through no log record.
 // Out of scope: the combiner, partitioned groups and growth (nrg_set_max_capacity).
@@ -225,6 +226,420 @@ __global__ __launch_bounds__(DG_TPB) void mf_fill_kernel(u64* words, u64 n) {
         words[i] = 0x0101010101010101ull;
 }
 
+// ---- Sizes (nrg_memfs_enable_sizes): SetAttr { ino, new_attrs } of benches/memfs.rs:26-85, :210-213 as
+// ---- ftruncate, and Writes that grow a file ------------------------------------------------------------
+// A file has a size 0 .. B beside its capacity B, and EVERY STORED BYTE AT OR PAST THE SIZE IS ZERO. So
+// growth and holes cost nothing, a Read is the unsized Read clipped at the size, and only a shrink has to
+// erase. A Read's clip, a GetAttr's answer and whether a SetAttr shrinks depend on the size at the
+// record's own log position, so a chunk of a sized context runs, in stream order:
+//   mfs_keys    one lane per record: its file as a sort key and its function on the size, one word:
+//               a valid Write of len > 0 is x -> max(x, offset + len), a valid SetAttr x -> s, every
+//               other record the identity (a record that names no file: file 0).
+//   file sort   sort_pairs on ceil(log2 F) bits, stable: a file's records in log order. None if F == 1.
+//   mfs_reduce / _aggscan / _scan   the segmented exclusive scan of the composed functions over the
+//               grouped records in tiles of MFS_TILE, the shape of mf_pread_reduce / _aggscan / _scan;
+//               one segment may be the whole chunk. The scan element (mfs_then) carries the size
+//               function {constant or max, v}, the shrinks already decided k, their smallest target m
+//               and at most one undecided SetAttr t, which shrinks exactly when t < the size at the
+//               segment's start; composition is associative, not commutative. _scan evaluates each
+//               record's prefix at the file's stored size: sc[i] = {size before, shrinks before},
+//               stores a shrink's target at ev[fstart + shrinks before] (fstart: the segment's first
+//               grouped position), and the segment's last record writes fm[file] = {fstart, shrinks,
+//               smallest target, new size}, stamped with the chunk's epoch. Nothing writes size[] here:
+//               every lane of the scan may still read it.
+//   mfs_expand  mf_expand with the size before the record for B in Read and GetAttr, and SetAttr.
+//   line sort   as above.
+//   mfs_lines   mf_lines plus the shrinks. A run's op carries the shrinks of its file before it; when
+//               that count passes the count already applied (c0), the wave first zeroes its bytes at or
+//               past the smallest target of ev[fstart + c0, fstart + count): right there, since no op
+//               touched the line in between and what grew the file afterwards touched other lines or
+//               comes later in the run. The check sits in the apply order, not with the MF_AHEAD loads.
+//               After the run come the remaining shrinks; a line with no run is cut at fm's smallest
+//               target. The range minimum is a forward walk of the file's list, 64 targets per step and
+//               one wave reduction: a chunk of E shrinks of one file costs a touched line E / 64 loads
+//               and at most min(E, run) reductions. The wave of a file's first line stores the new size.
+// What the sized kernels share.
+struct MfSz {
+    u64* size;        // [F] every file's size; bytes at or past it are zero
+    u32* fkey;        // [n] a record's file (0 for a record that names none)
+    u32* el;          // [n] a record's function on the size: MFS_CST | s, or the a of max(., a)
+    uint2* sc;        // [n] {the size before the record, the shrinks of its file before it in the chunk}
+    u32* ev;          // shrink targets, a file's at [fstart, fstart + nev) in log order
+    uint4* fm;        // [F] {fstart, nev, the smallest target, the new size} of a file the chunk names
+    u32* fep;         // [F] the epoch of the chunk that wrote fm last
+    uint4* agg;       // [tiles] scan-tile aggregates
+    u32 epoch;
+};
+
+// the smallest of ev[c0, c1), the same in every lane (c0 < c1, uniform)
+__device__ __forceinline__ u32 mfs_range_min(const u32* __restrict__ ev, u32 c0, u32 c1, u32 lane) {
+    u32 mn = 0xFFFFFFFFu;
+    for (u32 q = c0 + lane; q < c1; q += 64) mn = min(mn, ev[q]);
+#pragma unroll
+    for (u32 d = 32; d; d >>= 1) mn = min(mn, (u32)__shfl_xor((int)mn, (int)d, 64));
+    return mn;
+}
+
+constexpr u32 MFS_ITEMS = 4;
+constexpr u32 MFS_TILE = MF_TPB * MFS_ITEMS;
+constexpr u32 MFS_NONE = 0xFFFFFFFFu;
+constexpr u32 MFS_VMASK = (1u << 30) - 1, MFS_CST = 1u << 30, MFS_HEAD = 1u << 31;
+static_assert((1ull << MF_LOG2_MAX) < MFS_VMASK, "a size fits under the flags");
+
+// The scan element: x = v | MFS_CST (the size becomes v; else max(size, v)) | MFS_HEAD (a segment
+// starts inside), y = k, z = t (MFS_NONE: none; t set implies MFS_CST), w = m (MFS_NONE: none).
+__device__ __forceinline__ uint4 mfs_id() { return make_uint4(0, 0, MFS_NONE, MFS_NONE); }
+
+// F, then G
+__device__ __forceinline__ uint4 mfs_then(uint4 F, uint4 G) {
+    if (G.x & MFS_HEAD) return G;
+    const u32 fv = F.x & MFS_VMASK, gv = G.x & MFS_VMASK;
+    u32 k = F.y + G.y, t = F.z, m = F.w < G.w ? F.w : G.w;
+    if (G.z != MFS_NONE) {  // G's undecided SetAttr meets F's size: v, or max(x, v) >= v
+        if (G.z < fv) k++, m = m < G.z ? m : G.z;
+        else if (!(F.x & MFS_CST)) t = G.z;  // still x's to decide (F has no SetAttr: F.z is none)
+    }
+    const u32 v = (G.x & MFS_CST) ? gv : (fv > gv ? fv : gv);
+    return make_uint4((F.x & MFS_HEAD) | ((F.x | G.x) & MFS_CST) | v, k, t, m);
+}
+
+__device__ __forceinline__ uint4 mfs_shfl_up(uint4 v, u32 d) {
+    return make_uint4(__shfl_up(v.x, d, 64), __shfl_up(v.y, d, 64), __shfl_up(v.z, d, 64), __shfl_up(v.w, d, 64));
+}
+
+// exclusive scan of v over the workgroup's threads under mfs_then, and the workgroup's total. s_w:
+// MF_TPB / 64 elements; a caller that calls again puts a barrier between the calls.
+__device__ __forceinline__ uint4 mfs_block_excl(uint4 v, uint4* s_w, uint4* total) {
+    const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint4 inc = v;
+#pragma unroll
+    for (u32 d = 1; d < 64; d <<= 1) {
+        const uint4 o = mfs_shfl_up(inc, d);
+        if (lane >= d) inc = mfs_then(o, inc);
+    }
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    uint4 base = mfs_id(), tot = mfs_id();
+#pragma unroll
+    for (u32 k = 0; k < MF_TPB / 64; k++) {
+        const uint4 x = s_w[k];
+        if (k < w) base = mfs_then(base, x);
+        tot = mfs_then(tot, x);
+    }
+    *total = tot;
+    uint4 prev = mfs_shfl_up(inc, 1);
+    if (lane == 0) prev = mfs_id();
+    return mfs_then(base, prev);
+}
+
+__global__ __launch_bounds__(MF_TPB) void mfs_keys_kernel(MfJob j, MfSz z) {
+    const u64 i = (u64)blockIdx.x * MF_TPB + threadIdx.x;
+    if (i >= j.n) return;
+    const u64* r = mf_rec(j, i);
+    const u64 ino = r[0], off = r[1], w2 = r[2];
+    const u32 op = (u32)w2, len = (u32)(w2 >> 32);
+    const u64 B = 1ull << j.log2_b;
+    u32 f = 0, e = 0;
+    if (op <= NRG_MEMFS_SETATTR && len <= MF_LINE && ino >= NRG_MEMFS_FIRST_INO && ino - NRG_MEMFS_FIRST_INO < j.nfiles) {
+        f = (u32)(ino - NRG_MEMFS_FIRST_INO);
+        if (op == NRG_MEMFS_WRITE && len && off <= B && len <= B - off) e = (u32)(off + len);
+        if (op == NRG_MEMFS_SETATTR && off <= B) e = MFS_CST | (u32)off;
+    }
+    z.fkey[i] = f;
+    z.el[i] = e;
+}
+
+// Grouped position p of the chunk: its record, its file and its scan element. gk / gv: the sorted file
+// keys and record indices, or nullptr where F == 1 (the log order is the grouped order).
+struct MfsIn {
+    const u32* gk;
+    const u32* gv;
+    u64 n;
+};
+__device__ __forceinline__ uint4 mfs_load(const MfsIn& in, const MfSz& z, u64 p, u32* file, u32* rec) {
+    const u32 f = in.gk ? in.gk[p] : 0;
+    *file = f;
+    *rec = in.gv ? in.gv[p] : (u32)p;
+    const bool head = p == 0 || (in.gk && in.gk[p - 1] != f);
+    const u32 e = z.el[*rec];
+    return make_uint4(e | (head ? MFS_HEAD : 0), 0, (e & MFS_CST) ? (e & MFS_VMASK) : MFS_NONE, MFS_NONE);
+}
+
+// agg[tile] = the composition of the tile's elements
+__global__ __launch_bounds__(MF_TPB) void mfs_reduce_kernel(MfsIn in, MfSz z) {
+    __shared__ uint4 s_w[MF_TPB / 64];
+    const u64 first = (u64)blockIdx.x * MFS_TILE + threadIdx.x * MFS_ITEMS;
+    uint4 acc = mfs_id();
+#pragma unroll
+    for (u32 k = 0; k < MFS_ITEMS; k++) {
+        u32 f, rec;
+        if (first + k < in.n) acc = mfs_then(acc, mfs_load(in, z, first + k, &f, &rec));
+    }
+    uint4 tot;
+    (void)mfs_block_excl(acc, s_w, &tot);
+    if (threadIdx.x == 0) z.agg[blockIdx.x] = tot;
+}
+
+// agg[tile] = the composition of the tiles before it; one workgroup
+__global__ __launch_bounds__(MF_TPB) void mfs_aggscan_kernel(uint4* agg, u32 tiles) {
+    __shared__ uint4 s_w[MF_TPB / 64];
+    uint4 carry = mfs_id();
+    for (u32 b = 0; b < tiles; b += MF_TPB) {
+        const u32 i = b + threadIdx.x;
+        uint4 tot;
+        const uint4 ex = mfs_block_excl(i < tiles ? agg[i] : mfs_id(), s_w, &tot);
+        if (i < tiles) agg[i] = mfs_then(carry, ex);
+        carry = mfs_then(carry, tot);
+        __syncthreads();
+    }
+}
+
+// the first grouped position of file f (it has one)
+__device__ __forceinline__ u32 mfs_first(const MfsIn& in, u32 f) {
+    if (!in.gk) return 0;
+    u64 lo = 0, hi = in.n;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (in.gk[mid] < f) lo = mid + 1; else hi = mid;
+    }
+    return (u32)lo;
+}
+
+// sc, ev and fm; carried: agg holds the scanned aggregates (more than one tile)
+__global__ __launch_bounds__(MF_TPB) void mfs_scan_kernel(MfsIn in, MfSz z, u32 carried) {
+    __shared__ uint4 s_w[MF_TPB / 64];
+    const u64 first = (u64)blockIdx.x * MFS_TILE + threadIdx.x * MFS_ITEMS;
+    uint4 e[MFS_ITEMS], acc = mfs_id();
+    u32 file[MFS_ITEMS], rec[MFS_ITEMS];
+#pragma unroll
+    for (u32 k = 0; k < MFS_ITEMS; k++) {
+        e[k] = mfs_id(), file[k] = rec[k] = 0;
+        if (first + k < in.n) e[k] = mfs_load(in, z, first + k, &file[k], &rec[k]);
+        acc = mfs_then(acc, e[k]);
+    }
+    uint4 tot;
+    const uint4 ex = mfs_block_excl(acc, s_w, &tot);
+    uint4 run = mfs_then(carried ? z.agg[blockIdx.x] : mfs_id(), ex);
+#pragma unroll
+    for (u32 k = 0; k < MFS_ITEMS; k++) {
+        const u64 p = first + k;
+        if (p < in.n) {
+            const uint4 E = (e[k].x & MFS_HEAD) ? mfs_id() : run;  // the file's records of the chunk before this one
+            const u32 x0 = (u32)z.size[file[k]];
+            const bool pend = E.z != MFS_NONE && E.z < x0;
+            const u32 pv = E.x & MFS_VMASK;
+            const u32 sb = (E.x & MFS_CST) ? pv : (x0 > pv ? x0 : pv);
+            const u32 cb = E.y + (pend ? 1 : 0);
+            z.sc[rec[k]] = make_uint2(sb, cb);
+            const u32 s = e[k].x & MFS_VMASK;
+            const bool shrink = (e[k].x & MFS_CST) && s < sb;
+            const bool last = p + 1 == in.n || (in.gk && in.gk[p + 1] != file[k]);
+            if (shrink || last) {
+                const u32 fs = mfs_first(in, file[k]);
+                if (shrink) z.ev[fs + cb] = s;  // (fs + cb <= p: in bounds)
+                if (last) {
+                    u32 mn = E.w;
+                    if (pend) mn = mn < E.z ? mn : E.z;
+                    if (shrink) mn = mn < s ? mn : s;
+                    const u32 ns = (e[k].x & MFS_CST) ? s : (sb > s ? sb : s);
+                    z.fm[file[k]] = make_uint4(fs, cb + (shrink ? 1 : 0), mn, ns);
+                    z.fep[file[k]] = z.epoch;
+                }
+            }
+        }
+        run = mfs_then(run, e[k]);
+    }
+}
+
+// mf_expand of a sized context: sc[i].x is record i's file's size before the record
+__global__ __launch_bounds__(MF_TPB) void mfs_expand_kernel(MfJob j, const uint2* __restrict__ sc) {
+    __shared__ u64 s_n[MF_TPB];
+    const u32 t = threadIdx.x;
+    const u64 base = (u64)blockIdx.x * MF_TPB;
+    const u32 cnt = j.n - base < MF_TPB ? (u32)(j.n - base) : MF_TPB;
+    bool inval = false;
+    if (t < cnt) {
+        const u64 i = base + t;
+        const u64* r = mf_rec(j, i);
+        const u64 ino = r[0], off = r[1], w2 = r[2];
+        const u32 op = (u32)w2, len = (u32)(w2 >> 32);
+        const u64 B = 1ull << j.log2_b;
+        const u64 size = sc[i].x;
+        u64 nresp;
+        u32 cover = 0;
+        uint8_t sm = 0;
+        bool wr = false;
+        if (op > NRG_MEMFS_SETATTR || len > MF_LINE) {
+            nresp = NRG_MEMFS_EINVAL;
+            inval = true;
+        } else if (ino < NRG_MEMFS_FIRST_INO || ino - NRG_MEMFS_FIRST_INO >= j.nfiles) {
+            nresp = NRG_MEMFS_ENOENT;
+        } else if (op == NRG_MEMFS_GETATTR) {  // Attr(FileAttr): the size
+            nresp = size, sm = 1;
+        } else if (op == NRG_MEMFS_WRITE) {
+            if (off <= B && len <= B - off) nresp = len, cover = len, sm = 1, wr = true;  // Written(len)
+            else nresp = NRG_MEMFS_EFBIG;
+        } else if (op == NRG_MEMFS_SETATTR) {  // Attr: the new size; what a shrink erases is mf_lines' work
+            if (off <= B) nresp = off, sm = 1;
+            else nresp = NRG_MEMFS_EFBIG;
+        } else {  // Data(bytes), clipped at the end of the file
+            nresp = off >= size ? 0 : (len < size - off ? len : size - off);
+            cover = (u32)nresp, sm = 1;
+        }
+        u32 k0 = j.nlines, k1 = j.nlines;
+        u64 d = 0;
+        if (cover) {
+            const u64 start = ((ino - NRG_MEMFS_FIRST_INO) << j.log2_b) + off;  // < 2^29
+            k0 = (u32)(start >> 7);
+            const u32 kl = (u32)((start + cover - 1) >> 7);
+            if (kl != k0) k1 = kl;
+            d = start | ((u64)cover << 32) | ((u64)(wr ? 1 : 0) << 48);
+        }
+        *(uint2*)(j.keys + 2 * i) = make_uint2(k0, k1);
+        j.desc[i] = d;
+        s_n[t] = nresp;
+        const u64 g = j.lo + i;
+        if (j.resp && g >= j.rlo && g < j.rhi) j.some[g - j.rlo] = sm;
+    }
+    if (__any(inval) && (t & 63) == 0) atomicOr(&j.ctl->err, ERR_INVAL);
+    __syncthreads();
+    if (j.src)  // Log::append of a fused round
+        for (u32 w = t; w < cnt * MF_REC_WORDS; w += MF_TPB) {
+            const u32 rec = w / MF_REC_WORDS, q = w - rec * MF_REC_WORDS;
+            j.ring[((j.lo + base + rec) & j.ring_mask) * MF_REC_WORDS + q] = j.src[(base + rec) * MF_REC_WORDS + q];
+        }
+    if (j.resp)
+        for (u32 w = t; w < cnt * MF_RESP_WORDS; w += MF_TPB) {
+            const u32 rec = w / MF_RESP_WORDS, q = w - rec * MF_RESP_WORDS;
+            const u64 g = j.lo + base + rec;
+            if (g >= j.rlo && g < j.rhi) j.resp[(g - j.rlo) * MF_RESP_WORDS + q] = q ? 0 : s_n[rec];
+        }
+}
+
+// mf_lines of a sized context: the same walk, which also applies the chunk's shrinks in log order.
+__global__ __launch_bounds__(MF_TPB) void mfs_lines_kernel(MfJob j, const u32* __restrict__ sk,
+                                                           const u32* __restrict__ sv, u32 m, MfSz z) {
+    const u32 lane = threadIdx.x & 63;
+    const u32 X = __builtin_amdgcn_readfirstlane(blockIdx.x * (MF_TPB / 64) + (threadIdx.x >> 6));
+    if (X >= j.nlines) return;
+    u32 fstart = 0, nev = 0, fmin = 0xFFFFFFFFu, c0 = 0;  // the file's shrinks; c0: those already applied
+    const u32 fx0 = ((X << 7) & ((1u << j.log2_b) - 1)) + 2 * lane;  // this lane's first byte in its file
+    const u32 f = X >> (j.log2_b - 7);
+    if (z.fep[f] == z.epoch) {  // the chunk names the file
+        const uint4 q = z.fm[f];
+        fstart = q.x, nev = q.y, fmin = q.z;
+        if ((X & ((1u << (j.log2_b - 7)) - 1)) == 0 && lane == 0) z.size[f] = q.w;  // the file's first line commits
+    }
+    u32 lo = 0, hi = m;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (sk[mid] < X) lo = mid + 1; else hi = mid;
+    }
+    const u32 r0 = lo;
+    if (r0 >= m || sk[r0] != X) {  // no op of the chunk touches the line
+        if (nev && fmin < (fx0 - 2 * lane) + MF_LINE) {  // a shrink of the chunk cuts it
+            unsigned short* lp = (unsigned short*)(j.files + (u64)X * MF_LINE) + lane;
+            const u32 w = *lp;
+            *lp = (unsigned short)((fx0 >= fmin ? 0 : w & 0xFF) | (fx0 + 1 >= fmin ? 0 : w & 0xFF00));
+        }
+        return;
+    }
+    lo = r0 + 1, hi = m;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (sk[mid] <= X) lo = mid + 1; else hi = mid;
+    }
+    const u32 r1 = lo;
+    unsigned short* lp = (unsigned short*)(j.files + (u64)X * MF_LINE) + lane;
+    const u32 w = *lp;
+    u32 b0 = w & 0xFF, b1 = w >> 8;
+    const u32 gx0 = X * MF_LINE + 2 * lane;  // this lane's first byte in the store
+    uint8_t* const rbytes = (uint8_t*)j.resp;
+    u32 myrec = 0, mycb = 0;  // mycb: the shrinks of the file before the slot's record
+    u64 mydesc = 0;
+    if (r0 + lane < r1) {
+        myrec = sv[r0 + lane] >> 1;
+        mydesc = j.desc[myrec];
+        mycb = z.sc[myrec].y;
+    }
+    for (u32 t0 = r0; t0 < r1; t0 += 64) {
+        const u32 cnt = r1 - t0 < 64 ? r1 - t0 : 64;
+        u32 nrec = 0, ncb = 0;  // the next batch, fetched before this one is walked
+        u64 ndesc = 0;
+        if (t0 + 64 + lane < r1) {
+            nrec = sv[t0 + 64 + lane] >> 1;
+            ndesc = j.desc[nrec];
+            ncb = z.sc[nrec].y;
+        }
+        const u32 dlo = (u32)mydesc, dhi = (u32)(mydesc >> 32);  // (lanes at or past cnt hold 0: no bytes)
+        for (u32 k = 0; k < cnt; k += MF_AHEAD) {
+            u32 rec[MF_AHEAD], rel[MF_AHEAD], cn[MF_AHEAD], d0[MF_AHEAD], d1[MF_AHEAD];
+            bool wr[MF_AHEAD];
+#pragma unroll
+            for (u32 u = 0; u < MF_AHEAD; u++) {
+                const u32 st = __builtin_amdgcn_readlane(dlo, k + u), h = __builtin_amdgcn_readlane(dhi, k + u);
+                rec[u] = __builtin_amdgcn_readlane(myrec, k + u);
+                cn[u] = h & 0xFFFF;
+                wr[u] = (h >> 16) != 0;
+                rel[u] = gx0 - st;  // byte 0's offset into the op (wraps where the op starts later)
+                d0[u] = d1[u] = 0;
+                if (wr[u]) {
+                    const uint8_t* p = (const uint8_t*)(mf_rec(j, rec[u]) + 3);
+                    if (rel[u] < cn[u]) d0[u] = p[rel[u]];
+                    if (rel[u] + 1 < cn[u]) d1[u] = p[rel[u] + 1];
+                }
+            }
+#pragma unroll
+            for (u32 u = 0; u < MF_AHEAD; u++) {
+                const u32 cu = __builtin_amdgcn_readlane(mycb, k + u);
+                if (cu > c0) {  // the shrinks between the run's previous op and this one (slots past cnt: 0)
+                    const u32 tm = mfs_range_min(z.ev + fstart, c0, cu, lane);
+                    b0 = fx0 >= tm ? 0 : b0;
+                    b1 = fx0 + 1 >= tm ? 0 : b1;
+                    c0 = cu;
+                }
+                const bool in0 = rel[u] < cn[u], in1 = rel[u] + 1 < cn[u];
+                if (wr[u]) {
+                    b0 = in0 ? d0[u] : b0;
+                    b1 = in1 ? d1[u] : b1;
+                } else if (cn[u]) {
+                    const u64 g = j.lo + rec[u];
+                    if (rbytes && g >= j.rlo && g < j.rhi) {
+                        uint8_t* o = rbytes + (g - j.rlo) * sizeof(nrg_memfs_resp) + 8;
+                        if (in0) o[rel[u]] = (uint8_t)b0;
+                        if (in1) o[rel[u] + 1] = (uint8_t)b1;
+                    }
+                }
+            }
+        }
+        myrec = nrec, mydesc = ndesc, mycb = ncb;
+    }
+    if (nev > c0) {  // the shrinks after the run's last op
+        const u32 tm = mfs_range_min(z.ev + fstart, c0, nev, lane);
+        b0 = fx0 >= tm ? 0 : b0;
+        b1 = fx0 + 1 >= tm ? 0 : b1;
+    }
+    *lp = (unsigned short)(b0 | (b1 << 8));
+}
+
+// every size B: the state nrg_memfs_enable_sizes describes is the one it found
+__global__ __launch_bounds__(DG_TPB) void mfs_fill_kernel(u64* size, u64 n, u64 B) {
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) size[i] = B;
+}
+
+// nrg_restore of a sized image: ERR_INVAL for a size above B or a non-zero byte at or past a file's size
+__global__ __launch_bounds__(DG_TPB) void mfs_check_kernel(const u64* words, u64 n, u32 log2_wpf, const u64* size,
+                                                           DevCtl* ctl) {
+    bool bad = false;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 sz = size[i >> log2_wpf], off = (i & ((1ull << log2_wpf) - 1)) * 8, w = words[i];
+        if (sz > (8ull << log2_wpf)) bad = true;
+        else if (off >= sz) bad |= w != 0;
+        else if (off + 8 > sz) bad |= (w >> (8 * (sz - off))) != 0;
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&ctl->err, ERR_INVAL);
+}
+
 // ---- read-only reads (nrg_memfs_pread*): Replica::execute -> read_only of nr/src/replica.rs:483-497
 // ---- for benches/nrfs.rs:88-101 OpRd::FileRead, here pread of any length ---------------------------
 // n requests {ino, offset, len} against the store as it stands; the answers packed in request order.
@@ -261,14 +676,16 @@ struct MfRdJob {
     u64 cap;
     const uint8_t* files;
     u32 log2_b, nfiles;
+    const u64* size;  // a sized context's sizes: the clip (nullptr: B)
 };
 
 // request i's clipped length; ok: its ino names a file
 __device__ __forceinline__ u64 mf_rd_count(const MfRdJob& j, u64 i, bool* ok) {
     const u64 ino = j.rq[3 * i], off = j.rq[3 * i + 1], len = j.rq[3 * i + 2];
-    const u64 B = 1ull << j.log2_b;
     *ok = ino >= NRG_MEMFS_FIRST_INO && ino - NRG_MEMFS_FIRST_INO < j.nfiles;
-    return !*ok || off >= B ? 0 : (len < B - off ? len : B - off);
+    if (!*ok) return 0;
+    const u64 B = j.size ? j.size[ino - NRG_MEMFS_FIRST_INO] : 1ull << j.log2_b;
+    return off >= B ? 0 : (len < B - off ? len : B - off);
 }
 
 // exclusive scan of v over the workgroup's threads, and the workgroup's total. s_w: MF_TPB / 64 words;
@@ -455,22 +872,80 @@ static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     j.nlines = s.nlines;
     j.keys = s.d_keys;
     j.desc = s.d_desc;
-    NRG_LAUNCH(c, "mf_expand", mf_expand_kernel, (unsigned)((n + MF_TPB - 1) / MF_TPB), MF_TPB, 0, c->stream, j);
+    const unsigned eg = (unsigned)((n + MF_TPB - 1) / MF_TPB);
+    MfSz z{};
+    if (s.d_size) {  // the sizes at every log position of the chunk ("Sizes" above)
+        if (++s.epoch == 0) {
+            hipError_t e0 = hipMemsetAsync(s.d_fep, 0, s.files * sizeof(u32), c->stream);
+            if (e0 != hipSuccess) return e0;
+            s.epoch = 1;
+        }
+        z = MfSz{s.d_size, s.d_fkey, s.d_el, (uint2*)s.d_sc, s.d_ev, (uint4*)s.d_fm, s.d_fep, (uint4*)s.d_sagg, s.epoch};
+        NRG_LAUNCH(c, "mfs_keys", mfs_keys_kernel, eg, MF_TPB, 0, c->stream, j, z);
+        MfsIn in{nullptr, nullptr, n};
+        if (s.files > 1) {
+            u32 *gk = nullptr, *gv = nullptr;
+            timer_begin(c, "mfs_sort");
+            const hipError_t e1 = sort_pairs(c->sort, s.d_fkey, nullptr, n, (int)s.file_bits, c->stream, &gk, &gv);
+            timer_end(c, "mfs_sort");
+            if (e1 != hipSuccess) return e1;
+            in.gk = gk, in.gv = gv;
+        }
+        const unsigned tiles = (unsigned)((n + MFS_TILE - 1) / MFS_TILE);
+        if (tiles > 1) {
+            NRG_LAUNCH(c, "mfs_reduce", mfs_reduce_kernel, tiles, MF_TPB, 0, c->stream, in, z);
+            NRG_LAUNCH(c, "mfs_aggscan", mfs_aggscan_kernel, 1, MF_TPB, 0, c->stream, z.agg, (u32)tiles);
+        }
+        NRG_LAUNCH(c, "mfs_scan", mfs_scan_kernel, tiles, MF_TPB, 0, c->stream, in, z, tiles > 1 ? 1u : 0u);
+        NRG_LAUNCH(c, "mfs_expand", mfs_expand_kernel, eg, MF_TPB, 0, c->stream, j, (const uint2*)z.sc);
+    } else {
+        NRG_LAUNCH(c, "mf_expand", mf_expand_kernel, eg, MF_TPB, 0, c->stream, j);
+    }
     u32 *sk = nullptr, *sv = nullptr;
     timer_begin(c, "mf_sort");
     const hipError_t e = sort_pairs(c->sort, s.d_keys, nullptr, 2 * n, (int)s.key_bits, c->stream, &sk, &sv);
     timer_end(c, "mf_sort");
     if (e != hipSuccess) return e;
     const u32 per = MF_TPB / 64;
-    NRG_LAUNCH(c, "mf_lines", mf_lines_kernel, (s.nlines + per - 1) / per, MF_TPB, 0, c->stream, j, (const u32*)sk,
-               (const u32*)sv, (u32)(2 * n));
+    if (s.d_size)
+        NRG_LAUNCH(c, "mfs_lines", mfs_lines_kernel, (s.nlines + per - 1) / per, MF_TPB, 0, c->stream, j, (const u32*)sk,
+                   (const u32*)sv, (u32)(2 * n), z);
+    else
+        NRG_LAUNCH(c, "mf_lines", mf_lines_kernel, (s.nlines + per - 1) / per, MF_TPB, 0, c->stream, j, (const u32*)sk,
+                   (const u32*)sv, (u32)(2 * n));
     return hipGetLastError();
 }
 
 static hipError_t mf_fill(nrg_ctx* c) {
     const u64 words = c->mf.files * (1ull << c->mf.log2_b) / 8;
     mf_fill_kernel<<<copy_grid(words), DG_TPB, 0, c->stream>>>((u64*)c->mf.d_files, words);
+    if (c->mf.d_size)
+        mfs_fill_kernel<<<copy_grid(c->mf.files), DG_TPB, 0, c->stream>>>(c->mf.d_size, c->mf.files, 1ull << c->mf.log2_b);
     return hipGetLastError();
+}
+
+// nrg_memfs_enable_sizes: the size table (every size B) and the scratch of a sized chunk. The stream
+// has been drained. On a failed allocation the context stays unsized (mf_close frees what was made).
+static int mf_enable(nrg_ctx* c) {
+    MfHost& s = c->mf;
+    if (s.d_size) return NRG_OK;
+    const u64 mb = c->cfg.max_batch;
+    u64* size = nullptr;
+    HIPCHK(hipMalloc(&s.d_fkey, mb * sizeof(u32)));
+    HIPCHK(hipMalloc(&s.d_el, mb * sizeof(u32)));
+    HIPCHK(hipMalloc(&s.d_sc, mb * sizeof(uint2)));
+    HIPCHK(hipMalloc(&s.d_ev, mb * sizeof(u32)));
+    HIPCHK(hipMalloc(&s.d_fm, s.files * sizeof(uint4)));
+    HIPCHK(hipMalloc(&s.d_fep, s.files * sizeof(u32)));
+    HIPCHK(hipMalloc(&s.d_sagg, (mb / MFS_TILE + 1) * sizeof(uint4)));
+    HIPCHK(hipMalloc(&size, s.files * sizeof(u64)));
+    HIPCHK(hipMemsetAsync(s.d_fep, 0, s.files * sizeof(u32), c->stream));
+    mfs_fill_kernel<<<copy_grid(s.files), DG_TPB, 0, c->stream>>>(size, s.files, 1ull << s.log2_b);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    s.epoch = 0;
+    s.d_size = size;
+    return NRG_OK;
 }
 
 static int mf_open(nrg_ctx* c) {
@@ -486,6 +961,8 @@ static int mf_open(nrg_ctx* c) {
     s.nlines = (u32)((s.files << s.log2_b) / MF_LINE);
     s.key_bits = 1;  // ceil(log2(nlines + 1)): the sentinel is a key too
     while ((1ull << s.key_bits) <= s.nlines) s.key_bits++;
+    s.file_bits = 1;  // ceil(log2 F): what a sized chunk's file sort sorts by
+    while ((1ull << s.file_bits) < s.files) s.file_bits++;
     HIPCHK(hipMalloc(&s.d_files, s.files << s.log2_b));
     HIPCHK(hipMalloc(&s.d_keys, 2 * cf.max_batch * sizeof(u32)));
     HIPCHK(hipMalloc(&s.d_desc, cf.max_batch * sizeof(u64)));
@@ -498,7 +975,8 @@ static int mf_open(nrg_ctx* c) {
 
 static void mf_close(nrg_ctx* c) {
     MfHost& s = c->mf;
-    void* ptrs[] = {s.d_files, s.d_keys, s.d_desc, s.d_pagg};
+    void* ptrs[] = {s.d_files, s.d_keys, s.d_desc, s.d_pagg, s.d_size, s.d_fkey, s.d_el,
+                    s.d_sc,    s.d_ev,   s.d_fm,   s.d_fep,  s.d_sagg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
@@ -520,6 +998,19 @@ __global__ __launch_bounds__(DG_TPB) void mf_digest_kernel(const u64* words, u64
     dg_commit(c, sm, x, out3);
 }
 
+// a sized context's further items: one per file, (file << 32 | 0xFFFFFFFF, its size); no word index
+// reaches that key
+__global__ __launch_bounds__(DG_TPB) void mfs_digest_kernel(const u64* size, u64 n, u64* out3) {
+    u64 c = 0, sm = 0, x = 0;
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 h = dg_item((i << 32) | 0xFFFFFFFFull, size[i]);
+        c++;
+        sm += h;
+        x ^= h;
+    }
+    dg_commit(c, sm, x, out3);
+}
+
 static u64 mf_words(const nrg_ctx* c) { return (c->mf.files << c->mf.log2_b) / 8; }
 
 static hipError_t mf_digest(nrg_ctx* c, u64* d_out3) {
@@ -527,36 +1018,62 @@ static hipError_t mf_digest(nrg_ctx* c, u64* d_out3) {
     if (e != hipSuccess) return e;
     NRG_LAUNCH(c, "mf_digest", mf_digest_kernel, dg_grid(mf_words(c)), DG_TPB, 0, c->stream, (const u64*)c->mf.d_files,
                mf_words(c), c->mf.log2_b - 3, d_out3);
+    // (nrg_restore's comparison of an unsized image's digest, which has no size items: once)
+    if (c->mf.d_size && !c->mf.unsized_image)
+        NRG_LAUNCH(c, "mfs_digest", mfs_digest_kernel, dg_grid(c->mf.files), DG_TPB, 0, c->stream,
+                   (const u64*)c->mf.d_size, c->mf.files, d_out3);
+    c->mf.unsized_image = false;
     return hipGetLastError();
 }
 
 static int mf_items(nrg_ctx* c, u64* n) {
-    *n = mf_words(c);
+    *n = mf_words(c) + (c->mf.d_size ? c->mf.files : 0);
     return NRG_OK;
 }
 
-// The snapshot payload: the files' bytes in inode order (items: their 8-byte words).
-__global__ __launch_bounds__(DG_TPB) void mf_snapshot_kernel(const u64* words, u64 n, u64* buf, u64 cap, u64 log_idx,
-                                                             DevCtl* ctl) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_MEMFS, n, n * 8, log_idx, ctl);
-    if (snap_bytes(n * 8) > cap) return;
+// The snapshot payload: the files' bytes in inode order (items: their 8-byte words), and in a sized
+// context the nf = F sizes after them, one item each.
+__global__ __launch_bounds__(DG_TPB) void mf_snapshot_kernel(const u64* words, u64 n, const u64* size, u64 nf, u64* buf,
+                                                             u64 cap, u64 log_idx, DevCtl* ctl) {
+    const u64 items = n + nf;
+    if (blockIdx.x == 0 && threadIdx.x == 0) snap_head(buf, cap, NRG_DS_MEMFS, items, items * 8, log_idx, ctl);
+    if (snap_bytes(items * 8) > cap) return;
     u64* out = buf + SNAP_HDR / 8;
-    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) out[i] = words[i];
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < items; i += (u64)gridDim.x * DG_TPB)
+        out[i] = i < n ? words[i] : size[i - n];
 }
 
 static hipError_t mf_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
     NRG_LAUNCH(c, "mf_snapshot", mf_snapshot_kernel, copy_grid(mf_words(c)), DG_TPB, 0, c->stream,
-               (const u64*)c->mf.d_files, mf_words(c), (u64*)d_buf, cap, log_idx, c->d_ctl);
+               (const u64*)c->mf.d_files, mf_words(c), (const u64*)c->mf.d_size, c->mf.d_size ? c->mf.files : 0,
+               (u64*)d_buf, cap, log_idx, c->d_ctl);
     return hipGetLastError();
 }
 
 // An image goes only into a context of the same geometry. The header carries the item count alone:
 // another total is refused by check_only with nothing touched; the same total cut into other files
 // has another digest (the items' keys carry the file), which nrg_restore's comparison refuses.
+// An image of F * B / 8 + F items is a sized one: the F sizes follow the bytes, the context becomes
+// sized, and a size above B or a non-zero byte at or past a size latches ERR_INVAL on the device, which
+// nrg_restore reads before it compares the digests. An unsized image leaves a sized context sized, every
+// size B.
 static int mf_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
-    if (check_only) return items == mf_words(c) ? NRG_OK : NRG_E_INVAL;
+    const u64 words = mf_words(c);
+    if (check_only) return items == words || items == words + c->mf.files ? NRG_OK : NRG_E_INVAL;
     if (!d_payload) return hip_fail(mf_fill(c));
-    return hip_fail(hipMemcpyAsync(c->mf.d_files, d_payload, mf_words(c) * 8, hipMemcpyDeviceToDevice, c->stream));
+    int r;
+    if (items != words && (r = mf_enable(c))) return r;
+    HIPCHK(hipMemcpyAsync(c->mf.d_files, d_payload, words * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (items == words) {
+        c->mf.unsized_image = c->mf.d_size != nullptr;
+        if (c->mf.d_size)
+            mfs_fill_kernel<<<copy_grid(c->mf.files), DG_TPB, 0, c->stream>>>(c->mf.d_size, c->mf.files, 1ull << c->mf.log2_b);
+        return hip_fail(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(c->mf.d_size, (const u64*)d_payload + words, c->mf.files * 8, hipMemcpyDeviceToDevice, c->stream));
+    NRG_LAUNCH(c, "mfs_check", mfs_check_kernel, copy_grid(words), DG_TPB, 0, c->stream, (const u64*)c->mf.d_files, words,
+               c->mf.log2_b - 3, (const u64*)c->mf.d_size, c->d_ctl);
+    return hip_fail(hipGetLastError());
 }
 
 const DsOps* mf_ops() {
@@ -577,7 +1094,47 @@ static uint8_t* mf_file(nrg_ctx* c, uint64_t ino) {
     return c->mf.d_files + ((ino - NRG_MEMFS_FIRST_INO) << c->mf.log2_b);
 }
 
+// a sized context's size of file f, read from the device (what has been replayed so far)
+static int mf_size_get(nrg_ctx* c, uint64_t f, uint64_t* out) {
+    HIPCHK(hipMemcpyAsync(out, c->mf.d_size + f, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+static int mf_size_put(nrg_ctx* c, uint64_t f, uint64_t v) {
+    HIPCHK(hipMemcpyAsync(c->mf.d_size + f, &v, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
 extern "C" {
+
+int nrg_memfs_enable_sizes(nrg_ctx* c) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    HIPCHK(sync_all(c));
+    return mf_enable(c);
+}
+
+int nrg_memfs_size(nrg_ctx* c, uint64_t ino, uint64_t* size) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (!c->mf.d_size || !size || !mf_file(c, ino)) return NRG_E_INVAL;
+    return mf_size_get(c, ino - NRG_MEMFS_FIRST_INO, size);
+}
+
+int nrg_memfs_truncate(nrg_ctx* c, uint64_t ino, uint64_t size) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    uint8_t* f = mf_file(c, ino);
+    if (!c->mf.d_size || !f || size > (1ull << c->mf.log2_b)) return NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    uint64_t cur = 0;
+    if ((r = mf_size_get(c, ino - NRG_MEMFS_FIRST_INO, &cur))) return r;
+    if (size < cur) HIPCHK(hipMemsetAsync(f + size, 0, cur - size, c->stream));  // bytes [size, cur) are gone
+    return mf_size_put(c, ino - NRG_MEMFS_FIRST_INO, size);
+}
 
 int nrg_memfs_round_async(nrg_ctx* c, const nrg_memfs_op* d_ops, uint64_t n, uint32_t origin, nrg_memfs_resp* d_resp,
                           uint8_t* d_some) {
@@ -592,6 +1149,11 @@ int nrg_memfs_init(nrg_ctx* c, uint64_t ino, const uint8_t* bytes, uint64_t len)
     if (!f || len > (1ull << c->mf.log2_b) || (len && !bytes)) return NRG_E_INVAL;
     if (len) HIPCHK(hipMemcpyAsync(f, bytes, len, hipMemcpyHostToDevice, c->stream));
     HIPCHK(sync_all(c));
+    if (c->mf.d_size) {  // size = max(size, len)
+        uint64_t cur = 0;
+        if ((r = mf_size_get(c, ino - NRG_MEMFS_FIRST_INO, &cur))) return r;
+        if (len > cur) return mf_size_put(c, ino - NRG_MEMFS_FIRST_INO, len);
+    }
     return NRG_OK;
 }
 
@@ -602,7 +1164,8 @@ int nrg_memfs_read(nrg_ctx* c, uint64_t ino, uint64_t offset, uint64_t len, uint
     if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
     const uint8_t* f = mf_file(c, ino);
     if (!f) return NRG_E_INVAL;
-    const uint64_t B = 1ull << c->mf.log2_b;
+    uint64_t B = 1ull << c->mf.log2_b;
+    if (c->mf.d_size && (r = mf_size_get(c, ino - NRG_MEMFS_FIRST_INO, &B))) return r;  // clipped at the size
     *n = offset >= B ? 0 : (len < B - offset ? len : B - offset);
     if (*n && !buf) return NRG_E_INVAL;
     if (*n) HIPCHK(hipMemcpyAsync(buf, f + offset, *n, hipMemcpyDeviceToHost, c->stream));
@@ -617,9 +1180,10 @@ int nrg_memfs_dump(nrg_ctx* c, uint64_t ino, uint8_t* buf, uint64_t cap, uint64_
     const uint8_t* f = mf_file(c, ino);
     if (!f) return NRG_E_INVAL;
     *n = 1ull << c->mf.log2_b;
+    if (c->mf.d_size && (r = mf_size_get(c, ino - NRG_MEMFS_FIRST_INO, n))) return r;  // the file ends at its size
     if (*n > cap) return NRG_E_CAPACITY;
-    if (!buf) return NRG_E_INVAL;
-    HIPCHK(hipMemcpyAsync(buf, f, *n, hipMemcpyDeviceToHost, c->stream));
+    if (!buf) return *n ? NRG_E_INVAL : NRG_OK;
+    if (*n) HIPCHK(hipMemcpyAsync(buf, f, *n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
     return NRG_OK;
 }
@@ -668,6 +1232,7 @@ int nrg_memfs_pread_async(nrg_ctx* c, const nrg_memfs_rd* d_reqs, uint64_t n, ui
     j.files = s.d_files;
     j.log2_b = s.log2_b;
     j.nfiles = (u32)s.files;
+    j.size = s.d_size;
     const unsigned tiles = (unsigned)((n + MF_PR_SCAN - 1) / MF_PR_SCAN);
     if (tiles > 1) {
         NRG_LAUNCH(c, "mf_pread_reduce", mf_pread_reduce_kernel, tiles, MF_TPB, 0, c->stream, j, s.d_pagg);

@@ -30,6 +30,7 @@ from .replica import (
     MfGetAttr,
     MfPread,
     MfRead,
+    MfSetAttr,
     MfWrite,
     NrHashMap,
     Peek,
@@ -56,7 +57,7 @@ __all__ = [
     "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
     "Scan", "Seek", "SkipList", "SlPush",
-    "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfWrite",
+    "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfSetAttr", "MfWrite",
 ]
 
 

@@ -62,6 +62,7 @@ NRG_SCAN_MAX_LIMIT = 1024  # nrg_skiplist_scan: entries per query at most
 NRG_MEMFS_WRITE = 0
 NRG_MEMFS_READ = 1
 NRG_MEMFS_GETATTR = 2
+NRG_MEMFS_SETATTR = 3  # a sized context only (nrg_memfs_enable_sizes)
 NRG_MEMFS_FIRST_INO = 5
 NRG_MEMFS_ENOENT = 1
 NRG_MEMFS_EFBIG = 2
@@ -272,6 +273,9 @@ SIGNATURES = {
     "nrg_memfs_read": (C.c_int, [vp, u64, u64, u64, vp, u64p]),
     "nrg_memfs_dump": (C.c_int, [vp, u64, vp, u64, u64p]),
     "nrg_memfs_geometry": (C.c_int, [vp, u64p, u64p]),
+    "nrg_memfs_enable_sizes": (C.c_int, [vp]),
+    "nrg_memfs_size": (C.c_int, [vp, u64, u64p]),
+    "nrg_memfs_truncate": (C.c_int, [vp, u64, u64]),
     "nrg_memfs_pread": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
     "nrg_memfs_pread_async": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),

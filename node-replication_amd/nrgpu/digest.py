@@ -75,14 +75,21 @@ def skiplist(keys, vals):
     return pairs(keys, vals)
 
 
-def memfs(files):
+def memfs(files, sizes=None):
     """A file store's files in inode order, each a bytes-like of the same length B (a multiple of
-    8): the items are the aligned little-endian 8-byte words, keyed (file index << 32 | word index)."""
+    8): the items are the aligned little-endian 8-byte words, keyed (file index << 32 | word index).
+    sizes: a sized context's (nrg_memfs_enable_sizes) file sizes, one more item per file, keyed
+    (file index << 32 | 0xFFFFFFFF); `files` are still the B stored bytes, zero at and past the size."""
     keys, vals = [], []
     for f, data in enumerate(files):
         w = np.frombuffer(bytes(data), dtype="<u8")
         keys.append((_U64(f) << _U64(32)) | np.arange(w.size, dtype=_U64))
         vals.append(w)
+    if sizes is not None:
+        if len(sizes) != len(files):
+            raise ValueError("one size per file")
+        keys.append((np.arange(len(files), dtype=_U64) << _U64(32)) | _U64(0xFFFFFFFF))
+        vals.append(np.asarray(sizes, dtype=_U64))
     if not keys:
         return (0, 0, 0)
     return pairs(np.concatenate(keys), np.concatenate(vals))

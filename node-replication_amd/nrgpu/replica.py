@@ -726,6 +726,21 @@ class DeviceReplica:
         b = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
         L.check(self._lib.nrg_memfs_init(self._h, ino, _ptr(b) if b.size else None, b.size), "memfs_init")
 
+    def mf_enable_sizes(self):
+        """From here on the files have sizes: SetAttr is an op, Writes grow, Reads and GetAttr see the
+        size; every size starts as B (nrg_memfs_enable_sizes). Idempotent; there is no way back."""
+        L.check(self._lib.nrg_memfs_enable_sizes(self._h), "memfs_enable_sizes")
+
+    def mf_size(self, ino: int) -> int:
+        """The size of file `ino` of a sized context, as replayed so far (nrg_memfs_size)."""
+        n = C.c_uint64()
+        L.check(self._lib.nrg_memfs_size(self._h, ino, C.byref(n)), "memfs_size")
+        return n.value
+
+    def mf_truncate(self, ino: int, size: int):
+        """What a logged MfSetAttr does, directly and with no log traffic (nrg_memfs_truncate)."""
+        L.check(self._lib.nrg_memfs_truncate(self._h, ino, size), "memfs_truncate")
+
     def mf_read(self, ino: int, offset: int, size: int) -> bytes:
         """pread of a synced replica (nrg_memfs_read): up to `size` bytes of file `ino` from `offset`."""
         out = np.zeros(max(size, 1), np.uint8)
@@ -747,8 +762,8 @@ class DeviceReplica:
         [cap], int64 [n + 1], uint8 [n]); request i's bytes are data[offs[i]:offs[i + 1]]. `reqs`: a
         numpy array of MEMFS_RD_DTYPE (or [n, 3] u64: ino, offset, len), or a torch tensor on the GPU
         holding those records. cap=None sizes data from the requests on the host (a device tensor is
-        copied back for that), so that offs[n] == cap; with a cap of the caller's, bytes at or past
-        cap are not written and offs[n] > cap says so."""
+        copied back for that), so that offs[n] == cap (from B: in a sized context offs[n] <= cap); with
+        a cap of the caller's, bytes at or past cap are not written and offs[n] > cap says so."""
         import torch
 
         dev = torch.device("cuda", self.device)
@@ -778,7 +793,7 @@ class DeviceReplica:
         return data, offs, some
 
     def mf_dump(self, ino: int) -> bytes:
-        """The whole file `ino`: Replica::verify's view (nrg_memfs_dump)."""
+        """The whole file `ino`, in a sized context up to its size: Replica::verify's view (nrg_memfs_dump)."""
         _, b = self.mf_geometry()
         out = np.zeros(b, np.uint8)
         n = C.c_uint64()
@@ -927,6 +942,12 @@ class MfRead:  # benches/memfs.rs:73-78 OperationWr::Read{ino, offset, size}: a 
 @dataclass(frozen=True)
 class MfGetAttr:  # benches/memfs.rs:27-29 OperationWr::GetAttr{ino}
     ino: int
+
+
+@dataclass(frozen=True)
+class MfSetAttr:  # benches/memfs.rs:30-33 OperationWr::SetAttr{ino, new_attrs}: the size; a sized context only
+    ino: int
+    size: int
 
 
 @dataclass(frozen=True)
@@ -1121,19 +1142,20 @@ class SkipList:
 class MemFs:
     """NrMemFilesystem (benches/memfs.rs:106-292): files of fixed size, every op a log record
     (ReadOperation = (), :194-201). MfWrite -> ("written", len); MfRead -> ("data", bytes), the file
-    as every earlier record of the log left it; MfGetAttr -> ("attr", size); any of them ->
-    ("err", code) with code L.NRG_MEMFS_ENOENT / EFBIG / EINVAL. An MfWrite of more than 128 bytes is
-    encoded with its length and no data: the replay answers EINVAL."""
+    as every earlier record of the log left it; MfGetAttr -> ("attr", size); MfSetAttr -> ("attr", the
+    new size) once the replica's DeviceReplica.mf_enable_sizes() was called, ("err", EINVAL) before;
+    any of them -> ("err", code) with code L.NRG_MEMFS_ENOENT / EFBIG / EINVAL. An MfWrite of more
+    than 128 bytes is encoded with its length and no data: the replay answers EINVAL."""
 
     kind = L.NRG_DS_MEMFS
     rec_dtype = MEMFS_OP_DTYPE
-    _TAGS = {MfWrite: "written", MfRead: "data", MfGetAttr: "attr"}
+    _TAGS = {MfWrite: "written", MfRead: "data", MfGetAttr: "attr", MfSetAttr: "attr"}
 
     @staticmethod
     def encode(ops) -> np.ndarray:
         r = np.zeros(len(ops), MEMFS_OP_DTYPE)
         for i, o in enumerate(ops):
-            if not isinstance(o, (MfWrite, MfRead, MfGetAttr)):
+            if not isinstance(o, (MfWrite, MfRead, MfGetAttr, MfSetAttr)):
                 raise TypeError(f"not a file-store op: {o!r}")
             r["ino"][i] = o.ino
             if isinstance(o, MfWrite):
@@ -1142,6 +1164,8 @@ class MemFs:
                     r["data"][i, : len(o.data)] = np.frombuffer(bytes(o.data), np.uint8)
             elif isinstance(o, MfRead):
                 r["offset"][i], r["op"][i], r["len"][i] = o.offset, L.NRG_MEMFS_READ, o.size
+            elif isinstance(o, MfSetAttr):
+                r["offset"][i], r["op"][i] = o.size, L.NRG_MEMFS_SETATTR
             else:
                 r["op"][i] = L.NRG_MEMFS_GETATTR
         return r

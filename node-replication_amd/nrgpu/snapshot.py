@@ -14,7 +14,8 @@ and the payload: hashmap `items` {key, value} records in any order; stack `items
 first; queue `items` u64, front first; synthetic synth_n u64 words; vspace the `items` allocated
 pool tables of 512 u64, inner entries as stored (table_index * 4096 | flags); skip list `items`
 {key, value} records in strictly ascending key order; file store `items` = F * B / 8 u64 words, the
-files' bytes in inode order.
+files' bytes in inode order, and from a sized context (nrg_memfs_enable_sizes) the F sizes as u64
+after them, `items` = F * B / 8 + F (memfs_split() tells the two apart).
 
 unpack() reads an image of any kind; pack() builds one for the four flat kinds from a host model,
 its digest words from nrgpu.digest, so that a model can seed a GPU replica (DeviceReplica.restore).
@@ -94,6 +95,19 @@ def unpack(buf):
     return info, pay.view("<u8").copy()  # queue, synthetic
 
 
+def memfs_split(data, files: int):
+    """The payload of a file-store image (unpack's u8 array) of `files` files: (bytes, sizes) with
+    bytes a u8 array [F, B] and sizes a u64 array [F], or None for an unsized image. B is a power
+    of two, so F * B and F * B + 8 F cannot be confused; ValueError if the payload is neither."""
+    d = as_u8(data)
+    per, rem = divmod(d.size, files)
+    for b, sized in ((per, False), (per - 8, True)):
+        if rem == 0 and b >= 128 and b & (b - 1) == 0:
+            body = d[:files * b].reshape(files, b).copy()
+            return body, (d[files * b:].view("<u8").copy() if sized else None)
+    raise ValueError(f"snapshot: {d.size} bytes are not {files} files of a power-of-two size")
+
+
 def leaves(tables) -> np.ndarray:
     """nrg_vspace_dump's list from the pool tables of a vspace image: every leaf entry as
     (vaddr, entry), in ascending vaddr. Slots are walked in index order from the PML4 (table 0)
@@ -118,11 +132,12 @@ def leaves(tables) -> np.ndarray:
     return np.array(out, dtype=L.VSPACE_LEAF_DTYPE)
 
 
-def pack(kind: int, state, log_idx: int) -> np.ndarray:
+def pack(kind: int, state, log_idx: int, sizes=None) -> np.ndarray:
     """The image (u8 array) of a host model's state after replaying [0, log_idx): hashmap a
     (keys, vals) pair or a dict; stack the elements, bottom first; queue the elements, front first;
     synthetic the words; skip list as the hashmap (the records are written in ascending key order);
-    file store the files in inode order, each a bytes-like of the same length.
+    file store the files in inode order, each a bytes-like of the same length (the B stored bytes),
+    with sizes= one size per file for a sized image.
     The digest words are nrgpu.digest's."""
     if kind in (L.NRG_DS_HASHMAP, L.NRG_DS_SKIPLIST):
         if isinstance(state, dict):
@@ -152,7 +167,9 @@ def pack(kind: int, state, log_idx: int) -> np.ndarray:
         if not files or len({len(f) for f in files}) != 1 or len(files[0]) % 8:
             raise ValueError("files of one length, a multiple of 8")
         pay = np.frombuffer(b"".join(files), np.uint8)
-        items, dg = pay.size // 8, _digest.memfs(files)
+        if sizes is not None:
+            pay = np.concatenate([pay, np.asarray(sizes, dtype="<u8").reshape(len(files)).view(np.uint8)])
+        items, dg = pay.size // 8, _digest.memfs(files, sizes)
     else:
         raise ValueError(f"pack: kind {kind} has no flat state")
     nbytes = image_bytes(kind, items)
