@@ -34,6 +34,8 @@
  *                                 Read / GetAttr, all through the log)
  *   nrg_memfs_pread*              Replica::execute -> read_only of    nr/src/replica.rs:404-410, :483-497;
  *                                 OpRd::FileRead, any length          benches/nrfs.rs:16-18, :88-101
+ *   nrg_memfs_pwrite*             Replica::combine of OpWr::FileWrite, benches/nrfs.rs:103-115;
+ *                                 logged writes of any length         nr/src/replica.rs:544-595
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -186,8 +188,10 @@ typedef struct {
  *            Else some = 1, n = s (Attr: the size), data zero; size = s. Bytes [s, old size) are gone;
  *            where s is above the old size the new bytes read as zero.
  * Out of scope: directories, names, inode creation and removal, rename; capacity growth past B; the
- * SetAttrRequest fields other than the size; benches/nrfs.rs's whole-file 4096-byte ops; the combiner,
- * partitioned groups and nrg_set_max_capacity for this kind (NRG_E_INVAL from their entry points). */
+ * SetAttrRequest fields other than the size; the combiner, partitioned groups and
+ * nrg_set_max_capacity for this kind (NRG_E_INVAL from their entry points).
+ * A write of more than 128 bytes (benches/nrfs.rs's whole-file FileWrite) is a contiguous run of these
+ * records: nrg_memfs_pwrite* below cut it on the device. */
 #define NRG_MEMFS_WRITE 0u   /* OperationWr::Write{ino, offset, data[0..len)}  memfs.rs:66-72  */
 #define NRG_MEMFS_READ 1u    /* OperationWr::Read{ino, offset, size = len}      memfs.rs:73-78  */
 #define NRG_MEMFS_GETATTR 2u /* OperationWr::GetAttr{ino}: n = B, or the size    memfs.rs:27-29  */
@@ -835,6 +839,62 @@ int nrg_memfs_pread_async(nrg_ctx* ctx, const nrg_memfs_rd* d_reqs, uint64_t n, 
                           uint64_t* d_offs /* n + 1 */, uint8_t* d_some /* n */);
 int nrg_memfs_pread(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, uint8_t* data, uint64_t cap,
                     uint64_t* offs /* n + 1 */, uint8_t* some /* n */);
+/* Logged writes of any length: POSIX pwrite, and benches/nrfs.rs:103-115 OpWr::FileWrite(fd), which is
+ * memfs.write(fd, &write_buffer[fd - 1], 0) with a 4096-byte buffer. The record stays 152 bytes: a long
+ * write is a contiguous run of ordinary WRITE records in the log, atomic against every other op because
+ * a log has one appender and group rounds concatenate whole segments, and replayed by every replica
+ * like any other records. Request i writes data[data_off, data_off + len) to file `ino` at `offset`;
+ * data_off is explicit, so requests may share bytes (nrfs.rs writes one buffer to every file) and a
+ * failing request needs none. THE CUT of request i, checked in the replay's order (F files of B bytes):
+ *   ino outside the range     some = 0, written = NRG_MEMFS_ENOENT; one record {ino, offset, WRITE, len 0}
+ *   !(offset <= B && len <= B - offset)   (no overflow: len may be 2^64 - 1) some = 0, written =
+ *                             NRG_MEMFS_EFBIG, nothing changes: a Write that ends past the end fails
+ *                             whole; one record {ino, offset B, WRITE, len 1, data zero}, which the replay
+ *                             answers with EFBIG
+ *   len == 0                  some = 1, written = 0; one record {ino, offset, WRITE, len 0}
+ *   else                      some = 1, written = len; cut at the file's 128-byte line boundaries into
+ *                             f_i = ((offset + len - 1) >> 7) - (offset >> 7) + 1 records, fragment k
+ *                             (line_k = (offset >> 7) + k) covering
+ *                             [max(offset, line_k * 128), min(offset + len, (line_k + 1) * 128))
+ * Every request logs at least one record (a failed dispatch_mut is a log entry too). first[0..n] is the
+ * running sum of the f_i and T = first[n] the records of the call; a record's data bytes past its len
+ * are zero. A valid request with len > 0 whose data_off + len exceeds data_bytes (or overflows) is the
+ * caller's error: NRG_E_INVAL from the whole call, nothing logged; a failing request's data_off is not
+ * looked at. */
+typedef struct {
+    uint64_t ino, offset, len, data_off;
+} nrg_memfs_wr; /* 32 B */
+/* The cut as host arithmetic: no device is touched and no context is needed. first: n + 1 words;
+ * written and some (n each) may be NULL. NRG_E_INVAL: a geometry nrg_open refuses (log2_b outside
+ * 7 .. 26, files outside 1 .. 2^16, files << log2_b above 2^29), a NULL reqs or first with n > 0, or
+ * the data_off rule above. */
+int nrg_memfs_pwrite_plan(uint32_t log2_b, uint64_t files, const nrg_memfs_wr* reqs, uint64_t n, uint64_t data_bytes,
+                          uint64_t* first /* n + 1 */, uint64_t* written /* n */, uint8_t* some /* n */);
+/* Replica::combine for these writes. The requests are on the HOST (the log's tail is host state: T must
+ * be known before anything is queued, the rule seg_lens follows) and may be reused on return; the data
+ * is on the device. In order: the plan, catch-up on the log, then passes of at most log size - 8192
+ * records until all T are done: room in the ring (Log::append's GC), the cut written straight into the
+ * ring at the tail, the tail advanced, the pass replayed in chunks of max_batch with no responses
+ * wanted. A call of any T succeeds on any ring, a request's fragments stay contiguous in the log
+ * whatever chunks and passes they straddle, and everything is ordered on the context's stream.
+ * d_written / d_some (both or neither): the answers above, n each. *n_records = T (nullable). Works on
+ * sized contexts too: the records are ordinary Writes, so a pwrite past a file's size grows it and a
+ * gap reads as zero. n == 0: NRG_OK, nothing logged. NRG_E_INVAL: a context of another kind, a NULL
+ * reqs, a NULL d_data with data_bytes > 0, exactly one of d_written / d_some, or the plan's.
+ * NRG_E_CAPACITY: n > config.max_batch (the uploads of the requests and first[] are sized by it). */
+int nrg_memfs_pwrite_async(nrg_ctx* ctx, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* d_data,
+                           uint64_t data_bytes, uint32_t origin, uint64_t* d_written, uint8_t* d_some,
+                           uint64_t* n_records);
+/* The same with data, written and some on the host. Synchronous. */
+int nrg_memfs_pwrite(nrg_ctx* ctx, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* data, uint64_t data_bytes,
+                     uint32_t origin, uint64_t* written, uint8_t* some, uint64_t* n_records);
+/* The cut alone, into the caller's device buffer of cap records (8-byte aligned): exactly the records
+ * nrg_memfs_pwrite_async would put in the ring; the log and the replica are not touched. The output
+ * can be a segment of nrg_group_round_async (nrg_round.recs), which is how a replicated group carries
+ * long writes. *n_records = T (nullable). T > cap: NRG_E_CAPACITY with *n_records = T and no byte of
+ * d_recs written. Other errors as above. */
+int nrg_memfs_pwrite_records_async(nrg_ctx* ctx, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* d_data,
+                                   uint64_t data_bytes, nrg_memfs_op* d_recs, uint64_t cap, uint64_t* n_records);
 /* Sizes (see nrg_memfs_op above): from here on the context's files have sizes, NRG_MEMFS_SETATTR is an
  * op, Writes grow and Reads / GetAttr see the size. Every size starts as B, so the state described is
  * the one found. Synchronous, idempotent, no way back. NRG_E_NOT_SYNCED while ltail < tail. Replicas of

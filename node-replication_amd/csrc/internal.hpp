@@ -246,6 +246,10 @@ struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, conti
     void* d_fm = nullptr;        // [F] {first grouped position, shrinks, smallest target, new size}
     uint32_t* d_fep = nullptr;   // [F] the epoch of the chunk that wrote d_fm's entry
     void* d_sagg = nullptr;      // [max_batch / 1024 + 1] scan-tile aggregates
+    // Writes of any length (nrg_memfs_pwrite*): made by the first such call, nullptr before
+    uint64_t* d_wup = nullptr;   // the upload: [max_batch] requests of 4 words, then first[max_batch + 1]
+    uint64_t* h_wup = nullptr;   // its pinned host copy (the caller's requests may be reused on return)
+    hipEvent_t ev_wup = nullptr; // the last upload has left h_wup
 };
 
 struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*
@@ -403,6 +407,7 @@ int staging(Staging& st, uint64_t bytes);
 // replay [ltail, min(tail, end)) in chunks of at most max_batch records
 int exec_range(nrg_ctx* c, uint64_t resp_lo, uint64_t resp_hi, void* d_resp, uint8_t* d_some, uint64_t end = ~0ull);
 int reserve(nrg_ctx* c, uint64_t n);  // room for n records (Log::append's GC path)
+uint64_t append_max(const nrg_ctx* c);  // the longest append reserve accepts: log_size - GC_FROM_HEAD
 void note_origin(nrg_ctx* c, uint64_t first, uint64_t n, uint32_t origin);
 void commit_round(nrg_ctx* c, uint64_t lo, uint64_t n);  // [lo, lo + n) appended and replayed
 // Replica::combine for one batch of a kind whose rounds carry no reads: one replay pass that also

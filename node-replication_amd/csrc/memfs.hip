@@ -18,8 +18,9 @@
 // Out of scope: directories, names, inode creation and removal, rename.
 // Sizes (SetAttr as ftruncate, Writes that grow a file) are off unless nrg_memfs_enable_sizes was called:
 // the section "Sizes" below. Out of scope: capacity growth past B, the other SetAttrRequest fields.
-// Out of scope: benches/nrfs.rs's whole-file 4096-byte FileWrite (a record carries at most 128 bytes);
-// its read-only FileRead is nrg_memfs_pread* below, which goes through no log record.
+// benches/nrfs.rs's whole-file 4096-byte ops: its read-only FileRead is nrg_memfs_pread* below, which
+// goes through no log record; its FileWrite is nrg_memfs_pwrite* below, a write of any length as a
+// contiguous run of these records, cut on the device straight into the log ring (mf_frag).
 // Out of scope: the combiner, partitioned groups and growth (nrg_set_max_capacity).
 //
 // A file is cut into aligned 128-byte LINES; an op of at most 128 bytes touches at most two. Lines
@@ -50,6 +51,7 @@
 
 #include "../../include/nrgpu_testing.h"
 #include "internal.hpp"
+#include "memfs_plan.hpp"
 
 namespace nrg {
 
@@ -849,6 +851,97 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_copy_kernel(MfRdJob j) {
     }
 }
 
+// ---- writes of any length (nrg_memfs_pwrite*): Replica::combine for benches/nrfs.rs:103-115
+// ---- OpWr::FileWrite, here pwrite of any length ------------------------------------------------------
+// A long write is a contiguous run of ordinary Write records, cut at the file's 128-byte lines
+// (memfs_plan.hpp: the host plans first[0..n], the running sum of the requests' record counts, before
+// anything is queued). A request may be of 0 bytes or of a whole 64-MiB file, so no lane, wave or
+// workgroup is given a request: the OUTPUT is cut, the twin of mf_pread_copy.
+//   mf_frag   fragment records [t0, t1) of the call, each to record (pos0 + t - t0) & mask of dst: the
+//             log ring at the tail, or the caller's linear buffer. A workgroup takes MF_FR_TILE
+//             fragments and finds the first and last request of its tile by upper-bound searches of
+//             first[] (the same in every lane; every request has at least one record, so a fragment has
+//             exactly one request). MF_FR_LANES = 16 lanes take one fragment: the same search inside the
+//             tile's range (uniform within the 16), the request's four words, the cut (memfs_plan.hpp
+//             cut_of / frag_of, the host's own arithmetic); lane l then stores data word l, the first
+//             three lanes a header word each, the first lane of a request's first fragment its written
+//             and some. A record is 8-byte aligned (152 = 19 * 8) and its data starts at byte 24, so the
+//             widest aligned store is 8 bytes: 16 lanes store a record's 128 data bytes as one contiguous
+//             run. The source data + data_off + ... has any alignment: a lane reads the one or two
+//             aligned 8-byte words that hold its bytes and shifts, never a word that is not wholly
+//             inside [data, data + data_bytes): the head and the last bytes of data, where such a word
+//             would reach outside, are gathered byte by byte. Bytes past the record's len are zero.
+//             Plain loads and stores; no LDS, no atomics, no spinning.
+constexpr u32 MF_FR_LANES = 16;                      // lanes of one fragment: one per 8-byte data word
+constexpr u32 MF_FR_PER_WG = MF_TPB / MF_FR_LANES;   // fragments a workgroup writes at a time
+constexpr u32 MF_FR_TILE = 4 * MF_FR_PER_WG;         // fragments per workgroup
+static_assert(MF_FR_LANES * 8 == MF_LINE && MF_REC_WORDS == 3 + MF_FR_LANES, "one lane per data word of a record");
+static_assert(sizeof(nrg_memfs_wr) == 32, "ABI");
+static_assert(mfp::LINE == MF_LINE && mfp::LOG2_MIN == MF_LOG2_MIN && mfp::LOG2_MAX == MF_LOG2_MAX &&
+                  mfp::MAX_FILES == MF_MAX_FILES && mfp::MAX_BYTES == MF_MAX_BYTES,
+              "the plan's geometry is nrg_open's");
+
+struct MfWrJob {
+    const u64* rq;     // the requests in u64 words: ino, offset, len, data_off
+    const u64* first;  // [n + 1] the running sum of the requests' record counts
+    u64 n;
+    u64 t0, t1;        // the fragments of this launch
+    u64* dst;          // records in u64 words
+    u64 pos0, mask;    // fragment t is record (pos0 + t - t0) & mask of dst
+    const uint8_t* data;
+    u64 data_bytes;
+    u32 log2_b, nfiles;
+    u64* written;      // [n] (nullptr with some: not wanted)
+    uint8_t* some;
+};
+
+__global__ __launch_bounds__(MF_TPB) void mf_frag_kernel(MfWrJob j) {
+    const u64* __restrict__ first = j.first;
+    const u32 sub = threadIdx.x & (MF_FR_LANES - 1), grp = threadIdx.x / MF_FR_LANES;
+    const u64 a0 = j.t0 + (u64)blockIdx.x * MF_FR_TILE;
+    if (a0 >= j.t1) return;
+    const u64 a1 = a0 + MF_FR_TILE < j.t1 ? a0 + MF_FR_TILE : j.t1;
+    // requests r_first .. r_last - 1 hold the tile's fragments (the same in every lane)
+    const u64 r_first = mf_upper(first, 1, j.n, a0) - 1;
+    const u64 r_last = mf_upper(first, r_first + 1, j.n, a1 - 1);
+    const uint8_t* const dend = j.data + j.data_bytes;
+    for (u64 t = a0 + grp; t < a1; t += MF_FR_PER_WG) {
+        const u64 r = mf_upper(first, r_first + 1, r_last, t) - 1;  // first[r] <= t < first[r + 1]
+        const u64 ino = j.rq[4 * r], off = j.rq[4 * r + 1], len = j.rq[4 * r + 2];
+        const mfp::Cut c = mfp::cut_of(j.log2_b, j.nfiles, ino, off, len);
+        const u64 k = t - first[r];
+        u64 roff, src;
+        u32 rlen;
+        mfp::frag_of(j.log2_b, c.kind, off, len, k, &roff, &rlen, &src);
+        u64* rec = j.dst + ((j.pos0 + (t - j.t0)) & j.mask) * MF_REC_WORDS;
+        u64 w = 0;
+        const u32 b0 = 8 * sub;  // this lane's first byte of the record's data
+        if (c.kind == mfp::CUT_BYTES && b0 < rlen) {
+            const u32 cnt = rlen - b0 < 8 ? rlen - b0 : 8;
+            const uint8_t* s = j.data + j.rq[4 * r + 3] + src + b0;  // [s, s + cnt) lies inside data (the plan)
+            const u32 sh = (u32)((uintptr_t)s & 7);
+            const uint8_t* a = s - sh;  // the aligned words of the first and the last byte
+            const uint8_t* al = s + cnt - 1 - ((uintptr_t)(s + cnt - 1) & 7);
+            if (a >= j.data && al + 8 <= dend) {
+                w = *(const u64*)a;
+                if (sh) {
+                    w >>= 8 * sh;
+                    if (al != a) w |= *(const u64*)al << (64 - 8 * sh);
+                }
+            } else {  // the head or the last bytes of data
+                for (u32 q = 0; q < cnt; q++) w |= (u64)s[q] << (8 * q);
+            }
+            if (cnt < 8) w &= (1ull << (8 * cnt)) - 1;
+        }
+        rec[3 + sub] = w;
+        if (sub < 3) rec[sub] = sub == 0 ? ino : (sub == 1 ? roff : (u64)NRG_MEMFS_WRITE | ((u64)rlen << 32));
+        if (sub == 0 && k == 0 && j.written) {
+            j.written[r] = c.written;
+            j.some[r] = c.some;
+        }
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------
 static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
@@ -979,6 +1072,9 @@ static void mf_close(nrg_ctx* c) {
                     s.d_sc,    s.d_ev,   s.d_fm,   s.d_fep,  s.d_sagg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (s.d_wup) (void)hipFree(s.d_wup);  // nrg_memfs_pwrite*'s upload
+    if (s.h_wup) (void)hipHostFree(s.h_wup);
+    if (s.ev_wup) (void)hipEventDestroy(s.ev_wup);
 }
 
 static void mf_defaults(nrg_config* cfg) {
@@ -1105,6 +1201,58 @@ static int mf_size_put(nrg_ctx* c, uint64_t f, uint64_t v) {
     HIPCHK(hipMemcpyAsync(c->mf.d_size + f, &v, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(sync_all(c));
     return NRG_OK;
+}
+
+// ---- nrg_memfs_pwrite*: what the three entries share ----
+// the checks, in order: the kind, the batch bound, the pointers
+static int mf_pwrite_check(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* d_data, uint64_t data_bytes) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
+    if ((n && !reqs) || (data_bytes && !d_data)) return NRG_E_INVAL;
+    return NRG_OK;
+}
+
+// The upload of a planned call: the requests and first[] through the pinned copy into d_wup, on the
+// context's stream. The buffers are made by the first call (a context that never writes this way
+// allocates nothing) and freed by mf_close. first: n + 1 words.
+static int mf_pwrite_upload(nrg_ctx* c, const nrg_memfs_wr* reqs, const uint64_t* first, uint64_t n) {
+    MfHost& s = c->mf;
+    const uint64_t mb = c->cfg.max_batch, words = 4 * mb + mb + 1;
+    if (!s.d_wup) {
+        HIPCHK(hipMalloc(&s.d_wup, words * 8));
+        HIPCHK(hipHostMalloc(&s.h_wup, words * 8));
+        HIPCHK(hipEventCreateWithFlags(&s.ev_wup, hipEventDisableTiming));
+    } else {
+        HIPCHK(hipEventSynchronize(s.ev_wup));  // the previous call's upload has left the pinned copy
+    }
+    memcpy(s.h_wup, reqs, n * sizeof(nrg_memfs_wr));
+    memcpy(s.h_wup + 4 * mb, first, (n + 1) * 8);
+    HIPCHK(hipMemcpyAsync(s.d_wup, s.h_wup, n * sizeof(nrg_memfs_wr), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.d_wup + 4 * mb, s.h_wup + 4 * mb, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(s.ev_wup, c->stream));
+    return NRG_OK;
+}
+
+// fragments [t0, t1) of the uploaded call to records (pos0 + t - t0) & mask of dst
+static hipError_t mf_frag_launch(nrg_ctx* c, uint64_t n, uint64_t t0, uint64_t t1, void* dst, uint64_t pos0, uint64_t mask,
+                                 const uint8_t* d_data, uint64_t data_bytes, uint64_t* d_written, uint8_t* d_some) {
+    MfHost& s = c->mf;
+    MfWrJob j{};
+    j.rq = s.d_wup;
+    j.first = s.d_wup + 4 * c->cfg.max_batch;
+    j.n = n;
+    j.t0 = t0, j.t1 = t1;
+    j.dst = (u64*)dst;
+    j.pos0 = pos0, j.mask = mask;
+    j.data = d_data;
+    j.data_bytes = data_bytes;
+    j.log2_b = s.log2_b;
+    j.nfiles = (u32)s.files;
+    j.written = d_written;
+    j.some = d_some;
+    NRG_LAUNCH(c, "mf_frag", mf_frag_kernel, (unsigned)((t1 - t0 + MF_FR_TILE - 1) / MF_FR_TILE), MF_TPB, 0, c->stream, j);
+    return hipGetLastError();
 }
 
 extern "C" {
@@ -1277,6 +1425,79 @@ int nrg_memfs_pread(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, uint8_t* d
     }
     if ((r = check_err(c))) return r;
     return offs[n] > cap ? NRG_E_CAPACITY : NRG_OK;
+}
+
+int nrg_memfs_pwrite_plan(uint32_t log2_b, uint64_t files, const nrg_memfs_wr* reqs, uint64_t n, uint64_t data_bytes,
+                          uint64_t* first, uint64_t* written, uint8_t* some) {
+    return mfp::plan(log2_b, files, reqs, n, data_bytes, first, written, some);
+}
+
+int nrg_memfs_pwrite_async(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* d_data, uint64_t data_bytes,
+                           uint32_t origin, uint64_t* d_written, uint8_t* d_some, uint64_t* n_records) {
+    int r = mf_pwrite_check(c, reqs, n, d_data, data_bytes);
+    if (r) return r;
+    if ((d_written == nullptr) != (d_some == nullptr)) return NRG_E_INVAL;
+    if (n_records) *n_records = 0;
+    if (n == 0) return NRG_OK;
+    std::vector<uint64_t> first(n + 1);
+    if ((r = mfp::plan(c->mf.log2_b, c->mf.files, reqs, n, data_bytes, first.data(), nullptr, nullptr))) return r;
+    const uint64_t T = first[n];
+    // catch up on anything appended by others first (Replica::combine execs the whole log)
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    if ((r = mf_pwrite_upload(c, reqs, first.data(), n))) return r;
+    for (uint64_t done = 0; done < T;) {  // passes: what one append may carry, straight into the ring
+        const uint64_t m = T - done < append_max(c) ? T - done : append_max(c);
+        if ((r = reserve(c, m))) return r;
+        const uint64_t lo = c->tail;
+        HIPCHK(mf_frag_launch(c, n, done, done + m, c->d_ring, lo, c->log_size - 1, d_data, data_bytes, d_written, d_some));
+        note_origin(c, lo, m, origin);
+        c->tail = lo + m;
+        if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+        done += m;
+    }
+    if (n_records) *n_records = T;
+    return NRG_OK;
+}
+
+int nrg_memfs_pwrite(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* data, uint64_t data_bytes,
+                     uint32_t origin, uint64_t* written, uint8_t* some, uint64_t* n_records) {
+    int r = mf_pwrite_check(c, reqs, n, data, data_bytes);
+    if (r) return r;
+    if ((written == nullptr) != (some == nullptr)) return NRG_E_INVAL;
+    if (n == 0) {
+        if (n_records) *n_records = 0;
+        return NRG_OK;
+    }
+    Staging* g = c->stg;
+    if ((r = staging(g[0], data_bytes)) || (r = staging(g[1], n * 8)) || (r = staging(g[2], n))) return r;
+    if (data_bytes) HIPCHK(hipMemcpyAsync(g[0].p, data, data_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((r = nrg_memfs_pwrite_async(c, reqs, n, data_bytes ? (const uint8_t*)g[0].p : nullptr, data_bytes, origin,
+                                    written ? (uint64_t*)g[1].p : nullptr, written ? (uint8_t*)g[2].p : nullptr,
+                                    n_records)))
+        return r;
+    if (written) {
+        HIPCHK(hipMemcpyAsync(written, g[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(some, g[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_memfs_pwrite_records_async(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* d_data,
+                                   uint64_t data_bytes, nrg_memfs_op* d_recs, uint64_t cap, uint64_t* n_records) {
+    int r = mf_pwrite_check(c, reqs, n, d_data, data_bytes);
+    if (r) return r;
+    if ((uintptr_t)d_recs & 7) return NRG_E_INVAL;  // (records move as u64 words)
+    if (n_records) *n_records = 0;
+    if (n == 0) return NRG_OK;
+    std::vector<uint64_t> first(n + 1);
+    if ((r = mfp::plan(c->mf.log2_b, c->mf.files, reqs, n, data_bytes, first.data(), nullptr, nullptr))) return r;
+    const uint64_t T = first[n];
+    if (n_records) *n_records = T;
+    if (T > cap) return NRG_E_CAPACITY;
+    if (!d_recs) return NRG_E_INVAL;
+    if ((r = mf_pwrite_upload(c, reqs, first.data(), n))) return r;
+    return hip_fail(mf_frag_launch(c, n, 0, T, d_recs, 0, ~0ull, d_data, data_bytes, nullptr, nullptr));
 }
 
 }  // extern "C"

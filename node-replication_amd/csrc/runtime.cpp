@@ -120,6 +120,8 @@ int reserve(nrg_ctx* c, uint64_t n) {
     return NRG_OK;
 }
 
+uint64_t append_max(const nrg_ctx* c) { return c->log_size - GC_FROM_HEAD; }
+
 void note_origin(nrg_ctx* c, uint64_t first, uint64_t n, uint32_t origin) {
     if (!c->origins.empty()) {
         HostRun& b = c->origins.back();

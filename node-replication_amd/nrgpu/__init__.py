@@ -10,6 +10,7 @@ from .replica import (
     MEMFS_OP_DTYPE,
     MEMFS_RD_DTYPE,
     MEMFS_RESP_DTYPE,
+    MEMFS_WR_DTYPE,
     PUT_DTYPE,
     QUEUE_OP_DTYPE,
     STACK_OP_DTYPE,
@@ -29,6 +30,7 @@ from .replica import (
     MemFs,
     MfGetAttr,
     MfPread,
+    MfPwrite,
     MfRead,
     MfSetAttr,
     MfWrite,
@@ -49,6 +51,8 @@ from .replica import (
     Stack,
     VSpace,
     WriteOnly,
+    memfs_pwrite_plan,
+    memfs_wr,
 )
 
 __all__ = [
@@ -58,6 +62,7 @@ __all__ = [
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
     "Scan", "Seek", "SkipList", "SlPush",
     "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfSetAttr", "MfWrite",
+    "MEMFS_WR_DTYPE", "MfPwrite", "memfs_pwrite_plan", "memfs_wr",
 ]
 
 

@@ -78,6 +78,8 @@ MEMFS_OP_DTYPE = np.dtype([("ino", "<u8"), ("offset", "<u8"), ("op", "<u4"), ("l
 MEMFS_RESP_DTYPE = np.dtype([("n", "<u8"), ("data", "u1", (128,))])
 # nrg_memfs_rd (24 B): one request of nrg_memfs_pread
 MEMFS_RD_DTYPE = np.dtype([("ino", "<u8"), ("offset", "<u8"), ("len", "<u8")])
+# nrg_memfs_wr (32 B): one request of nrg_memfs_pwrite*: data[data_off, data_off + len) to `ino` at `offset`
+MEMFS_WR_DTYPE = np.dtype([("ino", "<u8"), ("offset", "<u8"), ("len", "<u8"), ("data_off", "<u8")])
 
 
 class NrgError(RuntimeError):
@@ -278,6 +280,10 @@ SIGNATURES = {
     "nrg_memfs_truncate": (C.c_int, [vp, u64, u64]),
     "nrg_memfs_pread": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
     "nrg_memfs_pread_async": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
+    "nrg_memfs_pwrite_plan": (C.c_int, [u32, u64, vp, u64, u64, vp, vp, vp]),
+    "nrg_memfs_pwrite_async": (C.c_int, [vp, vp, u64, vp, u64, u32, vp, vp, u64p]),
+    "nrg_memfs_pwrite": (C.c_int, [vp, vp, u64, vp, u64, u32, vp, vp, u64p]),
+    "nrg_memfs_pwrite_records_async": (C.c_int, [vp, vp, u64, vp, u64, vp, u64, u64p]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

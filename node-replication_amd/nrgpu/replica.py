@@ -36,6 +36,7 @@ VSPACE_LEAF_DTYPE = L.VSPACE_LEAF_DTYPE
 MEMFS_OP_DTYPE = L.MEMFS_OP_DTYPE
 MEMFS_RESP_DTYPE = L.MEMFS_RESP_DTYPE
 MEMFS_RD_DTYPE = L.MEMFS_RD_DTYPE
+MEMFS_WR_DTYPE = L.MEMFS_WR_DTYPE
 
 # nr/src/log.rs:22,26,36 ; nr/src/context.rs:12 ; nr/src/replica.rs:56
 DEFAULT_LOG_BYTES = 32 * 1024 * 1024
@@ -56,6 +57,33 @@ def _dptr(t) -> C.c_void_p:
     if isinstance(t, int):
         return C.c_void_p(t)
     return C.c_void_p(t.data_ptr())
+
+
+def memfs_wr(reqs) -> np.ndarray:
+    """Requests of nrg_memfs_pwrite* as a contiguous array of MEMFS_WR_DTYPE: from one, or from
+    [n, 4] u64 (ino, offset, len, data_off)."""
+    host = np.asarray(reqs)
+    if host.dtype != L.MEMFS_WR_DTYPE:
+        host = np.ascontiguousarray(host, np.uint64).reshape(-1, 4).view(L.MEMFS_WR_DTYPE)
+    return np.ascontiguousarray(host.reshape(-1))
+
+
+def memfs_pwrite_plan(log2_b: int, files: int, reqs, data_bytes: int):
+    """The cut of nrg_memfs_pwrite* as host arithmetic (nrg_memfs_pwrite_plan; no device, no context):
+    (first, written, some) for F = `files` files of 2^log2_b bytes. first[0..n] is the running sum of the
+    requests' record counts, first[n] the records of the call. ValueError for what the library refuses:
+    a geometry nrg_open does not accept, or a valid request whose bytes are not inside data."""
+    rq = memfs_wr(reqs)
+    n = len(rq)
+    first = np.zeros(n + 1, np.uint64)
+    written = np.zeros(n, np.uint64)
+    some = np.zeros(n, np.uint8)
+    code = L.load().nrg_memfs_pwrite_plan(log2_b, files, _ptr(rq) if n else None, n, data_bytes, _ptr(first),
+                                          _ptr(written) if n else None, _ptr(some) if n else None)
+    if code == L.NRG_E_INVAL:
+        raise ValueError("nrg_memfs_pwrite_plan: a geometry nrg_open refuses, or a request's bytes lie outside data")
+    L.check(code, "memfs_pwrite_plan")
+    return first, written, some
 
 
 def _stream_ordered(fn):
@@ -217,15 +245,22 @@ class DeviceReplica:
         # hashmap previous values, synthetic sums, queue pushed / popped values
         return np.uint64
 
-    def log_exec(self, resp_lo: int = 0, resp_hi: int = 0):
+    def log_exec_rc(self, resp_lo: int = 0, resp_hi: int = 0):
+        """nrg_log_exec with its code kept: (code, resp, some). The responses are copied out before the
+        error latch is read, so they are valid under NRG_E_INVAL too (a record outside its kind's domain)."""
         n = resp_hi - resp_lo
         resp = np.zeros(max(n, 1), self._resp_dtype())
         some = np.zeros(max(n, 1), np.uint8)
         if n > 0:
-            L.check(self._lib.nrg_log_exec(self._h, resp_lo, resp_hi, _ptr(resp), _ptr(some)), "exec")
+            rc = self._lib.nrg_log_exec(self._h, resp_lo, resp_hi, _ptr(resp), _ptr(some))
         else:
-            L.check(self._lib.nrg_log_exec(self._h, 0, 0, None, None), "exec")
-        return resp[:n], some[:n]
+            rc = self._lib.nrg_log_exec(self._h, 0, 0, None, None)
+        return rc, resp[:n], some[:n]
+
+    def log_exec(self, resp_lo: int = 0, resp_hi: int = 0):
+        rc, resp, some = self.log_exec_rc(resp_lo, resp_hi)
+        L.check(rc, "exec")
+        return resp, some
 
     @_stream_ordered
     def log_exec_device(self, resp_lo=0, resp_hi=0, d_resp=None, d_some=None):
@@ -792,6 +827,88 @@ class DeviceReplica:
         self.mf_pread_device(d_reqs if n else None, n, data if cap else None, cap, offs, some if n else None)
         return data, offs, some
 
+    @_stream_ordered
+    def mf_pwrite_device(self, reqs: np.ndarray, d_data, data_bytes: int, origin: int, d_written=None, d_some=None) -> int:
+        """Replica::combine for n logged writes of any length (nrg_memfs_pwrite_async): `reqs`, a host
+        array of MEMFS_WR_DTYPE, cut on the device into 128-byte Write records straight into the log
+        ring and replayed; the bytes come from the device buffer d_data. The answers go to d_written
+        (u64) / d_some (u8), both or neither. Returns the number of records logged.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        t = C.c_uint64()
+        L.check(self._lib.nrg_memfs_pwrite_async(self._h, _ptr(reqs) if len(reqs) else None, len(reqs), _dptr(d_data),
+                                                 data_bytes, origin, _dptr(d_written), _dptr(d_some), C.byref(t)),
+                "memfs_pwrite")
+        return t.value
+
+    @_stream_ordered
+    def mf_pwrite_records_device(self, reqs: np.ndarray, d_data, data_bytes: int, d_recs, cap: int) -> int:
+        """The cut alone (nrg_memfs_pwrite_records_async): the records mf_pwrite_device would log, into
+        the device buffer d_recs of cap records; the log and the replica are not touched. Returns the
+        number of records; NrgError(NRG_E_CAPACITY) when they exceed cap (nothing is written then).
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        t = C.c_uint64()
+        L.check(self._lib.nrg_memfs_pwrite_records_async(self._h, _ptr(reqs) if len(reqs) else None, len(reqs),
+                                                         _dptr(d_data), data_bytes, _dptr(d_recs), cap, C.byref(t)),
+                "memfs_pwrite_records")
+        return t.value
+
+    def mf_pwrite(self, reqs, data, origin: int = 1):
+        """Logged writes of any length: (written, some, n_records). `reqs`: a numpy array of
+        MEMFS_WR_DTYPE (or [n, 4] u64: ino, offset, len, data_off); request i writes data[data_off,
+        data_off + len) to file `ino` at `offset`, so requests may share bytes. written[i] = len and
+        some[i] = 1, or some[i] = 0 and written[i] = L.NRG_MEMFS_ENOENT / EFBIG (a write that ends past
+        the end of the file fails whole). n_records: the 128-byte Write records the call logged (every
+        request logs at least one). `data`: bytes or a numpy u8 array (the synchronous
+        nrg_memfs_pwrite; written and some are numpy arrays), or a torch u8 tensor on this replica's
+        GPU (nrg_memfs_pwrite_async, nothing waited for; written and some are torch tensors, int64 and
+        uint8)."""
+        rq = memfs_wr(reqs)
+        if hasattr(data, "data_ptr"):
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            d = data.contiguous()
+            nb = d.numel() * d.element_size()
+            written = torch.empty(len(rq), dtype=torch.int64, device=dev)
+            some = torch.empty(len(rq), dtype=torch.uint8, device=dev)
+            t = self.mf_pwrite_device(rq, d if nb else None, nb, origin, written if len(rq) else None,
+                                      some if len(rq) else None)
+            return written, some, t
+        b = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+        written = np.zeros(len(rq), np.uint64)
+        some = np.zeros(len(rq), np.uint8)
+        t = C.c_uint64()
+        L.check(self._lib.nrg_memfs_pwrite(self._h, _ptr(rq) if len(rq) else None, len(rq), _ptr(b) if b.size else None,
+                                           b.size, origin, _ptr(written) if len(rq) else None,
+                                           _ptr(some) if len(rq) else None, C.byref(t)), "memfs_pwrite")
+        return written, some, t.value
+
+    def mf_pwrite_records(self, reqs, data, device: bool = False):
+        """The records mf_pwrite(reqs, data) would log, as a numpy array of MEMFS_OP_DTYPE (the cut alone,
+        made on the GPU: nrg_memfs_pwrite_records_async; the log and the replica are not touched). With
+        device=True the records stay on the GPU: a torch u8 tensor of n_records * 152 bytes, what a
+        segment of a group round (nrg_round.recs) takes. `data` as in mf_pwrite."""
+        import torch
+
+        rq = memfs_wr(reqs)
+        dev = torch.device("cuda", self.device)
+        if hasattr(data, "data_ptr"):
+            d = data.contiguous()
+        else:
+            b = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+            d = torch.from_numpy(b.copy()).to(dev)
+        nb = d.numel() * d.element_size()
+        files, b = self.mf_geometry()
+        first, _, _ = memfs_pwrite_plan(b.bit_length() - 1, files, rq, nb)
+        T = int(first[-1])
+        recs = torch.empty(max(T, 1) * MEMFS_OP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        got = self.mf_pwrite_records_device(rq, d if nb else None, nb, recs, T)
+        assert got == T
+        recs = recs[: T * MEMFS_OP_DTYPE.itemsize]
+        if device:
+            return recs
+        return recs.cpu().numpy().view(MEMFS_OP_DTYPE).copy()
+
     def mf_dump(self, ino: int) -> bytes:
         """The whole file `ino`, in a sized context up to its size: Replica::verify's view (nrg_memfs_dump)."""
         _, b = self.mf_geometry()
@@ -948,6 +1065,13 @@ class MfGetAttr:  # benches/memfs.rs:27-29 OperationWr::GetAttr{ino}
 class MfSetAttr:  # benches/memfs.rs:30-33 OperationWr::SetAttr{ino, new_attrs}: the size; a sized context only
     ino: int
     size: int
+
+
+@dataclass(frozen=True)
+class MfPwrite:  # benches/nrfs.rs:103-115 OpWr::FileWrite: a logged write of any length (pwrite)
+    ino: int
+    offset: int
+    data: bytes
 
 
 @dataclass(frozen=True)
@@ -1145,16 +1269,29 @@ class MemFs:
     as every earlier record of the log left it; MfGetAttr -> ("attr", size); MfSetAttr -> ("attr", the
     new size) once the replica's DeviceReplica.mf_enable_sizes() was called, ("err", EINVAL) before;
     any of them -> ("err", code) with code L.NRG_MEMFS_ENOENT / EFBIG / EINVAL. An MfWrite of more
-    than 128 bytes is encoded with its length and no data: the replay answers EINVAL."""
+    than 128 bytes is encoded with its length and no data: the replay answers EINVAL.
+
+    MfPwrite (benches/nrfs.rs:103-115 OpWr::FileWrite) is a write of any length -> ("written", len), or
+    ("err", ENOENT / EFBIG); one that ends past the end of the file fails whole. It is logged as a
+    contiguous run of 128-byte Write records, the cut of nrg_memfs_pwrite* (include/nrgpu.h), which
+    needs the replica's geometry: Replica._combine encodes with encode_for(dev, ops) and hands
+    decode_ops the per-op record counts. One MfPwrite may expand into more records than
+    MAX_PENDING_OPS (the bound counts ops, and the combiner appends a batch in as many appends as the
+    log takes); an MfPwrite that alone expands into more records than one append can carry
+    (the log's entries less GC_FROM_HEAD) raises ValueError from execute_mut[_batch], before anything
+    is enqueued."""
 
     kind = L.NRG_DS_MEMFS
     rec_dtype = MEMFS_OP_DTYPE
-    _TAGS = {MfWrite: "written", MfRead: "data", MfGetAttr: "attr", MfSetAttr: "attr"}
+    record_errors = True  # a refused record is its op's ("err", EINVAL), not the replica's error (Replica._exec)
+    _TAGS = {MfWrite: "written", MfPwrite: "written", MfRead: "data", MfGetAttr: "attr", MfSetAttr: "attr"}
 
     @staticmethod
     def encode(ops) -> np.ndarray:
         r = np.zeros(len(ops), MEMFS_OP_DTYPE)
         for i, o in enumerate(ops):
+            if isinstance(o, MfPwrite):
+                raise TypeError("an MfPwrite is cut by the replica's geometry: MemFs.encode_counts(ops, log2_b, files)")
             if not isinstance(o, (MfWrite, MfRead, MfGetAttr, MfSetAttr)):
                 raise TypeError(f"not a file-store op: {o!r}")
             r["ino"][i] = o.ino
@@ -1171,18 +1308,93 @@ class MemFs:
         return r
 
     @staticmethod
-    def decode_ops(ops, resp, some) -> list:
+    def _pwrite_reqs(ops):
+        """The MfPwrite ops of `ops` as requests of nrg_memfs_pwrite* over their concatenated bytes."""
+        pw = [o for o in ops if isinstance(o, MfPwrite)]
+        rq = np.zeros(len(pw), L.MEMFS_WR_DTYPE)
+        rq["ino"] = [o.ino for o in pw]
+        rq["offset"] = [o.offset for o in pw]
+        rq["len"] = [len(o.data) for o in pw]
+        rq["data_off"][1:] = np.cumsum(rq["len"][:-1], dtype=np.uint64)
+        return pw, rq
+
+    @staticmethod
+    def record_counts(ops, log2_b: int, files: int) -> list:
+        """The log records each op becomes in a store of `files` files of 2^log2_b bytes: 1, or an
+        MfPwrite's fragments (nrg_memfs_pwrite_plan; no device is touched)."""
+        pw, rq = MemFs._pwrite_reqs(ops)
+        first, _, _ = memfs_pwrite_plan(log2_b, files, rq, int(rq["len"].sum(dtype=np.uint64)))
+        f = iter(np.diff(first).astype(np.int64).tolist())
+        return [next(f) if isinstance(o, MfPwrite) else 1 for o in ops]
+
+    @staticmethod
+    def encode_counts(ops, log2_b: int, files: int):
+        """(records, per-op record counts) of `ops` for a store of `files` files of 2^log2_b bytes: an
+        MfPwrite becomes the fragment records of nrg_memfs_pwrite* (the counts and answers from
+        nrg_memfs_pwrite_plan, the records built here with numpy; no device is touched), every other
+        op the one record of encode()."""
+        counts = MemFs.record_counts(ops, log2_b, files)
+        pw, rq = MemFs._pwrite_reqs(ops)
+        _, written, some = memfs_pwrite_plan(log2_b, files, rq, int(rq["len"].sum(dtype=np.uint64)))
+        recs = np.zeros(sum(counts), MEMFS_OP_DTYPE)
+        B, pos, q = 1 << log2_b, 0, 0
+        for o, c in zip(ops, counts):
+            if not isinstance(o, MfPwrite):
+                recs[pos] = MemFs.encode([o])[0]
+                pos += 1
+                continue
+            r = recs[pos:pos + c]
+            r["ino"], r["op"] = o.ino, L.NRG_MEMFS_WRITE
+            if not some[q]:  # one record that the replay answers with the same error
+                if int(written[q]) == L.NRG_MEMFS_EFBIG:
+                    r["offset"], r["len"] = B, 1
+                else:
+                    r["offset"] = o.offset
+            elif len(o.data) == 0:
+                r["offset"] = o.offset
+            else:  # cut at the file's 128-byte lines
+                line = (o.offset >> 7) + np.arange(c, dtype=np.int64)
+                lo = np.maximum(line << 7, o.offset)
+                hi = np.minimum((line + 1) << 7, o.offset + len(o.data))
+                r["offset"], r["len"] = lo, hi - lo
+                d = np.frombuffer(bytes(o.data), np.uint8)
+                for k in range(c):
+                    r["data"][k, : hi[k] - lo[k]] = d[lo[k] - o.offset:hi[k] - o.offset]
+            pos += c
+            q += 1
+        return recs, counts
+
+    @staticmethod
+    def encode_for(dev: DeviceReplica, ops):
+        """encode_counts with the geometry of the replica `dev` (read from its context; no device work)."""
+        files, b = dev.mf_geometry()
+        return MemFs.encode_counts(ops, b.bit_length() - 1, files)
+
+    @staticmethod
+    def records_for(dev: DeviceReplica, ops) -> list:
+        """record_counts with the geometry of the replica `dev`."""
+        files, b = dev.mf_geometry()
+        return MemFs.record_counts(ops, b.bit_length() - 1, files)
+
+    @staticmethod
+    def decode_ops(ops, resp, some, counts=None) -> list:
         """The responses of `ops` (a response does not say which op it answers; Replica._combine
-        passes the batch)."""
-        out = []
-        for o, r, s in zip(ops, resp, some):
-            n = int(r["n"])
-            if not s:
-                out.append(("err", n))
+        passes the batch). counts: the records each op became (encode_counts; None: one each); an
+        MfPwrite's fragments fold into one answer, ("written", the sum), or ("err", code) from its
+        failing record."""
+        out, pos = [], 0
+        for i, o in enumerate(ops):
+            c = 1 if counts is None else counts[i]
+            r, s = resp[pos:pos + c], some[pos:pos + c]
+            pos += c
+            bad = np.flatnonzero(np.asarray(s) == 0)
+            if len(bad):
+                out.append(("err", int(r["n"][bad[0]])))
             elif isinstance(o, MfRead):
-                out.append(("data", r["data"][:n].tobytes()))
+                n = int(r["n"][0])
+                out.append(("data", r["data"][0][:n].tobytes()))
             else:
-                out.append((MemFs._TAGS[type(o)], n))
+                out.append((MemFs._TAGS[type(o)], int(r["n"].sum(dtype=np.uint64))))
         return out
 
     @staticmethod
@@ -1321,7 +1533,7 @@ class Log:
                     return None
                 if clone_from not in self._replicas:
                     raise ValueError("clone_from is not registered with this log")
-                clone_from.dev.log_exec()  # to the tail: every copy holds every appended entry
+                clone_from._exec()  # to the tail: every copy holds every appended entry
                 if clone_from.dev.device == replica.dev.device:
                     p, nbytes, info = clone_from.dev.snapshot_device()
                     if info.log_idx == self.tail:
@@ -1438,6 +1650,17 @@ class Replica:
             q.extend(ops)
             return True
 
+    def _exec(self, resp_lo: int = 0, resp_hi: int = 0):
+        """DeviceReplica.log_exec for this replica's plug-in. A plug-in whose records can be refused
+        one by one (MemFs: `record_errors`) gets the refusal as that op's answer, ("err", EINVAL), and
+        every replica that replays the record latches NRG_E_INVAL once: here the latch is read, and
+        that code dropped, so that the op's caller gets the answer and no other replica an error for
+        an op that was not its own."""
+        rc, resp, some = self.dev.log_exec_rc(resp_lo, resp_hi)
+        if not (rc == L.NRG_E_INVAL and getattr(self.ds, "record_errors", False)):
+            L.check(rc, "exec")
+        return resp, some
+
     def _combine(self):
         """Replica::combine (nr/src/replica.rs:544-595): collect every thread's pending ops,
         append them as one batch, replay the log, route this replica's responses back."""
@@ -1450,18 +1673,38 @@ class Replica:
                         order.append((t, len(q)))
                         batch.extend(q)
                         self._ctx[t] = []
-            if batch:
+            if batch and getattr(self.ds, "encode_for", None):
+                # a plug-in whose ops may become several records each, cut by the replica's geometry
+                # (MemFs: MfPwrite): the batch goes into the log in as many appends as the log takes,
+                # split between ops, and the per-op record counts go to decode_ops
+                recs, counts = self.ds.encode_for(self.dev, batch)
+                lim = self.log.size - GC_FROM_HEAD
+                parts, i, pos = [], 0, 0
+                while i < len(batch):
+                    tot = counts[i]  # (execute_mut_batch refused an op of more than lim records)
+                    i += 1
+                    while i < len(batch) and tot + counts[i] <= lim:
+                        tot += counts[i]
+                        i += 1
+                    first = self.log.append(recs[pos:pos + tot], self.idx)
+                    parts.append(self._exec(first, first + tot))
+                    pos += tot
+                resp = np.concatenate([p[0] for p in parts])
+                some = np.concatenate([p[1] for p in parts])
+                out = self.ds.decode_ops(batch, resp, some, counts)
+            elif batch:
                 first = self.log.append(self.ds.encode(batch), self.idx)
                 resp, some = self.dev.log_exec(first, first + len(batch))
-                # a plug-in whose responses need their ops to be read (MemFs) decodes with the batch
+                # a plug-in whose responses need their ops to be read decodes with the batch
                 with_ops = getattr(self.ds, "decode_ops", None)
                 out = with_ops(batch, resp, some) if with_ops else self.ds.decode(resp, some)
+            if batch:
                 s = 0
                 for t, n in order:
                     self._resp[t].extend(out[s:s + n])
                     s += n
             else:
-                self.dev.log_exec()
+                self._exec()
             st = self.dev.log_state()
             self.log.ctail = max(self.log.ctail, st["ltail"])
 
@@ -1484,6 +1727,13 @@ class Replica:
         """Host batcher: enqueue many of this thread's writes, combine once."""
         tid = tok.id()
         ops = list(ops)
+        records_for = getattr(self.ds, "records_for", None)
+        if records_for is not None:  # (MemFs) an op that no single append can carry is refused here
+            lim = self.log.size - GC_FROM_HEAD
+            for o, c in zip(ops, records_for(self.dev, ops)):
+                if c > lim:
+                    raise ValueError(f"{type(o).__name__} expands into {c} log records; one append to this log carries "
+                                     f"at most {lim} (a larger Log, or several smaller writes)")
         self._combine_until(lambda: self._enqueue(ops, tid))
         want = len(ops)
         self._combine_until(lambda: len(self._resp[tid]) >= want)
@@ -1509,7 +1759,7 @@ class Replica:
         self._sync_to(self.log.ctail)
         with self._combiner:
             with self.log.lock:
-                self.dev.log_exec()
+                self._exec()
                 return self.ds.read_batch(self.dev, list(ops))
 
     def sync(self, tok: Optional[ReplicaToken] = None):
@@ -1521,7 +1771,7 @@ class Replica:
         the replica's data structure (materialised on the host)."""
         with self._combiner:
             with self.log.lock:
-                self.dev.log_exec()
+                self._exec()
                 self.dev.sync()
                 v(self.ds.snapshot(self.dev))
 
@@ -1530,5 +1780,5 @@ class Replica:
         replica's digest triple (DeviceReplica.digest); nothing is materialised on the host."""
         with self._combiner:
             with self.log.lock:
-                self.dev.log_exec()
+                self._exec()
                 return self.dev.digest()
