@@ -41,6 +41,9 @@
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
  *                                 cnr's key-partitioned logs         cnr/src/lib.rs:134-167 (LogMapper::hash),
  *                                 (one log per GPU, RCCL send/recv)  cnr/src/replica.rs:430-445, :673-736
+ *   nrg_memfs_owner, nrg_memfs_partition_async, nrg_memfs_route_back_async, nrg_group_file_round
+ *                                 nrfs-mlnr: one log per file        benches/nrfs.rs:25-39 (hash = fd - 1),
+ *                                 (files partitioned over the GPUs)  :132-141; cnr/src/replica.rs:430-445
  *
  * Conventions
  *   - Every function returns NRG_OK (0) or a negative NRG_E_* code. Nothing throws or aborts.
@@ -188,8 +191,10 @@ typedef struct {
  *            Else some = 1, n = s (Attr: the size), data zero; size = s. Bytes [s, old size) are gone;
  *            where s is above the old size the new bytes read as zero.
  * Out of scope: directories, names, inode creation and removal, rename; capacity growth past B; the
- * SetAttrRequest fields other than the size; the combiner, partitioned groups and
- * nrg_set_max_capacity for this kind (NRG_E_INVAL from their entry points).
+ * SetAttrRequest fields other than the size; the combiner, key-partitioned group rounds
+ * (nrg_group_partitioned_round*) and nrg_set_max_capacity for this kind (NRG_E_INVAL from their entry
+ * points). A group of file stores is partitioned by FILE instead, as benches/nrfs.rs runs it:
+ * nrg_group_file_round below.
  * A write of more than 128 bytes (benches/nrfs.rs's whole-file FileWrite) is a contiguous run of these
  * records: nrg_memfs_pwrite* below cut it on the device. */
 #define NRG_MEMFS_WRITE 0u   /* OperationWr::Write{ino, offset, data[0..len)}  memfs.rs:66-72  */
@@ -794,8 +799,8 @@ int nrg_skiplist_capacity(nrg_ctx* ctx, uint64_t* n_keys);
  * structure: nrg_log_append* / nrg_log_exec* with records of 152 B and responses of 136 B, and
  * replicated group rounds (nrg_group_round_async). At nrg_open every byte of every file is 0x01
  * (memfs.rs:118). Every call below returns NRG_E_INVAL on a context of another kind, and every
- * other kind's calls return NRG_E_INVAL on this one; nrg_set_max_capacity, the partitioned rounds
- * and nrg_combiner_open return NRG_E_INVAL. */
+ * other kind's calls return NRG_E_INVAL on this one; nrg_set_max_capacity, the key-partitioned rounds
+ * and nrg_combiner_open return NRG_E_INVAL. File-partitioned group rounds: nrg_group_file_round. */
 /* Replica::combine for one batch (memfs.rs:194-292 dispatch_mut per record, in order): append + exec
  * in one replay pass that also writes the log copy; responses of these n ops into d_resp / d_some
  * (both NULL: none wanted). d_ops and d_resp 8-byte aligned. n <= config.max_batch. */
@@ -1081,6 +1086,64 @@ int nrg_group_partitioned_round(nrg_group* g, const nrg_round* rounds);
 int nrg_group_partitioned_round_async(nrg_group* g, const nrg_round* rounds);
 /* Complete the round posted by nrg_group_partitioned_round_async, if any (its result). */
 int nrg_group_partitioned_flush(nrg_group* g);
+
+/* ---- file-partitioned file store (nrfs-mlnr{logs}) --------------------------------------------
+ * benches/nrfs.rs is a cnr benchmark with one log per file: LogMapper::hash() = fd - 1
+ * (benches/nrfs.rs:8, :25-39), LogStrategy::Custom(logs) (:132-141), hash % logs
+ * (cnr/src/replica.rs:430-445); ops on different files never share a log and each log replays on its
+ * own (:673-736). Across GPUs the log of partition p lives on rank p.
+ *   OWNER  of file `ino`: (ino - NRG_MEMFS_FIRST_INO) % parts, and 0 for an ino below NRG_MEMFS_FIRST_INO;
+ *          inos past the last file map by the same formula. Every member applies the same checks in the
+ *          same order, so an ENOENT / EINVAL / EFBIG answer is the same whichever member gives it.
+ *   STATE  every member is opened with the group's full geometry (the same F and B); a file-partitioned
+ *          round changes, on member p, only files that p owns, and a member's copy of a file it does not
+ *          own is never read or written by such a round (cnr: the logs are partitioned, every replica
+ *          still holds the structure).
+ *   ORDER  an owner replays what it received from rank 0, then rank 1, ..., each rank's part in issue
+ *          order: for every file the order of the NR global log W_0 || W_1 || ... restricted to that
+ *          file. Every op touches one file and its size only, so every response is bit for bit the
+ *          replicated round's and every file on its owner is bit for bit the replicated replica's. A
+ *          long write (nrg_memfs_pwrite_records_async) is a contiguous run of Write records of one ino:
+ *          one owner, and the stable partition keeps its order.
+ *   SIZES  either every member has nrg_memfs_enable_sizes on or none has (else NRG_E_INVAL, below). */
+uint32_t nrg_memfs_owner(uint64_t ino, uint32_t parts); /* benches/nrfs.rs:25-39, cnr/src/replica.rs:430-445 */
+/* Stable partition of n records by owner (device buffers, the replica's stream; benches/nrfs.rs:25-39,
+ * cnr/src/replica.rs:430-445, :673-736): d_out holds them grouped by owner 0 .. parts-1, each group in
+ * issue order, compact (no per-owner stride); d_pos[i] = where record i went; d_counts[p] = records of
+ * owner p (u64). n < 2^32 (NRG_E_CAPACITY), 1 <= parts <= NRG_MAX_PARTS; d_ops and d_out 8-byte aligned.
+ * Three launches: owner counts per tile of NRG_MEMFS_PARTITION_TILE records, a scan of them per owner,
+ * the scatter. No byte of d_out at or past n records is written. */
+#define NRG_MEMFS_PARTITION_TILE 256
+int nrg_memfs_partition_async(nrg_ctx* ctx, const nrg_memfs_op* d_ops, uint64_t n, uint32_t parts,
+                              nrg_memfs_op* d_out, uint32_t* d_pos, uint64_t* d_counts);
+/* d_dst[i] = d_src[d_pos[i]], d_dst_some[i] = d_src_some[d_pos[i]]: responses back into issue order
+ * (either pair may be NULL; benches/nrfs.rs:25-39, cnr/src/replica.rs:430-445, :673-736). */
+int nrg_memfs_route_back_async(nrg_ctx* ctx, const nrg_memfs_resp* d_src, const uint8_t* d_src_some,
+                               const uint32_t* d_pos, uint64_t n, nrg_memfs_resp* d_dst, uint8_t* d_dst_some);
+/* One file-partitioned round on every local member of a group of NRG_DS_MEMFS replicas, rank = partition
+ * (benches/nrfs.rs:25-39, cnr/src/replica.rs:430-445, :673-736). rounds[i].recs / n are member i's
+ * nrg_memfs_op records: anything nrg_memfs_round_async takes, the runs nrg_memfs_pwrite_records_async
+ * makes included. resp / some (nrg_memfs_resp, u8) are nullable: if either is NULL the rank asks for no
+ * responses, nothing travels back to it and its buffers are not written. get_keys / n_gets must be
+ * NULL / 0. A round is: one partition on the member's stream; an all-gather of every rank's records per
+ * owner and flags (its receive capacity, a local error, the kind, F, log2 B, sized, wants responses),
+ * read back under the group's deadline (NRG_E_TIMEOUT); the plan; where some rank must grow its receive
+ * buffers, a growth-confirm exchange; ncclSend / ncclRecv of the records to their owners (a rank's own
+ * part is a device copy); the owner's replay with nrg_memfs_round_async in slices of at most max_batch
+ * and origin = rank + 1; responses and some bytes back to the ranks that asked; one route-back launch.
+ * Everything runs on the replica's stream. Returns once the round is queued, after one host round trip
+ * for the counts; nrg_group_sync waits for the rest, and the caller's buffers stay borrowed until then.
+ * Every failure known before the first send / recv is agreed on by all ranks and returned by all of
+ * them, the round dropped everywhere (nothing of it written, no replica changed, the group usable):
+ *   NRG_E_INVAL     a rank with n > 0 and NULL recs (or recs / resp not 8-byte aligned), n_gets != 0, a
+ *                   rank whose replica is not a file store, ranks whose kinds, F, B or sized flags differ
+ *   NRG_E_CAPACITY  n >= 2^32
+ * An EINVAL record latches NRG_E_INVAL on its owner's replica and nrg_group_sync reports it, as ever.
+ * A one-rank group does not partition: it replays the caller's records into the caller's buffers
+ * (NRG_KNOB_EXP bit 16, measurement, makes it take the data-moving path). Row p of nrg_group_verify is
+ * the digest of a replica that replayed only owner p's records. Not for this mode: nrg_group_resync
+ * (every rank would end up with the root's files), a group-wide pread, a pipelined form. */
+int nrg_group_file_round(nrg_group* g, const nrg_round* rounds);
 
 /* Group-wide ordered reads of a partitioned skip-list group. A skip list exists for its order, and
  * under hash partitioning no member alone can answer lower_bound or a range count: every member

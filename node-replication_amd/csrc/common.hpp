@@ -58,6 +58,16 @@ __host__ __device__ __forceinline__ u32 key_owner(u64 key, u32 parts) {
     return (u32)(((mix64(key) & 0xFFFFFFFFull) * parts) >> 32);
 }
 
+// Owner of a file among `parts` file partitions (nrg_memfs_owner; benches/nrfs.rs:25-39 LogMapper::hash
+// = fd - 1, cnr/src/replica.rs:435 hash % logs): the file index modulo parts; an ino below the first
+// file belongs to owner 0. (Almost every index fits 32 bits: the 64-bit remainder is the rare arm.)
+constexpr u64 MF_FIRST_INO = 5;  // NRG_MEMFS_FIRST_INO
+__host__ __device__ __forceinline__ u32 file_owner(u64 ino, u32 parts) {
+    if (ino < MF_FIRST_INO) return 0u;
+    const u64 f = ino - MF_FIRST_INO;
+    return (f >> 32) == 0 ? (u32)f % parts : (u32)(f % parts);
+}
+
 // Home slot of a key: top bits of the mixed key.
 __device__ __forceinline__ u64 table_home(u64 key, u32 shift) { return mix64(key) >> shift; }
 

@@ -96,7 +96,8 @@ int member_init(Member& m, int nranks) {
     m.wx = x;
     m.gwx = x + 4;
     GCHK(hipHostMalloc(&m.h_gwx, WX_MAX * G * 8, hipHostMallocDefault));
-    return m.pt.init(m, nranks);
+    RCHK(m.pt.init(m, nranks));
+    return m.fp.init(m, nranks);
 }
 
 void member_free(Member& m, const Rccl* R) {
@@ -115,6 +116,7 @@ void member_free(Member& m, const Rccl* R) {
     if (m.h_gwx) (void)hipHostFree(m.h_gwx);
     m.pt.free();
     m.sk.free();
+    m.fp.free();
     if (m.ord_ev) (void)hipEventDestroy(m.ord_ev);
     if (m.pstream) (void)hipStreamSynchronize(m.pstream);
     if (m.pstream) (void)hipStreamDestroy(m.pstream);
@@ -146,7 +148,7 @@ int wait_until(nrg_group* g, Q query, const char* phase) {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     const auto dl = t0 + std::chrono::milliseconds(g->timeout_ms);
-    for (uint32_t spin = 0;; spin++) {
+    for (uint32_t naps = 0;;) {
         const hipError_t e = query();
         if (e == hipSuccess) return NRG_OK;
         if (e != hipErrorNotReady) return hip_rc(e);
@@ -157,9 +159,12 @@ int wait_until(nrg_group* g, Q query, const char* phase) {
                           phase, g->timeout_ms);
             return group_fail(g, NRG_E_TIMEOUT, what);
         }
-        // a host round trip is short: spin for the first 200 us, then back off
+        // a host round trip is short: spin for the first 200 us, then back off: 2000 naps of 20 us,
+        // then of 500 us. The naps are counted, not the queries: 200 us of polling is far more than
+        // 2000 queries, and a round's counts that sit behind a replay of a few hundred us (a
+        // file-partitioned round) must not cost a 500 us nap.
         if (now - t0 > std::chrono::microseconds(200))
-            std::this_thread::sleep_for(std::chrono::microseconds(spin < 2000 ? 20 : 500));
+            std::this_thread::sleep_for(std::chrono::microseconds(naps++ < 2000 ? 20 : 500));
     }
 }
 

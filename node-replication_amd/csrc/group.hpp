@@ -1,7 +1,8 @@
-// group.hpp — what the replica group's three files share (private to the library):
+// group.hpp — what the replica group's four files share (private to the library):
 //   group.cpp              the backend, join / open / close, the replicated round, sync, verify, resync
 //   group_partitioned.cpp  key-partitioned rounds (PtMember, PtGroup)
 //   group_reads.cpp        group-wide ordered reads of a partitioned skip-list group (SkMember)
+//   group_files.cpp        file-partitioned rounds of a file-store group (FpMember)
 // A member's state of a protocol is a struct of that protocol's file, embedded in Member: only the
 // owner's file touches its struct (the rule internal.hpp states for HmHost ... MfHost), and
 // member_init / member_free call its init / free. The decisions taken from exchanged words are
@@ -82,6 +83,33 @@ struct SkMember {
     void free();  // (group_reads.cpp; nothing to set up at join: the buffers grow with the first read)
 };
 
+// File-partitioned rounds of a file-store group (nrg_group_file_round): the state of one member. A
+// round is complete, as far as the host goes, when the call returns, so nothing rotates: the stream
+// orders a round's use of these buffers after the previous round's.
+enum FpBuf {
+    FB_OUT,     // its records grouped by owner (the partition's output)
+    FB_POS,     // where each of its records went
+    FB_CNT,     // its exchange words: records per owner (written by the partition), then FW_*
+    FB_ALLCNT,  // every rank's
+    FB_RREC,    // the records it received as an owner, in rank order
+    FB_RRESP,   // the responses to them
+    FB_RSOME,
+    FB_ARESP,   // the responses to its own records, in the partition output's order
+    FB_ASOME,
+    FB_ST,      // the growth-confirm exchange
+    FB_ALLST,
+    FB_N
+};
+
+struct FpMember {
+    DBuf b[FB_N];
+    uint64_t* h_cnt = nullptr;  // pinned: [nranks][nranks + FW_N], every rank's exchange words
+    hipEvent_t cnt_ev = nullptr;  // they are in h_cnt
+    FpPlan plan;
+    int init(Member& m, int nranks);  // (group_files.cpp)
+    void free();
+};
+
 struct Member {
     nrg_ctx* ctx = nullptr;
     int rank = 0;
@@ -109,6 +137,7 @@ struct Member {
     void* xmem = nullptr;
     PtMember pt;
     SkMember sk;
+    FpMember fp;
 };
 
 }  // namespace grp

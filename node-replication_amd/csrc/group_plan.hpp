@@ -1,8 +1,9 @@
 // group_plan.hpp — what a replica group decides from the words its ranks exchanged, as pure host
 // arithmetic: no HIP header and no RCCL header, so tests/group_plan.cpp checks it without a GPU.
 // Every rank runs these on the same exchanged words and so reaches the same code, the same plan and
-// the same byte offsets before any payload moves; group.cpp, group_partitioned.cpp and
-// group_reads.cpp do the waiting, the collectives and the launches around them.
+// the same byte offsets before any payload moves; group.cpp, group_partitioned.cpp, group_reads.cpp
+// and group_files.cpp do the waiting, the collectives and the launches around them
+// (tests/group_files_plan.cpp checks the file-partitioned part).
 #pragma once
 
 #include <stddef.h>
@@ -126,6 +127,86 @@ inline uint64_t replay_chunk(uint64_t log_size, uint64_t max_batch) {
     const uint64_t ring_room = log_size > 2 * GC_FROM_HEAD ? log_size - GC_FROM_HEAD : GC_FROM_HEAD;
     return std::max<uint64_t>(1, std::min<uint64_t>(max_batch, ring_room));
 }
+
+// ---- file-partitioned rounds of a file-store group (group_files.cpp) ------------------------------
+
+// Exchange words per rank (u64) of a file-partitioned round: [0, G) records per owner, then
+enum : uint64_t {
+    FW_CAP = 0,    // received records its buffers hold now
+    FW_ERR = 1,    // -NRG_E_* of a local failure before the exchange, else 0
+    FW_KIND = 2,   // the member's data structure (NRG_DS_*): every rank's must be NRG_DS_MEMFS
+    FW_FILES = 3,  // its F
+    FW_LOG2B = 4,  // its log2 B
+    FW_SIZED = 5,  // 1 when nrg_memfs_enable_sizes is on
+    FW_RESP = 6,   // 1 when this rank wants its responses
+    FW_N = 7,
+};
+
+// The exchanged matrix H holds G rows of fw_cw(G) words, in rank order.
+inline uint64_t fw_cw(int G) { return (uint64_t)G + FW_N; }
+inline uint64_t fw_recs(const uint64_t* H, int G, int s, int o) { return H[(size_t)s * fw_cw(G) + o]; }  // s -> owner o
+inline uint64_t fw_word(const uint64_t* H, int G, int s, uint64_t k) { return H[(size_t)s * fw_cw(G) + G + k]; }
+
+// What every rank concludes from H before any payload moves.
+struct FpAgree {
+    int rc = NRG_OK;        // the code every rank returns: the first FW_ERR in rank order, a rank that is no
+                            // file store, or ranks whose geometry or sized flags differ
+    bool any_grow = false;  // some rank receives more than its buffers hold: all confirm the growth
+    uint64_t wants = 0;     // bit s: rank s wants its responses (G <= NRG_MAX_PARTS = 64)
+};
+
+inline FpAgree fp_agree(const uint64_t* H, int G) {
+    FpAgree A;
+    for (int s = 0; s < G; s++)
+        if (fw_word(H, G, s, FW_ERR)) {
+            A.rc = -(int)fw_word(H, G, s, FW_ERR);  // the same answer on every rank
+            return A;
+        }
+    for (int s = 0; s < G; s++) {
+        bool same = fw_word(H, G, s, FW_KIND) == NRG_DS_MEMFS;
+        for (uint64_t k : {FW_FILES, FW_LOG2B, FW_SIZED}) same = same && fw_word(H, G, s, k) == fw_word(H, G, 0, k);
+        if (!same) {
+            A.rc = NRG_E_INVAL;
+            return A;
+        }
+    }
+    for (int s = 0; s < G; s++) {
+        if (fw_word(H, G, s, FW_RESP)) A.wants |= 1ull << s;
+        uint64_t r = 0;  // what rank s receives
+        for (int o = 0; o < G; o++) r += fw_recs(H, G, o, s);
+        A.any_grow |= r > fw_word(H, G, s, FW_CAP);
+    }
+    return A;
+}
+
+// A round's send / recv plan of one rank, every count and offset in records. The rank's partition
+// output is compact: owner o's group starts at to_off[o] = sum of to[o'], o' < o, and so do the
+// answers that come back for it. What it receives from rank s lies at from_off[s] = sum of
+// from[s'], s' < s: rank order, which is the global log order.
+struct FpPlan {
+    std::vector<uint64_t> to, to_off, from, from_off;
+    uint64_t sent = 0, recvd = 0;  // in all: sent is the rank's own n, if its partition agrees
+};
+
+inline void fp_plan_for(const uint64_t* H, int G, int r, FpPlan& P) {
+    P.to.assign(G, 0), P.to_off.assign(G, 0), P.from.assign(G, 0), P.from_off.assign(G, 0);
+    uint64_t a = 0, b = 0;
+    for (int o = 0; o < G; o++) {
+        P.to[o] = fw_recs(H, G, r, o);
+        P.from[o] = fw_recs(H, G, o, r);
+        P.to_off[o] = a, a += P.to[o];
+        P.from_off[o] = b, b += P.from[o];
+    }
+    P.sent = a;
+    P.recvd = b;
+}
+
+// byte offsets of a record, a response and a some byte at a position of the plan
+constexpr uint64_t FP_REC_BYTES = sizeof(nrg_memfs_op), FP_RESP_BYTES = sizeof(nrg_memfs_resp);
+static_assert(FP_REC_BYTES == 152 && FP_RESP_BYTES == 136, "file store record layout");
+inline uint64_t fp_rec_at(uint64_t records) { return records * FP_REC_BYTES; }
+inline uint64_t fp_resp_at(uint64_t records) { return records * FP_RESP_BYTES; }
+inline uint64_t fp_some_at(uint64_t records) { return records; }
 
 // ---- group-wide skip-list reads (group_reads.cpp) -------------------------------------------------
 

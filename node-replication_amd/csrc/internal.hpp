@@ -493,7 +493,14 @@ u64 pt_desc_words(u64 W, u64 R, u32 parts);
 hipError_t pt_route2(hipStream_t s, const u64* src_a, const uint8_t* src8_a, const u32* pos_a, u64 n_a, u64* dst_a,
                      uint8_t* dst8_a, const u64* src_b, const uint8_t* src8_b, const u32* pos_b, u64 n_b, u64* dst_b,
                      uint8_t* dst8_b);
-void pt_close(nrg_ctx* c);  // partition.hip: free the partition scratch (the hashmap's close)
+void pt_close(nrg_ctx* c);  // partition.hip: free the partition scratch (the hashmap's and the file store's close)
+// the file partition of file-store records (partition.hip; nrg_memfs_partition_async, group_files.cpp):
+// out = the n records grouped by file_owner, compact, each group in issue order; pos[i] = where record i
+// went; total[p] = records of owner p. On the context's stream; n < 2^32.
+hipError_t fp_partition(nrg_ctx* c, const nrg_memfs_op* in, u64 n, u32 parts, nrg_memfs_op* out, u32* pos, u64* total);
+// dst[i] = src[pos[i]], dst8[i] = src8[pos[i]] (either pair may be null)
+hipError_t fp_route(nrg_ctx* c, const nrg_memfs_resp* src, const uint8_t* src8, const u32* pos, u64 n,
+                    nrg_memfs_resp* dst, uint8_t* dst8);
 // hashmap.hip: the log's segment copy (nrg_log_append_segments_async)
 hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_stride, const u64* lens,
                          u64 dst_lo);

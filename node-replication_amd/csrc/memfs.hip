@@ -22,6 +22,10 @@
 // goes through no log record; its FileWrite is nrg_memfs_pwrite* below, a write of any length as a
 // contiguous run of these records, cut on the device straight into the log ring (mf_frag).
 // Out of scope: the combiner, partitioned groups and growth (nrg_set_max_capacity).
+// (That sentence speaks of the key-partitioned entry points, nrg_group_partitioned_round*, which still
+// return NRG_E_INVAL for this kind: a file has no key to hash. A group of file stores is partitioned by
+// file, as benches/nrfs.rs runs it, in group_files.cpp: nrg_group_file_round, with the record partition
+// and the response route-back in partition.hip.)
 //
 // A file is cut into aligned 128-byte LINES; an op of at most 128 bytes touches at most two. Lines
 // are independent of each other; within a line log order decides. A chunk of n records, in stream
@@ -1075,6 +1079,7 @@ static void mf_close(nrg_ctx* c) {
     if (s.d_wup) (void)hipFree(s.d_wup);  // nrg_memfs_pwrite*'s upload
     if (s.h_wup) (void)hipHostFree(s.h_wup);
     if (s.ev_wup) (void)hipEventDestroy(s.ev_wup);
+    pt_close(c);  // the scratch of this replica's file partitioning, if it ever partitioned
 }
 
 static void mf_defaults(nrg_config* cfg) {

@@ -20,6 +20,8 @@
 //                      per-owner counts of a wave live in lane `owner`), then out[dest] = record
 //                      and pos[i] = dest, dest = owner start + tile offset + wave offset + rank
 //   pt_gather_kernel   answers back to the caller's order: dst[i] = src[pos[i]]
+// The file store's records are partitioned by FILE, not by key (benches/nrfs.rs: one log per file):
+// fp_count_kernel / fp_scatter_kernel / fp_route_kernel further down, with pt_scan_kernel between them.
 #include "internal.hpp"
 
 namespace nrg {
@@ -433,6 +435,165 @@ static hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, con
     return hipGetLastError();
 }
 
+// ---- file partitioning of file-store records (nrg_memfs_partition_async, nrg_group_file_round) ----
+// benches/nrfs.rs:25-39 maps an op to the log of its file (LogMapper::hash = fd - 1), cnr/src/replica.rs
+// :430-445 takes it modulo the logs: file_owner (common.hpp). The same three launches as the key
+// partition above (tile counts, per-owner scan of them, scatter; no workgroup waits on another and
+// nothing global is atomic), for nrg_memfs_op records of 19 u64 words with the ino in word 0.
+// A record is too wide for a lane to carry, so the two halves of the scatter are split:
+//   the rank   one lane per record, one record per thread of a 256-record tile (the ballot loop of
+//              pt_scatter_kernel, one round); the record's destination goes to LDS (1 KiB per tile);
+//   the move   the tile's 256 * 19 words by the whole workgroup, thread t taking words t, t + 256, ...:
+//              the loads are contiguous over the whole tile, 8 bytes per lane (the widest aligned
+//              access of a 152-byte record, as mf_frag notes), all 19 in flight before the first
+//              store; the stores are contiguous inside a record and across the records of an owner's
+//              run, whose destinations are consecutive; the lanes of one record read one LDS word.
+// The route-back moves 17-word responses the same way with the sides exchanged: contiguous stores,
+// loads contiguous inside a record.
+constexpr u32 FP_TILE = PT_TPB;  // records per tile, one per thread (include/nrgpu.h says so to the tests)
+constexpr u32 FP_REC_WORDS = sizeof(nrg_memfs_op) / 8, FP_RESP_WORDS = sizeof(nrg_memfs_resp) / 8;
+static_assert(sizeof(nrg_memfs_op) == 152 && sizeof(nrg_memfs_resp) == 136 && MF_FIRST_INO == NRG_MEMFS_FIRST_INO &&
+                  PT_MAX_PARTS == NRG_MAX_PARTS && FP_TILE == NRG_MEMFS_PARTITION_TILE,
+              "file partition: record layout");
+
+__global__ __launch_bounds__(PT_TPB) void fp_count_kernel(const u64* __restrict__ in, u64 n, u32 parts,
+                                                          u32* __restrict__ tcnt) {
+    __shared__ u32 s_c[PT_MAX_PARTS];
+    if (threadIdx.x < PT_MAX_PARTS) s_c[threadIdx.x] = 0;
+    __syncthreads();
+    const u64 i = (u64)blockIdx.x * FP_TILE + threadIdx.x;
+    if (i < n) atomicAdd(&s_c[file_owner(in[i * FP_REC_WORDS], parts)], 1u);
+    __syncthreads();
+    if (threadIdx.x < parts) tcnt[(u64)blockIdx.x * parts + threadIdx.x] = s_c[threadIdx.x];
+}
+
+__global__ __launch_bounds__(PT_TPB) void fp_scatter_kernel(const u64* __restrict__ in, u64 n, u32 parts,
+                                                            const u32* __restrict__ toff, const u64* __restrict__ total,
+                                                            u64* __restrict__ out, u32* __restrict__ pos) {
+    __shared__ u32 s_base[PT_MAX_PARTS];          // owner start: exclusive prefix of the totals
+    __shared__ u32 s_wc[PT_WAVES][PT_MAX_PARTS];  // per wave counts, then wave offsets
+    __shared__ u32 s_dest[FP_TILE];               // where the tile's record j goes
+    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+    if (t == 0) {
+        u32 acc = 0;
+        for (u32 p = 0; p < parts; p++) {
+            s_base[p] = acc;
+            acc += (u32)total[p];
+        }
+    }
+    const u64 t0 = (u64)blockIdx.x * FP_TILE;
+    const u64 i = t0 + t;
+    const bool valid = i < n;
+    const u32 o = valid ? file_owner(in[i * FP_REC_WORDS], parts) : 0u;
+    u32 rank = 0, cnt = 0;  // cnt, lane p: this wave's records of owner p
+    u64 act = __ballot(valid);
+    while (act) {  // one ballot per distinct owner among the wave's 64 records (wave-uniform loop)
+        const int leader = __ffsll((long long)act) - 1;
+        const u32 ol = (u32)__shfl((int)o, leader, 64);
+        const u64 m = __ballot(valid && o == ol);
+        if (valid && o == ol) rank = (u32)__popcll(m & ((1ull << lane) - 1));
+        if ((u32)lane == ol) cnt = (u32)__popcll(m);
+        act &= ~m;
+    }
+    if ((u32)lane < parts) s_wc[w][lane] = cnt;
+    __syncthreads();
+    if (t < (int)parts) {
+        u32 acc = 0;
+        for (int q = 0; q < PT_WAVES; q++) {
+            const u32 c = s_wc[q][t];
+            s_wc[q][t] = acc;
+            acc += c;
+        }
+    }
+    __syncthreads();
+    u32 dest = 0xFFFFFFFFu;
+    if (valid) {
+        dest = s_base[o] + toff[(u64)blockIdx.x * parts + o] + s_wc[w][o] + rank;
+        pos[i] = dest;
+    }
+    s_dest[t] = dest;
+    __syncthreads();
+    // the move: word wd of the tile belongs to its record wd / 19
+    const u64 left = n - t0;
+    const u32 nw = (u32)(left < FP_TILE ? left : FP_TILE) * FP_REC_WORDS;
+    const u64* src = in + t0 * FP_REC_WORDS;
+    u64 v[FP_REC_WORDS];
+#pragma unroll
+    for (u32 k = 0; k < FP_REC_WORDS; k++) {
+        const u32 wd = k * PT_TPB + t;
+        v[k] = wd < nw ? src[wd] : 0ull;
+    }
+#pragma unroll
+    for (u32 k = 0; k < FP_REC_WORDS; k++) {
+        const u32 wd = k * PT_TPB + t;
+        const u32 j = wd / FP_REC_WORDS;
+        const u32 d = s_dest[j];
+        // (d < n always: the counts come from the same records; the bound keeps a caller that
+        // rewrites them under the kernels from storing outside out)
+        if (wd < nw && d < n) out[(u64)d * FP_REC_WORDS + (wd - j * FP_REC_WORDS)] = v[k];
+    }
+}
+
+// responses back into issue order: dst[i] = src[pos[i]] (17 words), dst8[i] = src8[pos[i]]
+__global__ __launch_bounds__(PT_TPB) void fp_route_kernel(const u64* __restrict__ src, const uint8_t* __restrict__ src8,
+                                                          const u32* __restrict__ pos, u64 n, u64* __restrict__ dst,
+                                                          uint8_t* __restrict__ dst8) {
+    __shared__ u32 s_pos[FP_TILE];
+    const int t = threadIdx.x;
+    const u64 t0 = (u64)blockIdx.x * FP_TILE;
+    const u64 i = t0 + t;
+    u32 p = 0xFFFFFFFFu;
+    if (i < n) {
+        p = pos[i];
+        if (dst8 && p < n) dst8[i] = src8[p];  // (p < n: see fp_scatter_kernel)
+    }
+    s_pos[t] = p;
+    __syncthreads();
+    if (!dst) return;
+    const u64 left = n - t0;
+    const u32 nw = (u32)(left < FP_TILE ? left : FP_TILE) * FP_RESP_WORDS;
+    u64* d = dst + t0 * FP_RESP_WORDS;
+    u64 v[FP_RESP_WORDS];
+    u32 ok = 0;
+#pragma unroll
+    for (u32 k = 0; k < FP_RESP_WORDS; k++) {
+        const u32 wd = k * PT_TPB + t;
+        const u32 j = wd / FP_RESP_WORDS;
+        const u32 pj = s_pos[j];
+        const bool live = wd < nw && pj < n;
+        v[k] = live ? src[(u64)pj * FP_RESP_WORDS + (wd - j * FP_RESP_WORDS)] : 0ull;
+        ok |= live ? 1u << k : 0u;
+    }
+#pragma unroll
+    for (u32 k = 0; k < FP_RESP_WORDS; k++)
+        if (ok >> k & 1) d[k * PT_TPB + t] = v[k];
+}
+
+hipError_t fp_partition(nrg_ctx* c, const nrg_memfs_op* in, u64 n, u32 parts, nrg_memfs_op* out, u32* pos, u64* total) {
+    if (parts == 0 || parts > PT_MAX_PARTS || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (n == 0) return hipMemsetAsync(total, 0, parts * sizeof(u64), c->stream);
+    const u64 ntiles = (n + FP_TILE - 1) / FP_TILE;
+    hipError_t e = pt_scratch(c, 2 * ntiles * parts);
+    if (e != hipSuccess) return e;
+    u32* tcnt = (u32*)c->pt.d_buf;
+    u32* toff = tcnt + ntiles * parts;
+    NRG_LAUNCH(c, "fp_count", fp_count_kernel, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n, parts, tcnt);
+    NRG_LAUNCH(c, "fp_scan", pt_scan_kernel, parts, PT_TPB, 0, c->stream, (const u32*)tcnt, (u32)ntiles, parts, toff,
+               total);
+    NRG_LAUNCH(c, "fp_scatter", fp_scatter_kernel, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n, parts,
+               (const u32*)toff, (const u64*)total, (u64*)out, pos);
+    return hipGetLastError();
+}
+
+hipError_t fp_route(nrg_ctx* c, const nrg_memfs_resp* src, const uint8_t* src8, const u32* pos, u64 n,
+                    nrg_memfs_resp* dst, uint8_t* dst8) {
+    if (n == 0 || (!dst && !dst8)) return hipSuccess;
+    if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    NRG_LAUNCH(c, "fp_route", fp_route_kernel, (unsigned)((n + FP_TILE - 1) / FP_TILE), PT_TPB, 0, c->stream,
+               (const u64*)src, src8, pos, n, (u64*)dst, dst8);
+    return hipGetLastError();
+}
+
 }  // namespace nrg
 
 // ---- the key-partitioning entry points (include/nrgpu.h) -------------------------
@@ -463,6 +624,32 @@ int nrg_route_back_async(nrg_ctx* c, const uint64_t* d_src, const uint8_t* d_src
     if (r) return r;
     if (n && (!d_pos || (d_dst && !d_src) || (d_dst8 && !d_src8))) return NRG_E_INVAL;
     HIPCHK(pt_gather(c, d_src, d_src8, d_pos, n, d_dst, d_dst8));
+    return NRG_OK;
+}
+
+// ---- the file-partitioning entry points (include/nrgpu.h; benches/nrfs.rs:25-39) -----------------
+uint32_t nrg_memfs_owner(uint64_t ino, uint32_t parts) { return parts ? nrg::file_owner(ino, parts) : 0u; }
+
+int nrg_memfs_partition_async(nrg_ctx* c, const nrg_memfs_op* d_ops, uint64_t n, uint32_t parts, nrg_memfs_op* d_out,
+                              uint32_t* d_pos, uint64_t* d_counts) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (parts == 0 || parts > NRG_MAX_PARTS || !d_counts) return NRG_E_INVAL;
+    if (n && (!d_ops || !d_out || !d_pos)) return NRG_E_INVAL;
+    if (((uintptr_t)d_ops | (uintptr_t)d_out) & 7) return NRG_E_INVAL;  // (records move as u64 words)
+    if (n >= (1ull << 32)) return NRG_E_CAPACITY;
+    HIPCHK(fp_partition(c, d_ops, n, parts, d_out, d_pos, d_counts));
+    return NRG_OK;
+}
+
+int nrg_memfs_route_back_async(nrg_ctx* c, const nrg_memfs_resp* d_src, const uint8_t* d_src_some, const uint32_t* d_pos,
+                               uint64_t n, nrg_memfs_resp* d_dst, uint8_t* d_dst_some) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (n && (!d_pos || (d_dst && !d_src) || (d_dst_some && !d_src_some))) return NRG_E_INVAL;
+    if (((uintptr_t)d_src | (uintptr_t)d_dst) & 7) return NRG_E_INVAL;
+    if (n >= (1ull << 32)) return NRG_E_CAPACITY;
+    HIPCHK(fp_route(c, d_src, d_src_some, d_pos, n, d_dst, d_dst_some));
     return NRG_OK;
 }
 

@@ -63,7 +63,18 @@ __all__ = [
     "Scan", "Seek", "SkipList", "SlPush",
     "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfSetAttr", "MfWrite",
     "MEMFS_WR_DTYPE", "MfPwrite", "memfs_pwrite_plan", "memfs_wr",
+    "FilePartitionedGroup", "PartitionedGroup", "ReplicaGroup", "memfs_owner", "key_owner",
 ]
+
+
+def __getattr__(name):
+    # the groups live in nrgpu.parallel, which needs torch.distributed: loaded on first use
+    if name in ("parallel", "FilePartitionedGroup", "PartitionedGroup", "ReplicaGroup", "memfs_owner", "key_owner"):
+        import importlib
+
+        mod = importlib.import_module(".parallel", __name__)
+        return mod if name == "parallel" else getattr(mod, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def device_count() -> int:

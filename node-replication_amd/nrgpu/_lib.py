@@ -68,6 +68,7 @@ NRG_MEMFS_ENOENT = 1
 NRG_MEMFS_EFBIG = 2
 NRG_MEMFS_EINVAL = 3
 NRG_MEMFS_MAX_DATA = 128  # data bytes a record carries at most
+NRG_MEMFS_PARTITION_TILE = 256  # records per tile of nrg_memfs_partition_async
 
 # nrg_vspace_op (32 B), nrg_vspace_resp (16 B) and nrg_vspace_leaf (16 B)
 VSPACE_OP_DTYPE = np.dtype([("vbase", "<u8"), ("pbase", "<u8"), ("len", "<u8"), ("op", "<u4"), ("rights", "<u4")])
@@ -325,6 +326,10 @@ SIGNATURES = {
     "nrg_group_partitioned_round": (C.c_int, [vp, C.POINTER(Round)]),
     "nrg_group_partitioned_round_async": (C.c_int, [vp, C.POINTER(Round)]),
     "nrg_group_partitioned_flush": (C.c_int, [vp]),
+    "nrg_memfs_owner": (C.c_uint32, [u64, C.c_uint32]),
+    "nrg_memfs_partition_async": (C.c_int, [vp, vp, u64, C.c_uint32, vp, vp, vp]),
+    "nrg_memfs_route_back_async": (C.c_int, [vp, vp, vp, vp, u64, vp, vp]),
+    "nrg_group_file_round": (C.c_int, [vp, C.POINTER(Round)]),
     "nrg_group_skiplist_seek": (C.c_int, [vp, C.POINTER(Seek), C.c_uint32]),
     "nrg_group_skiplist_range_count": (C.c_int, [vp, C.POINTER(Count)]),
     "nrg_group_skiplist_scan": (C.c_int, [vp, C.POINTER(Scan), C.c_uint32, C.c_uint32]),

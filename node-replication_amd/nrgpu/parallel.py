@@ -375,6 +375,45 @@ class PartitionedGroup(ReplicaGroup):
         return out[:n]
 
 
+# ---- file-partitioned file store (nrfs-mlnr) ---------------------------------------------------
+# benches/nrfs.rs is a cnr benchmark with one log per file (LogMapper::hash = fd - 1, :25-39; hash % logs,
+# cnr/src/replica.rs:430-445): ops on different files never share a log. Here partition p's log lives on
+# rank p; every rank holds all F files and a round changes, on rank p, only the files p owns.
+
+
+def memfs_owner(inos, parts: int):
+    """nrg_memfs_owner over an array: (ino - NRG_MEMFS_FIRST_INO) % parts, and 0 for an ino below
+    NRG_MEMFS_FIRST_INO (and for parts == 0, as the C function answers)."""
+    import numpy as np
+
+    ino = np.ascontiguousarray(inos).astype(np.uint64, copy=False).reshape(-1)
+    first = np.uint64(L.NRG_MEMFS_FIRST_INO)
+    if parts == 0:
+        return np.zeros(ino.shape, np.int64)
+    idx = np.where(ino >= first, ino - first, np.uint64(0))  # (below the first ino: 0 % parts = 0)
+    return (idx % np.uint64(parts)).astype(np.int64)
+
+
+class FilePartitionedGroup(ReplicaGroup):
+    """This rank's file-store replica as partition `rank` of a file-partitioned group
+    (nrg_group_file_round): every rank opened with the same F and B, sizes enabled on all or on none."""
+
+    def owner(self, ino: int) -> int:
+        """The rank that owns file `ino` in this group."""
+        return int(self._lib.nrg_memfs_owner(int(ino), self.world))
+
+    def round(self, recs, n: int, resp=None, some=None):
+        """One round of this rank's n nrg_memfs_op records (device tensor or raw pointer), queued once
+        the counts are exchanged; resp / some (n * 136 bytes, n bytes; both or neither) receive the
+        responses in issue order. sync() waits for it; the buffers stay borrowed until then."""
+        r = self._round
+        r.recs, r.n, r.resp, r.some = _ptr(recs), n, _ptr(resp), _ptr(some)
+        r.get_keys, r.n_gets, r.get_vals, r.get_found = 0, 0, 0, 0
+        rc = self._lib.nrg_group_file_round(self._h, C.byref(r))
+        if rc:
+            self._check(rc, "nrg_group_file_round")
+
+
 class PartitionedHashMap:
     """Key-partitioned rounds with the exchanges done by torch.distributed (all_to_all_single;
     gloo on CPU tests, see PartitionedGroup for RCCL). `replica` must provide
