@@ -44,6 +44,9 @@
  *   nrg_memfs_owner, nrg_memfs_partition_async, nrg_memfs_route_back_async, nrg_group_file_round
  *                                 nrfs-mlnr: one log per file        benches/nrfs.rs:25-39 (hash = fd - 1),
  *                                 (files partitioned over the GPUs)  :132-141; cnr/src/replica.rs:430-445
+ *   nrg_memfs_rd_partition_async, nrg_memfs_pread_repack_async, nrg_group_memfs_pread
+ *                                 exec_ro(OpRd::FileRead(fd)) routed benches/nrfs.rs:88-101, :146-152;
+ *                                 to the owner of the file's log     cnr/src/replica.rs:430-445
  *
  * Conventions
  *   - Every function returns NRG_OK (0) or a negative NRG_E_* code. Nothing throws or aborts.
@@ -1141,9 +1144,78 @@ int nrg_memfs_route_back_async(nrg_ctx* ctx, const nrg_memfs_resp* d_src, const 
  * An EINVAL record latches NRG_E_INVAL on its owner's replica and nrg_group_sync reports it, as ever.
  * A one-rank group does not partition: it replays the caller's records into the caller's buffers
  * (NRG_KNOB_EXP bit 16, measurement, makes it take the data-moving path). Row p of nrg_group_verify is
- * the digest of a replica that replayed only owner p's records. Not for this mode: nrg_group_resync
- * (every rank would end up with the root's files), a group-wide pread, a pipelined form. */
+ * the digest of a replica that replayed only owner p's records. After such a round the only correct
+ * copy of a file is its owner's: read with nrg_group_memfs_pread below, not with nrg_memfs_pread* on a
+ * member. Not for this mode: nrg_group_resync (every rank would end up with the root's files), a
+ * pipelined form. */
 int nrg_group_file_round(nrg_group* g, const nrg_round* rounds);
+
+/* The building blocks of the group-wide pread below, on one replica's stream (device buffers).
+ * nrg_memfs_rd_partition_async: the stable partition of n pread requests by the owner of their file
+ * (benches/nrfs.rs:25-39 LogMapper::hash, cnr/src/replica.rs:430-445), as nrg_memfs_partition_async
+ * partitions records: d_out grouped by owner 0 .. parts-1, each group in request order, compact;
+ * d_pos[i] = where request i went; d_counts[p] = requests of owner p. The same three launches over
+ * tiles of NRG_MEMFS_PARTITION_TILE requests; no byte of d_out at or past n requests is written.
+ * n < 2^32 (NRG_E_CAPACITY), 1 <= parts <= NRG_MAX_PARTS; d_reqs and d_out 8-byte aligned. */
+int nrg_memfs_rd_partition_async(nrg_ctx* ctx, const nrg_memfs_rd* d_reqs, uint64_t n, uint32_t parts,
+                                 nrg_memfs_rd* d_out, uint32_t* d_pos, uint64_t* d_counts);
+/* nrg_memfs_pread_repack_async: answers that lie packed in PARTITION order back into REQUEST order
+ * (the asker's half of OpRd::FileRead routed to its log's owner, benches/nrfs.rs:88-101, :146-152,
+ * cnr/src/replica.rs:430-445). Partition position p holds d_src_cnt[p] bytes and the byte d_src_some[p];
+ * d_src is their concatenation in partition order. Request i (at position p = d_pos[i], a permutation
+ * of 0 .. n-1) gets d_some[i] = d_src_some[p], d_offs[i + 1] = d_offs[i] + d_src_cnt[p] (n + 1 words,
+ * d_offs[0] = 0), and its bytes at d_data[d_offs[i] ..): the layout nrg_memfs_pread_async writes, by
+ * the same copy kernel (tiles of NRG_MF_PREAD_TILE output bytes), and as there no byte of d_data at or
+ * past min(cap, d_offs[n]) is ever written. d_src must be 16-byte aligned and READABLE up to the next
+ * multiple of 16 past its last byte (the copy reads the aligned 16-byte blocks around a source byte);
+ * NRG_E_INVAL otherwise, for d_src_cnt or d_offs not 8-byte aligned, and with n > 0 for a NULL
+ * d_src_cnt, d_src_some, d_pos, d_offs or d_some, or cap > 0 and a NULL d_data. n >= 2^32:
+ * NRG_E_CAPACITY. n == 0 writes d_offs[0] = 0. A position >= n counts as 0 bytes, some = 0. */
+int nrg_memfs_pread_repack_async(nrg_ctx* ctx, const uint8_t* d_src, const uint64_t* d_src_cnt,
+                                 const uint8_t* d_src_some, const uint32_t* d_pos, uint64_t n, uint8_t* d_data,
+                                 uint64_t cap, uint64_t* d_offs /* n + 1 */, uint8_t* d_some /* n */);
+/* Group-wide pread of a file-partitioned group: exec_ro(OpRd::FileRead(fd)) of benches/nrfs.rs:88-101,
+ * :146-152, routed to the owner of the file's log as cnr/src/replica.rs:430-445 routes it, here POSIX
+ * pread of any length as nrg_memfs_pread. reads[i] is local member i's part (device pointers on its GPU;
+ * reqs 8-byte aligned). Member r's some, offs and data are exactly what nrg_memfs_pread would give for
+ * r's requests on a replica whose every file is its OWNER's copy (sizes on: clipped at the owner's
+ * size); inos below NRG_MEMFS_FIRST_INO and past the last file answer some = 0 and no bytes, whichever
+ * owner the formula picks. Nothing is logged and no replica changes: the rows of nrg_group_verify are
+ * the same before and after. A collective shaped like nrg_group_skiplist_seek: every rank calls it, the
+ * ranks' n may differ, n = 0 on every rank returns NRG_OK after the exchange; it first completes queued
+ * group work as nrg_group_sync does (a latched device error is reported at the end) and returns when
+ * the answers are in the callers' buffers. config.max_reads does not apply: the scratch is the group's
+ * and grows on demand. On the replica's stream, host waits under the group's deadline:
+ *   1  the partition of the member's requests by owner (nrg_memfs_rd_partition_async); an all-gather of
+ *      every rank's requests per owner and its words (receive capacity, a local error, the kind, F,
+ *      log2 B, sized, cap), read back: host round trip 1, the agreement and the plan;
+ *   2  ncclSend / ncclRecv of the 24-byte requests to their owners (a rank's own part: a device copy);
+ *   3  the owner scans the clipped lengths of all it received (the kernels of nrg_memfs_pread_async):
+ *      a count and a some byte per request, and the bytes T[o][s] it owes each asker s;
+ *   4  counts and some bytes back to the askers; an all-gather of every owner's row of T, read back:
+ *      host round trip 2, the capacity decision and every byte offset;
+ *   5  the owner's packed bytes (the copy kernel of nrg_memfs_pread_async), sent to the askers;
+ *   6  the re-pack into request order (nrg_memfs_pread_repack_async).
+ * A one-rank group runs nrg_memfs_pread_async's kernels straight into the caller's buffers
+ * (NRG_KNOB_EXP bit 16, measurement, makes it take steps 1 to 6). Every failure is agreed on by all
+ * ranks from the exchanged words before any data byte moves, the first in rank order wins, and the
+ * group stays usable:
+ *   NRG_E_INVAL       n > 0 with a NULL reqs, offs or some; cap > 0 with a NULL data; reqs or offs not
+ *                     8-byte aligned; a member that is no file store; ranks whose F, B or sized flags differ
+ *   NRG_E_NOT_SYNCED  a member with ltail < tail
+ *   NRG_E_CAPACITY    n >= 2^32; or some rank's total exceeds its cap: then every rank's offs and some
+ *                     are complete, data[0, cap) is unspecified and nothing at or past cap is written,
+ *                     so a call with cap = 0 and data = NULL on every rank sizes the answer (offs[n]).
+ * NRG_E_COMM / NRG_E_TIMEOUT as nrg_group_verify. Out of scope: a pipelined form, nrg_group_resync. */
+typedef struct {
+    const nrg_memfs_rd* reqs; /* this member's requests */
+    uint64_t n;
+    uint8_t* data;            /* the packed answer */
+    uint64_t cap;
+    uint64_t* offs;           /* n + 1 */
+    uint8_t* some;            /* n */
+} nrg_pread;
+int nrg_group_memfs_pread(nrg_group* g, const nrg_pread* reads);
 
 /* Group-wide ordered reads of a partitioned skip-list group. A skip list exists for its order, and
  * under hash partitioning no member alone can answer lower_bound or a range count: every member

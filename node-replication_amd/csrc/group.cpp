@@ -97,7 +97,8 @@ int member_init(Member& m, int nranks) {
     m.gwx = x + 4;
     GCHK(hipHostMalloc(&m.h_gwx, WX_MAX * G * 8, hipHostMallocDefault));
     RCHK(m.pt.init(m, nranks));
-    return m.fp.init(m, nranks);
+    RCHK(m.fp.init(m, nranks));
+    return m.pr.init(m, nranks);
 }
 
 void member_free(Member& m, const Rccl* R) {
@@ -117,6 +118,7 @@ void member_free(Member& m, const Rccl* R) {
     m.pt.free();
     m.sk.free();
     m.fp.free();
+    m.pr.free();
     if (m.ord_ev) (void)hipEventDestroy(m.ord_ev);
     if (m.pstream) (void)hipStreamSynchronize(m.pstream);
     if (m.pstream) (void)hipStreamDestroy(m.pstream);

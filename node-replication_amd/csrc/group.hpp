@@ -1,8 +1,9 @@
-// group.hpp — what the replica group's four files share (private to the library):
+// group.hpp — what the replica group's five files share (private to the library):
 //   group.cpp              the backend, join / open / close, the replicated round, sync, verify, resync
 //   group_partitioned.cpp  key-partitioned rounds (PtMember, PtGroup)
 //   group_reads.cpp        group-wide ordered reads of a partitioned skip-list group (SkMember)
 //   group_files.cpp        file-partitioned rounds of a file-store group (FpMember)
+//   group_file_reads.cpp   the group-wide pread of such a group (PrMember)
 // A member's state of a protocol is a struct of that protocol's file, embedded in Member: only the
 // owner's file touches its struct (the rule internal.hpp states for HmHost ... MfHost), and
 // member_init / member_free call its init / free. The decisions taken from exchanged words are
@@ -110,6 +111,40 @@ struct FpMember {
     void free();
 };
 
+// The group-wide pread of a file-partitioned group (nrg_group_memfs_pread): the state of one member. The
+// call returns when the answers are in the callers' buffers, so nothing rotates.
+enum PrBuf {
+    RB_OUT,     // its requests grouped by owner (the partition's output)
+    RB_POS,     // where each of its requests went
+    RB_CNT,     // its words of the first exchange: requests per owner (written by the partition), then RW_*
+    RB_ALLCNT,  // every rank's
+    RB_RREQ,    // the requests it received as an owner, in rank order
+    RB_ROFFS,   // the scan of their clipped lengths (one more word than requests)
+    RB_RCNT,    // their clipped lengths
+    RB_RSOME,
+    RB_RAGG,    // the scan's tile aggregates
+    RB_TOT,     // its words of the second exchange: the bytes it owes each asker, then TW_*
+    RB_ALLTOT,  // every rank's
+    RB_SDATA,   // its packed answers as an owner, grouped by asker
+    RB_ACNT,    // the clipped lengths of its own requests, in the partition output's order
+    RB_ASOME,
+    RB_RDATA,   // its own answer packed in that order (16-byte aligned, readable to the next multiple of 16)
+    RB_SOFFS,   // the re-pack's scratch: where each position's bytes begin in RB_RDATA
+    RB_AAGG,    // ... and its scans' tile aggregates
+    RB_N
+};
+
+struct PrMember {
+    DBuf b[RB_N];
+    uint64_t* h_cnt = nullptr;  // pinned: [nranks][nranks + RW_N], every rank's words of the first exchange
+    uint64_t* h_tot = nullptr;  // pinned: [nranks][nranks + TW_N], of the second
+    hipEvent_t ev = nullptr;    // they are there
+    FpPlan plan;                // in requests
+    PrBytePlan bytes;
+    int init(Member& m, int nranks);  // (group_file_reads.cpp)
+    void free();
+};
+
 struct Member {
     nrg_ctx* ctx = nullptr;
     int rank = 0;
@@ -138,6 +173,7 @@ struct Member {
     PtMember pt;
     SkMember sk;
     FpMember fp;
+    PrMember pr;
 };
 
 }  // namespace grp
@@ -227,6 +263,10 @@ int pt_check(nrg_group* g);
 // A one-rank group owns every key, so its partition is the identity and so is the route-back
 // (NRG_KNOB_EXP bit 16, measurement, makes it move its data like a multi-rank one).
 inline bool pt_ident(const nrg_group* g, const Member& m) { return g->nranks == 1 && !(m.ctx->exp & 0x10000); }
+
+// ---- group_files.cpp ----
+// dst[k] = v[k], k < n <= FW_N, in stream order (the words are captured at the launch)
+int put_words(hipStream_t s, uint64_t* dst, const uint64_t* v, uint32_t n);
 
 // One collective step: post(member, i) enqueues member i's calls between ncclGroupStart and
 // ncclGroupEnd and returns the first refusal. The order is what keeps a peer from hanging: a

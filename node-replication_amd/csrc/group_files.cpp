@@ -272,6 +272,15 @@ int fp_round_ident(nrg_group* g, const nrg_round& x) {
 
 }  // namespace
 
+int nrg::grp::put_words(hipStream_t s, uint64_t* dst, const uint64_t* v, uint32_t n) {
+    if (n > FW_N) return NRG_E_INVAL;
+    FpWords w{};
+    for (uint32_t k = 0; k < n; k++) w.v[k] = v[k];
+    fp_words_kernel<<<1, 64, 0, s>>>(dst, w, n);
+    GCHK(hipGetLastError());
+    return NRG_OK;
+}
+
 extern "C" {
 
 int nrg_group_file_round(nrg_group* g, const nrg_round* rounds) {

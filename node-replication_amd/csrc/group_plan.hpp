@@ -1,9 +1,10 @@
 // group_plan.hpp — what a replica group decides from the words its ranks exchanged, as pure host
 // arithmetic: no HIP header and no RCCL header, so tests/group_plan.cpp checks it without a GPU.
 // Every rank runs these on the same exchanged words and so reaches the same code, the same plan and
-// the same byte offsets before any payload moves; group.cpp, group_partitioned.cpp, group_reads.cpp
-// and group_files.cpp do the waiting, the collectives and the launches around them
-// (tests/group_files_plan.cpp checks the file-partitioned part).
+// the same byte offsets before any payload moves; group.cpp, group_partitioned.cpp, group_reads.cpp,
+// group_files.cpp and group_file_reads.cpp do the waiting, the collectives and the launches around
+// them (tests/group_files_plan.cpp checks the file-partitioned part, tests/group_pread_plan.cpp the
+// group-wide pread's).
 #pragma once
 
 #include <stddef.h>
@@ -207,6 +208,121 @@ static_assert(FP_REC_BYTES == 152 && FP_RESP_BYTES == 136, "file store record la
 inline uint64_t fp_rec_at(uint64_t records) { return records * FP_REC_BYTES; }
 inline uint64_t fp_resp_at(uint64_t records) { return records * FP_RESP_BYTES; }
 inline uint64_t fp_some_at(uint64_t records) { return records; }
+
+// ---- group-wide pread of a file-partitioned group (group_file_reads.cpp) --------------------------
+
+// Exchange words per rank (u64) of the read's first exchange: [0, G) requests per owner, then
+enum : uint64_t {
+    RW_CAP = 0,    // received requests its buffers hold now
+    RW_ERR = 1,    // -NRG_E_* of a local failure before the exchange, else 0
+    RW_KIND = 2,   // the member's data structure (NRG_DS_*): every rank's must be NRG_DS_MEMFS
+    RW_FILES = 3,  // its F
+    RW_LOG2B = 4,  // its log2 B
+    RW_SIZED = 5,  // 1 when nrg_memfs_enable_sizes is on
+    RW_DCAP = 6,   // the bytes its caller's data buffer holds (nrg_pread::cap)
+    RW_N = 7,
+};
+// A row has the file round's layout (fw_cw words, the per-owner counts first), so fp_plan_for plans
+// the requests' way to their owners and the counts' way back: FpPlan in requests.
+static_assert((uint64_t)RW_N == (uint64_t)FW_N, "a read's exchange row is laid out as a file round's");
+inline uint64_t rw_cw(int G) { return fw_cw(G); }
+inline uint64_t rw_reqs(const uint64_t* H, int G, int s, int o) { return fw_recs(H, G, s, o); }  // s -> owner o
+inline uint64_t rw_word(const uint64_t* H, int G, int s, uint64_t k) { return fw_word(H, G, s, k); }
+
+// What every rank concludes from H before any request moves.
+struct PrAgree {
+    int rc = NRG_OK;        // the first RW_ERR in rank order, or ranks whose geometry or sized flags differ
+    bool any_grow = false;  // some owner receives more requests than its buffers hold: all confirm the growth
+    uint64_t asked = 0;     // requests of all ranks (0: nothing to answer)
+};
+
+inline PrAgree pr_agree(const uint64_t* H, int G) {
+    PrAgree A;
+    for (int s = 0; s < G; s++)
+        if (rw_word(H, G, s, RW_ERR)) {
+            A.rc = -(int)rw_word(H, G, s, RW_ERR);  // the same answer on every rank
+            return A;
+        }
+    for (int s = 0; s < G; s++) {
+        bool same = rw_word(H, G, s, RW_KIND) == NRG_DS_MEMFS;
+        for (uint64_t k : {RW_FILES, RW_LOG2B, RW_SIZED}) same = same && rw_word(H, G, s, k) == rw_word(H, G, 0, k);
+        if (!same) {
+            A.rc = NRG_E_INVAL;
+            return A;
+        }
+    }
+    for (int s = 0; s < G; s++) {
+        uint64_t r = 0;  // what owner s receives
+        for (int o = 0; o < G; o++) r += rw_reqs(H, G, o, s);
+        A.any_grow |= r > rw_word(H, G, s, RW_CAP);
+        A.asked += r;
+    }
+    return A;
+}
+
+// Words per rank (u64) of the second exchange: [0, G) T[o][s], the bytes owner o answers asker s with, then
+enum : uint64_t {
+    TW_SCAP = 0,  // the bytes its packed send buffer holds now
+    TW_RCAP = 1,  // the bytes its receive buffer holds now
+    TW_N = 2,
+};
+inline uint64_t tw_cw(int G) { return (uint64_t)G + TW_N; }
+inline uint64_t tw_bytes(const uint64_t* T, int G, int o, int s) { return T[(size_t)o * tw_cw(G) + s]; }  // owner o -> s
+inline uint64_t tw_word(const uint64_t* T, int G, int o, uint64_t k) { return T[(size_t)o * tw_cw(G) + G + k]; }
+
+// The re-pack's wide path reads the aligned 16-byte blocks around a source byte: a receive buffer of
+// `bytes` answer bytes is readable up to the next multiple of 16.
+inline uint64_t pr_recv_room(uint64_t bytes) { return (bytes + 15) / 16 * 16; }
+
+// An asker's answer in bytes: column s of T. (A count is at most B <= 2^26 and a rank asks fewer than
+// 2^32 requests: no sum wraps.)
+inline uint64_t pr_answer_bytes(const uint64_t* T, int G, int s) {
+    uint64_t t = 0;
+    for (int o = 0; o < G; o++) t += tw_bytes(T, G, o, s);
+    return t;
+}
+
+// What every rank concludes from both exchanges before any data byte moves.
+struct PrBytes {
+    int rc = NRG_OK;        // NRG_E_CAPACITY: some rank's answer exceeds its RW_DCAP
+    bool any_grow = false;  // some rank's send or receive buffer has to grow: all confirm the growth
+};
+
+inline PrBytes pr_bytes_agree(const uint64_t* H, const uint64_t* T, int G) {
+    PrBytes B;
+    for (int s = 0; s < G; s++) {
+        const uint64_t answer = pr_answer_bytes(T, G, s);
+        if (answer > rw_word(H, G, s, RW_DCAP)) B.rc = NRG_E_CAPACITY;
+        uint64_t packed = 0;  // what s sends as an owner: row s
+        for (int a = 0; a < G; a++) packed += tw_bytes(T, G, s, a);
+        B.any_grow |= packed > tw_word(T, G, s, TW_SCAP) || pr_recv_room(answer) > tw_word(T, G, s, TW_RCAP);
+    }
+    return B;
+}
+
+// The data's send / recv plan of one rank, in bytes. As an owner its packed answers lie grouped by
+// asker in rank order: asker s's at to_off[s], a prefix of row T[r][.]. As an asker it receives owner
+// o's bytes at from_off[o], a prefix of column T[.][r]: its answer packed in partition order.
+struct PrBytePlan {
+    std::vector<uint64_t> to, to_off, from, from_off;
+    uint64_t sent = 0, recvd = 0;
+};
+
+inline void pr_byte_plan_for(const uint64_t* T, int G, int r, PrBytePlan& P) {
+    P.to.assign(G, 0), P.to_off.assign(G, 0), P.from.assign(G, 0), P.from_off.assign(G, 0);
+    uint64_t a = 0, b = 0;
+    for (int o = 0; o < G; o++) {
+        P.to[o] = tw_bytes(T, G, r, o);
+        P.from[o] = tw_bytes(T, G, o, r);
+        P.to_off[o] = a, a += P.to[o];
+        P.from_off[o] = b, b += P.from[o];
+    }
+    P.sent = a;
+    P.recvd = b;
+}
+
+constexpr uint64_t PR_REQ_BYTES = sizeof(nrg_memfs_rd);
+static_assert(PR_REQ_BYTES == 24, "file store request layout");
 
 // ---- group-wide skip-list reads (group_reads.cpp) -------------------------------------------------
 

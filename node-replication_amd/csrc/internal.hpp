@@ -232,6 +232,9 @@ struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, conti
     uint64_t* d_desc = nullptr;  // [max_batch] record descriptors
     // scratch of one nrg_memfs_pread_async: [ceil(max_reads / 1024)] scan-tile aggregates
     uint64_t* d_pagg = nullptr;
+    // scratch of one nrg_memfs_pread_repack_async, grown on demand: n + 1 source offsets, then aggregates
+    uint64_t* d_rpk = nullptr;
+    uint64_t rpk_words = 0;
     // Sizes (nrg_memfs_enable_sizes; nullptr: the context is unsized and none of the below exists)
     uint64_t* d_size = nullptr;  // [F] every file's size; stored bytes at or past it are zero
     uint32_t file_bits = 0;      // ceil(log2 F): what a sized chunk's file sort sorts by
@@ -501,6 +504,29 @@ hipError_t fp_partition(nrg_ctx* c, const nrg_memfs_op* in, u64 n, u32 parts, nr
 // dst[i] = src[pos[i]], dst8[i] = src8[pos[i]] (either pair may be null)
 hipError_t fp_route(nrg_ctx* c, const nrg_memfs_resp* src, const uint8_t* src8, const u32* pos, u64 n,
                     nrg_memfs_resp* dst, uint8_t* dst8);
+// ... and of pread requests (nrg_memfs_rd_partition_async, group_file_reads.cpp): the same, 24-byte records
+hipError_t rd_partition(nrg_ctx* c, const nrg_memfs_rd* in, u64 n, u32 parts, nrg_memfs_rd* out, u32* pos, u64* total);
+// memfs.hip: the pread kernels over n < 2^32 requests in the caller's device buffers, on the context's
+// stream (the replica group's group-wide pread; no max_reads bound: d_agg is the caller's scratch of
+// mf_pread_agg_words(n) words).
+u64 mf_pread_agg_words(u64 n);
+u64 mf_pread_bound(const nrg_ctx* c, u64 n, u64 cap);  // the most bytes n requests can answer, or cap if that is less
+// the scan: d_offs[0 .. n], d_some and, if given, every request's clipped length d_cnt
+hipError_t mf_pread_scan_launch(nrg_ctx* c, const nrg_memfs_rd* d_reqs, u64 n, u64* d_offs, uint8_t* d_some, u64* d_cnt,
+                                u64* d_agg);
+// the copy of the scanned requests' bytes into d_data[0, min(cap, d_offs[n])); bound: what the host
+// knows that minimum cannot exceed (the grid)
+hipError_t mf_pread_copy_launch(nrg_ctx* c, const nrg_memfs_rd* d_reqs, u64 n, const u64* d_offs, uint8_t* d_data, u64 cap,
+                                u64 bound);
+// an owner's bytes per asker: d_out[s], s < G, from the offsets at the asker boundaries of its recvd requests
+// (d_allcnt: every rank's exchange words, cw per rank, requests per owner first)
+hipError_t mf_pread_totals_launch(nrg_ctx* c, const u64* d_offs, u64 recvd, const u64* d_allcnt, u32 G, u32 cw, u32 rank,
+                                  u64* d_out);
+// nrg_memfs_pread_repack_async's two halves: d_offs, d_some and d_src_offs[0 .. n] (scratch); then the bytes
+hipError_t mf_repack_scan_launch(nrg_ctx* c, const u64* d_src_cnt, const uint8_t* d_src_some, const u32* d_pos, u64 n,
+                                 u64* d_offs, uint8_t* d_some, u64* d_src_offs, u64* d_agg);
+hipError_t mf_repack_copy_launch(nrg_ctx* c, const uint8_t* d_src, const u64* d_src_offs, const u32* d_pos, u64 n,
+                                 const u64* d_offs, uint8_t* d_data, u64 cap, u64 bound);
 // hashmap.hip: the log's segment copy (nrg_log_append_segments_async)
 hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_stride, const u64* lens,
                          u64 dst_lo);

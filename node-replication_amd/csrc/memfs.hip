@@ -665,6 +665,15 @@ __global__ __launch_bounds__(DG_TPB) void mfs_check_kernel(const u64* words, u64
 //              the output) is gathered byte by byte, stepping to the next request, or searching for it
 //              where the next is empty, and stored whole when all 16 bytes are output bytes.
 //              Plain loads and stores; no LDS, no atomics, no spinning.
+// The kernels are templates over where a request's count and bytes come from. PACKED = false is the
+// store, above. PACKED = true is the re-pack of a group-wide pread (nrg_memfs_pread_repack_async,
+// group_file_reads.cpp): the owners' answers lie packed in PARTITION order in a buffer, position p
+// holding src_cnt[p] bytes, and request i sits at p = pos[i]. The scan then sums src_cnt (once in
+// partition order for the positions' offsets src_offs, once through pos for offs) and the copy is the
+// same variable-length move with the source address src + src_offs[pos[r]] instead of the file's: one
+// kernel, balanced over the tiles of the OUTPUT either way. The wide path reads the aligned 16-byte
+// blocks around a source byte, so a packed source is 16-byte aligned and readable up to the next
+// multiple of 16 past its end, as a file is by its size.
 constexpr u32 MF_PR_ITEMS = 4;                      // requests per lane of the scan
 constexpr u32 MF_PR_SCAN = MF_TPB * MF_PR_ITEMS;    // requests per scan tile
 constexpr u32 MF_PREAD_TILE = 16384;                // output bytes per copy workgroup (measured)
@@ -683,10 +692,25 @@ struct MfRdJob {
     const uint8_t* files;
     u32 log2_b, nfiles;
     const u64* size;  // a sized context's sizes: the clip (nullptr: B)
+    u64* cnt;         // [n] every request's clipped length as well (nullptr: not wanted)
+    // A packed source instead of the store (PACKED kernels, the re-pack of a group-wide pread): request
+    // i's answer is the src_cnt[p] bytes at src + src_offs[p] and the byte src_some[p], p = pos[i]
+    // (pos == nullptr: p = i; src_some == nullptr: 1; some == nullptr: not written).
+    const uint8_t* src;
+    const u64 *src_offs, *src_cnt;
+    const uint8_t* src_some;
+    const u32* pos;
 };
 
-// request i's clipped length; ok: its ino names a file
+// request i's clipped length; ok: its ino names a file. PACKED: what its owner counted and answered
+// (a position outside [0, n) is no request's: nothing).
+template <bool PACKED>
 __device__ __forceinline__ u64 mf_rd_count(const MfRdJob& j, u64 i, bool* ok) {
+    if constexpr (PACKED) {
+        const u64 p = j.pos ? j.pos[i] : i;
+        *ok = p < j.n && (!j.src_some || j.src_some[p]);
+        return p < j.n ? j.src_cnt[p] : 0;
+    }
     const u64 ino = j.rq[3 * i], off = j.rq[3 * i + 1], len = j.rq[3 * i + 2];
     *ok = ino >= NRG_MEMFS_FIRST_INO && ino - NRG_MEMFS_FIRST_INO < j.nfiles;
     if (!*ok) return 0;
@@ -718,6 +742,7 @@ __device__ __forceinline__ u64 mf_block_excl(u64 v, u64* s_w, u64* total) {
 }
 
 // agg[tile] = the sum of the tile's clipped lengths
+template <bool PACKED>
 __global__ __launch_bounds__(MF_TPB) void mf_pread_reduce_kernel(MfRdJob j, u64* agg) {
     __shared__ u64 s_w[MF_TPB / 64];
     const u64 first = (u64)blockIdx.x * MF_PR_SCAN + threadIdx.x * MF_PR_ITEMS;
@@ -725,7 +750,7 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_reduce_kernel(MfRdJob j, u64*
 #pragma unroll
     for (u32 k = 0; k < MF_PR_ITEMS; k++) {
         bool ok;
-        if (first + k < j.n) sum += mf_rd_count(j, first + k, &ok);
+        if (first + k < j.n) sum += mf_rd_count<PACKED>(j, first + k, &ok);
     }
     u64 tot;
     (void)mf_block_excl(sum, s_w, &tot);
@@ -747,6 +772,7 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_aggscan_kernel(u64* agg, u32 
 }
 
 // some[i], offs[i] and offs[n]; agg: the scanned aggregates, or nullptr for a single tile
+template <bool PACKED>
 __global__ __launch_bounds__(MF_TPB) void mf_pread_scan_kernel(MfRdJob j, const u64* agg) {
     __shared__ u64 s_w[MF_TPB / 64];
     const u64 first = (u64)blockIdx.x * MF_PR_SCAN + threadIdx.x * MF_PR_ITEMS;
@@ -756,8 +782,9 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_scan_kernel(MfRdJob j, const 
         c[k] = 0;
         if (first + k < j.n) {
             bool ok;
-            c[k] = mf_rd_count(j, first + k, &ok);
-            j.some[first + k] = ok ? 1 : 0;
+            c[k] = mf_rd_count<PACKED>(j, first + k, &ok);
+            if (!PACKED || j.some) j.some[first + k] = ok ? 1 : 0;
+            if (!PACKED && j.cnt) j.cnt[first + k] = c[k];
         }
         sum += c[k];
     }
@@ -781,13 +808,17 @@ __device__ __forceinline__ u64 mf_upper(const u64* offs, u64 lo, u64 hi, u64 p) 
     return lo;
 }
 
-// the store's address of packed byte `lo` of request r, whose bytes begin at packed position lo
+// where the first byte of request r's answer lies (r has bytes): in the store, or PACKED in src
+template <bool PACKED>
 __device__ __forceinline__ const uint8_t* mf_rd_src(const MfRdJob& j, u64 r) {
+    if constexpr (PACKED) return j.src + j.src_offs[j.pos[r]];
     return j.files + ((j.rq[3 * r] - NRG_MEMFS_FIRST_INO) << j.log2_b) + j.rq[3 * r + 1];
 }
 
 // Positions below are packed positions plus mis = data & 15, so that a multiple of 16 is an aligned
-// address of the output: the output bytes are [mis, aend).
+// address of the output: the output bytes are [mis, aend). The kernel is the same for both sources: a
+// PACKED one is 16-byte aligned and readable up to the next multiple of 16 past its end, as a file is.
+template <bool PACKED>
 __global__ __launch_bounds__(MF_TPB) void mf_pread_copy_kernel(MfRdJob j) {
     const u64* __restrict__ offs = j.offs;
     const u64 total = offs[j.n];
@@ -808,14 +839,14 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_copy_kernel(MfRdJob j) {
             const u64 lo = a > v0 ? a : v0, hi = a + 16 < a1 ? a + 16 : a1;  // the chunk's output bytes
             u64 r = mf_upper(offs, r_first + 1, r_last, lo - mis) - 1;
             u64 rl = offs[r] + mis, rh = offs[r + 1] + mis;  // request r's bytes: rl <= lo < rh
-            const uint8_t* src = mf_rd_src(j, r);
+            const uint8_t* src = mf_rd_src<PACKED>(j, r);
             const bool whole = hi - lo == 16;
             if (whole && a + 16 <= rh) {  // inside one request
                 const uint8_t* s = src + (a - rl);
                 const u32 sh = (u32)((uintptr_t)s & 15);
                 const ulonglong2 x = *(const ulonglong2*)(s - sh);
                 u64 w0 = x.x, w1 = x.y;
-                if (sh) {  // (the chunk's last byte lies in the second 16 bytes: inside the file)
+                if (sh) {  // (the chunk's last byte lies in the second 16 bytes: inside the file or the source)
                     const ulonglong2 y = *(const ulonglong2*)(s - sh + 16);
                     u64 w2 = y.x;
                     if (sh >= 8) w0 = w1, w1 = y.x, w2 = y.y;
@@ -837,7 +868,7 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_copy_kernel(MfRdJob j) {
                         r = mf_upper(offs, r + 1, r_last, q - mis) - 1;
                         rl = offs[r] + mis, rh = offs[r + 1] + mis;
                     }
-                    src = mf_rd_src(j, r);
+                    src = mf_rd_src<PACKED>(j, r);
                 }
                 const u64 byte = src[q - rl];
                 const u32 k = (u32)(q - a);
@@ -853,6 +884,120 @@ __global__ __launch_bounds__(MF_TPB) void mf_pread_copy_kernel(MfRdJob j) {
             }
         }
     }
+}
+
+// out[s] = the bytes this owner answers asker s with, from the scanned offsets at the asker boundaries:
+// it holds the requests of rank 0, then rank 1, ..., and allcnt (every rank's exchange words, cw per
+// rank, its requests per owner first) says how many of each. One thread per asker.
+__global__ void mf_pread_totals_kernel(const u64* __restrict__ offs, u64 recvd, const u64* __restrict__ allcnt, u32 G,
+                                       u32 cw, u32 rank, u64* __restrict__ out) {
+    const u32 s = threadIdx.x;
+    if (s >= G) return;
+    u64 lo = 0;
+    for (u32 q = 0; q < s; q++) lo += allcnt[(u64)q * cw + rank];
+    u64 hi = lo + allcnt[(u64)s * cw + rank];
+    lo = lo < recvd ? lo : recvd;  // (the plan gives hi <= recvd: the bound keeps the loads inside offs)
+    hi = hi < recvd ? hi : recvd;
+    out[s] = offs[hi] - offs[lo];
+}
+
+// ---- the launchers of the kernels above: nrg_memfs_pread_async, nrg_memfs_pread_repack_async and the
+// ---- replica group's group-wide pread (group_file_reads.cpp), which brings its own scratch -----------
+static MfRdJob mf_rd_job(const nrg_ctx* c, u64 n, u64* offs, uint8_t* some) {
+    MfRdJob j{};
+    j.n = n;
+    j.offs = offs;
+    j.some = some;
+    j.files = c->mf.d_files;
+    j.log2_b = c->mf.log2_b;
+    j.nfiles = (u32)c->mf.files;
+    j.size = c->mf.d_size;
+    return j;
+}
+
+template <bool PACKED>
+static hipError_t mf_scan_launch(nrg_ctx* c, const MfRdJob& j, u64* agg) {
+    if (j.n == 0) return j.offs ? hipMemsetAsync(j.offs, 0, sizeof(u64), c->stream) : hipSuccess;
+    const unsigned tiles = (unsigned)((j.n + MF_PR_SCAN - 1) / MF_PR_SCAN);
+    if (tiles > 1) {
+        NRG_LAUNCH(c, PACKED ? "mf_repack_reduce" : "mf_pread_reduce", mf_pread_reduce_kernel<PACKED>, tiles, MF_TPB, 0,
+                   c->stream, j, agg);
+        NRG_LAUNCH(c, PACKED ? "mf_repack_aggscan" : "mf_pread_aggscan", mf_pread_aggscan_kernel, 1, MF_TPB, 0, c->stream,
+                   agg, (u32)tiles);
+    }
+    NRG_LAUNCH(c, PACKED ? "mf_repack_scan" : "mf_pread_scan", mf_pread_scan_kernel<PACKED>, tiles, MF_TPB, 0, c->stream, j,
+               tiles > 1 ? (const u64*)agg : (const u64*)nullptr);
+    return hipGetLastError();
+}
+
+// one workgroup per tile of the `bound` bytes the host knows the output cannot exceed (the tiles that
+// exist are strided over, surplus workgroups exit)
+template <bool PACKED>
+static hipError_t mf_copy_launch(nrg_ctx* c, const MfRdJob& j, u64 bound) {
+    if (j.n == 0 || bound == 0) return hipSuccess;
+    const u64 ct = (bound + 15 + MF_PREAD_TILE - 1) / MF_PREAD_TILE;
+    NRG_LAUNCH(c, PACKED ? "mf_repack_copy" : "mf_pread_copy", mf_pread_copy_kernel<PACKED>,
+               (unsigned)(ct < MF_PR_MAX_GRID ? ct : MF_PR_MAX_GRID), MF_TPB, 0, c->stream, j);
+    return hipGetLastError();
+}
+
+u64 mf_pread_agg_words(u64 n) { return (n + MF_PR_SCAN - 1) / MF_PR_SCAN; }
+
+// the most bytes n requests can answer, or cap if that is less
+u64 mf_pread_bound(const nrg_ctx* c, u64 n, u64 cap) {
+    const u32 lb = c->mf.log2_b;
+    return n > (~0ull >> lb) || (n << lb) > cap ? cap : n << lb;
+}
+
+hipError_t mf_pread_scan_launch(nrg_ctx* c, const nrg_memfs_rd* d_reqs, u64 n, u64* d_offs, uint8_t* d_some, u64* d_cnt,
+                                u64* d_agg) {
+    MfRdJob j = mf_rd_job(c, n, d_offs, d_some);
+    j.rq = (const u64*)d_reqs;
+    j.cnt = d_cnt;
+    return mf_scan_launch<false>(c, j, d_agg);
+}
+
+hipError_t mf_pread_copy_launch(nrg_ctx* c, const nrg_memfs_rd* d_reqs, u64 n, const u64* d_offs, uint8_t* d_data, u64 cap,
+                                u64 bound) {
+    MfRdJob j = mf_rd_job(c, n, const_cast<u64*>(d_offs), nullptr);
+    j.rq = (const u64*)d_reqs;
+    j.data = d_data;
+    j.cap = cap;
+    return mf_copy_launch<false>(c, j, bound);
+}
+
+hipError_t mf_pread_totals_launch(nrg_ctx* c, const u64* d_offs, u64 recvd, const u64* d_allcnt, u32 G, u32 cw, u32 rank,
+                                  u64* d_out) {
+    if (G == 0 || G > 64) return hipErrorInvalidValue;
+    NRG_LAUNCH(c, "mf_pread_totals", mf_pread_totals_kernel, 1, 64, 0, c->stream, d_offs, recvd, d_allcnt, G, cw, rank,
+               d_out);
+    return hipGetLastError();
+}
+
+hipError_t mf_repack_scan_launch(nrg_ctx* c, const u64* d_src_cnt, const uint8_t* d_src_some, const u32* d_pos, u64 n,
+                                 u64* d_offs, uint8_t* d_some, u64* d_src_offs, u64* d_agg) {
+    // where each position's bytes begin in the source: the scan of the counts in partition order
+    MfRdJob a = mf_rd_job(c, n, d_src_offs, nullptr);
+    a.src_cnt = d_src_cnt;
+    hipError_t e = mf_scan_launch<true>(c, a, d_agg);
+    if (e != hipSuccess) return e;
+    // ... and in the output: the scan of the same counts in request order, with the some bytes
+    MfRdJob b = mf_rd_job(c, n, d_offs, d_some);
+    b.src_cnt = d_src_cnt;
+    b.src_some = d_src_some;
+    b.pos = d_pos;
+    return mf_scan_launch<true>(c, b, d_agg);
+}
+
+hipError_t mf_repack_copy_launch(nrg_ctx* c, const uint8_t* d_src, const u64* d_src_offs, const u32* d_pos, u64 n,
+                                 const u64* d_offs, uint8_t* d_data, u64 cap, u64 bound) {
+    MfRdJob j = mf_rd_job(c, n, const_cast<u64*>(d_offs), nullptr);
+    j.src = d_src;
+    j.src_offs = d_src_offs;
+    j.pos = d_pos;
+    j.data = d_data;
+    j.cap = cap;
+    return mf_copy_launch<true>(c, j, bound);
 }
 
 // ---- writes of any length (nrg_memfs_pwrite*): Replica::combine for benches/nrfs.rs:103-115
@@ -1076,6 +1221,7 @@ static void mf_close(nrg_ctx* c) {
                     s.d_sc,    s.d_ev,   s.d_fm,   s.d_fep,  s.d_sagg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (s.d_rpk) (void)hipFree(s.d_rpk);  // nrg_memfs_pread_repack_async's scratch
     if (s.d_wup) (void)hipFree(s.d_wup);  // nrg_memfs_pwrite*'s upload
     if (s.h_wup) (void)hipHostFree(s.h_wup);
     if (s.ev_wup) (void)hipEventDestroy(s.ev_wup);
@@ -1360,47 +1506,42 @@ static int mf_pread_check(nrg_ctx* c, const void* reqs, uint64_t n, const void* 
     return NRG_OK;
 }
 
-// the most bytes n requests can answer, or cap if that is less
-static uint64_t mf_pread_bound(const nrg_ctx* c, uint64_t n, uint64_t cap) {
-    const uint32_t lb = c->mf.log2_b;
-    return n > (~0ull >> lb) || (n << lb) > cap ? cap : n << lb;
-}
-
 int nrg_memfs_pread_async(nrg_ctx* c, const nrg_memfs_rd* d_reqs, uint64_t n, uint8_t* d_data, uint64_t cap,
                           uint64_t* d_offs, uint8_t* d_some) {
     int r = mf_pread_check(c, d_reqs, n, d_data, cap, d_offs, d_some);
     if (r) return r;
-    if (n == 0) {
-        if (d_offs) HIPCHK(hipMemsetAsync(d_offs, 0, sizeof(uint64_t), c->stream));
-        return NRG_OK;
-    }
+    // the total is on the device: the copy's grid comes from the host's bound, surplus workgroups exit
+    HIPCHK(mf_pread_scan_launch(c, d_reqs, n, d_offs, d_some, nullptr, c->mf.d_pagg));
+    return hip_fail(mf_pread_copy_launch(c, d_reqs, n, d_offs, d_data, cap, mf_pread_bound(c, n, cap)));
+}
+
+// The packed answers' scratch of nrg_memfs_pread_repack_async on a plain replica, grown on demand (the
+// replica's stream is drained before a reallocation): the positions' offsets and the scan aggregates.
+static hipError_t mf_repack_scratch(nrg_ctx* c, uint64_t words) {
     MfHost& s = c->mf;
-    MfRdJob j{};
-    j.rq = (const u64*)d_reqs;
-    j.n = n;
-    j.offs = d_offs;
-    j.some = d_some;
-    j.data = d_data;
-    j.cap = cap;
-    j.files = s.d_files;
-    j.log2_b = s.log2_b;
-    j.nfiles = (u32)s.files;
-    j.size = s.d_size;
-    const unsigned tiles = (unsigned)((n + MF_PR_SCAN - 1) / MF_PR_SCAN);
-    if (tiles > 1) {
-        NRG_LAUNCH(c, "mf_pread_reduce", mf_pread_reduce_kernel, tiles, MF_TPB, 0, c->stream, j, s.d_pagg);
-        NRG_LAUNCH(c, "mf_pread_aggscan", mf_pread_aggscan_kernel, 1, MF_TPB, 0, c->stream, s.d_pagg, (u32)tiles);
-    }
-    NRG_LAUNCH(c, "mf_pread_scan", mf_pread_scan_kernel, tiles, MF_TPB, 0, c->stream, j,
-               tiles > 1 ? (const u64*)s.d_pagg : (const u64*)nullptr);
-    // the total is on the device: the grid comes from the host's bound, surplus workgroups exit
-    const uint64_t bound = mf_pread_bound(c, n, cap);
-    if (bound) {
-        const uint64_t ct = (bound + 15 + MF_PREAD_TILE - 1) / MF_PREAD_TILE;
-        NRG_LAUNCH(c, "mf_pread_copy", mf_pread_copy_kernel, (unsigned)(ct < MF_PR_MAX_GRID ? ct : MF_PR_MAX_GRID), MF_TPB,
-                   0, c->stream, j);
-    }
-    return hip_fail(hipGetLastError());
+    if (s.rpk_words >= words) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    if (s.d_rpk) (void)hipFree(s.d_rpk);
+    s.d_rpk = nullptr;
+    s.rpk_words = 0;
+    if ((e = hipMalloc((void**)&s.d_rpk, words * 8)) != hipSuccess) return e;
+    s.rpk_words = words;
+    return hipSuccess;
+}
+
+int nrg_memfs_pread_repack_async(nrg_ctx* c, const uint8_t* d_src, const uint64_t* d_src_cnt, const uint8_t* d_src_some,
+                                 const uint32_t* d_pos, uint64_t n, uint8_t* d_data, uint64_t cap, uint64_t* d_offs,
+                                 uint8_t* d_some) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (((uintptr_t)d_src & 15) || (((uintptr_t)d_src_cnt | (uintptr_t)d_offs) & 7)) return NRG_E_INVAL;
+    if (n && (!d_src_cnt || !d_src_some || !d_pos || !d_offs || !d_some || (cap && !d_data))) return NRG_E_INVAL;
+    if (n >= (1ull << 32)) return NRG_E_CAPACITY;  // positions are u32
+    HIPCHK(mf_repack_scratch(c, n + 1 + mf_pread_agg_words(n)));
+    uint64_t* so = c->mf.d_rpk;
+    HIPCHK(mf_repack_scan_launch(c, d_src_cnt, d_src_some, d_pos, n, d_offs, d_some, so, so + n + 1));
+    return hip_fail(mf_repack_copy_launch(c, d_src, so, d_pos, n, d_offs, d_data, cap, mf_pread_bound(c, n, cap)));
 }
 
 int nrg_memfs_pread(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, uint8_t* data, uint64_t cap, uint64_t* offs,

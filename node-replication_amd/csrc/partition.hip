@@ -21,7 +21,8 @@
 //                      and pos[i] = dest, dest = owner start + tile offset + wave offset + rank
 //   pt_gather_kernel   answers back to the caller's order: dst[i] = src[pos[i]]
 // The file store's records are partitioned by FILE, not by key (benches/nrfs.rs: one log per file):
-// fp_count_kernel / fp_scatter_kernel / fp_route_kernel further down, with pt_scan_kernel between them.
+// fp_count_kernel / fp_scatter_kernel / fp_route_kernel further down, with pt_scan_kernel between them;
+// the requests of a group-wide pread go the same way (rd_scatter_kernel).
 #include "internal.hpp"
 
 namespace nrg {
@@ -452,27 +453,29 @@ static hipError_t pt_gather(nrg_ctx* c, const u64* src, const uint8_t* src8, con
 // loads contiguous inside a record.
 constexpr u32 FP_TILE = PT_TPB;  // records per tile, one per thread (include/nrgpu.h says so to the tests)
 constexpr u32 FP_REC_WORDS = sizeof(nrg_memfs_op) / 8, FP_RESP_WORDS = sizeof(nrg_memfs_resp) / 8;
+constexpr u32 RD_REQ_WORDS = sizeof(nrg_memfs_rd) / 8;  // a pread request {ino, offset, len}: rd_partition below
 static_assert(sizeof(nrg_memfs_op) == 152 && sizeof(nrg_memfs_resp) == 136 && MF_FIRST_INO == NRG_MEMFS_FIRST_INO &&
                   PT_MAX_PARTS == NRG_MAX_PARTS && FP_TILE == NRG_MEMFS_PARTITION_TILE,
               "file partition: record layout");
 
+// (WORDS: u64 words per record, the ino in word 0: an nrg_memfs_op's 19, or a pread request's 3)
+template <u32 WORDS>
 __global__ __launch_bounds__(PT_TPB) void fp_count_kernel(const u64* __restrict__ in, u64 n, u32 parts,
                                                           u32* __restrict__ tcnt) {
     __shared__ u32 s_c[PT_MAX_PARTS];
     if (threadIdx.x < PT_MAX_PARTS) s_c[threadIdx.x] = 0;
     __syncthreads();
     const u64 i = (u64)blockIdx.x * FP_TILE + threadIdx.x;
-    if (i < n) atomicAdd(&s_c[file_owner(in[i * FP_REC_WORDS], parts)], 1u);
+    if (i < n) atomicAdd(&s_c[file_owner(in[i * WORDS], parts)], 1u);
     __syncthreads();
     if (threadIdx.x < parts) tcnt[(u64)blockIdx.x * parts + threadIdx.x] = s_c[threadIdx.x];
 }
 
-__global__ __launch_bounds__(PT_TPB) void fp_scatter_kernel(const u64* __restrict__ in, u64 n, u32 parts,
-                                                            const u32* __restrict__ toff, const u64* __restrict__ total,
-                                                            u64* __restrict__ out, u32* __restrict__ pos) {
-    __shared__ u32 s_base[PT_MAX_PARTS];          // owner start: exclusive prefix of the totals
-    __shared__ u32 s_wc[PT_WAVES][PT_MAX_PARTS];  // per wave counts, then wave offsets
-    __shared__ u32 s_dest[FP_TILE];               // where the tile's record j goes
+// The rank: where the tile's record of this thread goes in the compact output (valid: it has one, of
+// owner o). s_base (owner start: exclusive prefix of the totals) and s_wc (per wave counts, then wave
+// offsets) are the calling kernel's LDS; every thread of the workgroup calls this.
+__device__ __forceinline__ u32 fp_dest(bool valid, u32 o, u32 parts, const u32* __restrict__ toff,
+                                       const u64* __restrict__ total, u32* s_base, u32 (*s_wc)[PT_MAX_PARTS]) {
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
     if (t == 0) {
         u32 acc = 0;
@@ -481,10 +484,6 @@ __global__ __launch_bounds__(PT_TPB) void fp_scatter_kernel(const u64* __restric
             acc += (u32)total[p];
         }
     }
-    const u64 t0 = (u64)blockIdx.x * FP_TILE;
-    const u64 i = t0 + t;
-    const bool valid = i < n;
-    const u32 o = valid ? file_owner(in[i * FP_REC_WORDS], parts) : 0u;
     u32 rank = 0, cnt = 0;  // cnt, lane p: this wave's records of owner p
     u64 act = __ballot(valid);
     while (act) {  // one ballot per distinct owner among the wave's 64 records (wave-uniform loop)
@@ -506,11 +505,22 @@ __global__ __launch_bounds__(PT_TPB) void fp_scatter_kernel(const u64* __restric
         }
     }
     __syncthreads();
-    u32 dest = 0xFFFFFFFFu;
-    if (valid) {
-        dest = s_base[o] + toff[(u64)blockIdx.x * parts + o] + s_wc[w][o] + rank;
-        pos[i] = dest;
-    }
+    return valid ? s_base[o] + toff[(u64)blockIdx.x * parts + o] + s_wc[w][o] + rank : 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(PT_TPB) void fp_scatter_kernel(const u64* __restrict__ in, u64 n, u32 parts,
+                                                            const u32* __restrict__ toff, const u64* __restrict__ total,
+                                                            u64* __restrict__ out, u32* __restrict__ pos) {
+    __shared__ u32 s_base[PT_MAX_PARTS];
+    __shared__ u32 s_wc[PT_WAVES][PT_MAX_PARTS];
+    __shared__ u32 s_dest[FP_TILE];  // where the tile's record j goes
+    const int t = threadIdx.x;
+    const u64 t0 = (u64)blockIdx.x * FP_TILE;
+    const u64 i = t0 + t;
+    const bool valid = i < n;
+    const u32 o = valid ? file_owner(in[i * FP_REC_WORDS], parts) : 0u;
+    const u32 dest = fp_dest(valid, o, parts, toff, total, s_base, s_wc);
+    if (valid) pos[i] = dest;
     s_dest[t] = dest;
     __syncthreads();
     // the move: word wd of the tile belongs to its record wd / 19
@@ -531,6 +541,26 @@ __global__ __launch_bounds__(PT_TPB) void fp_scatter_kernel(const u64* __restric
         // (d < n always: the counts come from the same records; the bound keeps a caller that
         // rewrites them under the kernels from storing outside out)
         if (wd < nw && d < n) out[(u64)d * FP_REC_WORDS + (wd - j * FP_REC_WORDS)] = v[k];
+    }
+}
+
+// A pread request is three words, so a lane carries its own: the rank above, then three 8-byte stores
+// (every destination index is bounded by n, as above).
+__global__ __launch_bounds__(PT_TPB) void rd_scatter_kernel(const u64* __restrict__ in, u64 n, u32 parts,
+                                                            const u32* __restrict__ toff, const u64* __restrict__ total,
+                                                            u64* __restrict__ out, u32* __restrict__ pos) {
+    __shared__ u32 s_base[PT_MAX_PARTS];
+    __shared__ u32 s_wc[PT_WAVES][PT_MAX_PARTS];
+    const u64 i = (u64)blockIdx.x * FP_TILE + threadIdx.x;
+    const bool valid = i < n;
+    u64 ino = 0, off = 0, len = 0;
+    if (valid) ino = in[i * RD_REQ_WORDS], off = in[i * RD_REQ_WORDS + 1], len = in[i * RD_REQ_WORDS + 2];
+    const u32 dest = fp_dest(valid, valid ? file_owner(ino, parts) : 0u, parts, toff, total, s_base, s_wc);
+    if (!valid) return;
+    pos[i] = dest;
+    if (dest < n) {
+        u64* d = out + (u64)dest * RD_REQ_WORDS;
+        d[0] = ino, d[1] = off, d[2] = len;
     }
 }
 
@@ -577,10 +607,27 @@ hipError_t fp_partition(nrg_ctx* c, const nrg_memfs_op* in, u64 n, u32 parts, nr
     if (e != hipSuccess) return e;
     u32* tcnt = (u32*)c->pt.d_buf;
     u32* toff = tcnt + ntiles * parts;
-    NRG_LAUNCH(c, "fp_count", fp_count_kernel, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n, parts, tcnt);
+    NRG_LAUNCH(c, "fp_count", fp_count_kernel<FP_REC_WORDS>, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n, parts, tcnt);
     NRG_LAUNCH(c, "fp_scan", pt_scan_kernel, parts, PT_TPB, 0, c->stream, (const u32*)tcnt, (u32)ntiles, parts, toff,
                total);
     NRG_LAUNCH(c, "fp_scatter", fp_scatter_kernel, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n, parts,
+               (const u32*)toff, (const u64*)total, (u64*)out, pos);
+    return hipGetLastError();
+}
+
+hipError_t rd_partition(nrg_ctx* c, const nrg_memfs_rd* in, u64 n, u32 parts, nrg_memfs_rd* out, u32* pos, u64* total) {
+    if (parts == 0 || parts > PT_MAX_PARTS || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (n == 0) return hipMemsetAsync(total, 0, parts * sizeof(u64), c->stream);
+    const u64 ntiles = (n + FP_TILE - 1) / FP_TILE;
+    hipError_t e = pt_scratch(c, 2 * ntiles * parts);
+    if (e != hipSuccess) return e;
+    u32* tcnt = (u32*)c->pt.d_buf;
+    u32* toff = tcnt + ntiles * parts;
+    NRG_LAUNCH(c, "rd_count", fp_count_kernel<RD_REQ_WORDS>, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n,
+               parts, tcnt);
+    NRG_LAUNCH(c, "rd_scan", pt_scan_kernel, parts, PT_TPB, 0, c->stream, (const u32*)tcnt, (u32)ntiles, parts, toff,
+               total);
+    NRG_LAUNCH(c, "rd_scatter", rd_scatter_kernel, (unsigned)ntiles, PT_TPB, 0, c->stream, (const u64*)in, n, parts,
                (const u32*)toff, (const u64*)total, (u64*)out, pos);
     return hipGetLastError();
 }
@@ -639,6 +686,18 @@ int nrg_memfs_partition_async(nrg_ctx* c, const nrg_memfs_op* d_ops, uint64_t n,
     if (((uintptr_t)d_ops | (uintptr_t)d_out) & 7) return NRG_E_INVAL;  // (records move as u64 words)
     if (n >= (1ull << 32)) return NRG_E_CAPACITY;
     HIPCHK(fp_partition(c, d_ops, n, parts, d_out, d_pos, d_counts));
+    return NRG_OK;
+}
+
+int nrg_memfs_rd_partition_async(nrg_ctx* c, const nrg_memfs_rd* d_reqs, uint64_t n, uint32_t parts, nrg_memfs_rd* d_out,
+                                 uint32_t* d_pos, uint64_t* d_counts) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (parts == 0 || parts > NRG_MAX_PARTS || !d_counts) return NRG_E_INVAL;
+    if (n && (!d_reqs || !d_out || !d_pos)) return NRG_E_INVAL;
+    if (((uintptr_t)d_reqs | (uintptr_t)d_out) & 7) return NRG_E_INVAL;  // (requests move as u64 words)
+    if (n >= (1ull << 32)) return NRG_E_CAPACITY;
+    HIPCHK(rd_partition(c, d_reqs, n, parts, d_out, d_pos, d_counts));
     return NRG_OK;
 }
 

@@ -69,6 +69,7 @@ NRG_MEMFS_EFBIG = 2
 NRG_MEMFS_EINVAL = 3
 NRG_MEMFS_MAX_DATA = 128  # data bytes a record carries at most
 NRG_MEMFS_PARTITION_TILE = 256  # records per tile of nrg_memfs_partition_async
+NRG_MF_PREAD_TILE = 16384  # output bytes per workgroup of nrg_memfs_pread's copy and of the re-pack
 
 # nrg_vspace_op (32 B), nrg_vspace_resp (16 B) and nrg_vspace_leaf (16 B)
 VSPACE_OP_DTYPE = np.dtype([("vbase", "<u8"), ("pbase", "<u8"), ("len", "<u8"), ("op", "<u4"), ("rights", "<u4")])
@@ -183,6 +184,19 @@ class Count(C.Structure):
         ("his", C.c_void_p),
         ("n", C.c_uint64),
         ("counts", C.c_void_p),
+    ]
+
+
+class Pread(C.Structure):
+    """nrg_pread: one group member's requests of nrg_group_memfs_pread (device pointers on its GPU)."""
+
+    _fields_ = [
+        ("reqs", C.c_void_p),
+        ("n", C.c_uint64),
+        ("data", C.c_void_p),
+        ("cap", C.c_uint64),
+        ("offs", C.c_void_p),
+        ("some", C.c_void_p),
     ]
 
 
@@ -330,6 +344,9 @@ SIGNATURES = {
     "nrg_memfs_partition_async": (C.c_int, [vp, vp, u64, C.c_uint32, vp, vp, vp]),
     "nrg_memfs_route_back_async": (C.c_int, [vp, vp, vp, vp, u64, vp, vp]),
     "nrg_group_file_round": (C.c_int, [vp, C.POINTER(Round)]),
+    "nrg_memfs_rd_partition_async": (C.c_int, [vp, vp, u64, C.c_uint32, vp, vp, vp]),
+    "nrg_memfs_pread_repack_async": (C.c_int, [vp, vp, vp, vp, vp, u64, vp, u64, vp, vp]),
+    "nrg_group_memfs_pread": (C.c_int, [vp, C.POINTER(Pread)]),
     "nrg_group_skiplist_seek": (C.c_int, [vp, C.POINTER(Seek), C.c_uint32]),
     "nrg_group_skiplist_range_count": (C.c_int, [vp, C.POINTER(Count)]),
     "nrg_group_skiplist_scan": (C.c_int, [vp, C.POINTER(Scan), C.c_uint32, C.c_uint32]),

@@ -396,7 +396,8 @@ def memfs_owner(inos, parts: int):
 
 class FilePartitionedGroup(ReplicaGroup):
     """This rank's file-store replica as partition `rank` of a file-partitioned group
-    (nrg_group_file_round): every rank opened with the same F and B, sizes enabled on all or on none."""
+    (nrg_group_file_round, nrg_group_memfs_pread): every rank opened with the same F and B, sizes enabled
+    on all or on none."""
 
     def owner(self, ino: int) -> int:
         """The rank that owns file `ino` in this group."""
@@ -412,6 +413,28 @@ class FilePartitionedGroup(ReplicaGroup):
         rc = self._lib.nrg_group_file_round(self._h, C.byref(r))
         if rc:
             self._check(rc, "nrg_group_file_round")
+
+    def pread(self, reqs, cap: Optional[int] = None):
+        """nrg_group_memfs_pread (a collective: every rank calls it, with its own requests and any number
+        of them): POSIX pread of each request against its file's owner. reqs: a device uint8 tensor of
+        24-byte nrg_memfs_rd requests, or None for an idle rank. cap defaults to n * B. Returns (data,
+        offs, some): data[offs[i]:offs[i + 1]] are request i's bytes (data has cap bytes), offs n + 1
+        int64 words, some n bytes. NRG_E_CAPACITY (raised) when a rank's answer exceeds its cap."""
+        n = 0 if reqs is None else reqs.numel() // 24
+        dev = torch.device("cuda", torch.cuda.current_device()) if reqs is None else reqs.device
+        if cap is None:
+            B = C.c_uint64()
+            L.check(self._lib.nrg_memfs_geometry(self.replica._h, None, C.byref(B)), "nrg_memfs_geometry")
+            cap = n * B.value
+        data = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        offs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        some = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)  # the buffers exist before the replica's stream writes them
+        rd = L.Pread(_ptr(reqs), n, data.data_ptr() if cap else 0, cap, offs.data_ptr(), some.data_ptr())
+        rc = self._lib.nrg_group_memfs_pread(self._h, C.byref(rd))
+        if rc:
+            self._check(rc, "nrg_group_memfs_pread")
+        return data[:cap], offs, some[:n]
 
 
 class PartitionedHashMap:
