@@ -25,6 +25,8 @@
  *   nrg_stack_*                   Stack Dispatch                    benches/stack.rs:36-84, nr/tests/stack.rs:31-96
  *   nrg_*_reserve / _capacity,    Vec::reserve / capacity, SegQueue's  benches/stack.rs:36-84,
  *   nrg_set_max_capacity          segments, VSpace's heap tables     benches/lockfree_comparisons.rs:75-101, benches/vspace.rs:388-419
+ *   nrg_memfs_reserve, and        the growing vector behind          benches/memfs.rs:106-192 (a write past the end
+ *   nrg_set_max_capacity on it    NrMemFilesystem's files            extends the file)
  *   nrg_synth_*                   AbstractDataStructure Dispatch     benches/synthetic.rs:60-195
  *   nrg_queue_*                   FIFO queue Dispatch (SegQueueWrapper) benches/lockfree.rs:43-52, benches/lockfree_comparisons.rs:75-101
  *   nrg_vspace_*                  VSpace Dispatch (x86-64 page table) benches/vspace.rs:177-381, :436-467, :499-526
@@ -193,11 +195,14 @@ typedef struct {
  *            After the EINVAL and ENOENT checks: s > B: some = 0, n = NRG_MEMFS_EFBIG, nothing changes.
  *            Else some = 1, n = s (Attr: the size), data zero; size = s. Bytes [s, old size) are gone;
  *            where s is above the old size the new bytes read as zero.
- * Out of scope: directories, names, inode creation and removal, rename; capacity growth past B; the
- * SetAttrRequest fields other than the size; the combiner, key-partitioned group rounds
- * (nrg_group_partitioned_round*) and nrg_set_max_capacity for this kind (NRG_E_INVAL from their entry
- * points). A group of file stores is partitioned by FILE instead, as benches/nrfs.rs runs it:
- * nrg_group_file_round below.
+ * CAPACITY GROWTH (the file system behind memfs.rs keeps a file's bytes in a growing vector). Without it a
+ * file holds B bytes for its whole life; capacity growth past B is off unless sizes are enabled and nrg_set_max_capacity gave the context a bound of max bytes per file: then WRITE
+ * is valid exactly when offset + len <= max and SETATTR when s <= max, and B grows to hold what is
+ * admitted; "File store: capacity growth" below. Without a bound everything above holds as it stands.
+ * Out of scope: directories, names, inode creation and removal, rename; the SetAttrRequest fields other
+ * than the size; the combiner and key-partitioned group rounds (nrg_group_partitioned_round*) for this
+ * kind (NRG_E_INVAL from their entry points). A group of file stores is partitioned by FILE instead, as
+ * benches/nrfs.rs runs it: nrg_group_file_round below.
  * A write of more than 128 bytes (benches/nrfs.rs's whole-file FileWrite) is a contiguous run of these
  * records: nrg_memfs_pwrite* below cut it on the device. */
 #define NRG_MEMFS_WRITE 0u   /* OperationWr::Write{ino, offset, data[0..len)}  memfs.rs:66-72  */
@@ -328,7 +333,8 @@ int nrg_join(nrg_ctx* ctx);
  * are ABI. The skip list (a SkipMap allocates a node per key) takes the bound in keys: the host keeps
  * len_ub, the exact key count when last read plus every record replayed or prefilled since, and before
  * a chunk could pass the capacity the exact count is read and the runs are reallocated, clipped to the
- * bound (<= 2^28). NRG_E_INVAL: a hashmap (it has config.hashmap_max_log2_slots), a synthetic or a vspace
+ * bound (<= 2^28). The file store takes the bound in BYTES PER FILE and grows by what the admitted records
+ * need, a pure function of the log prefix: "File store: capacity growth" below. NRG_E_INVAL: a hashmap (it has config.hashmap_max_log2_slots), a synthetic or a vspace
  * context; a nonzero bound below the current capacity or above the kind's nrg_open bound (stack
  * < 2^31, queue <= 2^32). NRG_E_NOMEM from a round call: the larger buffer could not be allocated;
  * nothing of the chunk was launched and the replica is unchanged. Synchronous; like every direct
@@ -802,8 +808,8 @@ int nrg_skiplist_capacity(nrg_ctx* ctx, uint64_t* n_keys);
  * structure: nrg_log_append* / nrg_log_exec* with records of 152 B and responses of 136 B, and
  * replicated group rounds (nrg_group_round_async). At nrg_open every byte of every file is 0x01
  * (memfs.rs:118). Every call below returns NRG_E_INVAL on a context of another kind, and every
- * other kind's calls return NRG_E_INVAL on this one; nrg_set_max_capacity, the key-partitioned rounds
- * and nrg_combiner_open return NRG_E_INVAL. File-partitioned group rounds: nrg_group_file_round. */
+ * other kind's calls return NRG_E_INVAL on this one; the key-partitioned rounds and nrg_combiner_open
+ * return NRG_E_INVAL. File-partitioned group rounds: nrg_group_file_round. */
 /* Replica::combine for one batch (memfs.rs:194-292 dispatch_mut per record, in order): append + exec
  * in one replay pass that also writes the log copy; responses of these n ops into d_resp / d_some
  * (both NULL: none wanted). d_ops and d_resp 8-byte aligned. n <= config.max_batch. */
@@ -929,6 +935,55 @@ int nrg_memfs_size(nrg_ctx* ctx, uint64_t ino, uint64_t* size);
  * files as nrg_memfs_init seeds bytes (replicas of one log must be given the same). NRG_E_INVAL: sizes
  * not enabled, an ino outside the range or size > B; NRG_E_NOT_SYNCED while ltail < tail. Synchronous. */
 int nrg_memfs_truncate(nrg_ctx* ctx, uint64_t ino, uint64_t size);
+/* File store: capacity growth. A sized context only (the invariant "every stored byte at or past the
+ * size is zero" defines the new bytes: they are zero, and holes cost nothing); in an unsized context
+ * nrg_set_max_capacity and nrg_memfs_reserve return NRG_E_INVAL.
+ *   THE BOUND   nrg_set_max_capacity(ctx, max_bytes): the unit is BYTES PER FILE. max_bytes is a power of
+ *               two, at least the current B, at most 2^26, with F * max_bytes <= 2^29 (nrg_open's limits);
+ *               else NRG_E_INVAL. 0 turns growth off. NRG_E_NOT_SYNCED while ltail < tail: a record is
+ *               admitted by the bound in force at its own log index, so replicas of one log must set the
+ *               bound at the same log index (nrg_memfs_enable_sizes' rule).
+ *   ADMISSION   with a bound of max: a valid WRITE with len > 0 and offset + len <= max, and a valid
+ *               SETATTR with size <= max, are admitted. Everything else EFBIG covers still answers EFBIG and
+ *               changes nothing (offset + len overflowing 64 bits included). The EINVAL and ENOENT checks
+ *               come first: such a record never causes growth, whatever its offset says.
+ *   CAPACITY    B after any log prefix = max(B at open or the last reserve, the power of two at or above
+ *               the largest admitted end (offset + len, or a SetAttr's size) so far). It is a PURE
+ *               FUNCTION OF THE PREFIX: a maximum, with no doubling rule beyond the rounding. This is
+ *               stronger than the other kinds' guarantee: B, and with it nrg_digest (whose items are every
+ *               word of every file up to B), does not depend on how the log was cut into chunks. A replica
+ *               that runs a fused round and one that follows the ring with nrg_sync in other chunk sizes
+ *               end with the same geometry and the same digest. B changes before a chunk is replayed, to
+ *               what the whole chunk needs; nothing observable happens mid-chunk, since GETATTR answers
+ *               the size, not the capacity. While B < max a replayed chunk costs one more small kernel and
+ *               an 8-byte readback; at B == max the store is a fixed one and nothing is launched or read.
+ *               NRG_E_NOMEM from a round call: the larger store could not be allocated, nothing of the
+ *               chunk was launched and the replica is unchanged.
+ *   DIRECT      nrg_memfs_truncate(ino, size) with B < size <= max grows first; nrg_memfs_init with
+ *               len > B stays NRG_E_INVAL. nrg_memfs_pwrite[_async] decides EFBIG against max, takes the
+ *               need of all its requests from its plan and grows once before its first pass (no readback).
+ *               nrg_memfs_pwrite_records_async decides EFBIG against max (against B with no bound) and does
+ *               not grow: the replay of its records does. A caller of nrg_memfs_pwrite_plan passes the log2
+ *               it wants admission decided against (log2 max under a bound).
+ *   READS       nrg_memfs_pread*, nrg_memfs_read, nrg_memfs_dump, nrg_memfs_geometry, nrg_digest and
+ *               snapshots see the geometry as it stands at the call.
+ *   RESTORE     with a bound, an image of a sized store with the same F and a power-of-two B_img in
+ *               (B, max] is accepted: the context is reallocated to B_img first. B_img < B stays
+ *               NRG_E_INVAL (the store never shrinks); without a bound the rule is as before.
+ *               nrg_group_resync follows.
+ *   GROUPS      replicated rounds: every replica replays every record; set the bound on every member.
+ *               File-partitioned rounds and group-wide preads (nrg_group_file_round,
+ *               nrg_group_memfs_pread): an owner replays only its own files' records, so growth under
+ *               replay would let the members' B diverge. A member with a bound set reports NRG_E_INVAL in
+ *               its exchange word and every rank returns that code together. Such groups grow with
+ *               nrg_memfs_reserve on every member.
+ * nrg_memfs_reserve: the explicit, synchronous half. file_bytes is rounded up to a power of two; never
+ * shrinks (a request the store satisfies returns NRG_OK and does nothing); NRG_E_INVAL beyond nrg_open's
+ * limits or in an unsized context. Works with or without a bound; a store reserved beyond its bound is a
+ * fixed one. nrg_memfs_geometry reports the current B. nrg_memfs_max_capacity: *max_bytes = the bound, 0
+ * for none (no device is touched). */
+int nrg_memfs_reserve(nrg_ctx* ctx, uint64_t file_bytes);
+int nrg_memfs_max_capacity(nrg_ctx* ctx, uint64_t* max_bytes);
 
 /* ---- multi-GPU replica groups (RCCL over xGMI) --------------------------------------------
  * The reference shares ONE log between replicas through cache-coherent memory: every replica's

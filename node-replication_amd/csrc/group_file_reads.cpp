@@ -79,6 +79,7 @@ int recv_grow(Member& m, uint64_t n) {
 int local_check(const Member& m, const nrg_pread& x) {
     const nrg_ctx* c = m.ctx;
     if (c->cfg.ds_kind != NRG_DS_MEMFS) return NRG_E_INVAL;
+    if (c->growth.max_items) return NRG_E_INVAL;  // a bound on a member: group_files.cpp local_check
     if ((x.n && (!x.reqs || !x.offs || !x.some)) || (x.cap && !x.data)) return NRG_E_INVAL;
     if (((uintptr_t)x.reqs | (uintptr_t)x.offs) & 7) return NRG_E_INVAL;
     if (c->ltail < c->tail) return NRG_E_NOT_SYNCED;

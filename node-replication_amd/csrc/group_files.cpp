@@ -75,6 +75,10 @@ uint64_t recv_cap(const Member& m, int G) {
 // what this member's own part of the round is worth before anything is exchanged
 int local_check(const Member& m, const nrg_round& x) {
     if (m.ctx->cfg.ds_kind != NRG_DS_MEMFS || (x.n && !x.recs) || x.n_gets || x.get_keys) return NRG_E_INVAL;
+    // An owner replays its own files' records alone, so growth under replay would let the members' B
+    // diverge: a member with a bound (nrg_set_max_capacity) is refused, and every rank learns it from the
+    // exchange. Such a group grows with nrg_memfs_reserve on every member.
+    if (m.ctx->growth.max_items) return NRG_E_INVAL;
     if (((uintptr_t)x.recs | (uintptr_t)x.resp) & 7) return NRG_E_INVAL;  // (records and responses move as u64 words)
     if (x.n >= (1ull << 32)) return NRG_E_CAPACITY;                        // positions are u32
     return NRG_OK;

@@ -227,6 +227,10 @@ struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, conti
     uint32_t log2_b = 0;
     uint32_t nlines = 0;    // F * B / 128: the 128-byte lines of the store; as a slot key, the sentinel
     uint32_t key_bits = 0;  // ceil(log2(nlines + 1)): what the slot sort sorts by
+    // Capacity growth (nrg_set_max_capacity, sized contexts only; "Capacity growth" in memfs.hip)
+    uint32_t max_log2 = 0;       // log2 of the bound in bytes per file (0: none, a fixed capacity)
+    uint64_t* d_need = nullptr;  // the largest admitted end the need kernel has seen (made with the first bound)
+    bool planned = false;        // the host planned the records being replayed and has grown: no need check
     // scratch of one chunk
     uint32_t* d_keys = nullptr;  // [2 * max_batch] slot keys
     uint64_t* d_desc = nullptr;  // [max_batch] record descriptors
@@ -323,6 +327,10 @@ struct DsOps {
     // fails nothing of it has been launched and the replica is as it was
     hipError_t (*grow)(nrg_ctx* c, u64 new_cap);
     bool auto_grow;  // grows under replay up to nrg_set_max_capacity's bound (else: nrg_*_reserve only)
+    // nrg_set_max_capacity of a kind whose bound is not an item count (the file store: bytes per file),
+    // in place of the runtime's own, which reads `items`; the stream has been drained (nullptr: an item
+    // count, the runtime's)
+    int (*set_bound)(nrg_ctx* c, u64 max);
 };
 const DsOps *hm_ops(), *st_ops(), *sy_ops(), *qu_ops(), *vs_ops(), *sl_ops(), *mf_ops();
 const DsOps* ds_ops(uint32_t kind);  // runtime.cpp; nullptr for an unknown kind
@@ -346,7 +354,7 @@ struct nrg_ctx {
 
     nrg::DevCtl* d_ctl = nullptr;
 
-    nrg::Growth growth;  // of the context's kind (stack, queue, skip list)
+    nrg::Growth growth;  // of the context's kind (stack, queue, skip list; the file store keeps its bound here)
 
     uint64_t rounds = 0;  // replay rounds launched (statistics)
     // set only through nrg_test_set_knob (include/nrgpu_testing.h)

@@ -17,15 +17,18 @@
 // Write's range (EFBIG).
 // Out of scope: directories, names, inode creation and removal, rename.
 // Sizes (SetAttr as ftruncate, Writes that grow a file) are off unless nrg_memfs_enable_sizes was called:
-// the section "Sizes" below. Out of scope: capacity growth past B, the other SetAttrRequest fields.
+// the section "Sizes" below. Out of scope: the other SetAttrRequest fields.
+// Capacity growth past B (nrg_set_max_capacity, nrg_memfs_reserve; sized contexts only): the section
+// "Capacity growth" below. B is read from the context by every call; nothing holds a value from open.
 // benches/nrfs.rs's whole-file 4096-byte ops: its read-only FileRead is nrg_memfs_pread* below, which
 // goes through no log record; its FileWrite is nrg_memfs_pwrite* below, a write of any length as a
 // contiguous run of these records, cut on the device straight into the log ring (mf_frag).
-// Out of scope: the combiner, partitioned groups and growth (nrg_set_max_capacity).
+// Out of scope: the combiner, partitioned groups and growth inside a partitioned round.
 // (That sentence speaks of the key-partitioned entry points, nrg_group_partitioned_round*, which still
 // return NRG_E_INVAL for this kind: a file has no key to hash. A group of file stores is partitioned by
 // file, as benches/nrfs.rs runs it, in group_files.cpp: nrg_group_file_round, with the record partition
-// and the response route-back in partition.hip.)
+// and the response route-back in partition.hip; a member with a growth bound is refused there, since an
+// owner replays its own files' records alone, and such a group grows with nrg_memfs_reserve.)
 //
 // A file is cut into aligned 128-byte LINES; an op of at most 128 bytes touches at most two. Lines
 // are independent of each other; within a line log order decides. A chunk of n records, in stream
@@ -80,6 +83,8 @@ struct MfJob {
     DevCtl* ctl;
     uint8_t* files;  // F files of B bytes, inode order
     u32 log2_b, nfiles;
+    u64 adm;         // sized kernels: what a Write's end and a SetAttr's size are admitted against: B, or
+                     // the growth bound where one is set above it ("Capacity growth" below)
     u32 nlines;      // F * B / 128: the sentinel key
     u32* keys;       // [2n] slot keys
     u64* desc;       // [n] first byte in the store | count << 32 | is-write << 48; 0: touches nothing
@@ -344,7 +349,7 @@ __global__ __launch_bounds__(MF_TPB) void mfs_keys_kernel(MfJob j, MfSz z) {
     const u64* r = mf_rec(j, i);
     const u64 ino = r[0], off = r[1], w2 = r[2];
     const u32 op = (u32)w2, len = (u32)(w2 >> 32);
-    const u64 B = 1ull << j.log2_b;
+    const u64 B = j.adm;  // (B itself without a growth bound; a Write of len > 0 that passes ends within B)
     u32 f = 0, e = 0;
     if (op <= NRG_MEMFS_SETATTR && len <= MF_LINE && ino >= NRG_MEMFS_FIRST_INO && ino - NRG_MEMFS_FIRST_INO < j.nfiles) {
         f = (u32)(ino - NRG_MEMFS_FIRST_INO);
@@ -469,7 +474,7 @@ __global__ __launch_bounds__(MF_TPB) void mfs_expand_kernel(MfJob j, const uint2
         const u64* r = mf_rec(j, i);
         const u64 ino = r[0], off = r[1], w2 = r[2];
         const u32 op = (u32)w2, len = (u32)(w2 >> 32);
-        const u64 B = 1ull << j.log2_b;
+        const u64 B = j.adm;  // (as in mfs_keys; a Write of no bytes may lie past B: it touches nothing)
         const u64 size = sc[i].x;
         u64 nresp;
         u32 cover = 0;
@@ -644,6 +649,63 @@ __global__ __launch_bounds__(DG_TPB) void mfs_check_kernel(const u64* words, u64
         else if (off + 8 > sz) bad |= (w >> (8 * (sz - off))) != 0;
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(&ctl->err, ERR_INVAL);
+}
+
+// ---- Capacity growth (nrg_set_max_capacity, nrg_memfs_reserve): the file system behind benches/memfs.rs
+// ---- keeps a file's bytes in a growing vector, so a write past the end extends the file ---------------
+// Sized contexts only: every stored byte at or past a size is zero, so the bytes a larger capacity adds
+// are zero and nothing else has to be said about them. With a bound of max bytes per file, B after a log
+// prefix is max(B at open or the last reserve, the power of two at or above the largest end admitted so
+// far) (memfs_plan.hpp mf_rec_need, mf_grow_log2): a maximum, so it does not depend on how the log was
+// cut into chunks, and neither does the digest. B changes BEFORE a chunk is replayed, to what the whole
+// chunk needs; after that "within B" and "within max" are the same test for every record of the chunk
+// that carries bytes, so the line keys and descriptors stay inside the store. The sized kernels test
+// against MfJob::adm = max(B, max), which also gives a Write of no bytes or a refused record the same
+// answer however the log was cut. While a bound is set and B < max a chunk first runs
+//   mf_need   one lane per record: mf_rec_need, a wave reduction, the workgroup's maximum and, where it
+//             is above B, one atomicMax into the context's need word (a running maximum: never reset, so
+//             no memset rides on the round). The host reads the word back (8 bytes and a stream
+//             synchronise, timed as "mf_room") and, where B does not hold it,
+//   mf_grow   moves the F files from stride B to stride B' into a new allocation and zeroes each file's
+//             tail [B, B') in the same pass: 16-byte loads and stores, grid-stride over the NEW store,
+//             no atomics. Then the stream is synchronised (there is no stream-ordered free), the old
+//             store freed and log2_b, nlines (the sentinel key) and key_bits follow. Scratch sized by
+//             max_batch or by F does not change.
+// At B >= max the store is a fixed one and nothing of this is launched or read. A path whose records
+// the host planned itself (nrg_memfs_pwrite*) takes the need from its plan, grows once and replays
+// with MfHost::planned set: no need kernel, no readback.
+__global__ __launch_bounds__(MF_TPB) void mf_need_kernel(MfJob j, u64 max_bytes, u64* need) {
+    __shared__ u64 s_w[MF_TPB / 64];
+    const u64 i = (u64)blockIdx.x * MF_TPB + threadIdx.x;
+    u64 v = 0;
+    if (i < j.n) {
+        const u64* r = mf_rec(j, i);
+        const u64 w2 = r[2];
+        v = mfp::mf_rec_need(r[0], r[1], (u32)w2, (u32)(w2 >> 32), j.nfiles, max_bytes);
+    }
+#pragma unroll
+    for (u32 d = 32; d; d >>= 1) {
+        const u64 o = __shfl_xor(v, (int)d, 64);
+        v = o > v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 m = 0;
+#pragma unroll
+        for (u32 k = 0; k < MF_TPB / 64; k++) m = s_w[k] > m ? s_w[k] : m;
+        if (m > (1ull << j.log2_b)) atomicMax((unsigned long long*)need, (unsigned long long)m);
+    }
+}
+
+// to: F files of 16 << to_l4 bytes; from: the same files of 16 << from_l4 (from_l4 < to_l4). n: the
+// 16-byte units of `to`.
+__global__ __launch_bounds__(DG_TPB) void mf_grow_kernel(const uint4* __restrict__ from, uint4* __restrict__ to, u64 n,
+                                                         u32 from_l4, u32 to_l4) {
+    for (u64 i = blockIdx.x * (u64)DG_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * DG_TPB) {
+        const u64 f = i >> to_l4, w = i & ((1ull << to_l4) - 1);
+        to[i] = w < (1ull << from_l4) ? from[(f << from_l4) + w] : make_uint4(0, 0, 0, 0);
+    }
 }
 
 // ---- read-only reads (nrg_memfs_pread*): Replica::execute -> read_only of nr/src/replica.rs:483-497
@@ -1092,6 +1154,79 @@ __global__ __launch_bounds__(MF_TPB) void mf_frag_kernel(MfWrJob j) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------
+// everything that follows from a file's capacity 2^log2_b
+static void mf_set_geometry(MfHost& s, u32 log2_b) {
+    s.log2_b = log2_b;
+    s.nlines = (u32)((s.files << s.log2_b) / MF_LINE);
+    s.key_bits = 1;  // ceil(log2(nlines + 1)): the sentinel is a key too
+    while ((1ull << s.key_bits) <= s.nlines) s.key_bits++;
+}
+
+// may a store of this context's F files hold file_bytes (a power of two) each? nrg_open's limits
+static bool mf_cap_ok(const nrg_ctx* c, u64 file_bytes) {
+    return file_bytes >= (1ull << MF_LOG2_MIN) && file_bytes <= (1ull << MF_LOG2_MAX) && !(file_bytes & (file_bytes - 1)) &&
+           c->mf.files * file_bytes <= MF_MAX_BYTES;
+}
+
+static u32 mf_log2(u64 pow2) {
+    u32 l = 0;
+    while ((1ull << l) < pow2) l++;
+    return l;
+}
+
+static u64 mf_capacity(const nrg_ctx* c) { return 1ull << c->mf.log2_b; }
+
+// DsOps::grow: the store at new_cap bytes per file (a power of two above B within nrg_open's limits),
+// "Capacity growth" above. With keep == false the old bytes are not moved (nrg_restore: the image
+// replaces them). If the allocation fails nothing has been launched: the replica is as it was.
+static hipError_t mf_regrow(nrg_ctx* c, u64 new_cap, bool keep) {
+    MfHost& s = c->mf;
+    if (new_cap <= mf_capacity(c) || !mf_cap_ok(c, new_cap)) return hipErrorInvalidValue;
+    const u32 nl2 = mf_log2(new_cap);
+    uint8_t* nf = nullptr;
+    if (hipMalloc(&nf, s.files << nl2) != hipSuccess) {
+        (void)hipGetLastError();  // (the failure is reported by the return value alone)
+        return hipErrorOutOfMemory;
+    }
+    hipError_t e = hipSuccess;
+    if (keep) {
+        const u64 units = (s.files << nl2) / 16;
+        NRG_LAUNCH(c, "mf_grow", mf_grow_kernel, copy_grid(units), DG_TPB, 0, c->stream, (const uint4*)s.d_files, (uint4*)nf,
+                   units, s.log2_b - 4, nl2 - 4);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        (void)hipFree(nf);
+        return e;
+    }
+    (void)hipFree(s.d_files);
+    s.d_files = nf;
+    mf_set_geometry(s, nl2);
+    return hipSuccess;
+}
+
+static hipError_t mf_grow(nrg_ctx* c, u64 new_cap) { return mf_regrow(c, new_cap, true); }
+
+// Before a chunk of a context with a bound above B: the chunk's need (mf_need), read back, and the grow
+// where B does not hold it. j: the chunk's records and the geometry as it stands.
+static hipError_t mf_room(nrg_ctx* c, const MfJob& j) {
+    MfHost& s = c->mf;
+    NRG_LAUNCH(c, "mf_need", mf_need_kernel, (unsigned)((j.n + MF_TPB - 1) / MF_TPB), MF_TPB, 0, c->stream, j,
+               1ull << s.max_log2, s.d_need);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    u64 need = 0;
+    timer_begin(c, "mf_room");
+    e = hipMemcpyAsync(&need, s.d_need, sizeof(u64), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    timer_end(c, "mf_room");
+    if (e != hipSuccess) return e;
+    const u32 to = mfp::mf_grow_log2(s.log2_b, need, s.max_log2);
+    return to > s.log2_b ? mf_grow(c, 1ull << to) : hipSuccess;
+}
+
 static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
     if (n == 0) return hipSuccess;
@@ -1102,6 +1237,12 @@ static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     j.ring_mask = c->log_size - 1;
     j.lo = lo;
     j.n = n;
+    if (s.max_log2 > s.log2_b && !s.planned) {  // the store grows first if the chunk needs it
+        j.log2_b = s.log2_b;
+        j.nfiles = (u32)s.files;
+        const hipError_t eg = mf_room(c, j);
+        if (eg != hipSuccess) return eg;
+    }
     const bool want = d_resp != nullptr && d_some != nullptr && resp_lo < resp_hi && resp_lo < lo + n && resp_hi > lo;
     j.rlo = want ? resp_lo : 0;
     j.rhi = want ? resp_hi : 0;
@@ -1111,6 +1252,7 @@ static hipError_t mf_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u6
     j.files = s.d_files;
     j.log2_b = s.log2_b;
     j.nfiles = (u32)s.files;
+    j.adm = 1ull << (s.max_log2 > s.log2_b ? s.max_log2 : s.log2_b);
     j.nlines = s.nlines;
     j.keys = s.d_keys;
     j.desc = s.d_desc;
@@ -1198,11 +1340,8 @@ static int mf_open(nrg_ctx* c) {
         cf.queue_capacity > MF_MAX_FILES || (cf.queue_capacity << cf.log2_slots) > MF_MAX_BYTES ||
         cf.max_batch > MF_MAX_BATCH)
         return NRG_E_INVAL;
-    s.log2_b = cf.log2_slots;
     s.files = cf.queue_capacity;
-    s.nlines = (u32)((s.files << s.log2_b) / MF_LINE);
-    s.key_bits = 1;  // ceil(log2(nlines + 1)): the sentinel is a key too
-    while ((1ull << s.key_bits) <= s.nlines) s.key_bits++;
+    mf_set_geometry(s, cf.log2_slots);
     s.file_bits = 1;  // ceil(log2 F): what a sized chunk's file sort sorts by
     while ((1ull << s.file_bits) < s.files) s.file_bits++;
     HIPCHK(hipMalloc(&s.d_files, s.files << s.log2_b));
@@ -1218,7 +1357,7 @@ static int mf_open(nrg_ctx* c) {
 static void mf_close(nrg_ctx* c) {
     MfHost& s = c->mf;
     void* ptrs[] = {s.d_files, s.d_keys, s.d_desc, s.d_pagg, s.d_size, s.d_fkey, s.d_el,
-                    s.d_sc,    s.d_ev,   s.d_fm,   s.d_fep,  s.d_sagg};
+                    s.d_sc,    s.d_ev,   s.d_fm,   s.d_fep,  s.d_sagg, s.d_need};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (s.d_rpk) (void)hipFree(s.d_rpk);  // nrg_memfs_pread_repack_async's scratch
@@ -1304,10 +1443,25 @@ static hipError_t mf_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
 // sized, and a size above B or a non-zero byte at or past a size latches ERR_INVAL on the device, which
 // nrg_restore reads before it compares the digests. An unsized image leaves a sized context sized, every
 // size B.
+// With a bound (nrg_set_max_capacity) a sized image of the same F and a power-of-two B_img in (B, max] is
+// taken too: the store is reallocated to B_img first, no old byte copied. A smaller B_img stays refused:
+// the store never shrinks.
+// log2 of the capacity of an image of `items` items that may go into this context; 0: none may
+static u32 mf_image_log2(const nrg_ctx* c, u64 items) {
+    const MfHost& s = c->mf;
+    if (items == mf_words(c) || items == mf_words(c) + s.files) return s.log2_b;
+    for (u32 l = s.log2_b + 1; l <= s.max_log2; l++)
+        if (items == (s.files << l) / 8 + s.files) return l;
+    return 0;
+}
+
 static int mf_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only) {
-    const u64 words = mf_words(c);
-    if (check_only) return items == words || items == words + c->mf.files ? NRG_OK : NRG_E_INVAL;
+    const u32 il = d_payload || check_only ? mf_image_log2(c, items) : c->mf.log2_b;
+    if (check_only) return il ? NRG_OK : NRG_E_INVAL;
     if (!d_payload) return hip_fail(mf_fill(c));
+    if (!il) return NRG_E_INVAL;
+    if (il > c->mf.log2_b) HIPCHK(mf_regrow(c, 1ull << il, false));
+    const u64 words = mf_words(c);
     int r;
     if (items != words && (r = mf_enable(c))) return r;
     HIPCHK(hipMemcpyAsync(c->mf.d_files, d_payload, words * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -1323,10 +1477,30 @@ static int mf_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_o
     return hip_fail(hipGetLastError());
 }
 
+// nrg_set_max_capacity: the bound in bytes per file, 0 for none. No item count is read: the need of a
+// chunk is not a count (the len_ub fast path of capacity.hpp does not apply), so Growth carries the
+// bound alone. The stream has been drained.
+static int mf_set_bound(nrg_ctx* c, u64 max_bytes) {
+    MfHost& s = c->mf;
+    if (!s.d_size) return NRG_E_INVAL;  // the new bytes are defined by the sizes' invariant
+    if (max_bytes && (!mf_cap_ok(c, max_bytes) || !growth_bound_ok(max_bytes, mf_capacity(c), mf_ops()->cap_limit)))
+        return NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;  // a record is admitted by the bound at its own log index
+    if (max_bytes && !s.d_need) {
+        HIPCHK(hipMalloc(&s.d_need, sizeof(u64)));
+        HIPCHK(hipMemsetAsync(s.d_need, 0, sizeof(u64), c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    s.max_log2 = max_bytes ? mf_log2(max_bytes) : 0;
+    c->growth = Growth{max_bytes, 0};
+    return NRG_OK;
+}
+
 const DsOps* mf_ops() {
     static const DsOps ops = {sizeof(nrg_memfs_op), sizeof(nrg_memfs_resp), mf_open, mf_close, nullptr,
                               mf_replay_chunk, floor_ltail, nullptr, nullptr, mf_defaults, mf_digest,
-                              mf_items, mf_snapshot, mf_restore};
+                              mf_items, mf_snapshot, mf_restore, 1ull << MF_LOG2_MAX, mf_capacity, mf_grow,
+                              true, mf_set_bound};
     return &ops;
 }
 
@@ -1352,6 +1526,11 @@ static int mf_size_put(nrg_ctx* c, uint64_t f, uint64_t v) {
     HIPCHK(hipMemcpyAsync(c->mf.d_size + f, &v, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(sync_all(c));
     return NRG_OK;
+}
+
+// log2 of what a Write's end and a SetAttr's size are admitted against: B, or the bound where it is above
+static uint32_t mf_admit_log2(const nrg_ctx* c) {
+    return c->mf.max_log2 > c->mf.log2_b ? c->mf.max_log2 : c->mf.log2_b;
 }
 
 // ---- nrg_memfs_pwrite*: what the three entries share ----
@@ -1387,7 +1566,8 @@ static int mf_pwrite_upload(nrg_ctx* c, const nrg_memfs_wr* reqs, const uint64_t
 
 // fragments [t0, t1) of the uploaded call to records (pos0 + t - t0) & mask of dst
 static hipError_t mf_frag_launch(nrg_ctx* c, uint64_t n, uint64_t t0, uint64_t t1, void* dst, uint64_t pos0, uint64_t mask,
-                                 const uint8_t* d_data, uint64_t data_bytes, uint64_t* d_written, uint8_t* d_some) {
+                                 const uint8_t* d_data, uint64_t data_bytes, uint64_t* d_written, uint8_t* d_some,
+                                 uint32_t adm_log2) {
     MfHost& s = c->mf;
     MfWrJob j{};
     j.rq = s.d_wup;
@@ -1398,7 +1578,7 @@ static hipError_t mf_frag_launch(nrg_ctx* c, uint64_t n, uint64_t t0, uint64_t t
     j.pos0 = pos0, j.mask = mask;
     j.data = d_data;
     j.data_bytes = data_bytes;
-    j.log2_b = s.log2_b;
+    j.log2_b = adm_log2;  // the plan's: what the requests were admitted against
     j.nfiles = (u32)s.files;
     j.written = d_written;
     j.some = d_some;
@@ -1426,9 +1606,10 @@ int nrg_memfs_size(nrg_ctx* c, uint64_t ino, uint64_t* size) {
 int nrg_memfs_truncate(nrg_ctx* c, uint64_t ino, uint64_t size) {
     int r = need(c, NRG_DS_MEMFS);
     if (r) return r;
-    uint8_t* f = mf_file(c, ino);
-    if (!c->mf.d_size || !f || size > (1ull << c->mf.log2_b)) return NRG_E_INVAL;
+    if (!c->mf.d_size || !mf_file(c, ino) || size > (1ull << mf_admit_log2(c))) return NRG_E_INVAL;
     if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    if (size > mf_capacity(c)) HIPCHK(mf_grow(c, 1ull << mfp::mf_grow_log2(c->mf.log2_b, size, c->mf.max_log2)));
+    uint8_t* f = mf_file(c, ino);
     uint64_t cur = 0;
     if ((r = mf_size_get(c, ino - NRG_MEMFS_FIRST_INO, &cur))) return r;
     if (size < cur) HIPCHK(hipMemsetAsync(f + size, 0, cur - size, c->stream));  // bytes [size, cur) are gone
@@ -1484,6 +1665,22 @@ int nrg_memfs_dump(nrg_ctx* c, uint64_t ino, uint8_t* buf, uint64_t cap, uint64_
     if (!buf) return *n ? NRG_E_INVAL : NRG_OK;
     if (*n) HIPCHK(hipMemcpyAsync(buf, f, *n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(sync_all(c));
+    return NRG_OK;
+}
+
+int nrg_memfs_reserve(nrg_ctx* c, uint64_t file_bytes) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (!c->mf.d_size || file_bytes > (1ull << MF_LOG2_MAX)) return NRG_E_INVAL;
+    const uint64_t want = pow2_at_least(file_bytes);
+    if (want <= mf_capacity(c)) return NRG_OK;  // never shrinks
+    if (!mf_cap_ok(c, want)) return NRG_E_INVAL;
+    return reserve_common(c, NRG_DS_MEMFS, want);
+}
+
+int nrg_memfs_max_capacity(nrg_ctx* c, uint64_t* max_bytes) {
+    if (!c || !max_bytes || c->cfg.ds_kind != NRG_DS_MEMFS) return NRG_E_INVAL;
+    *max_bytes = c->growth.max_items;
     return NRG_OK;
 }
 
@@ -1585,17 +1782,28 @@ int nrg_memfs_pwrite_async(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_t n, con
     if ((d_written == nullptr) != (d_some == nullptr)) return NRG_E_INVAL;
     if (n_records) *n_records = 0;
     if (n == 0) return NRG_OK;
+    // EFBIG is decided against the bound where one is set (the catch-up below may grow B, never past it)
+    const uint32_t adm = mf_admit_log2(c);
     std::vector<uint64_t> first(n + 1);
-    if ((r = mfp::plan(c->mf.log2_b, c->mf.files, reqs, n, data_bytes, first.data(), nullptr, nullptr))) return r;
+    if ((r = mfp::plan(adm, c->mf.files, reqs, n, data_bytes, first.data(), nullptr, nullptr))) return r;
     const uint64_t T = first[n];
     // catch up on anything appended by others first (Replica::combine execs the whole log)
     if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    // the need of all the requests is in the plan: grow once, and the passes make no readback
+    const uint32_t to = mfp::mf_grow_log2(c->mf.log2_b, mfp::plan_need(adm, c->mf.files, reqs, n), adm);
+    if (to > c->mf.log2_b) HIPCHK(mf_grow(c, 1ull << to));
     if ((r = mf_pwrite_upload(c, reqs, first.data(), n))) return r;
+    struct Planned {  // for the passes' replays
+        bool& f;
+        explicit Planned(bool& x) : f(x) { f = true; }
+        ~Planned() { f = false; }
+    } planned(c->mf.planned);
     for (uint64_t done = 0; done < T;) {  // passes: what one append may carry, straight into the ring
         const uint64_t m = T - done < append_max(c) ? T - done : append_max(c);
         if ((r = reserve(c, m))) return r;
         const uint64_t lo = c->tail;
-        HIPCHK(mf_frag_launch(c, n, done, done + m, c->d_ring, lo, c->log_size - 1, d_data, data_bytes, d_written, d_some));
+        HIPCHK(mf_frag_launch(c, n, done, done + m, c->d_ring, lo, c->log_size - 1, d_data, data_bytes, d_written, d_some,
+                              adm));
         note_origin(c, lo, m, origin);
         c->tail = lo + m;
         if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
@@ -1637,13 +1845,16 @@ int nrg_memfs_pwrite_records_async(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_
     if (n_records) *n_records = 0;
     if (n == 0) return NRG_OK;
     std::vector<uint64_t> first(n + 1);
-    if ((r = mfp::plan(c->mf.log2_b, c->mf.files, reqs, n, data_bytes, first.data(), nullptr, nullptr))) return r;
+    // admitted against the bound where one is set, against B otherwise; nothing grows here: the replay of
+    // these records does
+    const uint32_t adm = mf_admit_log2(c);
+    if ((r = mfp::plan(adm, c->mf.files, reqs, n, data_bytes, first.data(), nullptr, nullptr))) return r;
     const uint64_t T = first[n];
     if (n_records) *n_records = T;
     if (T > cap) return NRG_E_CAPACITY;
     if (!d_recs) return NRG_E_INVAL;
     if ((r = mf_pwrite_upload(c, reqs, first.data(), n))) return r;
-    return hip_fail(mf_frag_launch(c, n, 0, T, d_recs, 0, ~0ull, d_data, data_bytes, nullptr, nullptr));
+    return hip_fail(mf_frag_launch(c, n, 0, T, d_recs, 0, ~0ull, d_data, data_bytes, nullptr, nullptr, adm));
 }
 
 }  // extern "C"

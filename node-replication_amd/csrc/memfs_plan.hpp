@@ -4,6 +4,8 @@
 // call, moves the log's tail, which is host state); memfs.hip's mf_frag kernel builds fragment t of the
 // call with the same cut_of() and frag_of(), compiled for the device. Log content is observable
 // (nrg_test_ring_read), so the cut is specified in nrgpu.h and both sides follow it from here.
+// The arithmetic of capacity growth (what a record needs, the capacity that holds it) is at the end,
+// shared the same way and checked by tests/memfs_grow_policy.cpp.
 #pragma once
 
 #include <stddef.h>
@@ -86,6 +88,45 @@ inline int plan(uint32_t log2_b, uint64_t files, const nrg_memfs_wr* reqs, uint6
     }
     if (first) first[n] = run;
     return NRG_OK;
+}
+
+// ---- capacity growth (nrg_set_max_capacity / nrg_memfs_reserve on a file store, include/nrgpu.h) ----
+// The capacity after a log prefix is max(the capacity at open or the last reserve, the power of two at
+// or above the largest admitted end so far): a maximum, so folding it record by record, chunk by chunk
+// or over the whole prefix gives the same number. memfs.hip's mf_need kernel, its host paths and
+// tests/memfs_grow_policy.cpp share the two functions below.
+
+// The end (bytes of its file) a record asks the store to hold under a bound of max_bytes per file, or 0:
+// a valid Write of len > 0 with offset + len <= max_bytes, a valid SetAttr of size <= max_bytes. Checked
+// in the replay's order, so an EINVAL or ENOENT record asks for nothing whatever its offset says, and
+// neither does a record the replay answers with EFBIG (offset + len may not overflow).
+NRG_MFP_HD inline uint64_t mf_rec_need(uint64_t ino, uint64_t offset, uint32_t op, uint32_t len, uint64_t files,
+                                       uint64_t max_bytes) {
+    if (op > NRG_MEMFS_SETATTR || len > LINE) return 0;
+    if (ino < NRG_MEMFS_FIRST_INO || ino - NRG_MEMFS_FIRST_INO >= files) return 0;
+    if (op == NRG_MEMFS_WRITE) return len && offset <= max_bytes && len <= max_bytes - offset ? offset + len : 0;
+    if (op == NRG_MEMFS_SETATTR) return offset <= max_bytes ? offset : 0;
+    return 0;
+}
+
+// log2 of the capacity that holds `need` bytes per file: log2_b itself where they fit, else the power of
+// two at or above need, never past max_log2 (an admitted need is within it; a store reserved beyond its
+// bound stays as it is).
+NRG_MFP_HD inline uint32_t mf_grow_log2(uint32_t log2_b, uint64_t need, uint32_t max_log2) {
+    uint32_t l = log2_b;
+    while (l < max_log2 && (1ull << l) < need) l++;
+    return l;
+}
+
+// The need of a planned call: the largest end of the requests that plan(log2_adm, ...) admits with bytes.
+inline uint64_t plan_need(uint32_t log2_adm, uint64_t files, const nrg_memfs_wr* reqs, uint64_t n) {
+    uint64_t need = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const nrg_memfs_wr& r = reqs[i];
+        if (cut_of(log2_adm, files, r.ino, r.offset, r.len).kind == CUT_BYTES && r.offset + r.len > need)
+            need = r.offset + r.len;
+    }
+    return need;
 }
 
 }  // namespace mfp

@@ -456,13 +456,13 @@ int nrg_sync(nrg_ctx* c) {
 }
 
 // The bound of a kind that grows under replay as its reference structure does (Vec, SegQueue), in
-// the kind's items (DsOps::auto_grow).
+// the kind's items (DsOps::auto_grow), or in the kind's own unit through DsOps::set_bound.
 int nrg_set_max_capacity(nrg_ctx* c, uint64_t max_items) {
     if (!c || !c->ops->auto_grow) return NRG_E_INVAL;
     int r = use_device(c);
     if (r) return r;
     HIPCHK(sync_all(c));
-    return set_max(c, max_items);
+    return c->ops->set_bound ? c->ops->set_bound(c, max_items) : set_max(c, max_items);
 }
 
 int nrg_join(nrg_ctx* c) {

@@ -293,6 +293,8 @@ SIGNATURES = {
     "nrg_memfs_enable_sizes": (C.c_int, [vp]),
     "nrg_memfs_size": (C.c_int, [vp, u64, u64p]),
     "nrg_memfs_truncate": (C.c_int, [vp, u64, u64]),
+    "nrg_memfs_reserve": (C.c_int, [vp, u64]),
+    "nrg_memfs_max_capacity": (C.c_int, [vp, u64p]),
     "nrg_memfs_pread": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
     "nrg_memfs_pread_async": (C.c_int, [vp, vp, u64, vp, u64, vp, vp]),
     "nrg_memfs_pwrite_plan": (C.c_int, [u32, u64, vp, u64, u64, vp, vp, vp]),

@@ -403,6 +403,13 @@ class FilePartitionedGroup(ReplicaGroup):
         """The rank that owns file `ino` in this group."""
         return int(self._lib.nrg_memfs_owner(int(ino), self.world))
 
+    def reserve(self, file_bytes: int):
+        """Room for `file_bytes` bytes in every file on this rank's replica (nrg_memfs_reserve; sized
+        contexts). Every rank calls it with the same value between rounds: a file-partitioned round
+        needs the same B everywhere, and refuses members with a growth bound (nrg_set_max_capacity),
+        since an owner replays its own files' records alone."""
+        L.check(self._lib.nrg_memfs_reserve(self.replica._h, int(file_bytes)), "nrg_memfs_reserve")
+
     def round(self, recs, n: int, resp=None, some=None):
         """One round of this rank's n nrg_memfs_op records (device tensor or raw pointer), queued once
         the counts are exchanged; resp / some (n * 136 bytes, n bytes; both or neither) receive the

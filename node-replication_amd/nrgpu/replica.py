@@ -552,7 +552,9 @@ class DeviceReplica:
 
     def set_max_capacity(self, max_items: int):
         """Automatic growth of a stack, queue or skip-list replica up to `max_items` elements; 0 (the state after
-        open) is a fixed capacity (nrg_set_max_capacity). Synchronous."""
+        open) is a fixed capacity (nrg_set_max_capacity). Synchronous. A file store (sizes enabled) takes
+        the bound in BYTES PER FILE, a power of two: a Write or SetAttr that ends within it is admitted and
+        B grows to the power of two that holds it (include/nrgpu.h "File store: capacity growth")."""
         max_items = int(max_items)
         if max_items < 0 or max_items >= 2**64:
             raise ValueError("max_items must be a u64")
@@ -756,6 +758,21 @@ class DeviceReplica:
         L.check(self._lib.nrg_memfs_geometry(self._h, C.byref(f), C.byref(b)), "memfs_geometry")
         return f.value, b.value
 
+    def mf_reserve(self, file_bytes: int):
+        """Room for `file_bytes` bytes in every file, rounded up to a power of two; never shrinks; a sized
+        context only (nrg_memfs_reserve). mf_geometry() reports the new B."""
+        self._reserve(self._lib.nrg_memfs_reserve, L.NRG_DS_MEMFS, "mf_reserve", file_bytes)
+
+    def mf_max_capacity(self) -> int:
+        """The growth bound in bytes per file, 0 for none (nrg_memfs_max_capacity; no device work)."""
+        return self._capacity(self._lib.nrg_memfs_max_capacity, L.NRG_DS_MEMFS, "mf_max_capacity")
+
+    def mf_admit_log2(self) -> int:
+        """log2 of what a write's end is admitted against: the growth bound where one is set above B, else
+        B. What a caller of memfs_pwrite_plan passes for this replica."""
+        _, b = self.mf_geometry()
+        return max(b, self.mf_max_capacity()).bit_length() - 1
+
     def mf_init(self, ino: int, data):
         """Set the first len(data) bytes of file `ino` directly, before any replay (nrg_memfs_init)."""
         b = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))
@@ -898,8 +915,8 @@ class DeviceReplica:
             b = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
             d = torch.from_numpy(b.copy()).to(dev)
         nb = d.numel() * d.element_size()
-        files, b = self.mf_geometry()
-        first, _, _ = memfs_pwrite_plan(b.bit_length() - 1, files, rq, nb)
+        files, _ = self.mf_geometry()
+        first, _, _ = memfs_pwrite_plan(self.mf_admit_log2(), files, rq, nb)
         T = int(first[-1])
         recs = torch.empty(max(T, 1) * MEMFS_OP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         got = self.mf_pwrite_records_device(rq, d if nb else None, nb, recs, T)
@@ -1264,7 +1281,8 @@ class SkipList:
 
 
 class MemFs:
-    """NrMemFilesystem (benches/memfs.rs:106-292): files of fixed size, every op a log record
+    """NrMemFilesystem (benches/memfs.rs:106-292): files of fixed size (or, with sizes enabled and
+    DeviceReplica.set_max_capacity, files that grow up to a bound), every op a log record
     (ReadOperation = (), :194-201). MfWrite -> ("written", len); MfRead -> ("data", bytes), the file
     as every earlier record of the log left it; MfGetAttr -> ("attr", size); MfSetAttr -> ("attr", the
     new size) once the replica's DeviceReplica.mf_enable_sizes() was called, ("err", EINVAL) before;
@@ -1366,15 +1384,17 @@ class MemFs:
 
     @staticmethod
     def encode_for(dev: DeviceReplica, ops):
-        """encode_counts with the geometry of the replica `dev` (read from its context; no device work)."""
-        files, b = dev.mf_geometry()
-        return MemFs.encode_counts(ops, b.bit_length() - 1, files)
+        """encode_counts with the geometry of the replica `dev` (read from its context; no device work):
+        admission is decided against its growth bound where one is set (DeviceReplica.mf_admit_log2), and
+        the replay of the records grows the store."""
+        files, _ = dev.mf_geometry()
+        return MemFs.encode_counts(ops, dev.mf_admit_log2(), files)
 
     @staticmethod
     def records_for(dev: DeviceReplica, ops) -> list:
         """record_counts with the geometry of the replica `dev`."""
-        files, b = dev.mf_geometry()
-        return MemFs.record_counts(ops, b.bit_length() - 1, files)
+        files, _ = dev.mf_geometry()
+        return MemFs.record_counts(ops, dev.mf_admit_log2(), files)
 
     @staticmethod
     def decode_ops(ops, resp, some, counts=None) -> list:
@@ -1422,6 +1442,16 @@ class MemFs:
         data, offs, some = data.cpu().numpy(), offs.cpu().numpy(), some.cpu().numpy()
         return [("data", data[offs[i]:offs[i + 1]].tobytes()) if some[i] else ("err", L.NRG_MEMFS_ENOENT)
                 for i in range(len(ops))]
+
+    @staticmethod
+    def clone_prepare(dev: DeviceReplica, peer: DeviceReplica):
+        """Before `dev` is restored from `peer`'s image (Replica(..., clone_from=peer)): a peer with a
+        growth bound may have grown past the B `dev` was opened with, and nrg_restore takes a larger image
+        only under a bound, so `dev` gets sizes and the peer's bound first."""
+        bound = peer.mf_max_capacity()
+        if bound:
+            dev.mf_enable_sizes()
+            dev.set_max_capacity(bound)
 
     @staticmethod
     def snapshot(dev: DeviceReplica):
@@ -1534,6 +1564,9 @@ class Log:
                 if clone_from not in self._replicas:
                     raise ValueError("clone_from is not registered with this log")
                 clone_from._exec()  # to the tail: every copy holds every appended entry
+                prepare = getattr(replica.ds, "clone_prepare", None)
+                if prepare is not None:  # (MemFs: the peer's growth bound, so that its grown image is taken)
+                    prepare(replica.dev, clone_from.dev)
                 if clone_from.dev.device == replica.dev.device:
                     p, nbytes, info = clone_from.dev.snapshot_device()
                     if info.log_idx == self.tail:
