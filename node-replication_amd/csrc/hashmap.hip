@@ -1223,6 +1223,16 @@ __device__ __forceinline__ void small_body(const SmallJob& j, Slot* table, u32 s
             const long long sl = claim_slot(table, kk, table_home(kk, shift), tmask, &fresh);
             if (sl < 0) {
                 atomicOr(&ctl->err, ERR_TABLE_FULL);
+                // its Puts answer None, as the partition apply answers a Put that found no slot
+                for (u32 i = 0, seen = 0; j.prev && seen < c; i++) {
+                    if (s_ent[i] != (uint16_t)h) continue;
+                    seen++;
+                    const u64 g = j.lo + i;
+                    if (g >= j.resp_lo && g < j.resp_hi) {
+                        j.prev[g - j.resp_lo] = 0;
+                        j.prevf[g - j.resp_lo] = 0;
+                    }
+                }
                 s_cnt[h] = 0;  // the Gets of this key find it absent, as the other paths leave it
                 continue;
             }
