@@ -38,6 +38,8 @@
  *                                 OpRd::FileRead, any length          benches/nrfs.rs:16-18, :88-101
  *   nrg_memfs_pwrite*             Replica::combine of OpWr::FileWrite, benches/nrfs.rs:103-115;
  *                                 logged writes of any length         nr/src/replica.rs:544-595
+ *   nrg_memfs_pread_logged*       Replica::combine of OperationWr::Read, benches/memfs.rs:73-78, :267-282;
+ *                                 logged reads of any length          nr/src/replica.rs:544-595
  *   nrg_group_*                   the shared Log across NUMA nodes   nr/src/log.rs:494-511 (every replica
  *                                 (RCCL all-gather of write segments) replays every entry), :473-524
  *   nrg_key_owner, nrg_hashmap_partition*, nrg_group_partitioned_round
@@ -909,6 +911,72 @@ int nrg_memfs_pwrite(nrg_ctx* ctx, const nrg_memfs_wr* reqs, uint64_t n, const u
  * d_recs written. Other errors as above. */
 int nrg_memfs_pwrite_records_async(nrg_ctx* ctx, const nrg_memfs_wr* reqs, uint64_t n, const uint8_t* d_data,
                                    uint64_t data_bytes, nrg_memfs_op* d_recs, uint64_t cap, uint64_t* n_records);
+/* Logged reads of any length: POSIX pread THROUGH THE LOG, the read benches/memfs.rs:73-78, :267-282 has
+ * (OperationWr::Read { ino, fh, offset, size: u32 } is a write operation: its answer is the file as every
+ * earlier record of the log left it). nrg_memfs_pread* above reads the local replica when it is called and
+ * is no record; a single READ record carries at most 128 bytes. Here the record stays 152 bytes and the
+ * response 136: a long read is a contiguous run of ordinary NRG_MEMFS_READ records in the log, one per
+ * 128-byte line it touches, atomic against every other op for the reason a long write is (one appender;
+ * group rounds concatenate whole segments), and replayed by every replica like any other records.
+ * Requests are nrg_memfs_rd {ino, offset, len}. Let A = 2^adm, adm the log2 the requests are admitted
+ * against: the growth bound where one is set above B, B otherwise (the rule of
+ * nrg_memfs_pwrite_records_async: a group round may grow the store before the records are replayed).
+ * THE CUT of request i, checked in the replay's order:
+ *   ino outside the range       one record {ino, offset, READ, len 0}; some = 0, planned = 0 (the replay
+ *                               answers NRG_MEMFS_ENOENT)
+ *   len == 0 or offset >= A     one record {ino, offset, READ, len 0}; some = 1, planned = 0
+ *   else                        planned = min(len, A - offset) (no overflow: len may be 2^64 - 1, "read to
+ *                               the end"); one record per line of [offset, offset + planned), fragment k
+ *                               (line_k = (offset >> 7) + k) covering
+ *                               [max(offset, line_k * 128), min(offset + planned, (line_k + 1) * 128));
+ *                               some = 1
+ * Every request logs at least one record, and all 128 data bytes of a cut record are zero. first[0..n] is
+ * the running sum of the record counts, T = first[n]; offs[0..n] is the running sum of planned. Both are
+ * host arithmetic, known before anything is queued.
+ * THE ANSWER of request i: some[i] as above; count[i], the bytes read; the bytes at
+ * data[offs[i] .. offs[i] + count[i]). Request i owns the slot [offs[i], offs[i + 1]), and no byte of data
+ * outside [offs[i], offs[i] + count[i]) is written, for any i. In an unsized context count[i] ==
+ * planned[i] (A == B): data is packed exactly as nrg_memfs_pread would pack the same requests at that log
+ * position, with the same offs. In a sized context count[i] = min(planned[i], max(size - offset, 0)) with
+ * the file's size at the run's log position (it cannot change inside the run: Reads only). offs[n] > cap
+ * is NRG_E_CAPACITY from the call WITH NOTHING LOGGED: the total is host-known. */
+/* The cut as host arithmetic: no device, no context. first: n + 1 words; offs (n + 1) and some (n) may be
+ * NULL. NRG_E_INVAL: a geometry nrg_open refuses (as nrg_memfs_pwrite_plan), a NULL reqs or first with
+ * n > 0. */
+int nrg_memfs_pread_logged_plan(uint32_t log2_adm, uint64_t files, const nrg_memfs_rd* reqs, uint64_t n,
+                                uint64_t* first /* n + 1 */, uint64_t* offs /* n + 1 */, uint8_t* some /* n */);
+/* Replica::combine for these reads. The requests are on the HOST and may be reused on return; data,
+ * counts and some are on the device. In order: the plan (offs, host, n + 1 words, nullable, is filled
+ * here, also when the call then returns NRG_E_CAPACITY), catch-up on the log, then passes of at most
+ * min(log size - 8192, max_batch) records until all T are done: room in the ring, the cut written straight
+ * into the ring at the tail, the tail advanced, the pass replayed with its responses into library scratch
+ * (made by the first call, sized by max_batch), and the responses gathered into the slots. A request's
+ * fragments may straddle passes: counts accumulate in stream order. Everything is ordered on the
+ * context's stream. d_counts (8-byte aligned) / d_some: both or neither, n each. *n_records = T
+ * (nullable). n == 0: NRG_OK, nothing logged. NRG_E_INVAL: a context of another kind, a NULL reqs, a NULL
+ * d_data with cap > 0, exactly one of d_counts / d_some, a misaligned d_counts. NRG_E_CAPACITY:
+ * n > config.max_batch, or offs[n] > cap. */
+int nrg_memfs_pread_logged_async(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, uint32_t origin, uint8_t* d_data,
+                                 uint64_t cap, uint64_t* d_counts, uint8_t* d_some, uint64_t* offs /* n + 1 */,
+                                 uint64_t* n_records);
+/* The same with data, counts and some on the host, through the staging buffers. Synchronous. */
+int nrg_memfs_pread_logged(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, uint32_t origin, uint8_t* data,
+                           uint64_t cap, uint64_t* counts, uint8_t* some, uint64_t* offs /* n + 1 */,
+                           uint64_t* n_records);
+/* The cut alone, into the caller's device buffer of cap records (8-byte aligned): exactly the records
+ * nrg_memfs_pread_logged_async would put in the ring; the log and the replica are not touched. The output
+ * can be a segment of nrg_group_round_async (nrg_round.recs) or of nrg_group_file_round, which is how a
+ * group carries long reads. *n_records = T (nullable). T > cap: NRG_E_CAPACITY with *n_records = T and no
+ * byte of d_recs written. */
+int nrg_memfs_pread_logged_records_async(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, nrg_memfs_op* d_recs,
+                                         uint64_t cap, uint64_t* n_records);
+/* The way back alone: the T responses (d_resp, d_resp_some; 8-byte aligned) that a round wrote for such a
+ * segment, into the slots of d_data and d_counts / d_some (both or neither). It reads nothing of the
+ * replica. NRG_E_INVAL: T != first[n], a NULL d_resp or d_resp_some with n > 0; NRG_E_CAPACITY:
+ * offs[n] > cap; the rest as the async call. */
+int nrg_memfs_pread_logged_gather_async(nrg_ctx* ctx, const nrg_memfs_rd* reqs, uint64_t n, const nrg_memfs_resp* d_resp,
+                                        const uint8_t* d_resp_some, uint64_t T, uint8_t* d_data, uint64_t cap,
+                                        uint64_t* d_counts, uint8_t* d_some);
 /* Sizes (see nrg_memfs_op above): from here on the context's files have sizes, NRG_MEMFS_SETATTR is an
  * op, Writes grow and Reads / GetAttr see the size. Every size starts as B, so the state described is
  * the one found. Synchronous, idempotent, no way back. NRG_E_NOT_SYNCED while ltail < tail. Replicas of

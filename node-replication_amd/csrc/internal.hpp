@@ -254,6 +254,10 @@ struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, conti
     uint32_t* d_fep = nullptr;   // [F] the epoch of the chunk that wrote d_fm's entry
     void* d_sagg = nullptr;      // [max_batch / 1024 + 1] scan-tile aggregates
     // Writes of any length (nrg_memfs_pwrite*): made by the first such call, nullptr before
+    // (and logged reads of any length, nrg_memfs_pread_logged*: [max_batch] requests of 3 words, then
+    // first[max_batch + 1] and offs[max_batch + 1]; 5 * max_batch + 2 words hold either)
+    uint64_t* d_rresp = nullptr; // logged reads: one pass's responses, [max_batch] of 136 bytes, then its
+                                 // some bytes; made by the first nrg_memfs_pread_logged[_async]
     uint64_t* d_wup = nullptr;   // the upload: [max_batch] requests of 4 words, then first[max_batch + 1]
     uint64_t* h_wup = nullptr;   // its pinned host copy (the caller's requests may be reused on return)
     hipEvent_t ev_wup = nullptr; // the last upload has left h_wup

@@ -23,6 +23,9 @@
 // benches/nrfs.rs's whole-file 4096-byte ops: its read-only FileRead is nrg_memfs_pread* below, which
 // goes through no log record; its FileWrite is nrg_memfs_pwrite* below, a write of any length as a
 // contiguous run of these records, cut on the device straight into the log ring (mf_frag).
+// memfs.rs's own Read with a size of any length is nrg_memfs_pread_logged* below: a contiguous run of
+// Read records (mf_rfrag), replayed like any others, their responses gathered into the caller's bytes
+// (mf_rgather, mf_rcount).
 // Out of scope: the combiner, partitioned groups and growth inside a partitioned round.
 // (That sentence speaks of the key-partitioned entry points, nrg_group_partitioned_round*, which still
 // return NRG_E_INVAL for this kind: a file has no key to hash. A group of file stores is partitioned by
@@ -1153,6 +1156,163 @@ __global__ __launch_bounds__(MF_TPB) void mf_frag_kernel(MfWrJob j) {
     }
 }
 
+// ---- logged reads of any length (nrg_memfs_pread_logged*): memfs.rs:73-78, :267-282 OperationWr::Read
+// ---- with a size of any length, the read the structure is named for ---------------------------------
+// A long read is a contiguous run of ordinary Read records, one per 128-byte line of what the request
+// plans to read (memfs_plan.hpp rcut_of: planned = min(len, A - offset), A the admission bound); request i
+// owns the slot [offs[i], offs[i + 1]) of the caller's buffer, offs the running sum of planned. first[]
+// and offs[] are host arithmetic, uploaded with the requests. The run is replayed by mf_expand / mf_lines
+// (or their sized twins) like any other records; one pass's 136-byte responses go to library scratch and
+// from there into the slots.
+//   mf_rfrag    mf_frag's twin without a data source: fragments [t0, t1) of the uploaded call to records
+//               (pos0 + t - t0) & mask of dst, the same tile and 16-lane shape, the request found by the
+//               same upper-bound search of first[]. Three header words and sixteen zero data words, as
+//               8-byte stores: the ring holds what MemFs.encode makes of an MfRead.
+//   mf_rgather  cut by OUTPUT, as mf_pread_copy is: the slot bytes [p0, p1) that fragments [t0, t1) own
+//               are cut into MF_RG_TILE-byte tiles of the destination's aligned 8-byte words, one word
+//               per lane and step. A workgroup finds the first and last request of its tile by upper-bound
+//               searches of offs[] (a run of empty slots is skipped whole), a lane its word's request by
+//               the same search inside that range. Byte q of request i's slot is byte idx of fragment
+//               k = ((offset + q) >> 7) - (offset >> 7) (memfs_plan.hpp rfrag_at) and is copied iff idx is
+//               below that response's n. A word whose 8 bytes lie in one fragment below its n is the one
+//               or two aligned 8-byte loads around the source, a shift and one 8-byte store; any other
+//               word (a fragment or request boundary, the clip, the ragged ends of the pass) goes byte by
+//               byte, and only the bytes that pass the test are stored. Nothing outside
+//               [offs[i], offs[i] + count_i) is written.
+//   mf_rcount   one lane per request that has fragments in [t0, t1): its fragments' n are full, then at
+//               most one partial, then zero, so the sum is a binary search for the first fragment that is
+//               not full. The pass that holds a request's first fragment stores count and some; a later
+//               pass adds, in stream order.
+// Plain loads and stores; no LDS, no atomics, no spinning.
+constexpr u32 MF_RG_TILE = 8 * MF_TPB * 4;  // slot bytes per gather workgroup: four words per lane
+constexpr u32 MF_RG_MAX_GRID = 1u << 20;    // gather workgroups at most; the tiles are strided over
+
+struct MfRlJob {
+    const u64* rq;     // the requests in u64 words: ino, offset, len
+    const u64* first;  // [n + 1] the running sum of the requests' record counts
+    const u64* offs;   // [n + 1] the running sum of planned
+    u64 n;
+    u64 t0, t1;        // the fragments of this launch
+    u64* dst;          // mf_rfrag: records in u64 words
+    u64 pos0, mask;    //           fragment t is record (pos0 + t - t0) & mask of dst
+    u32 log2_adm, nfiles;
+    const u64* resp;   // mf_rgather / mf_rcount: fragment t's response is resp + (t - t0) * MF_RESP_WORDS
+    const uint8_t* rsome;
+    uint8_t* data;     // the slots
+    u64 p0, p1;        // the slot bytes fragments [t0, t1) own
+    u64* cnt;          // [n]
+    uint8_t* some;     // [n]
+    u64 r0, nr;        // mf_rcount: requests [r0, r0 + nr) have fragments in [t0, t1)
+};
+
+__global__ __launch_bounds__(MF_TPB) void mf_rfrag_kernel(MfRlJob j) {
+    const u64* __restrict__ first = j.first;
+    const u32 sub = threadIdx.x & (MF_FR_LANES - 1), grp = threadIdx.x / MF_FR_LANES;
+    const u64 a0 = j.t0 + (u64)blockIdx.x * MF_FR_TILE;
+    if (a0 >= j.t1) return;
+    const u64 a1 = a0 + MF_FR_TILE < j.t1 ? a0 + MF_FR_TILE : j.t1;
+    const u64 r_first = mf_upper(first, 1, j.n, a0) - 1;
+    const u64 r_last = mf_upper(first, r_first + 1, j.n, a1 - 1);
+    for (u64 t = a0 + grp; t < a1; t += MF_FR_PER_WG) {
+        const u64 r = mf_upper(first, r_first + 1, r_last, t) - 1;  // first[r] <= t < first[r + 1]
+        const u64 ino = j.rq[3 * r], off = j.rq[3 * r + 1], len = j.rq[3 * r + 2];
+        const mfp::RCut c = mfp::rcut_of(j.log2_adm, j.nfiles, ino, off, len);
+        u64 roff;
+        u32 rlen;
+        mfp::rfrag_of(c, off, t - first[r], &roff, &rlen);
+        u64* rec = j.dst + ((j.pos0 + (t - j.t0)) & j.mask) * MF_REC_WORDS;
+        rec[3 + sub] = 0;
+        if (sub < 3) rec[sub] = sub == 0 ? ino : (sub == 1 ? roff : (u64)NRG_MEMFS_READ | ((u64)rlen << 32));
+    }
+}
+
+// Positions below are slot positions plus mis = data & 7, so that a multiple of 8 is an aligned address
+// of the output.
+__global__ __launch_bounds__(MF_TPB) void mf_rgather_kernel(MfRlJob j) {
+    const u64* __restrict__ offs = j.offs;
+    const u64 mis = (uintptr_t)j.data & 7;
+    uint8_t* const out = j.data - mis;
+    const u64 v0 = j.p0 + mis, v1 = j.p1 + mis;  // this launch's bytes, not empty
+    const u64 w0 = v0 & ~7ull;
+    const u64 ntiles = (v1 - w0 + MF_RG_TILE - 1) / MF_RG_TILE;
+    const uint8_t* const rbytes = (const uint8_t*)j.resp;
+    for (u64 tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const u64 a0 = w0 + tile * MF_RG_TILE;
+        const u64 a1 = a0 + MF_RG_TILE < v1 ? a0 + MF_RG_TILE : v1;
+        const u64 b0 = a0 > v0 ? a0 : v0;  // the tile's bytes are [b0, a1), not empty
+        // requests r_first .. r_last - 1 hold them (the same in every lane)
+        const u64 r_first = mf_upper(offs, 1, j.n, b0 - mis) - 1;
+        const u64 r_last = mf_upper(offs, r_first + 1, j.n, a1 - 1 - mis);
+        for (u64 a = a0 + 8 * threadIdx.x; a < a1; a += 8 * MF_TPB) {
+            const u64 lo = a > b0 ? a : b0, hi = a + 8 < a1 ? a + 8 : a1;  // the word's bytes of this launch
+            u64 r = mf_upper(offs, r_first + 1, r_last, lo - mis) - 1;
+            u64 rl = offs[r] + mis, rh = offs[r + 1] + mis;  // request r's slot: rl <= lo < rh
+            u64 off = j.rq[3 * r + 1];
+            u32 idx;
+            u64 k = mfp::rfrag_at(off, lo - rl, &idx);
+            const uint8_t* rp = rbytes + (j.first[r] + k - j.t0) * sizeof(nrg_memfs_resp);
+            u64 nn = *(const u64*)rp;
+            if (hi - lo == 8 && a + 8 <= rh && idx + 8 <= MF_LINE && (u64)idx + 8 <= nn) {  // inside one fragment's bytes
+                const uint8_t* s = rp + 8 + idx;
+                const u32 sh = idx & 7;  // (a response and its data are 8-byte aligned)
+                u64 w = *(const u64*)(s - sh);
+                if (sh) w = (w >> (8 * sh)) | (*(const u64*)(s - sh + 8) << (64 - 8 * sh));  // (within data: idx + 8 <= 128)
+                *(u64*)(out + a) = w;
+                continue;
+            }
+            for (u64 q = lo; q < hi; q++) {
+                bool moved = false;
+                if (q >= rh) {  // the next request that has a slot
+                    r++;
+                    rl = rh, rh = offs[r + 1] + mis;
+                    if (rh <= q) {  // an empty one: search past the run
+                        r = mf_upper(offs, r + 1, r_last, q - mis) - 1;
+                        rl = offs[r] + mis, rh = offs[r + 1] + mis;
+                    }
+                    off = j.rq[3 * r + 1];
+                    moved = true;
+                }
+                u32 ix;
+                const u64 kq = mfp::rfrag_at(off, q - rl, &ix);
+                if (moved || kq != k) {
+                    k = kq;
+                    rp = rbytes + (j.first[r] + k - j.t0) * sizeof(nrg_memfs_resp);
+                    nn = *(const u64*)rp;
+                }
+                if (ix < nn) out[q] = rp[8 + ix];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MF_TPB) void mf_rcount_kernel(MfRlJob j) {
+    const u64 x = (u64)blockIdx.x * MF_TPB + threadIdx.x;
+    if (x >= j.nr) return;
+    const u64 r = j.r0 + x;
+    const u64 f0 = j.first[r], f1 = j.first[r + 1];
+    const u64 klo = (f0 > j.t0 ? f0 : j.t0) - f0, khi = (f1 < j.t1 ? f1 : j.t1) - f0;  // its fragments here, not empty
+    const u64 off = j.rq[3 * r + 1];
+    const mfp::RCut c = mfp::rcut_of(j.log2_adm, j.nfiles, j.rq[3 * r], off, j.rq[3 * r + 2]);
+    u64 sum = 0;
+    if (c.bytes) {
+        // the first fragment of [klo, khi) whose n is below its planned length (khi: none)
+        u64 lo = klo, hi = khi;
+        while (lo < hi) {
+            const u64 mid = lo + ((hi - lo) >> 1);
+            const u64 full = mfp::rfrag_pos(off, c.planned, c.frags, mid + 1) - mfp::rfrag_pos(off, c.planned, c.frags, mid);
+            if (j.resp[(f0 + mid - j.t0) * MF_RESP_WORDS] >= full) lo = mid + 1; else hi = mid;
+        }
+        sum = mfp::rfrag_pos(off, c.planned, c.frags, lo) - mfp::rfrag_pos(off, c.planned, c.frags, klo);
+        if (lo < khi) sum += j.resp[(f0 + lo - j.t0) * MF_RESP_WORDS];
+    }
+    if (klo == 0) {
+        j.cnt[r] = sum;
+        j.some[r] = j.rsome[f0 - j.t0];
+    } else {
+        j.cnt[r] += sum;
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------
 // everything that follows from a file's capacity 2^log2_b
 static void mf_set_geometry(MfHost& s, u32 log2_b) {
@@ -1361,7 +1521,8 @@ static void mf_close(nrg_ctx* c) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (s.d_rpk) (void)hipFree(s.d_rpk);  // nrg_memfs_pread_repack_async's scratch
-    if (s.d_wup) (void)hipFree(s.d_wup);  // nrg_memfs_pwrite*'s upload
+    if (s.d_rresp) (void)hipFree(s.d_rresp);  // nrg_memfs_pread_logged*'s responses of one pass
+    if (s.d_wup) (void)hipFree(s.d_wup);  // nrg_memfs_pwrite*'s and nrg_memfs_pread_logged*'s upload
     if (s.h_wup) (void)hipHostFree(s.h_wup);
     if (s.ev_wup) (void)hipEventDestroy(s.ev_wup);
     pt_close(c);  // the scratch of this replica's file partitioning, if it ever partitioned
@@ -1543,19 +1704,29 @@ static int mf_pwrite_check(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_t n, con
     return NRG_OK;
 }
 
-// The upload of a planned call: the requests and first[] through the pinned copy into d_wup, on the
-// context's stream. The buffers are made by the first call (a context that never writes this way
-// allocates nothing) and freed by mf_close. first: n + 1 words.
-static int mf_pwrite_upload(nrg_ctx* c, const nrg_memfs_wr* reqs, const uint64_t* first, uint64_t n) {
+// The upload buffers of a planned call (a logged write's or a logged read's): made by the first such
+// call, after that the wait for the previous call's upload to have left the pinned copy.
+static int mf_wup_ready(nrg_ctx* c) {
     MfHost& s = c->mf;
-    const uint64_t mb = c->cfg.max_batch, words = 4 * mb + mb + 1;
+    const uint64_t words = 5 * c->cfg.max_batch + 2;
     if (!s.d_wup) {
         HIPCHK(hipMalloc(&s.d_wup, words * 8));
         HIPCHK(hipHostMalloc(&s.h_wup, words * 8));
         HIPCHK(hipEventCreateWithFlags(&s.ev_wup, hipEventDisableTiming));
     } else {
-        HIPCHK(hipEventSynchronize(s.ev_wup));  // the previous call's upload has left the pinned copy
+        HIPCHK(hipEventSynchronize(s.ev_wup));
     }
+    return NRG_OK;
+}
+
+// The upload of a planned call: the requests and first[] through the pinned copy into d_wup, on the
+// context's stream. The buffers are made by the first call (a context that never writes this way
+// allocates nothing) and freed by mf_close. first: n + 1 words.
+static int mf_pwrite_upload(nrg_ctx* c, const nrg_memfs_wr* reqs, const uint64_t* first, uint64_t n) {
+    MfHost& s = c->mf;
+    const uint64_t mb = c->cfg.max_batch;
+    int r = mf_wup_ready(c);
+    if (r) return r;
     memcpy(s.h_wup, reqs, n * sizeof(nrg_memfs_wr));
     memcpy(s.h_wup + 4 * mb, first, (n + 1) * 8);
     HIPCHK(hipMemcpyAsync(s.d_wup, s.h_wup, n * sizeof(nrg_memfs_wr), hipMemcpyHostToDevice, c->stream));
@@ -1584,6 +1755,109 @@ static hipError_t mf_frag_launch(nrg_ctx* c, uint64_t n, uint64_t t0, uint64_t t
     j.some = d_some;
     NRG_LAUNCH(c, "mf_frag", mf_frag_kernel, (unsigned)((t1 - t0 + MF_FR_TILE - 1) / MF_FR_TILE), MF_TPB, 0, c->stream, j);
     return hipGetLastError();
+}
+
+// ---- nrg_memfs_pread_logged*: what the entries share ----
+// the checks, in order: the kind, the batch bound, the pointers
+static int mf_rl_check(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n) {
+    int r = need(c, NRG_DS_MEMFS);
+    if (r) return r;
+    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;
+    if (n && !reqs) return NRG_E_INVAL;
+    return NRG_OK;
+}
+
+// The upload of a planned call: the requests, first[] and offs[] (n + 1 words each) through the pinned
+// copy into d_wup, on the context's stream.
+static int mf_rl_upload(nrg_ctx* c, const nrg_memfs_rd* reqs, const uint64_t* first, const uint64_t* offs, uint64_t n) {
+    MfHost& s = c->mf;
+    const uint64_t mb = c->cfg.max_batch;
+    int r = mf_wup_ready(c);
+    if (r) return r;
+    memcpy(s.h_wup, reqs, n * sizeof(nrg_memfs_rd));
+    memcpy(s.h_wup + 3 * mb, first, (n + 1) * 8);
+    memcpy(s.h_wup + 3 * mb + n + 1, offs, (n + 1) * 8);  // (right after first[]: one copy takes both)
+    HIPCHK(hipMemcpyAsync(s.d_wup, s.h_wup, n * sizeof(nrg_memfs_rd), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.d_wup + 3 * mb, s.h_wup + 3 * mb, 2 * (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(s.ev_wup, c->stream));
+    return NRG_OK;
+}
+
+static MfRlJob mf_rl_job(nrg_ctx* c, uint64_t n, uint64_t t0, uint64_t t1, uint32_t adm_log2) {
+    MfHost& s = c->mf;
+    const uint64_t mb = c->cfg.max_batch;
+    MfRlJob j{};
+    j.rq = s.d_wup;
+    j.first = s.d_wup + 3 * mb;
+    j.offs = s.d_wup + 3 * mb + n + 1;
+    j.n = n;
+    j.t0 = t0, j.t1 = t1;
+    j.log2_adm = adm_log2;  // the plan's
+    j.nfiles = (u32)s.files;
+    return j;
+}
+
+// fragments [t0, t1) of the uploaded call to records (pos0 + t - t0) & mask of dst
+static hipError_t mf_rfrag_launch(nrg_ctx* c, uint64_t n, uint64_t t0, uint64_t t1, void* dst, uint64_t pos0, uint64_t mask,
+                                  uint32_t adm_log2) {
+    MfRlJob j = mf_rl_job(c, n, t0, t1, adm_log2);
+    j.dst = (u64*)dst;
+    j.pos0 = pos0, j.mask = mask;
+    NRG_LAUNCH(c, "mf_rfrag", mf_rfrag_kernel, (unsigned)((t1 - t0 + MF_FR_TILE - 1) / MF_FR_TILE), MF_TPB, 0, c->stream, j);
+    return hipGetLastError();
+}
+
+// the request of fragment t (< first[n]): first[r] <= t < first[r + 1]
+static uint64_t mf_rl_req(const uint64_t* first, uint64_t n, uint64_t t) {
+    uint64_t lo = 1, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (first[mid] <= t) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+// where fragment t's bytes start in the slot space; t == first[n]: offs[n]
+static uint64_t mf_rl_pos(const nrg_ctx* c, uint32_t adm, const nrg_memfs_rd* reqs, const uint64_t* first, const uint64_t* offs,
+                          uint64_t n, uint64_t t) {
+    if (t >= first[n]) return offs[n];
+    const uint64_t r = mf_rl_req(first, n, t);
+    const mfp::RCut cut = mfp::rcut_of(adm, c->mf.files, reqs[r].ino, reqs[r].offset, reqs[r].len);
+    return offs[r] + (cut.bytes ? mfp::rfrag_pos(reqs[r].offset, cut.planned, cut.frags, t - first[r]) : 0);
+}
+
+// The way back: the responses of fragments [t0, t1) (d_resp, d_rsome: that many) into the slots, and the
+// counts and some bytes of the requests that have fragments there (d_counts == nullptr: not wanted).
+static hipError_t mf_rgather_launch(nrg_ctx* c, uint32_t adm, const nrg_memfs_rd* reqs, const uint64_t* first,
+                                    const uint64_t* offs, uint64_t n, uint64_t t0, uint64_t t1, const void* d_resp,
+                                    const uint8_t* d_rsome, uint8_t* d_data, uint64_t* d_counts, uint8_t* d_some) {
+    MfRlJob j = mf_rl_job(c, n, t0, t1, adm);
+    j.resp = (const u64*)d_resp;
+    j.rsome = d_rsome;
+    j.data = d_data;
+    j.cnt = d_counts;
+    j.some = d_some;
+    j.p0 = mf_rl_pos(c, adm, reqs, first, offs, n, t0);
+    j.p1 = mf_rl_pos(c, adm, reqs, first, offs, n, t1);
+    if (j.p1 > j.p0) {
+        const uint64_t tiles = (j.p1 - j.p0 + 7 + MF_RG_TILE - 1) / MF_RG_TILE;
+        NRG_LAUNCH(c, "mf_rgather", mf_rgather_kernel, (unsigned)(tiles < MF_RG_MAX_GRID ? tiles : MF_RG_MAX_GRID), MF_TPB, 0,
+                   c->stream, j);
+    }
+    if (d_counts) {
+        j.r0 = mf_rl_req(first, n, t0);
+        j.nr = mf_rl_req(first, n, t1 - 1) - j.r0 + 1;
+        NRG_LAUNCH(c, "mf_rcount", mf_rcount_kernel, (unsigned)((j.nr + MF_TPB - 1) / MF_TPB), MF_TPB, 0, c->stream, j);
+    }
+    return hipGetLastError();
+}
+
+// the plan of a call on this context: first, offs (n + 1 each) against the admission bound
+static int mf_rl_plan(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, std::vector<uint64_t>& first,
+                      std::vector<uint64_t>& offs) {
+    first.resize(n + 1);
+    offs.resize(n + 1);
+    return mfp::read_plan(mf_admit_log2(c), c->mf.files, reqs, n, first.data(), offs.data(), nullptr);
 }
 
 extern "C" {
@@ -1855,6 +2129,129 @@ int nrg_memfs_pwrite_records_async(nrg_ctx* c, const nrg_memfs_wr* reqs, uint64_
     if (!d_recs) return NRG_E_INVAL;
     if ((r = mf_pwrite_upload(c, reqs, first.data(), n))) return r;
     return hip_fail(mf_frag_launch(c, n, 0, T, d_recs, 0, ~0ull, d_data, data_bytes, nullptr, nullptr, adm));
+}
+
+int nrg_memfs_pread_logged_plan(uint32_t log2_adm, uint64_t files, const nrg_memfs_rd* reqs, uint64_t n, uint64_t* first,
+                                uint64_t* offs, uint8_t* some) {
+    return mfp::read_plan(log2_adm, files, reqs, n, first, offs, some);
+}
+
+int nrg_memfs_pread_logged_async(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, uint32_t origin, uint8_t* d_data,
+                                 uint64_t cap, uint64_t* d_counts, uint8_t* d_some, uint64_t* offs, uint64_t* n_records) {
+    int r = mf_rl_check(c, reqs, n);
+    if (r) return r;
+    if ((d_counts == nullptr) != (d_some == nullptr) || ((uintptr_t)d_counts & 7) || (cap && !d_data)) return NRG_E_INVAL;
+    if (n_records) *n_records = 0;
+    if (n == 0) {
+        if (offs) offs[0] = 0;
+        return NRG_OK;
+    }
+    const uint32_t adm = mf_admit_log2(c);
+    std::vector<uint64_t> first, po;
+    if ((r = mf_rl_plan(c, reqs, n, first, po))) return r;
+    if (offs) memcpy(offs, po.data(), (n + 1) * 8);
+    const uint64_t T = first[n];
+    if (po[n] > cap) return NRG_E_CAPACITY;  // host-known: nothing is logged
+    // catch up on anything appended by others first (Replica::combine execs the whole log)
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    MfHost& s = c->mf;
+    const uint64_t mb = c->cfg.max_batch;
+    if (!s.d_rresp) HIPCHK(hipMalloc(&s.d_rresp, mb * sizeof(nrg_memfs_resp) + mb));
+    uint8_t* const rsome = (uint8_t*)(s.d_rresp + mb * MF_RESP_WORDS);
+    if ((r = mf_rl_upload(c, reqs, first.data(), po.data(), n))) return r;
+    struct Planned {  // a pass of Reads needs no growth: no need check, no readback
+        bool& f;
+        explicit Planned(bool& x) : f(x) { f = true; }
+        ~Planned() { f = false; }
+    } planned(s.planned);
+    // passes: what one append may carry and the scratch holds, so a pass is one replay chunk
+    const uint64_t pass = append_max(c) < mb ? append_max(c) : mb;
+    for (uint64_t done = 0; done < T;) {
+        const uint64_t m = T - done < pass ? T - done : pass;
+        if ((r = reserve(c, m))) return r;
+        const uint64_t lo = c->tail;
+        HIPCHK(mf_rfrag_launch(c, n, done, done + m, c->d_ring, lo, c->log_size - 1, adm));
+        note_origin(c, lo, m, origin);
+        c->tail = lo + m;
+        if ((r = exec_range(c, lo, lo + m, s.d_rresp, rsome))) return r;
+        HIPCHK(mf_rgather_launch(c, adm, reqs, first.data(), po.data(), n, done, done + m, s.d_rresp, rsome, d_data, d_counts,
+                                 d_some));
+        done += m;
+    }
+    if (n_records) *n_records = T;
+    return NRG_OK;
+}
+
+int nrg_memfs_pread_logged(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, uint32_t origin, uint8_t* data, uint64_t cap,
+                           uint64_t* counts, uint8_t* some, uint64_t* offs, uint64_t* n_records) {
+    int r = mf_rl_check(c, reqs, n);
+    if (r) return r;
+    if ((counts == nullptr) != (some == nullptr) || (cap && !data)) return NRG_E_INVAL;
+    if (n == 0) {
+        if (n_records) *n_records = 0;
+        if (offs) offs[0] = 0;
+        return NRG_OK;
+    }
+    std::vector<uint64_t> first, po;
+    if ((r = mf_rl_plan(c, reqs, n, first, po))) return r;
+    const uint64_t total = po[n] <= cap ? po[n] : 0;  // (above cap the call below refuses before it logs)
+    Staging* g = c->stg;
+    if ((r = staging(g[0], total ? total : 1)) || (r = staging(g[1], n * 8)) || (r = staging(g[2], n))) return r;
+    if ((r = nrg_memfs_pread_logged_async(c, reqs, n, origin, (uint8_t*)g[0].p, cap, (uint64_t*)g[1].p, (uint8_t*)g[2].p, offs,
+                                          n_records)))
+        return r;
+    // only a request's count bytes may land in the caller's data: through host copies of the slots
+    std::vector<uint64_t> cn(n);
+    std::vector<uint8_t> bytes(total);
+    HIPCHK(hipMemcpyAsync(cn.data(), g[1].p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (some) HIPCHK(hipMemcpyAsync(some, g[2].p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    uint64_t lo = ~0ull, hi = 0;  // the slot bytes that hold answers
+    for (uint64_t i = 0; i < n; i++)
+        if (cn[i]) lo = po[i] < lo ? po[i] : lo, hi = po[i] + cn[i] > hi ? po[i] + cn[i] : hi;
+    if (hi > lo) {
+        HIPCHK(hipMemcpyAsync(bytes.data() + lo, (uint8_t*)g[0].p + lo, hi - lo, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    for (uint64_t i = 0; i < n; i++) {
+        if (cn[i]) memcpy(data + po[i], bytes.data() + po[i], cn[i]);
+        if (counts) counts[i] = cn[i];
+    }
+    return check_err(c);
+}
+
+int nrg_memfs_pread_logged_records_async(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, nrg_memfs_op* d_recs, uint64_t cap,
+                                         uint64_t* n_records) {
+    int r = mf_rl_check(c, reqs, n);
+    if (r) return r;
+    if ((uintptr_t)d_recs & 7) return NRG_E_INVAL;  // (records move as u64 words)
+    if (n_records) *n_records = 0;
+    if (n == 0) return NRG_OK;
+    std::vector<uint64_t> first, po;
+    if ((r = mf_rl_plan(c, reqs, n, first, po))) return r;
+    const uint64_t T = first[n];
+    if (n_records) *n_records = T;
+    if (T > cap) return NRG_E_CAPACITY;
+    if (!d_recs) return NRG_E_INVAL;
+    if ((r = mf_rl_upload(c, reqs, first.data(), po.data(), n))) return r;
+    return hip_fail(mf_rfrag_launch(c, n, 0, T, d_recs, 0, ~0ull, mf_admit_log2(c)));
+}
+
+int nrg_memfs_pread_logged_gather_async(nrg_ctx* c, const nrg_memfs_rd* reqs, uint64_t n, const nrg_memfs_resp* d_resp,
+                                        const uint8_t* d_resp_some, uint64_t T, uint8_t* d_data, uint64_t cap,
+                                        uint64_t* d_counts, uint8_t* d_some) {
+    int r = mf_rl_check(c, reqs, n);
+    if (r) return r;
+    if ((d_counts == nullptr) != (d_some == nullptr) || (((uintptr_t)d_counts | (uintptr_t)d_resp) & 7) || (cap && !d_data))
+        return NRG_E_INVAL;
+    if (n == 0) return T ? NRG_E_INVAL : NRG_OK;
+    std::vector<uint64_t> first, po;
+    if ((r = mf_rl_plan(c, reqs, n, first, po))) return r;
+    if (T != first[n] || !d_resp || !d_resp_some) return NRG_E_INVAL;
+    if (po[n] > cap) return NRG_E_CAPACITY;
+    if ((r = mf_rl_upload(c, reqs, first.data(), po.data(), n))) return r;
+    return hip_fail(mf_rgather_launch(c, mf_admit_log2(c), reqs, first.data(), po.data(), n, 0, T, d_resp, d_resp_some, d_data,
+                                      d_counts, d_some));
 }
 
 }  // extern "C"

@@ -4,6 +4,9 @@
 // call, moves the log's tail, which is host state); memfs.hip's mf_frag kernel builds fragment t of the
 // call with the same cut_of() and frag_of(), compiled for the device. Log content is observable
 // (nrg_test_ring_read), so the cut is specified in nrgpu.h and both sides follow it from here.
+// The read-shaped cut of the logged reads of any length (nrg_memfs_pread_logged*: rcut_of, rfrag_of,
+// rfrag_pos, rfrag_at, read_plan) follows the writes', shared with mf_rfrag / mf_rgather / mf_rcount the
+// same way and checked by tests/memfs_read_plan.cpp.
 // The arithmetic of capacity growth (what a record needs, the capacity that holds it) is at the end,
 // shared the same way and checked by tests/memfs_grow_policy.cpp.
 #pragma once
@@ -87,6 +90,70 @@ inline int plan(uint32_t log2_b, uint64_t files, const nrg_memfs_wr* reqs, uint6
         if (some) some[i] = c.some;
     }
     if (first) first[n] = run;
+    return NRG_OK;
+}
+
+// ---- logged reads of any length (nrg_memfs_pread_logged*, include/nrgpu.h) ---------------------------
+// The read-shaped cut: a request {ino, offset, len} becomes one Read record per 128-byte line of what it
+// plans to read, planned = min(len, A - offset) with A = 2^log2_adm, and owns planned bytes of the
+// caller's buffer (its slot). memfs.hip's mf_rfrag and mf_rgather kernels use these same functions.
+struct RCut {
+    uint64_t frags;    // f_i >= 1
+    uint64_t planned;  // bytes of the slot
+    uint8_t some;
+    uint8_t bytes;     // planned > 0: the records ask for bytes
+};
+
+// checked in the order the replay checks a record: the ino, then the range (no overflow: len may be
+// 2^64 - 1, "read to the end", and offset anything)
+NRG_MFP_HD inline RCut rcut_of(uint32_t log2_adm, uint64_t files, uint64_t ino, uint64_t offset, uint64_t len) {
+    const uint64_t A = 1ull << log2_adm;
+    if (ino < NRG_MEMFS_FIRST_INO || ino - NRG_MEMFS_FIRST_INO >= files) return RCut{1, 0, 0, 0};
+    if (len == 0 || offset >= A) return RCut{1, 0, 1, 0};
+    const uint64_t planned = len < A - offset ? len : A - offset;
+    return RCut{((offset + planned - 1) >> LINE_LOG2) - (offset >> LINE_LOG2) + 1, planned, 1, 1};
+}
+
+// Where fragment k of a request with bytes starts inside the request's slot; k == frags gives planned.
+NRG_MFP_HD inline uint64_t rfrag_pos(uint64_t offset, uint64_t planned, uint64_t frags, uint64_t k) {
+    if (k == 0) return 0;
+    if (k >= frags) return planned;
+    return (((offset >> LINE_LOG2) + k) << LINE_LOG2) - offset;
+}
+
+// Record k (< frags) of a request: the record's offset and len.
+NRG_MFP_HD inline void rfrag_of(const RCut& c, uint64_t offset, uint64_t k, uint64_t* rec_off, uint32_t* rec_len) {
+    if (!c.bytes) {
+        *rec_off = offset, *rec_len = 0;
+    } else {
+        const uint64_t lo = rfrag_pos(offset, c.planned, c.frags, k), hi = rfrag_pos(offset, c.planned, c.frags, k + 1);
+        *rec_off = offset + lo, *rec_len = (uint32_t)(hi - lo);
+    }
+}
+
+// The fragment of the slot's byte q (< planned) and the byte's index inside that fragment's response.
+NRG_MFP_HD inline uint64_t rfrag_at(uint64_t offset, uint64_t q, uint32_t* idx) {
+    const uint64_t k = ((offset + q) >> LINE_LOG2) - (offset >> LINE_LOG2);
+    *idx = k ? (uint32_t)((offset + q) & (LINE - 1)) : (uint32_t)q;
+    return k;
+}
+
+// nrg_memfs_pread_logged_plan. first: n + 1 words; offs: n + 1 words or NULL; some: n or NULL.
+inline int read_plan(uint32_t log2_adm, uint64_t files, const nrg_memfs_rd* reqs, uint64_t n, uint64_t* first,
+                     uint64_t* offs, uint8_t* some) {
+    if (!geometry_ok(log2_adm, files)) return NRG_E_INVAL;
+    if (n && (!reqs || !first)) return NRG_E_INVAL;
+    uint64_t run = 0, bytes = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const RCut c = rcut_of(log2_adm, files, reqs[i].ino, reqs[i].offset, reqs[i].len);
+        first[i] = run;
+        run += c.frags;
+        if (offs) offs[i] = bytes;
+        bytes += c.planned;
+        if (some) some[i] = c.some;
+    }
+    if (first) first[n] = run;
+    if (offs) offs[n] = bytes;
     return NRG_OK;
 }
 

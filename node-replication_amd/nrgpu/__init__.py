@@ -30,6 +30,7 @@ from .replica import (
     MemFs,
     MfGetAttr,
     MfPread,
+    MfPreadLogged,
     MfPwrite,
     MfRead,
     MfSetAttr,
@@ -51,7 +52,9 @@ from .replica import (
     Stack,
     VSpace,
     WriteOnly,
+    memfs_pread_logged_plan,
     memfs_pwrite_plan,
+    memfs_rd,
     memfs_wr,
 )
 
@@ -63,6 +66,7 @@ __all__ = [
     "Scan", "Seek", "SkipList", "SlPush",
     "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfSetAttr", "MfWrite",
     "MEMFS_WR_DTYPE", "MfPwrite", "memfs_pwrite_plan", "memfs_wr",
+    "MfPreadLogged", "memfs_pread_logged_plan", "memfs_rd",
     "FilePartitionedGroup", "PartitionedGroup", "ReplicaGroup", "memfs_owner", "key_owner",
 ]
 

@@ -301,6 +301,11 @@ SIGNATURES = {
     "nrg_memfs_pwrite_async": (C.c_int, [vp, vp, u64, vp, u64, u32, vp, vp, u64p]),
     "nrg_memfs_pwrite": (C.c_int, [vp, vp, u64, vp, u64, u32, vp, vp, u64p]),
     "nrg_memfs_pwrite_records_async": (C.c_int, [vp, vp, u64, vp, u64, vp, u64, u64p]),
+    "nrg_memfs_pread_logged_plan": (C.c_int, [u32, u64, vp, u64, vp, vp, vp]),
+    "nrg_memfs_pread_logged_async": (C.c_int, [vp, vp, u64, u32, vp, u64, vp, vp, vp, u64p]),
+    "nrg_memfs_pread_logged": (C.c_int, [vp, vp, u64, u32, vp, u64, vp, vp, vp, u64p]),
+    "nrg_memfs_pread_logged_records_async": (C.c_int, [vp, vp, u64, vp, u64, u64p]),
+    "nrg_memfs_pread_logged_gather_async": (C.c_int, [vp, vp, u64, vp, vp, u64, vp, u64, vp, vp]),
     "nrg_synth_read": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_read_async": (C.c_int, [vp, vp, u64, vp]),
     "nrg_synth_dump": (C.c_int, [vp, vp, u64, u64p]),

@@ -86,6 +86,33 @@ def memfs_pwrite_plan(log2_b: int, files: int, reqs, data_bytes: int):
     return first, written, some
 
 
+def memfs_rd(reqs) -> np.ndarray:
+    """Requests of nrg_memfs_pread* as a contiguous array of MEMFS_RD_DTYPE: from one, or from
+    [n, 3] u64 (ino, offset, len)."""
+    host = np.asarray(reqs)
+    if host.dtype != L.MEMFS_RD_DTYPE:
+        host = np.ascontiguousarray(host, np.uint64).reshape(-1, 3).view(L.MEMFS_RD_DTYPE)
+    return np.ascontiguousarray(host.reshape(-1))
+
+
+def memfs_pread_logged_plan(log2_adm: int, files: int, reqs):
+    """The cut of nrg_memfs_pread_logged* as host arithmetic (nrg_memfs_pread_logged_plan; no device, no
+    context): (first, offs, some) for F = `files` files admitted against 2^log2_adm bytes. first[0..n] is
+    the running sum of the requests' record counts, offs[0..n] the running sum of the bytes they plan to
+    read (request i owns data[offs[i]:offs[i + 1]]). ValueError for a geometry nrg_open does not accept."""
+    rq = memfs_rd(reqs)
+    n = len(rq)
+    first = np.zeros(n + 1, np.uint64)
+    offs = np.zeros(n + 1, np.uint64)
+    some = np.zeros(n, np.uint8)
+    code = L.load().nrg_memfs_pread_logged_plan(log2_adm, files, _ptr(rq) if n else None, n, _ptr(first), _ptr(offs),
+                                                _ptr(some) if n else None)
+    if code == L.NRG_E_INVAL:
+        raise ValueError("nrg_memfs_pread_logged_plan: a geometry nrg_open refuses")
+    L.check(code, "memfs_pread_logged_plan")
+    return first, offs, some
+
+
 def _stream_ordered(fn):
     """Stream-ordering contract of every `*_device` helper (and join): the call is ordered AFTER
     all work already queued on torch's current stream (so buffers torch filled or copied there
@@ -926,6 +953,81 @@ class DeviceReplica:
             return recs
         return recs.cpu().numpy().view(MEMFS_OP_DTYPE).copy()
 
+    @_stream_ordered
+    def mf_pread_logged_device(self, reqs: np.ndarray, origin: int, d_data, cap: int, d_counts=None, d_some=None):
+        """Replica::combine for n logged reads of any length (nrg_memfs_pread_logged_async): `reqs`, a
+        host array of MEMFS_RD_DTYPE, cut on the device into 128-byte Read records straight into the log
+        ring, replayed, and the responses gathered into the slots of the device buffer d_data (cap
+        bytes). d_counts (u64) / d_some (u8): both or neither. Returns (offs, n_records): the slots'
+        offsets (numpy, n + 1) and the records logged. Only data[offs[i]:offs[i] + counts[i]] is written.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        t = C.c_uint64()
+        offs = np.zeros(len(reqs) + 1, np.uint64)
+        L.check(self._lib.nrg_memfs_pread_logged_async(self._h, _ptr(reqs) if len(reqs) else None, len(reqs), origin,
+                                                       _dptr(d_data), cap, _dptr(d_counts), _dptr(d_some), _ptr(offs),
+                                                       C.byref(t)), "memfs_pread_logged")
+        return offs, t.value
+
+    @_stream_ordered
+    def mf_pread_logged_records_device(self, reqs: np.ndarray, d_recs, cap: int) -> int:
+        """The cut alone (nrg_memfs_pread_logged_records_async): the records mf_pread_logged_device would
+        log, into the device buffer d_recs of cap records; the log and the replica are not touched.
+        Returns the number of records; NrgError(NRG_E_CAPACITY) when they exceed cap (nothing is written).
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        t = C.c_uint64()
+        L.check(self._lib.nrg_memfs_pread_logged_records_async(self._h, _ptr(reqs) if len(reqs) else None, len(reqs),
+                                                               _dptr(d_recs), cap, C.byref(t)), "memfs_pread_logged_records")
+        return t.value
+
+    @_stream_ordered
+    def mf_pread_logged_gather_device(self, reqs: np.ndarray, d_resp, d_resp_some, T: int, d_data, cap: int, d_counts=None,
+                                      d_some=None):
+        """The way back alone (nrg_memfs_pread_logged_gather_async): the T responses a round wrote for the
+        records of mf_pread_logged_records, into the slots of d_data and d_counts / d_some.
+        Ordered after torch's current stream, and torch's stream after it (_stream_ordered)."""
+        L.check(self._lib.nrg_memfs_pread_logged_gather_async(self._h, _ptr(reqs) if len(reqs) else None, len(reqs),
+                                                              _dptr(d_resp), _dptr(d_resp_some), T, _dptr(d_data), cap,
+                                                              _dptr(d_counts), _dptr(d_some)), "memfs_pread_logged_gather")
+
+    def mf_pread_logged(self, reqs, origin: int = 1, cap: Optional[int] = None):
+        """Logged reads of any length: (data, offs, counts, some), torch tensors on this replica's GPU
+        (uint8 [cap], int64 [n + 1], int64 [n], uint8 [n]); request i's bytes are
+        data[offs[i]:offs[i] + counts[i]], the file as every earlier record of the log left it. `reqs`: a
+        numpy array of MEMFS_RD_DTYPE (or [n, 3] u64: ino, offset, len). cap=None sizes data from the plan
+        (offs[n]); data starts as zeros, and bytes outside the answers are not written."""
+        import torch
+
+        rq = memfs_rd(reqs)
+        n = len(rq)
+        dev = torch.device("cuda", self.device)
+        if cap is None:
+            files, _ = self.mf_geometry()
+            cap = int(memfs_pread_logged_plan(self.mf_admit_log2(), files, rq)[1][-1])
+        data = torch.zeros(cap, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(n, dtype=torch.int64, device=dev)
+        some = torch.zeros(n, dtype=torch.uint8, device=dev)
+        offs, _ = self.mf_pread_logged_device(rq, origin, data if cap else None, cap, counts if n else None,
+                                              some if n else None)
+        return data, torch.from_numpy(offs.astype(np.int64)).to(dev), counts, some
+
+    def mf_pread_logged_records(self, reqs, device: bool = False):
+        """The records mf_pread_logged(reqs) would log, as a numpy array of MEMFS_OP_DTYPE (the cut alone,
+        made on the GPU; the log and the replica are not touched). With device=True the records stay on
+        the GPU: a torch u8 tensor of n_records * 152 bytes, what a segment of a group round takes."""
+        import torch
+
+        rq = memfs_rd(reqs)
+        dev = torch.device("cuda", self.device)
+        files, _ = self.mf_geometry()
+        T = int(memfs_pread_logged_plan(self.mf_admit_log2(), files, rq)[0][-1])
+        recs = torch.empty(max(T, 1) * MEMFS_OP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        got = self.mf_pread_logged_records_device(rq, recs, T)
+        assert got == T
+        recs = recs[: T * MEMFS_OP_DTYPE.itemsize]
+        if device:
+            return recs
+        return recs.cpu().numpy().view(MEMFS_OP_DTYPE).copy()
+
     def mf_dump(self, ino: int) -> bytes:
         """The whole file `ino`, in a sized context up to its size: Replica::verify's view (nrg_memfs_dump)."""
         _, b = self.mf_geometry()
@@ -1089,6 +1191,13 @@ class MfPwrite:  # benches/nrfs.rs:103-115 OpWr::FileWrite: a logged write of an
     ino: int
     offset: int
     data: bytes
+
+
+@dataclass(frozen=True)
+class MfPreadLogged:  # benches/memfs.rs:73-78, :267-282 OperationWr::Read with a size of any length: logged
+    ino: int
+    offset: int
+    size: int
 
 
 @dataclass(frozen=True)
@@ -1297,12 +1406,17 @@ class MemFs:
     MAX_PENDING_OPS (the bound counts ops, and the combiner appends a batch in as many appends as the
     log takes); an MfPwrite that alone expands into more records than one append can carry
     (the log's entries less GC_FROM_HEAD) raises ValueError from execute_mut[_batch], before anything
-    is enqueued."""
+    is enqueued.
+
+    MfPreadLogged (memfs.rs:73-78, :267-282 OperationWr::Read, here with a size of any length) ->
+    ("data", bytes), clipped at the end of the file, or ("err", ENOENT): an execute_mut op like MfRead,
+    logged as a contiguous run of 128-byte Read records, one per line it touches (the cut of
+    nrg_memfs_pread_logged*), and folded from the run's responses. The rules of MfPwrite hold for it."""
 
     kind = L.NRG_DS_MEMFS
     rec_dtype = MEMFS_OP_DTYPE
     record_errors = True  # a refused record is its op's ("err", EINVAL), not the replica's error (Replica._exec)
-    _TAGS = {MfWrite: "written", MfPwrite: "written", MfRead: "data", MfGetAttr: "attr", MfSetAttr: "attr"}
+    _TAGS = {MfWrite: "written", MfPwrite: "written", MfRead: "data", MfPreadLogged: "data", MfGetAttr: "attr", MfSetAttr: "attr"}
 
     @staticmethod
     def encode(ops) -> np.ndarray:
@@ -1310,6 +1424,8 @@ class MemFs:
         for i, o in enumerate(ops):
             if isinstance(o, MfPwrite):
                 raise TypeError("an MfPwrite is cut by the replica's geometry: MemFs.encode_counts(ops, log2_b, files)")
+            if isinstance(o, MfPreadLogged):
+                raise TypeError("an MfPreadLogged is cut by the replica's geometry: MemFs.encode_counts(ops, log2_b, files)")
             if not isinstance(o, (MfWrite, MfRead, MfGetAttr, MfSetAttr)):
                 raise TypeError(f"not a file-store op: {o!r}")
             r["ino"][i] = o.ino
@@ -1337,13 +1453,26 @@ class MemFs:
         return pw, rq
 
     @staticmethod
+    def _pread_reqs(ops):
+        """The MfPreadLogged ops of `ops` as requests of nrg_memfs_pread_logged*."""
+        pr = [o for o in ops if isinstance(o, MfPreadLogged)]
+        rq = np.zeros(len(pr), L.MEMFS_RD_DTYPE)
+        rq["ino"] = [o.ino for o in pr]
+        rq["offset"] = [o.offset for o in pr]
+        rq["len"] = [o.size for o in pr]
+        return pr, rq
+
+    @staticmethod
     def record_counts(ops, log2_b: int, files: int) -> list:
         """The log records each op becomes in a store of `files` files of 2^log2_b bytes: 1, or an
-        MfPwrite's fragments (nrg_memfs_pwrite_plan; no device is touched)."""
+        MfPwrite's or MfPreadLogged's fragments (nrg_memfs_pwrite_plan, nrg_memfs_pread_logged_plan; no
+        device is touched)."""
         pw, rq = MemFs._pwrite_reqs(ops)
         first, _, _ = memfs_pwrite_plan(log2_b, files, rq, int(rq["len"].sum(dtype=np.uint64)))
         f = iter(np.diff(first).astype(np.int64).tolist())
-        return [next(f) if isinstance(o, MfPwrite) else 1 for o in ops]
+        _, rd = MemFs._pread_reqs(ops)
+        g = iter(np.diff(memfs_pread_logged_plan(log2_b, files, rd)[0]).astype(np.int64).tolist())
+        return [next(f) if isinstance(o, MfPwrite) else next(g) if isinstance(o, MfPreadLogged) else 1 for o in ops]
 
     @staticmethod
     def encode_counts(ops, log2_b: int, files: int):
@@ -1356,7 +1485,21 @@ class MemFs:
         _, written, some = memfs_pwrite_plan(log2_b, files, rq, int(rq["len"].sum(dtype=np.uint64)))
         recs = np.zeros(sum(counts), MEMFS_OP_DTYPE)
         B, pos, q = 1 << log2_b, 0, 0
+        _, rd = MemFs._pread_reqs(ops)
+        _, roffs, _ = memfs_pread_logged_plan(log2_b, files, rd)
+        planned, p = np.diff(roffs).astype(np.int64), 0
         for o, c in zip(ops, counts):
+            if isinstance(o, MfPreadLogged):  # one Read per line of what it plans to read; no data bytes
+                r = recs[pos:pos + c]
+                r["ino"], r["op"], r["offset"] = o.ino, L.NRG_MEMFS_READ, o.offset
+                if planned[p]:
+                    line = (o.offset >> 7) + np.arange(c, dtype=np.int64)
+                    lo = np.maximum(line << 7, o.offset)
+                    hi = np.minimum((line + 1) << 7, o.offset + int(planned[p]))
+                    r["offset"], r["len"] = lo, hi - lo
+                pos += c
+                p += 1
+                continue
             if not isinstance(o, MfPwrite):
                 recs[pos] = MemFs.encode([o])[0]
                 pos += 1
@@ -1401,7 +1544,7 @@ class MemFs:
         """The responses of `ops` (a response does not say which op it answers; Replica._combine
         passes the batch). counts: the records each op became (encode_counts; None: one each); an
         MfPwrite's fragments fold into one answer, ("written", the sum), or ("err", code) from its
-        failing record."""
+        failing record; an MfPreadLogged's fold into ("data", each fragment's data[:n] concatenated)."""
         out, pos = [], 0
         for i, o in enumerate(ops):
             c = 1 if counts is None else counts[i]
@@ -1413,6 +1556,8 @@ class MemFs:
             elif isinstance(o, MfRead):
                 n = int(r["n"][0])
                 out.append(("data", r["data"][0][:n].tobytes()))
+            elif isinstance(o, MfPreadLogged):  # each fragment's data[:n], concatenated
+                out.append(("data", b"".join(r["data"][k][:int(r["n"][k])].tobytes() for k in range(c))))
             else:
                 out.append((MemFs._TAGS[type(o)], int(r["n"].sum(dtype=np.uint64))))
         return out
@@ -1428,7 +1573,7 @@ class MemFs:
         nrg_memfs_pread_async for the batch. memfs.rs itself has no read operations (ReadOperation =
         ()): its MfRead is an execute_mut op and is refused here."""
         for o in ops:
-            if isinstance(o, MfRead):
+            if isinstance(o, (MfRead, MfPreadLogged)):
                 raise TypeError("MfRead is an execute_mut op (memfs.rs: ReadOperation = ()); the read-only read is MfPread")
             if not isinstance(o, MfPread):
                 raise TypeError(f"not a file-store read: {o!r}")
