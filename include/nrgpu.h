@@ -722,8 +722,9 @@ int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_
  * :73-97): that is nrg_group_partitioned_round on a group of skip-list replicas, with
  * nrg_skiplist_prefill_partition and the group-wide ordered reads nrg_group_skiplist_seek /
  * nrg_group_skiplist_range_count / nrg_group_skiplist_scan (the cnr section below). Out of scope: there is no combiner
- * (nrg_combiner_open returns NRG_E_INVAL, as for the page table) and no removal of keys (the
- * reference's wrapper has none). Every call below returns NRG_E_INVAL on a context of another kind. */
+ * (nrg_combiner_open returns NRG_E_INVAL, as for the page table), no removal of keys in partitioned
+ * rounds (nrg_skiplist_enable_removal below: replicated groups and single replicas only) and no
+ * pop_front / pop_back. Every call below returns NRG_E_INVAL on a context of another kind. */
 /* Replica::combine for one batch of Push(k, v) records (nr/src/replica.rs:544-595): Log::append of the
  * n records in d_ops (device) with `origin`, then Log::exec, with the log copy written by the
  * replay's first pass. Responses (d_resp[i] = the key, d_some[i] = 1; nullable) as nrg_log_exec_async
@@ -803,6 +804,37 @@ int nrg_skiplist_prefill_partition(nrg_ctx* ctx, uint64_t n, uint64_t val_offset
 int nrg_skiplist_reserve(nrg_ctx* ctx, uint64_t n_keys);
 /* The current capacity in keys: 2^config.log2_slots, or what growth made of it. */
 int nrg_skiplist_capacity(nrg_ctx* ctx, uint64_t* n_keys);
+/* Removal of keys (SkipMap::remove; the reference's SkipListWrapper has no such op, the SkipMap that
+ * Replica::verify hands out has). A record is {key, val} with both fields spanning all of u64, so the
+ * context opts in, as nrg_memfs_enable_sizes does:
+ * From here on a record whose val == tombstone is Remove(key) (SkipMap::remove); every other record is
+ * Push as before. Synchronous, no way back. NRG_E_NOT_SYNCED while ltail < tail. Calling it again with
+ * the same tombstone is NRG_OK; with another one NRG_E_INVAL. Replicas of one log, and every member of a
+ * group, enable it at the same log index with the same tombstone. A context that never calls it
+ * behaves as before in every respect ({k, 2^64 - 1} is an ordinary Push there) and launches the same
+ * kernels.
+ *   Responses, in log order, one op at a time: Push(k, v) answers (k, some = 1), unchanged. Remove(k)
+ * answers (the previous value, some = 1) if k was present at that log position, else (0, some = 0);
+ * k is absent afterwards either way. The answer depends on the records before it, also those of the
+ * same chunk: Push(k, v), Remove(k) answers v; Remove(k), Remove(k) answers Some, then None.
+ *   A Remove is an ordinary 16-byte record: nrg_log_append* / nrg_log_exec*, nrg_skiplist_round_async,
+ * the ring's wrap and GC, nrg_group_round_async and nrg_group_resync carry it unchanged. The
+ * nrg_skiplist_prefill* calls run the same pipeline: on an enabled context a prefilled record whose
+ * value is the tombstone is a Remove too. Partitioned rounds (nrg_group_partitioned_round*) return
+ * NRG_E_INVAL when a member has removal enabled (a partitioned Push response is written by the asker
+ * from its own records, which is wrong for a Remove): the round is dropped like one with any other
+ * bad argument, nothing of it is written and no log moves; nrg_combiner_open stays NRG_E_INVAL.
+ *   Capacity: a chunk's new keys are admitted against the key count BEFORE the chunk's own removals
+ * (a full map replaying Remove(a), Push(new b) in one chunk latches NRG_E_CAPACITY); the room a chunk
+ * frees is there for the next chunk. The host's bounds (growth, compaction) stay upper bounds: on an
+ * enabled context the host reads the exact counts back once per chunk (DESIGN.md "Skip list replay",
+ * Removal), so they are then the counts themselves.
+ *   A snapshot does not record the setting: a context restored from an image, or resynced, keeps its
+ * own. */
+int nrg_skiplist_enable_removal(nrg_ctx* ctx, uint64_t tombstone);
+/* Query, no device touched: *enabled = 1 and *tombstone once removal is on, else 0 and 0 (either
+ * pointer may be NULL). */
+int nrg_skiplist_removal(nrg_ctx* ctx, uint64_t* tombstone, int* enabled);
 
 /* ---- file store (kind NRG_DS_MEMFS; benches/memfs.rs) ---------------------------------------
  * NrMemFilesystem (benches/memfs.rs:106-192) behind Dispatch (:194-292) with ReadOperation = (): every
@@ -1440,7 +1472,9 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
  * launches), its chunk merge "sl_merge" and a compaction of the delta run into the base run
  * "sl_compact" (one launch each: the launches counted are the compactions); its batched reads are
  * "sl_get", "sl_seek", "sl_range_count" and "sl_walk" (nrg_skiplist_scan: "sl_scan" is the chunk
- * replay's prefix scan); the file store's chunk is "mf_expand", "mf_sort" (event records around the
+ * replay's prefix scan); with removal enabled a chunk also has "sl_rm_resp" (the Removes' responses),
+ * "sl_rm_state" (event records around the state readback) and, only when a run loses keys,
+ * "sl_drop_base" / "sl_drop_delta"; the file store's chunk is "mf_expand", "mf_sort" (event records around the
  * slot sort's launches) and "mf_lines". nrg_kernel_time reads (timed
  * launches, their total milliseconds) after synchronising. */
 int nrg_kernel_timing(nrg_ctx* ctx, int enable);

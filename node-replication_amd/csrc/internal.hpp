@@ -106,10 +106,13 @@ struct VsState {
 };
 
 // The skip list's device state (skiplist.hip): keys in the base and in the delta run, and the delta
-// count before the chunk being replayed with that chunk's new keys (what its merge reads).
+// count before the chunk being replayed with that chunk's new keys (what its merge reads). With removal
+// enabled (nrg_skiplist_enable_removal) a chunk's scan also leaves the keys the chunk removes from each
+// run: nb and nd_in are then already the counts after the drop passes the host launches next.
 struct SlState {
     u64 nb, nd;
     u64 nd_in, nnew;
+    u64 kb, kd;
 };
 
 struct HostRun {  // origin tags of appended log ranges (the Entry::replica field)
@@ -219,6 +222,12 @@ struct SlHost {  // skip list / ordered map (skiplist.hip): two sorted runs with
     // The compaction policy: nd_ub bounds the delta count from above, as Growth::len_ub bounds the key
     // count: the exact count when it was last read plus every record replayed since.
     uint64_t nd_ub = 0;
+    // Removal (nrg_skiplist_enable_removal; off: none of the below exists and no chunk looks at it)
+    bool removal = false;
+    uint64_t tombstone = 0;       // a record whose val equals it is Remove(key)
+    uint32_t* d_kidx = nullptr;   // [max_batch] where a surviving Remove found its key
+    uint32_t* d_kcnt = nullptr;   // [2 * tiles] removed base / delta keys per tile, then their offsets
+    uint32_t *d_deadb = nullptr, *d_deadd = nullptr;  // [max_batch] the chunk's dead indices of each run, ascending
 };
 
 struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, contiguous in inode order
@@ -548,6 +557,7 @@ hipError_t sl_seek_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u64* d
 hipError_t sl_count_launch(nrg_ctx* c, const u64* d_los, const u64* d_his, u64 n, u64* d_counts);
 hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 limit, u64* d_okeys, u64* d_ovals,
                           u32* d_counts);
+bool sl_removal(const nrg_ctx* c);  // nrg_skiplist_enable_removal was called (group_partitioned.cpp refuses such a member)
 // queue.hip
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads (the combiner)
 }  // namespace nrg

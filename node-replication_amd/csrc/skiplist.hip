@@ -34,6 +34,25 @@
 //                the other base buffer; delta becomes empty
 // The host does not know nd exactly: it keeps an upper bound (nd when last read plus every record
 // replayed since) and reads the counts, one synchronise, only when the bound passes delta_max.
+//
+// Removal (nrg_skiplist_enable_removal; DESIGN.md "Skip list replay", Removal). On an enabled context a
+// record whose val is the tombstone is Remove(key) (SkipMap::remove). The runs stay dense: a removed key
+// is dropped physically, so no reader, digest, snapshot or merge ever sees a dead entry. A chunk there:
+//   sl_stream, sort   unchanged (a Remove's response (key, 1) is overwritten below)
+//   sl_rm_resp        a Remove's response: from the record before it in sorted order if that has the
+//                     same key (a Push: its value; a Remove: None), else a lookup of the state before
+//                     the chunk. It only reads the runs and is a launch of its own ahead of sl_resolve,
+//                     whose surviving Pushes store values in place from other lanes and workgroups.
+//   sl_resolve<true>  a surviving Remove that hits a run records the index (kidx) and flags the run;
+//                     a miss does nothing (it is no new key). Three counts per tile.
+//   sl_scan<true>     the misses as before, checked against the counts BEFORE the chunk's removals;
+//                     the kill counts kb, kd; the state then already holds the counts after the drops
+//   sl_scatter<true>  the misses, and the dead indices of each run, ascending (survivors are sorted by
+//                     key and so are the runs)
+//   (the host reads the state back: it cannot know otherwise whether a buffer flips)
+//   sl_drop_base      only when kb > 0: the base run without its dead indices into the other buffer
+//   sl_drop_delta     only when kd > 0: the same for the delta run, before the merge of the new keys
+//   sl_merge, sl_compact   as before, on exact counts
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -52,12 +71,15 @@ constexpr u32 SL_MERGE_ITEMS = 8;    // outputs per lane of a merge
 constexpr u32 SL_MERGE_PART = 2048;  // outputs per merge workgroup: SL_TPB * SL_MERGE_ITEMS
 constexpr int SL_SCAN_TPB = 1024;
 constexpr u32 SL_MAX_GRID = 4096;    // merge workgroups launched at most; the rest by stride
+constexpr u32 SL_DROP_ITEMS = 8;     // inputs per lane of a drop pass
+constexpr u32 SL_DROP_PART = 2048;   // inputs per drop workgroup and turn: SL_TPB * SL_DROP_ITEMS
 constexpr u32 SL_LOG2_MIN = 4, SL_LOG2_MAX = 28, SL_LOG2_DEFAULT = 24;
 // delta_max unless NRG_KNOB_SL_DELTA_MAX sets it (microbench/skiplist_round.py, DESIGN.md "Skip list replay")
 constexpr u64 SL_DELTA_DEFAULT = 1ull << 22;
 static_assert(SL_MERGE_PART == SL_TPB * SL_MERGE_ITEMS, "a merge workgroup's lanes cover its partition");
 static_assert(SL_SORT_TILE == SORT_TILE, "the radix sort's tile, mirrored for the tests' chunk sizes");
 static_assert(SL_RES_TILE == SL_TPB, "resolve and scatter take one record per lane");
+static_assert(SL_DROP_PART == SL_TPB * SL_DROP_ITEMS, "a drop workgroup's lanes cover its partition");
 
 struct SlJob {
     const nrg_put* src;  // the batch of a fused round or a prefill, or nullptr: read from the ring
@@ -76,17 +98,24 @@ struct SlJob {
     u32* sp;                 // [n] their chunk positions
     u32* k32;                // [n] low / high words (radix sort input)
     u32* pv;                 // [n] permutation after the low-word sort
-    uint8_t* miss;           // [n] survivor found in neither run
+    uint8_t* miss;           // [n] survivor found in neither run (removal: | SL_KILL_BASE / SL_KILL_DELTA)
     u32* tcnt;               // [tiles] misses per tile, then their exclusive offsets
     u64 *nk, *nv;            // the chunk's new keys, sorted
+    // removal only (nullptr / 0 otherwise)
+    u64 tomb;                // val of a Remove record
+    u32* kidx;               // [n] the run index a surviving Remove hit
+    u32* kcnt;               // [2 * tiles] base kills per tile, then delta kills; then their offsets
+    u32 *deadb, *deadd;      // the chunk's dead indices of base and of delta, ascending
 };
+constexpr uint8_t SL_MISS = 1, SL_KILL_BASE = 2, SL_KILL_DELTA = 4;  // SlJob::miss flags
 
 __device__ __forceinline__ nrg_put sl_load(const SlJob& j, u64 i) {
     return j.src ? j.src[i] : j.ring[(j.lo + i) & j.ring_mask];
 }
 
 // first index with a[idx] >= k (lower) or > k (upper), in [0, n]
-__device__ __forceinline__ u64 sl_lower(const u64* __restrict__ a, u64 n, u64 k) {
+template <typename T>  // (u64 keys of a run; u32 run indices of a chunk's dead list)
+__device__ __forceinline__ u64 sl_lower(const T* __restrict__ a, u64 n, u64 k) {
     u64 lo = 0, hi = n;
     while (lo < hi) {
         const u64 mid = lo + ((hi - lo) >> 1);
@@ -167,46 +196,90 @@ __global__ __launch_bounds__(SL_TPB) void sl_gather_kernel(SlJob j, const u32* _
     j.sk[i] = sl_load(j, p).key;
 }
 
+// Removal: the response of every Remove in the response window, one lane per sorted position. The
+// record before it in sorted order, if it has the same key, is the latest record of that key ahead of
+// it in the log (equal keys lie in ascending log position) and decides alone: a Push leaves its value,
+// a Remove leaves nothing. The first record of a key asks the state before the chunk. Reads the runs
+// only: sl_resolve, which writes them, is a later launch.
+__global__ __launch_bounds__(SL_TPB) void sl_rm_resp_kernel(SlJob j) {
+    const u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x;
+    if (i >= j.n) return;
+    const u32 p = j.sp[i];
+    const u64 g = j.lo + p;
+    if (g < j.rlo || g >= j.rhi) return;
+    const nrg_put r = sl_load(j, p);
+    if (r.val != j.tomb) return;
+    u64 v = 0;
+    uint8_t f = 0;
+    if (i > 0 && j.sk[i - 1] == r.key) {
+        const u64 pv = sl_load(j, j.sp[i - 1]).val;
+        if (pv != j.tomb) v = pv, f = 1;
+    } else {
+        const u64 nb = j.st->nb, nd = j.st->nd;
+        const u64 ib = sl_lower(j.bk, nb, r.key);
+        if (ib < nb && j.bk[ib] == r.key) {
+            v = j.bv[ib], f = 1;
+        } else {
+            const u64 id = sl_lower(j.dk, nd, r.key);
+            if (id < nd && j.dk[id] == r.key) v = j.dv[id], f = 1;
+        }
+    }
+    j.resp[g - j.rlo] = v;  // Some(previous value) or None (SkipMap::remove)
+    j.some[g - j.rlo] = f;
+}
+
+// RM: the context has removal enabled. A surviving Remove that hits a run stores nothing: it notes the
+// index and flags the run; one that misses is no new key.
+template <bool RM>
 __global__ __launch_bounds__(SL_TPB) void sl_resolve_kernel(SlJob j) {
-    __shared__ u32 s_cnt[SL_TPB / 64];
+    constexpr int NC = RM ? 3 : 1;  // what a tile counts: misses, base kills, delta kills
+    __shared__ u32 s_cnt[NC][SL_TPB / 64];
     const u64 i = (u64)blockIdx.x * SL_RES_TILE + threadIdx.x;
-    bool miss = false;
+    uint8_t f = 0;
     if (i < j.n) {
         const u64 k = j.sk[i];
         // equal keys lie in ascending log position: the last one is the chunk's last writer
         if (i + 1 == j.n || j.sk[i + 1] != k) {
             const u64 v = sl_load(j, j.sp[i]).val;
+            const bool rm = RM && v == j.tomb;
             const u64 nb = j.st->nb, nd = j.st->nd;
             const u64 ib = sl_lower(j.bk, nb, k);
             if (ib < nb && j.bk[ib] == k) {
-                j.bv[ib] = v;
+                if (rm) j.kidx[i] = (u32)ib, f = SL_KILL_BASE; else j.bv[ib] = v;
             } else {
                 const u64 id = sl_lower(j.dk, nd, k);
-                if (id < nd && j.dk[id] == k) j.dv[id] = v; else miss = true;
+                if (id < nd && j.dk[id] == k) {
+                    if (rm) j.kidx[i] = (u32)id, f = SL_KILL_DELTA; else j.dv[id] = v;
+                } else if (!rm) {
+                    f = SL_MISS;
+                }
             }
         }
-        j.miss[i] = miss ? 1 : 0;
+        j.miss[i] = f;
     }
-    const u64 b = __ballot(miss);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (u32)__popcll(b);
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        const u64 b = __ballot((f >> q) & 1);
+        if ((threadIdx.x & 63) == 0) s_cnt[q][threadIdx.x >> 6] = (u32)__popcll(b);
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        u32 c = 0;
-        for (int w = 0; w < SL_TPB / 64; w++) c += s_cnt[w];
-        j.tcnt[blockIdx.x] = c;
+#pragma unroll
+        for (int q = 0; q < NC; q++) {
+            u32 c = 0;
+            for (int w = 0; w < SL_TPB / 64; w++) c += s_cnt[q][w];
+            if (q == 0) j.tcnt[blockIdx.x] = c; else j.kcnt[(q - 1) * gridDim.x + blockIdx.x] = c;
+        }
     }
 }
 
-// One workgroup: tcnt becomes the tiles' exclusive offsets; the number of new keys is clipped to the
-// room left (nb + nd + nnew <= cap, and the delta buffer), ERR_CAPACITY latched when anything was
-// clipped: the chunk's largest new keys are then left out and len stays within the capacity.
-__global__ __launch_bounds__(SL_SCAN_TPB) void sl_scan_kernel(SlJob j, u32 tiles) {
-    __shared__ u32 s_scan[SL_SCAN_TPB];
+// cnt[0, tiles) becomes its exclusive prefix sums, by the workgroup; the total
+__device__ __forceinline__ u32 sl_scan_tiles(u32* cnt, u32 tiles, u32* s_scan) {
     const u32 t = threadIdx.x;
     const u32 per = (tiles + SL_SCAN_TPB - 1) / SL_SCAN_TPB;
     const u32 i0 = t * per < tiles ? t * per : tiles, i1 = i0 + per < tiles ? i0 + per : tiles;
     u32 mine = 0;
-    for (u32 i = i0; i < i1; i++) mine += j.tcnt[i];
+    for (u32 i = i0; i < i1; i++) mine += cnt[i];
     s_scan[t] = mine;
     __syncthreads();
     for (u32 s = 1; s < SL_SCAN_TPB; s <<= 1) {
@@ -217,13 +290,34 @@ __global__ __launch_bounds__(SL_SCAN_TPB) void sl_scan_kernel(SlJob j, u32 tiles
     }
     u32 run = s_scan[t] - mine;
     for (u32 i = i0; i < i1; i++) {
-        const u32 c = j.tcnt[i];
-        j.tcnt[i] = run;
+        const u32 c = cnt[i];
+        cnt[i] = run;
         run += c;
+    }
+    const u32 total = s_scan[SL_SCAN_TPB - 1];
+    __syncthreads();  // s_scan may be filled again
+    return total;
+}
+
+// One workgroup: tcnt becomes the tiles' exclusive offsets; the number of new keys is clipped to the
+// room left (nb + nd + nnew <= cap, and the delta buffer), ERR_CAPACITY latched when anything was
+// clipped: the chunk's largest new keys are then left out and len stays within the capacity.
+// RM: the two kill counts likewise. The room is what the runs leave BEFORE the chunk's own removals
+// (the keys a chunk frees are room for the next chunk); nb and nd_in then drop by the kills, which is
+// what the drop passes (launched by the host from kb, kd) make true before the merge reads nd_in.
+template <bool RM>
+__global__ __launch_bounds__(SL_SCAN_TPB) void sl_scan_kernel(SlJob j, u32 tiles) {
+    __shared__ u32 s_scan[SL_SCAN_TPB];
+    const u32 t = threadIdx.x;
+    const u32 total = sl_scan_tiles(j.tcnt, tiles, s_scan);
+    u32 kb = 0, kd = 0;
+    if (RM) {
+        kb = sl_scan_tiles(j.kcnt, tiles, s_scan);
+        kd = sl_scan_tiles(j.kcnt + tiles, tiles, s_scan);
     }
     if (t == 0) {
         const u64 nb = j.st->nb, nd = j.st->nd;
-        u64 nnew = s_scan[SL_SCAN_TPB - 1];
+        u64 nnew = total;
         u64 room = nb + nd < j.cap ? j.cap - (nb + nd) : 0;
         const u64 droom = nd < j.dcap ? j.dcap - nd : 0;  // (never the smaller one under the host's policy)
         if (droom < room) room = droom;
@@ -231,26 +325,95 @@ __global__ __launch_bounds__(SL_SCAN_TPB) void sl_scan_kernel(SlJob j, u32 tiles
             nnew = room;
             atomicOr(&j.ctl->err, ERR_CAPACITY);
         }
-        j.st->nd_in = nd;
+        if (RM) {
+            j.st->nb = nb - kb;
+            j.st->kb = kb;
+            j.st->kd = kd;
+        }
+        j.st->nd_in = nd - kd;
         j.st->nnew = nnew;
-        j.st->nd = nd + nnew;
+        j.st->nd = nd - kd + nnew;
     }
 }
 
+template <bool RM>
 __global__ __launch_bounds__(SL_TPB) void sl_scatter_kernel(SlJob j) {
-    __shared__ u32 s_cnt[SL_TPB / 64];
+    constexpr int NC = RM ? 3 : 1;
+    __shared__ u32 s_cnt[NC][SL_TPB / 64];
     const u64 i = (u64)blockIdx.x * SL_RES_TILE + threadIdx.x;
-    const bool miss = i < j.n && j.miss[i];
-    const u64 b = __ballot(miss);
+    const uint8_t f = i < j.n ? j.miss[i] : 0;
     const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_cnt[w] = (u32)__popcll(b);
+    u64 b[NC];
+#pragma unroll
+    for (int q = 0; q < NC; q++) {
+        b[q] = __ballot((f >> q) & 1);
+        if (lane == 0) s_cnt[q][w] = (u32)__popcll(b[q]);
+    }
     __syncthreads();
-    if (!miss) return;
-    u32 pos = j.tcnt[blockIdx.x] + (u32)__popcll(b & ((1ull << lane) - 1));
-    for (u32 q = 0; q < w; q++) pos += s_cnt[q];
-    if (pos < j.st->nnew) {
-        j.nk[pos] = j.sk[i];
-        j.nv[pos] = sl_load(j, j.sp[i]).val;
+    if (!f) return;
+    const int c = f == SL_MISS ? 0 : (f == SL_KILL_BASE ? 1 : 2);  // (a survivor carries one flag)
+    u32 pos = c == 0 ? j.tcnt[blockIdx.x] : j.kcnt[(c - 1) * gridDim.x + blockIdx.x];
+#pragma unroll
+    for (int q = 0; q < NC; q++)
+        if (q == c) {
+            pos += (u32)__popcll(b[q] & ((1ull << lane) - 1));
+            for (u32 x = 0; x < w; x++) pos += s_cnt[q][x];
+        }
+    if (c == 0) {
+        if (pos < j.st->nnew) {
+            j.nk[pos] = j.sk[i];
+            j.nv[pos] = sl_load(j, j.sp[i]).val;
+        }
+    } else {
+        (c == 1 ? j.deadb : j.deadd)[pos] = j.kidx[i];
+    }
+}
+
+// Removal's drop pass: the run in[0, n) without the nk indices dead[] lists (ascending, distinct, < n)
+// into out[0, n - nk), a stream compaction. A workgroup takes a contiguous range [x0, x1) of
+// SL_DROP_PART inputs per turn: its slice of the list is dead[d0, d1) by two binary searches, its
+// outputs start at x0 - d0 (every dead index below x0 is one output less). The slice marks a byte
+// per input in LDS; then, SL_TPB consecutive inputs at a time, the lanes flag, rank themselves by
+// ballot and the waves' counts, and store. No workgroup waits on another, no atomics; n and nk are the
+// host's (it has read the state back), so nothing here reads the state.
+__global__ __launch_bounds__(SL_TPB) void sl_drop_kernel(const u64* __restrict__ ik, const u64* __restrict__ iv, u64 n,
+                                                         const u32* __restrict__ dead, u32 nk, u64* __restrict__ ok,
+                                                         u64* __restrict__ ov) {
+    __shared__ uint8_t s_dead[SL_DROP_PART];
+    __shared__ u32 s_cnt[SL_TPB / 64];
+    const u32 t = threadIdx.x, lane = t & 63, w = t >> 6;
+    for (u64 part = blockIdx.x; part * SL_DROP_PART < n; part += gridDim.x) {
+        const u64 x0 = part * SL_DROP_PART, x1 = x0 + SL_DROP_PART < n ? x0 + SL_DROP_PART : n;
+        const u32 d0 = (u32)sl_lower(dead, nk, x0), d1 = (u32)sl_lower(dead, nk, x1);
+        __syncthreads();  // the previous partition is done with the marks
+        for (u32 q = t; q < SL_DROP_PART; q += SL_TPB) s_dead[q] = 0;
+        __syncthreads();
+        for (u32 q = d0 + t; q < d1; q += SL_TPB) {
+            const u64 off = (u64)dead[q] - x0;
+            if (off < SL_DROP_PART) s_dead[off] = 1;  // (always: dead[d0, d1) lies in [x0, x1))
+        }
+        __syncthreads();
+        u64 out = x0 - d0;
+        for (u32 it = 0; it < SL_DROP_ITEMS; it++) {
+            const u32 o = it * SL_TPB + t;
+            const u64 x = x0 + o;
+            const bool keep = x < x1 && !s_dead[o];
+            const u64 b = __ballot(keep);
+            if (lane == 0) s_cnt[w] = (u32)__popcll(b);
+            __syncthreads();
+            u32 pos = (u32)__popcll(b & ((1ull << lane) - 1)), tot = 0;
+            for (u32 q = 0; q < SL_TPB / 64; q++) {
+                const u32 c = s_cnt[q];
+                if (q < w) pos += c;
+                tot += c;
+            }
+            if (keep) {
+                ok[out + pos] = ik[x];
+                ov[out + pos] = iv[x];
+            }
+            out += tot;
+            __syncthreads();  // the counts are written again
+        }
     }
 }
 
@@ -533,6 +696,55 @@ static hipError_t sl_compact(nrg_ctx* c, u64 nb, u64 nd) {
     return hipGetLastError();
 }
 
+static unsigned sl_drop_grid(u64 n) {
+    const u64 g = (n + SL_DROP_PART - 1) / SL_DROP_PART;
+    return g < 1 ? 1u : (g > SL_MAX_GRID ? SL_MAX_GRID : (unsigned)g);
+}
+
+// The rest of a chunk on a context with removal, after the sort. The records live on the device, so
+// whether a run loses keys (and its buffer flips) is known only from the state: one readback per chunk,
+// 48 bytes and a synchronise. After it the host knows nb and nd exactly and its bounds are the counts.
+static hipError_t sl_chunk_rm(nrg_ctx* c, SlJob& j, u32 tiles) {
+    SlHost& s = c->sl;
+    hipError_t e;
+    const unsigned g256 = (unsigned)((j.n + SL_TPB - 1) / SL_TPB);
+    if (j.resp) NRG_LAUNCH(c, "sl_rm_resp", sl_rm_resp_kernel, g256, SL_TPB, 0, c->stream, j);
+    NRG_LAUNCH(c, "sl_resolve", sl_resolve_kernel<true>, tiles, SL_TPB, 0, c->stream, j);
+    NRG_LAUNCH(c, "sl_scan", sl_scan_kernel<true>, 1, SL_SCAN_TPB, 0, c->stream, j, tiles);
+    NRG_LAUNCH(c, "sl_scatter", sl_scatter_kernel<true>, tiles, SL_TPB, 0, c->stream, j);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    SlState st{};
+    timer_begin(c, "sl_rm_state");
+    e = sl_read_state(c, &st);
+    timer_end(c, "sl_rm_state");
+    if (e != hipSuccess) return e;
+    if (st.kb > j.n || st.kd > j.n || st.nb + st.kb > s.cap || st.nd_in + st.kd > s.dcap) return hipErrorUnknown;  // (never)
+    if (st.kb) {
+        NRG_LAUNCH(c, "sl_drop_base", sl_drop_kernel, sl_drop_grid(st.nb + st.kb), SL_TPB, 0, c->stream,
+                   (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], st.nb + st.kb, (const u32*)s.d_deadb,
+                   (u32)st.kb, s.d_bk[s.bcur ^ 1], s.d_bv[s.bcur ^ 1]);
+        s.bcur ^= 1;
+    }
+    if (st.kd) {
+        NRG_LAUNCH(c, "sl_drop_delta", sl_drop_kernel, sl_drop_grid(st.nd_in + st.kd), SL_TPB, 0, c->stream,
+                   (const u64*)s.d_dk[s.dcur], (const u64*)s.d_dv[s.dcur], st.nd_in + st.kd, (const u32*)s.d_deadd,
+                   (u32)st.kd, s.d_dk[s.dcur ^ 1], s.d_dv[s.dcur ^ 1]);
+        s.dcur ^= 1;
+    }
+    SlMerge m{};
+    m.ak = s.d_dk[s.dcur], m.av = s.d_dv[s.dcur], m.bk = j.nk, m.bv = j.nv;
+    m.st = s.d_state;
+    m.from_state = 1;
+    m.ok = s.d_dk[s.dcur ^ 1], m.ov = s.d_dv[s.dcur ^ 1];
+    NRG_LAUNCH(c, "sl_merge", sl_merge_kernel, sl_merge_grid(st.nd), SL_TPB, 0, c->stream, m);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    s.dcur ^= 1;
+    s.nd_ub = st.nd;
+    if (c->growth.max_items) c->growth.len_ub = st.nb + st.nd;
+    if (st.nd > s.delta_max) return sl_compact(c, st.nb, st.nd);
+    return hipSuccess;
+}
+
 // One chunk of n <= max_batch records through the pipeline. `wring`: src is a fused round's batch and
 // the log copy is written; a prefill passes its records as src with no log position behind them.
 static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u64 n, u64 resp_lo, u64 resp_hi,
@@ -562,6 +774,8 @@ static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u
     j.dcap = s.dcap;
     j.sk = s.d_sk, j.sp = s.d_sp, j.k32 = s.d_k32, j.pv = s.d_pv, j.miss = s.d_miss, j.tcnt = s.d_tcnt;
     j.nk = s.d_nk, j.nv = s.d_nv;
+    const bool rm = s.removal;
+    if (rm) j.tomb = s.tombstone, j.kidx = s.d_kidx, j.kcnt = s.d_kcnt, j.deadb = s.d_deadb, j.deadd = s.d_deadd;
     const unsigned g256 = (unsigned)((n + SL_TPB - 1) / SL_TPB);
     NRG_LAUNCH(c, "sl_stream", sl_stream_kernel, g256, SL_TPB, 0, c->stream, j);
     timer_begin(c, "sl_sort");
@@ -578,9 +792,10 @@ static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u
     }
     timer_end(c, "sl_sort");
     const u32 tiles = (u32)((n + SL_RES_TILE - 1) / SL_RES_TILE);
-    NRG_LAUNCH(c, "sl_resolve", sl_resolve_kernel, tiles, SL_TPB, 0, c->stream, j);
-    NRG_LAUNCH(c, "sl_scan", sl_scan_kernel, 1, SL_SCAN_TPB, 0, c->stream, j, tiles);
-    NRG_LAUNCH(c, "sl_scatter", sl_scatter_kernel, tiles, SL_TPB, 0, c->stream, j);
+    if (rm) return sl_chunk_rm(c, j, tiles);
+    NRG_LAUNCH(c, "sl_resolve", sl_resolve_kernel<false>, tiles, SL_TPB, 0, c->stream, j);
+    NRG_LAUNCH(c, "sl_scan", sl_scan_kernel<false>, 1, SL_SCAN_TPB, 0, c->stream, j, tiles);
+    NRG_LAUNCH(c, "sl_scatter", sl_scatter_kernel<false>, tiles, SL_TPB, 0, c->stream, j);
     SlMerge m{};
     m.ak = j.dk, m.av = j.dv, m.bk = j.nk, m.bv = j.nv;
     m.st = s.d_state;
@@ -643,7 +858,8 @@ static void sl_close(nrg_ctx* c) {
     sl_free_pair(s.d_bk);
     sl_free_pair(s.d_bv);
     sl_free_delta(s);
-    void* ptrs[] = {s.d_state, s.d_sk, s.d_nk, s.d_nv, s.d_sp, s.d_k32, s.d_pv, s.d_miss, s.d_tcnt};
+    void* ptrs[] = {s.d_state, s.d_sk,   s.d_nk,   s.d_nv,   s.d_sp,    s.d_k32,  s.d_pv,
+                    s.d_miss,  s.d_tcnt, s.d_kidx, s.d_kcnt, s.d_deadb, s.d_deadd};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
@@ -745,6 +961,23 @@ static int sl_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_o
 }
 
 static u64 sl_capacity(const nrg_ctx* c) { return c->sl.cap; }
+
+bool sl_removal(const nrg_ctx* c) { return c->cfg.ds_kind == NRG_DS_SKIPLIST && c->sl.removal; }
+
+// nrg_skiplist_enable_removal on a drained stream: the scratch of a chunk's removals (sl_close frees
+// it, also after a failure half way: the flag is set last)
+static int sl_enable_removal(nrg_ctx* c, u64 tombstone) {
+    SlHost& s = c->sl;
+    const u64 mb = c->cfg.max_batch ? c->cfg.max_batch : 1;
+    const u64 tiles = (mb + SL_RES_TILE - 1) / SL_RES_TILE;
+    if (!s.d_kidx) HIPCHK(hipMalloc(&s.d_kidx, mb * 4));
+    if (!s.d_deadb) HIPCHK(hipMalloc(&s.d_deadb, mb * 4));
+    if (!s.d_deadd) HIPCHK(hipMalloc(&s.d_deadd, mb * 4));
+    if (!s.d_kcnt) HIPCHK(hipMalloc(&s.d_kcnt, 2 * tiles * 4));
+    s.tombstone = tombstone;
+    s.removal = true;
+    return NRG_OK;
+}
 
 const DsOps* sl_ops() {
     static const DsOps ops = {sizeof(nrg_put), sizeof(uint64_t), sl_open, sl_close, nullptr, sl_replay_chunk,
@@ -1096,6 +1329,22 @@ int nrg_skiplist_prefill_partition(nrg_ctx* c, uint64_t n, uint64_t val_offset, 
     }
     HIPCHK(sync_all(c));
     return check_err(c);
+}
+
+int nrg_skiplist_enable_removal(nrg_ctx* c, uint64_t tombstone) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    if (c->sl.removal) return tombstone == c->sl.tombstone ? NRG_OK : NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    HIPCHK(sync_all(c));
+    return sl_enable_removal(c, tombstone);
+}
+
+int nrg_skiplist_removal(nrg_ctx* c, uint64_t* tombstone, int* enabled) {  // no device is touched
+    if (!c || c->cfg.ds_kind != NRG_DS_SKIPLIST) return NRG_E_INVAL;
+    if (tombstone) *tombstone = c->sl.removal ? c->sl.tombstone : 0;
+    if (enabled) *enabled = c->sl.removal ? 1 : 0;
+    return NRG_OK;
 }
 
 int nrg_skiplist_reserve(nrg_ctx* c, uint64_t n_keys) { return reserve_common(c, NRG_DS_SKIPLIST, n_keys); }

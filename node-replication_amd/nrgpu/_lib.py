@@ -285,6 +285,8 @@ SIGNATURES = {
     "nrg_skiplist_prefill_partition": (C.c_int, [vp, u64, u64, C.c_uint32, C.c_uint32]),
     "nrg_skiplist_reserve": (C.c_int, [vp, u64]),
     "nrg_skiplist_capacity": (C.c_int, [vp, u64p]),
+    "nrg_skiplist_enable_removal": (C.c_int, [vp, u64]),
+    "nrg_skiplist_removal": (C.c_int, [vp, u64p, C.POINTER(C.c_int)]),
     "nrg_memfs_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
     "nrg_memfs_init": (C.c_int, [vp, u64, vp, u64]),
     "nrg_memfs_read": (C.c_int, [vp, u64, u64, u64, vp, u64p]),

@@ -778,6 +778,32 @@ class DeviceReplica:
         """The keys the map has room for (nrg_skiplist_capacity)."""
         return self._capacity(self._lib.nrg_skiplist_capacity, L.NRG_DS_SKIPLIST, "sl_capacity")
 
+    def sl_enable_removal(self, tombstone: int = 2**64 - 1):
+        """From here on a record whose val == tombstone is Remove(key) (nrg_skiplist_enable_removal).
+        Idempotent for one tombstone; there is no way back. Every replica of a log enables it at the
+        same log index."""
+        L.check(self._lib.nrg_skiplist_enable_removal(self._h, tombstone), "skiplist_enable_removal")
+
+    def sl_removal(self):
+        """The tombstone, or None while removal is off (nrg_skiplist_removal)."""
+        t, on = C.c_uint64(), C.c_int()
+        L.check(self._lib.nrg_skiplist_removal(self._h, C.byref(t), C.byref(on)), "skiplist_removal")
+        return t.value if on.value else None
+
+    def sl_remove(self, keys, origin: int = 1):
+        """SkipMap::remove for a batch, in order: Remove(key) records appended to the log and replayed.
+        Returns (prev u64[n], found u8[n]): the value each key had at its log position, found = 0 (and
+        prev = 0) where it was absent."""
+        tomb = self.sl_removal()
+        if tomb is None:
+            raise L.NrgError(L.NRG_E_INVAL, "sl_remove: removal is not enabled (sl_enable_removal)")
+        recs = np.zeros(len(keys), PUT_DTYPE)
+        recs["key"], recs["val"] = np.asarray(keys, np.uint64), tomb
+        if len(recs) == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint8)
+        first = self.log_append(recs, origin)
+        return self.log_exec(first, first + len(recs))
+
     # -- file store ----------------------------------------------------------------
     def mf_geometry(self):
         """(F, B): the number of files and a file's bytes (nrg_memfs_geometry)."""
@@ -1149,6 +1175,16 @@ class SlPush:  # benches/lockfree.rs:86-97 OpWr::Push(key, val) on the skip list
 
 
 @dataclass(frozen=True)
+class SlRemove:  # SkipMap::remove(key): a record {key, tombstone}; the replicas called sl_enable_removal(tombstone)
+    key: int
+    tombstone: int = 2**64 - 1
+
+    @property
+    def val(self) -> int:
+        return self.tombstone
+
+
+@dataclass(frozen=True)
 class Seek:  # SkipMap::lower_bound / upper_bound; mode: L.NRG_SEEK_GE / GT / LE / LT
     key: int
     mode: int
@@ -1347,10 +1383,18 @@ class VSpace:
 class SkipList:
     """SkipListWrapper (benches/lockfree_partitioned.rs:86-118): an ordered map u64 -> u64. SlPush ->
     the key (Ok(Some(key))); Get -> the value or None; Seek -> (key, value) or None; Scan -> a list of
-    (key, value) in the scan's order."""
+    (key, value) in the scan's order. SlRemove -> the previous value or None, once every replica of the
+    log has called its DeviceReplica.sl_enable_removal(); before, its record is a Push of the tombstone."""
 
     kind = L.NRG_DS_SKIPLIST
     rec_dtype = PUT_DTYPE
+
+    @staticmethod
+    def clone_prepare(dev: DeviceReplica, peer: DeviceReplica):
+        """Before `dev` is restored from `peer`'s image: an image does not carry the removal setting."""
+        tomb = peer.sl_removal()
+        if tomb is not None:
+            dev.sl_enable_removal(tomb)
 
     @staticmethod
     def encode(ops) -> np.ndarray:
