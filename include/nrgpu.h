@@ -552,6 +552,49 @@ int nrg_hashmap_capacity(nrg_ctx* ctx, uint32_t* log2_slots);
 int nrg_hashmap_dump(nrg_ctx* ctx, uint64_t* keys, uint64_t* vals, uint64_t cap, uint64_t* n);
 /* Order-independent digest of the contents: count, sum and xor of mix64(k ^ mix64(v)). */
 int nrg_hashmap_digest(nrg_ctx* ctx, uint64_t out[3]);
+/* Removal of keys (std::collections::HashMap::remove, the container behind NrHashMap,
+ * benches/hashmap.rs:77-79: the previous value or None, and the key is absent afterwards; the
+ * reference's OpWr has no Remove). A record is {key, val} with both fields spanning all of u64, so the
+ * context opts in, as nrg_skiplist_enable_removal does:
+ * From here on a record whose val == tombstone is Remove(key); every other record is Put as before.
+ * Synchronous, no way back; it flushes the deferred half. NRG_E_NOT_SYNCED while ltail < tail. Calling
+ * it again with the same tombstone is NRG_OK; with another one NRG_E_INVAL. NRG_E_INVAL also for a
+ * context that is not a hashmap, while a combiner is open on it, and if any present value equals the
+ * tombstone (one scan of the table before anything changes: the replica stays as it was). Replicas of
+ * one log, and every member of a group, enable it at the same log index with the same tombstone. A
+ * context that never calls it behaves as before in every respect ({k, 2^64 - 1} is an ordinary Put
+ * there) and launches the same kernels.
+ *   Responses go where previous values go, in log order, one op at a time: Put(k, v) and Remove(k) both
+ * answer (the previous value, 1) if k was present at that log position, else (0, 0). The answer depends
+ * on the records before it, also those of the same chunk: Put(k, v), Remove(k) answers v; Remove(k),
+ * Remove(k) answers Some, then None; Remove(k), Put(k, v) answers Some, then None.
+ *   A Remove is an ordinary 16-byte record: nrg_log_append* / nrg_log_exec*, nrg_hashmap_round_async,
+ * nrg_hashmap_round_segments_async, nrg_group_round_async, nrg_group_resync and the partitioned rounds
+ * (nrg_group_partitioned_round*: the owner replays it and its answer travels as a previous value) carry
+ * it unchanged. nrg_hashmap_prefill* with a tombstone value returns NRG_E_INVAL. nrg_combiner_open
+ * on an enabled context returns NRG_E_INVAL.
+ *   A removed key keeps its slot, marked dead, until a rehash (growth, or a purge) drops it; a later
+ * Put of the key revives the slot. nrg_hashmap_size, Gets, dump, digest, snapshots and group verify
+ * see live keys only, and none of them depends on when a replica grew or purged. Dead slots count
+ * against the table: nrg_hashmap_occupancy is what the load limit and NRG_E_TABLE_FULL see. With
+ * automatic growth the replay purges or grows by itself; a fixed table (or one at its maximum) needs
+ * nrg_hashmap_purge before its dead slots fill it (DESIGN.md "NrHashMap", Removal).
+ *   Every write round of an enabled context takes one schedule (the previous-value partition round),
+ * whatever NRG_KNOB_PART / _SMALL_MAX / _STAMP_MAX say.
+ *   A snapshot holds live pairs only and does not record the setting: a context restored from an
+ * image, or resynced, keeps its own. nrg_restore of an image that holds the tombstone as a value into
+ * an enabled context returns NRG_E_INVAL, the replica unchanged. */
+int nrg_hashmap_enable_removal(nrg_ctx* ctx, uint64_t tombstone);
+/* Query, no device touched: *enabled = 1 and *tombstone once removal is on, else 0 and 0 (either
+ * pointer may be NULL). */
+int nrg_hashmap_removal(nrg_ctx* ctx, uint64_t* tombstone, int* enabled);
+/* Slots taken: live keys plus dead slots (nrg_hashmap_size is the live keys). Without removal the two
+ * are equal. */
+int nrg_hashmap_occupancy(nrg_ctx* ctx, uint64_t* slots_taken);
+/* Drop the dead slots: a rehash into a fresh table of the same size, synchronous, under the rules of
+ * nrg_hashmap_reserve (NRG_E_NOMEM: the old table is intact). NRG_OK and nothing launched when there
+ * are no dead slots or removal is off. */
+int nrg_hashmap_purge(nrg_ctx* ctx);
 
 /* ---- Flat combining on the host ---------------------------------------------------------- */
 /* Replica's flat combiner for many client threads (nr/src/context.rs:88-194,
@@ -1467,7 +1510,9 @@ int nrg_gen_stack_ops_async(nrg_ctx* ctx, nrg_stack_op* d_out, uint64_t n, uint6
  * unperturbed). The main replay kernel ("hm_round") is timed with start/stop events stamped
  * from its own dispatch (hipExtLaunchKernelGGL); multi-kernel pipelines ("hm_prev",
  * "st_replay", "sy_replay") with event records around them; a table growth's two passes are
- * "hm_grow_init" and "hm_rehash", a snapshot's table scan "hm_snapshot", a restore's two passes
+ * "hm_grow_init" and "hm_rehash" (a purge's too: nrg_hashmap_purge and the automatic one), the
+ * tombstone scan of nrg_hashmap_enable_removal and of a restore into an enabled context is
+ * "hm_find_val", a snapshot's table scan "hm_snapshot", a restore's two passes
  * "hm_restore_init" and "hm_restore"; the skip list's chunk sort is "sl_sort" (event records around its
  * launches), its chunk merge "sl_merge" and a compaction of the delta run into the base run
  * "sl_compact" (one launch each: the launches counted are the compactions); its batched reads are

@@ -559,6 +559,8 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
     if (!nrg::ds_ops(kind)) return NRG_E_INVAL;
     // the page table, the skip list and the file store have no combiner (include/nrgpu.h)
     if (kind == NRG_DS_VSPACE || kind == NRG_DS_SKIPLIST || kind == NRG_DS_MEMFS) return NRG_E_INVAL;
+    // a hashmap with removal enabled runs one schedule, without the small rounds the combiner is built on
+    if (nrg::hm_removal(ctx)) return NRG_E_INVAL;
     const uint64_t cap = (uint64_t)max_threads * MAX_PENDING;
     if (cap > ctx->cfg.max_batch || (kind == NRG_DS_HASHMAP && cap > ctx->cfg.max_reads)) return NRG_E_CAPACITY;
     int r = nrg::ctx_use_device(ctx);
@@ -652,6 +654,7 @@ extern "C" int nrg_combiner_open(nrg_ctx* ctx, uint32_t max_threads, nrg_combine
         comb_free(m);
         return NRG_E_NOMEM;
     }
+    ctx->comb.open++;
     *out = m;
     return NRG_OK;
 }
@@ -669,6 +672,7 @@ extern "C" int nrg_combiner_close(nrg_combiner* m) {
     if (hipStreamSynchronize((hipStream_t)nrg_get_stream(m->ctx)) != hipSuccess) rc = NRG_E_HIP;
     m->ctx->pipeline = m->saved_pipeline;
     m->ctx->hm.small_max = m->saved_small;
+    m->ctx->comb.open--;
     comb_free(m);
     return rc;
 }

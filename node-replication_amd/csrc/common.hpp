@@ -74,7 +74,9 @@ __device__ __forceinline__ u64 table_home(u64 key, u32 shift) { return mix64(key
 // The probe sequence of a key with home slot `home`, p = 0, 1, 2, ...: round the home's group of four
 // slots (one 128-B line) from the home slot on, then round the next group from the same offset, and so
 // on, wrapping at the table's end. It is a function of the key alone, every walk of a chain goes
-// through it, and no key is ever deleted (a full group stays full), so a present key lies in the first
+// through it, and no key is ever deleted (a full group stays full): a key that is removed
+// (nrg_hashmap_enable_removal) keeps its slot, which is marked dead and still holds the key, until a
+// rehash builds a new table without it. So a present key lies in the first
 // group of its sequence that had an empty slot when the key was inserted: a reader that sees a group
 // with an empty slot and no match has its answer, absent, without looking at a later group.
 __host__ __device__ constexpr u64 probe_slot(u64 home, u64 p, u64 tmask) {
@@ -142,6 +144,7 @@ struct __attribute__((aligned(64))) DevCtl {
     long long depth_next;  // stack: ... of parity 1; a chunk starts from the other parity's slot
     u64 pad;
     Slot sp;          // hashmap: side slot of the key EMPTY_KEY (val, stamps; key unused)
+    u64 occ_total;    // hashmap with removal: slots taken, live and dead (hm_count; nkeys_total is the live ones)
 };
 
 __device__ __forceinline__ u64 ld_relaxed(const u64* p) {

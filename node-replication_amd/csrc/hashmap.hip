@@ -35,6 +35,12 @@
 //   chunk resolves. It runs at the memory-side request floor (profiles/r04_papply_phases.txt).
 //   With previous values every Put keeps its entry and one wave walks each chunk in log order:
 //   a Put's previous value is its predecessor's, else the key's value before the chunk, else None.
+// Removal (nrg_hashmap_enable_removal; std::collections::HashMap::remove on the HashMap<u64, u64> of
+//   benches/hashmap.rs:77-79; DESIGN.md "NrHashMap", Removal): on an enabled context a record whose
+//   value is the tombstone is Remove(key), and every write round is a previous-value partition round
+//   with the apply kernel's removal arm. A removed key keeps its slot, DEAD: val = tombstone for the
+//   table scans, both stamps 0 for the Gets (which then always consult the stamp); a Put revives it, a
+//   rehash drops it. A context that never enables launches what it always launched.
 #include <cstring>
 
 #include "internal.hpp"
@@ -695,6 +701,10 @@ struct PApplyJob {
     u32 stall;  // NRG_KNOB_STALL (tests)
     u64* dbg;   // (NRG_KNOB_EXP bit 2, diagnostic) per bucket, 8 words: [0] start [1] counts scanned
                 // [2] first chunk hashed [3] its slots resolved [4] its stores done [5] end [6] chunks
+    // removal (hm_papply_kernel<true, 256, false, true> alone reads these; they stay last, so the
+    // fields above are where the other instantiations have always found them)
+    u64 tomb;       // an entry whose value is this is Remove(key)
+    u64* dead_acc;  // [HM_CREATED_SLOTS] slots that died minus slots revived (wrapping)
 };
 
 // T threads per workgroup (rounds without previous values: 256, 512 or 1024 over at most 1024,
@@ -718,9 +728,12 @@ __device__ __forceinline__ u32 pa_hash(u64 k, u32 ht) { return (u32)(mix64(k) >>
 // round trips for most keys instead of one or two per key). on[r]: key r takes part (not the
 // side key). Out: slot[r] (-1: table full), fresh[r] (this call claimed it: epoch-1 stamps
 // written), val[r] = the slot's value before this call (found keys; WANT_VAL).
-template <int N, bool WANT_VAL>
+// FIND (removal): key r claims only if claim[r]; else its probe ends at the first empty slot, as a
+// reader's does, with slot[r] = PA_ABSENT and the table untouched.
+constexpr long long PA_ABSENT = -2;
+template <int N, bool WANT_VAL, bool FIND = false>
 __device__ __forceinline__ void pa_resolve(Slot* table, u32 shift, u64 tmask, const u64* k, const bool* on,
-                                           long long* slot, bool* fresh, u64* val) {
+                                           long long* slot, bool* fresh, u64* val, const bool* claim = nullptr) {
     u64 s[N], kk[N], vv[N];
     u32 st[N];  // 0 done, 1 key loaded, 2 CAS needed, 3 moved on to the chain's next slot
 #pragma unroll
@@ -751,7 +764,12 @@ __device__ __forceinline__ void pa_resolve(Slot* table, u32 shift, u64 tmask, co
                 if (WANT_VAL) val[r] = vv[r];
                 st[r] = 0;
             } else if (kk[r] == EMPTY_KEY) {
-                st[r] = 2;
+                if (FIND && !claim[r]) {
+                    slot[r] = PA_ABSENT;
+                    st[r] = 0;
+                } else {
+                    st[r] = 2;
+                }
             } else {
                 s[r] = probe_next(s[r], pr, tmask);
                 st[r] = 3;
@@ -797,14 +815,34 @@ __device__ __forceinline__ void pa_resolve(Slot* table, u32 shift, u64 tmask, co
             st[r] = 1;
         }
     }
+    // every slot probed and none matched: a table with no empty slot left. A key that would have
+    // claimed is refused (slot -1); a find-only probe has its answer, absent, as a reader's has.
+    if constexpr (FIND) {
+#pragma unroll
+        for (int r = 0; r < N; r++)
+            if (st[r] != 0 && !claim[r]) slot[r] = PA_ABSENT;
+    }
 }
 
 // NT: the table values are stored streamed (round 6; rounds of <= PA_NT_MAX Puts, see the launch)
-template <bool PREV, int T, bool NT = false>
+// RM: removal (nrg_hashmap_enable_removal; every write round of an enabled context). An entry whose
+// value is j.tomb is Remove(key) (HashMap::remove): it answers what a Put answers, None after a
+// Remove, and leaves the key without a value. A removed key keeps its slot (common.hpp probe_slot:
+// no slot is ever emptied), which becomes DEAD: val = tomb, both stamps 0. Per key and chunk:
+//   first entry   find the slot; claim one only if the key has a Put in this chunk (s_hf bit 1), so a
+//                 Remove of an absent key takes no slot. A dead slot is "no value before the chunk"
+//                 and is remembered for revival (s_hf bit 2).
+//   last entry    live: the value, and the two present stamps if the slot was dead; not live and a slot
+//                 exists (it was live, or a Put of this chunk claimed it): the slot dies.
+// created_acc counts claims (occupancy); dead_acc the deaths minus the revivals.
+template <bool PREV, int T, bool NT = false, bool RM = false>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4))) void hm_papply_kernel(PApplyJob j) {
+    static_assert(!RM || (PREV && !NT), "removal rides the previous-value arm");
     using G = PaGeo<PREV, T>;
     constexpr int PA_TPB = G::TPB, C = G::C, HT = G::HT, PER = G::PER;
     constexpr u32 NOFIRST = 0xFFFFFFFFu;
+    constexpr u32 NO_SLOT = 0xFFFFFFFDu;  // RM: the key holds no slot (absent, and only removed in this chunk)
+    constexpr u32 HF_LIVE = 1u, HF_PUT = 2u, HF_DEAD = 4u;  // s_hf: bits 1 and 2 are RM's
     extern __shared__ u32 s_dyn[];  // s_pre[ntiles + 1] entry prefix, s_off[ntiles] (u16)
     __shared__ u64 s_hk[HT];
     __shared__ u32 s_hp[HT + 1];   // last chunk position + 1 of the key; [HT]: the side key
@@ -818,6 +856,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
     __shared__ uint16_t s_eh[PREV ? C : 1];
     __shared__ u32 s_ei[PREV ? C : 1];
     __shared__ u32 s_created;
+    __shared__ int s_died;  // RM: deaths minus revivals
     // Workgroups are dealt to the 8 XCDs round-robin; bucket b goes to workgroup 8 (b % per) + b / per
     // (per = nb / 8), so each XCD takes a contiguous range of buckets. Neighbouring buckets' entry
     // runs and count words share lines, and those lines are then fetched into one XCD's L2
@@ -849,6 +888,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
             s_h1[h] = NOFIRST;
             s_mk[h] = 0;
         }
+        if (RM) s_hf[h] = 0;
     }
     u32 total;
     u32 run = block_scan_excl<PA_TPB>(loc, &total);  // (its barriers also order the initialisation above)
@@ -863,11 +903,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
     if (threadIdx.x == 0) {
         s_pre[nt] = total;
         s_created = 0;
+        if (RM) s_died = 0;
     }
     __syncthreads();
     PA_MARK(1, wall_clock64());
     PA_MARK(6, (total + C - 1) / C);
     u32 created = 0;
+    int died = 0;
     // entry tile map of the chunk at `base`
     auto map_chunk = [&](u32 base, uint16_t* map) {
         const u32 cn = total - base < (u32)C ? total - base : (u32)C;
@@ -940,6 +982,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
                 s_ev[p] = x[r].y;
                 s_eh[p] = (uint16_t)h;
                 s_ei[p] = ix[r];
+                if (RM && x[r].y != j.tomb) atomicOr(&s_hf[h], HF_PUT);  // (s_hf is 0 between chunks)
             }
         }
         __syncthreads();
@@ -988,7 +1031,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
             }
         } else {
             // the key's first entry: its slot and its value before the chunk
-            bool fst[PER], on[PER], fr[PER];
+            bool fst[PER], on[PER], fr[PER], cl[PER];
             u64 kx[PER], vx[PER];
             long long sl[PER];
 #pragma unroll
@@ -998,12 +1041,45 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
                 on[r] = fst[r] && x[r].x != EMPTY_KEY;
                 kx[r] = x[r].x;
                 vx[r] = 0;
+                cl[r] = RM && fst[r] && (s_hf[hh[r]] & HF_PUT);
             }
-            pa_resolve<PER, true>(j.table, j.shift, j.tmask, kx, on, sl, fr, vx);
+            if constexpr (RM) pa_resolve<PER, true, true>(j.table, j.shift, j.tmask, kx, on, sl, fr, vx, cl);
+            else pa_resolve<PER, true>(j.table, j.shift, j.tmask, kx, on, sl, fr, vx);
 #pragma unroll
             for (int r = 0; r < PER; r++) {
                 if (!fst[r]) continue;
                 const u32 h = hh[r];
+                if constexpr (RM) {
+                    // (this thread alone writes the key's s_hf here: the Puts' atomicOr ran before the barrier)
+                    u32 f = cl[r] ? HF_PUT : 0u;
+                    if (x[r].x == EMPTY_KEY) {
+                        if (j.ctl->sp_claim) {
+                            const u64 v0 = j.ctl->sp.val;
+                            s_hs[h] = SIDE_ID;
+                            s_lv[h] = v0;
+                            f |= v0 == j.tomb ? HF_DEAD : HF_LIVE;
+                        } else if (cl[r]) {
+                            j.ctl->sp_claim = 1;
+                            j.ctl->sp.st[0] = j.ctl->sp.st[1] = STAMP_PRESENT;
+                            created++;
+                            s_hs[h] = SIDE_ID;
+                        } else {
+                            s_hs[h] = NO_SLOT;
+                        }
+                    } else if (sl[r] == PA_ABSENT) {
+                        s_hs[h] = NO_SLOT;
+                    } else if (sl[r] < 0) {
+                        atomicOr(&j.ctl->err, ERR_TABLE_FULL);
+                        s_hs[h] = FULL_SLOT;
+                    } else {
+                        s_hs[h] = (u32)sl[r];
+                        created += fr[r];
+                        s_lv[h] = vx[r];
+                        if (!fr[r]) f |= vx[r] == j.tomb ? HF_DEAD : HF_LIVE;
+                    }
+                    s_hf[h] = f;
+                    continue;
+                }
                 if (x[r].x == EMPTY_KEY) {
                     s_hs[h] = SIDE_ID;
                     if (j.ctl->sp_claim) {
@@ -1045,8 +1121,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
                         if (lower) {
                             pv = pv_lane;
                             pf = 1;
+                            if (RM && pv_lane == j.tomb) {  // the predecessor is a Remove
+                                pv = 0;
+                                pf = 0;
+                            }
                         } else {
-                            pf = s_hf[h] ? 1 : 0;
+                            pf = (RM ? s_hf[h] & HF_LIVE : s_hf[h]) ? 1 : 0;
                             pv = pf ? s_lv[h] : 0;
                         }
                         const u64 g = j.lo + s_ei[p];
@@ -1055,8 +1135,17 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
                             j.prevf[g - j.resp_lo] = pf;
                         }
                         if ((m >> lane) == 1ull) {  // the key's last entry in this step
-                            s_lv[h] = val;
-                            s_hf[h] = 1;
+                            if constexpr (RM) {
+                                if (val == j.tomb) {  // a Remove leaves the running value empty
+                                    s_hf[h] &= ~HF_LIVE;
+                                } else {
+                                    s_lv[h] = val;
+                                    s_hf[h] |= HF_LIVE;
+                                }
+                            } else {
+                                s_lv[h] = val;
+                                s_hf[h] = 1;
+                            }
                             s_mk[h] = 0;
                         }
                     }
@@ -1070,8 +1159,29 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
                 if (p >= cn || s_hp[hh[r]] != p + 1) continue;
                 const u32 h = hh[r];
                 const u32 sl = s_hs[h];
-                if (sl == SIDE_ID) j.ctl->sp.val = s_lv[h];
-                else if (sl != FULL_SLOT) j.table[sl].val = s_lv[h];  // (streamed, with the answers: slower, profiles/r06/papply_nt.txt)
+                if constexpr (RM) {
+                    const u32 f = s_hf[h];
+                    Slot* t = sl == SIDE_ID ? &j.ctl->sp : sl < NO_SLOT ? &j.table[sl] : nullptr;
+                    if (t && (f & HF_LIVE)) {
+                        t->val = s_lv[h];
+                        if (f & HF_DEAD) {  // revived
+                            u64x2 z;
+                            z.x = z.y = STAMP_PRESENT;
+                            *(u64x2*)&t->st[0] = z;
+                            died--;
+                        }
+                    } else if (t && !(f & HF_DEAD)) {  // it was live, or a Put of this chunk claimed it: it dies
+                        u64x2 z;
+                        z.x = z.y = 0;
+                        t->val = j.tomb;
+                        *(u64x2*)&t->st[0] = z;
+                        died++;
+                    }
+                    s_hf[h] = 0;
+                } else {
+                    if (sl == SIDE_ID) j.ctl->sp.val = s_lv[h];
+                    else if (sl != FULL_SLOT) j.table[sl].val = s_lv[h];  // (streamed, with the answers: slower, profiles/r06/papply_nt.txt)
+                }
                 if (h < HT) s_hk[h] = EMPTY_KEY;
                 s_hp[h] = 0;
                 s_h1[h] = NOFIRST;
@@ -1081,8 +1191,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(PREV ? 3 : 4)
         if (base == 0) PA_MARK(4, wall_clock64());
     }
     if (created) atomicAdd(&s_created, created);
+    if (RM && died) atomicAdd(&s_died, died);
     __syncthreads();
     if (threadIdx.x == 0 && s_created) atomicAdd(&j.created_acc[b % HM_CREATED_SLOTS], (u64)s_created);
+    if (RM && threadIdx.x == 0 && s_died) atomicAdd(&j.dead_acc[b % HM_CREATED_SLOTS], (u64)(long long)s_died);
     PA_MARK(5, wall_clock64());
 #undef PA_MARK
 }
@@ -1551,8 +1663,11 @@ __global__ __launch_bounds__(TPB) void hm_init_table_kernel(Slot* table, u64 slo
 constexpr int RH_TPB = 256, RH_Q = 8;
 constexpr u64 RH_RUN = 4096;  // old slots per workgroup
 static_assert(RH_RUN % ((u64)RH_TPB * RH_Q) == 0, "a run is whole batches");
+// With removal enabled (rm) a dead slot (val == tomb) is not moved, and a dead side key gives its slot
+// back: after a rehash every taken slot holds a live key. The new table may then be one of the SAME
+// size (hm_grow's purge).
 __global__ __launch_bounds__(RH_TPB) void hm_rehash_kernel(const Slot* __restrict__ old, u64 old_slots, Slot* table,
-                                                           u32 shift, u64 tmask, DevCtl* ctl) {
+                                                           u32 shift, u64 tmask, DevCtl* ctl, bool rm, u64 tomb) {
     __shared__ u32 s_moved;
     if (threadIdx.x == 0) s_moved = 0;
     __syncthreads();
@@ -1570,7 +1685,7 @@ __global__ __launch_bounds__(RH_TPB) void hm_rehash_kernel(const Slot* __restric
             if (s < old_slots) e = *(const u64x2*)&old[s];
             k[q] = e.x;
             v[q] = e.y;
-            on[q] = e.x != EMPTY_KEY;
+            on[q] = e.x != EMPTY_KEY && !(rm && e.y == tomb);
         }
         u64 s[RH_Q];
         bool any = false;
@@ -1610,8 +1725,12 @@ __global__ __launch_bounds__(RH_TPB) void hm_rehash_kernel(const Slot* __restric
     if (threadIdx.x == 0) {
         u64 m = s_moved;
         if (blockIdx.x == 0 && ctl->sp_claim) {  // the side slot lives in DevCtl and does not move
-            ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
-            m++;
+            if (rm && ctl->sp.val == tomb) {
+                ctl->sp_claim = 0;
+            } else {
+                ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
+                m++;
+            }
         }
         if (m) atomicAdd((unsigned long long*)&ctl->nkeys, (unsigned long long)m);  // (hm_grow zeroed it)
     }
@@ -1619,27 +1738,34 @@ __global__ __launch_bounds__(RH_TPB) void hm_rehash_kernel(const Slot* __restric
 
 // Epoch renormalisation (before the 32-bit epoch wraps): every present key becomes "present
 // since before the replay rounds" (epoch 1); claims in flight do not exist at this point.
-__global__ __launch_bounds__(TPB) void hm_renorm_kernel(Slot* table, u64 slots, DevCtl* ctl) {
+// With removal enabled (rm) a dead slot (val == tomb, stamps 0) stays dead.
+__global__ __launch_bounds__(TPB) void hm_renorm_kernel(Slot* table, u64 slots, DevCtl* ctl, bool rm, u64 tomb) {
     for (u64 s = blockIdx.x * (u64)TPB + threadIdx.x; s < slots; s += (u64)gridDim.x * TPB) {
-        if (table[s].key == EMPTY_KEY) continue;
+        const u64x2 e = *(const u64x2*)&table[s];
+        if (e.x == EMPTY_KEY || (rm && e.y == tomb)) continue;
         u64x2 z;
         z.x = z.y = STAMP_PRESENT;
         *(u64x2*)&table[s].st[0] = z;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && ctl->sp_claim) ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && ctl->sp_claim && !(rm && ctl->sp.val == tomb))
+        ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
 }
 
 // NrHashMap::default (benches/hashmap.rs:91-100): keys 0..n-1 -> k + off, inserted directly.
+// With removal enabled (dead_acc given; no value is the tombstone, the host checked) a key whose slot is
+// dead is revived: counted out of dead_acc, so both counts stay exact.
 __global__ __launch_bounds__(TPB) void hm_prefill_range_kernel(Slot* table, u64 n, u64 off, u32 shift, u64 tmask,
-                                                               DevCtl* ctl, u32 part, u32 parts) {
-    __shared__ u32 s_ins;
-    if (threadIdx.x == 0) s_ins = 0;
+                                                               DevCtl* ctl, u32 part, u32 parts, u64 tomb,
+                                                               u64* dead_acc) {
+    __shared__ u32 s_ins, s_rev;
+    if (threadIdx.x == 0) s_ins = s_rev = 0;
     __syncthreads();
-    u32 inserted = 0;
+    u32 inserted = 0, revived = 0;
     for (u64 k = blockIdx.x * (u64)TPB + threadIdx.x; k < n; k += (u64)gridDim.x * TPB) {
         if (parts > 1 && key_owner(k, parts) != part) continue;  // a key partition's share only
         if (k == EMPTY_KEY) {  // only reachable for n = 2^64, kept for the full key domain
             inserted += ctl->sp_claim == 0;
+            revived += dead_acc && ctl->sp_claim && ctl->sp.val == tomb;
             ctl->sp.val = k + off;
             ctl->sp.st[0] = ctl->sp.st[1] = STAMP_PRESENT;
             ctl->sp_claim = 1;
@@ -1651,41 +1777,77 @@ __global__ __launch_bounds__(TPB) void hm_prefill_range_kernel(Slot* table, u64 
             atomicOr(&ctl->err, ERR_TABLE_FULL);
             continue;
         }
+        revived += dead_acc && !fresh && table[s].val == tomb;
         table[s].val = k + off;
         table[s].st[0] = table[s].st[1] = STAMP_PRESENT;
         inserted += fresh;
     }
     if (inserted) atomicAdd(&s_ins, inserted);
+    if (revived) atomicAdd(&s_rev, revived);
     __syncthreads();
     if (threadIdx.x == 0 && s_ins) atomicAdd(&ctl->nkeys, (u64)s_ins);
+    if (threadIdx.x == 0 && s_rev) atomicAdd(&dead_acc[blockIdx.x % HM_CREATED_SLOTS], 0ull - (u64)s_rev);
 }
 
 // number of keys = direct inserts (ctl->nkeys) + keys created by replay rounds
-__global__ __launch_bounds__(TPB) void hm_count_kernel(const u64* __restrict__ acc, u64 n, DevCtl* ctl) {
-    __shared__ u64 s_w[TPB / 64];
-    u64 x = 0;
-    for (u64 q = threadIdx.x; q < n; q += TPB) x += acc[q];
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
+// With removal enabled (dead given) that sum is the occupancy, the slots taken (DevCtl::occ_total), and
+// the number of keys is the occupancy minus the dead slots (deaths minus revivals, a wrapping sum).
+__global__ __launch_bounds__(TPB) void hm_count_kernel(const u64* __restrict__ acc, u64 n, DevCtl* ctl,
+                                                       const u64* __restrict__ dead) {
+    __shared__ u64 s_w[TPB / 64], s_d[TPB / 64];
+    u64 x = 0, d = 0;
+    for (u64 q = threadIdx.x; q < n; q += TPB) {
+        x += acc[q];
+        if (dead) d += dead[q];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        x += __shfl_xor(x, off, 64);
+        d += __shfl_xor(d, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_w[threadIdx.x >> 6] = x;
+        s_d[threadIdx.x >> 6] = d;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        u64 t = ctl->nkeys;
-        for (int w = 0; w < TPB / 64; w++) t += s_w[w];
-        ctl->nkeys_total = t;
+        u64 t = ctl->nkeys, dd = 0;
+        for (int w = 0; w < TPB / 64; w++) {
+            t += s_w[w];
+            dd += s_d[w];
+        }
+        ctl->occ_total = t;
+        ctl->nkeys_total = t - dd;
     }
 }
 
+// nrg_hashmap_enable_removal / nrg_restore into an enabled context: how many of the n {key, value}
+// pairs, `stride` words apart, hold `tomb` as their value (table: empty slots are no pairs), added to
+// DevCtl::counter.
+__global__ __launch_bounds__(TPB) void hm_find_val_kernel(const u64* __restrict__ pairs, u64 n, u32 stride, bool table,
+                                                          u64 tomb, DevCtl* ctl) {
+    u32 hits = 0;
+    for (u64 i = blockIdx.x * (u64)TPB + threadIdx.x; i < n; i += (u64)gridDim.x * TPB) {
+        const u64x2 e = *(const u64x2*)&pairs[i * stride];
+        hits += e.y == tomb && !(table && e.x == EMPTY_KEY);
+    }
+    if (table && blockIdx.x == 0 && threadIdx.x == 0 && ctl->sp_claim && ctl->sp.val == tomb) hits++;
+    for (int off = 32; off > 0; off >>= 1) hits += __shfl_xor(hits, off, 64);
+    if ((threadIdx.x & 63) == 0 && hits) atomicAdd(&ctl->counter, (u64)hits);
+}
+
+// (rm, here and in the digest and the snapshot: removal is enabled, and a slot whose value is tomb is
+// dead, a removed key that keeps its slot; no live value equals tomb there)
 __global__ __launch_bounds__(TPB) void hm_dump_kernel(const Slot* __restrict__ table, u64 slots, DevCtl* ctl,
-                                                      u64* __restrict__ ok, u64* __restrict__ ov) {
+                                                      u64* __restrict__ ok, u64* __restrict__ ov, bool rm, u64 tomb) {
     const u64 gid = blockIdx.x * (u64)TPB + threadIdx.x;
-    if (gid == 0 && ctl->sp_claim) {
+    if (gid == 0 && ctl->sp_claim && !(rm && ctl->sp.val == tomb)) {
         const u64 i = atomicAdd(&ctl->counter, 1ull);
         ok[i] = EMPTY_KEY;
         ov[i] = ctl->sp.val;
     }
     for (u64 s = gid; s < slots; s += (u64)gridDim.x * TPB) {
         const u64x2 e = *(const u64x2*)&table[s];
-        if (e.x != EMPTY_KEY) {
+        if (e.x != EMPTY_KEY && !(rm && e.y == tomb)) {
             const u64 i = atomicAdd(&ctl->counter, 1ull);
             ok[i] = e.x;
             ov[i] = e.y;
@@ -1694,11 +1856,11 @@ __global__ __launch_bounds__(TPB) void hm_dump_kernel(const Slot* __restrict__ t
 }
 
 __global__ __launch_bounds__(TPB) void hm_digest_kernel(const Slot* __restrict__ table, u64 slots,
-                                                        const DevCtl* ctl, u64* out3) {
+                                                        const DevCtl* ctl, u64* out3, bool rm, u64 tomb) {
     __shared__ u64 s_c[TPB / 64], s_s[TPB / 64], s_x[TPB / 64];
     const u64 gid = blockIdx.x * (u64)TPB + threadIdx.x;
     u64 c = 0, sm = 0, x = 0;
-    if (gid == 0 && ctl->sp_claim) {
+    if (gid == 0 && ctl->sp_claim && !(rm && ctl->sp.val == tomb)) {
         const u64 h = mix64(EMPTY_KEY ^ mix64(ctl->sp.val));
         c++;
         sm += h;
@@ -1706,7 +1868,7 @@ __global__ __launch_bounds__(TPB) void hm_digest_kernel(const Slot* __restrict__
     }
     for (u64 s = gid; s < slots; s += (u64)gridDim.x * TPB) {
         const u64x2 e = *(const u64x2*)&table[s];
-        if (e.x != EMPTY_KEY) {
+        if (e.x != EMPTY_KEY && !(rm && e.y == tomb)) {
             const u64 h = mix64(e.x ^ mix64(e.y));
             c++;
             sm += h;
@@ -1752,7 +1914,8 @@ constexpr int SN_Q = 16;
 constexpr u64 SN_TILE = (u64)TPB * SN_Q;
 static_assert(SN_Q * (TPB / 64) == 64, "the row counts of a tile are scanned by one wave, one per lane");
 __global__ __launch_bounds__(TPB) void hm_snapshot_kernel(const Slot* __restrict__ table, u64 slots, DevCtl* ctl,
-                                                          u64x2* __restrict__ out, u64 cap_items) {
+                                                          u64x2* __restrict__ out, u64 cap_items, bool rm,
+                                                          u64 tomb) {
     __shared__ u32 s_cnt[64];
     __shared__ u64 s_base;
     const u32 lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1767,6 +1930,7 @@ __global__ __launch_bounds__(TPB) void hm_snapshot_kernel(const Slot* __restrict
             e[q].x = EMPTY_KEY;
             e[q].y = 0;
             if (s < slots) e[q] = *(const u64x2*)&table[s];
+            if (rm && e[q].y == tomb) e[q].x = EMPTY_KEY;  // a dead slot: no pair
         }
 #pragma unroll
         for (int q = 0; q < SN_Q; q++) {
@@ -1804,11 +1968,11 @@ __global__ __launch_bounds__(TPB) void hm_snapshot_kernel(const Slot* __restrict
 }
 
 // After the scan: the side key's pair behind the table's, then the header or the refusal.
-__global__ void hm_snapshot_head_kernel(DevCtl* ctl, u64* buf, u64 cap, u64 log_idx) {
+__global__ void hm_snapshot_head_kernel(DevCtl* ctl, u64* buf, u64 cap, u64 log_idx, bool rm, u64 tomb) {
     if (threadIdx.x || blockIdx.x) return;
     u64 n = ctl->counter;
     const u64 cap_items = cap >= SNAP_HDR ? (cap - SNAP_HDR) / 16 : 0;
-    if (ctl->sp_claim) {
+    if (ctl->sp_claim && !(rm && ctl->sp.val == tomb)) {
         if (n < cap_items) {
             buf[SNAP_HDR / 8 + 2 * n] = EMPTY_KEY;
             buf[SNAP_HDR / 8 + 2 * n + 1] = ctl->sp.val;
@@ -1948,7 +2112,9 @@ static hipError_t launch(nrg_ctx* c, Launch& L) {
     L.ij.plain = L.sj.plain = L.rj.plain = L.ix == IX_STAMP && nix;  // stamp rounds keep plain stores (st_out)
     // reads beside a bucket or partition pass (which only read the table, or not even that), or
     // alone, with no stamp round's apply riding along: the table is quiescent
-    L.rj.quiet = (L.ix != IX_STAMP || nix == 0) && L.aj.nblocks == 0;
+    // (removal enabled: a removed key's slot still holds the key, with zeroed stamps, so every read
+    // there consults the stamp -- read_role's resolve() answers absent for stamp 0)
+    L.rj.quiet = (L.ix != IX_STAMP || nix == 0) && L.aj.nblocks == 0 && !c->hm.removal;
     u32 blocks = nix + L.aj.nblocks + L.rj.nblocks;
     if (blocks == 0) return hipSuccess;
     // a pending skew sample rides in the launch's last block. (The combiner's error copy,
@@ -2043,7 +2209,7 @@ static hipError_t hm_alloc(nrg_ctx* c, u64 mb) {
 
 static void hm_close(nrg_ctx* c) {
     void* ptrs[] = {c->hm.d_table, c->hm.d_created, c->hm.d_bk_ent, c->hm.d_bk_idx, c->hm.d_bk_cnt, c->hm.d_put_slot[0],
-                    c->hm.d_put_slot[1], c->hm.d_dup};
+                    c->hm.d_put_slot[1], c->hm.d_dup, c->hm.d_dead};
     for (void* p : ptrs) (void)hipFree(p);
     if (c->hm.h_dup) (void)hipHostFree((void*)c->hm.h_dup);
     pt_close(c);  // the scratch of this replica's key partitioning, if it ever partitioned
@@ -2105,8 +2271,11 @@ static u32 hm_slots_for(u64 keys) {
 // folded into DevCtl::nkeys (exact) and the created-key counters cleared. Then the stream is
 // synchronised, the old table freed and the new one installed. If the allocation fails nothing
 // has been launched but the flush: the old table stays installed and the replica is as it was.
+// With removal enabled the rehash drops the dead slots, and new_log2 may be the current size: a purge.
 static hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
-    if (new_log2 > 30 || (1ull << new_log2) <= c->hm.slots) return hipErrorInvalidValue;
+    const bool rm = c->hm.removal;
+    if (new_log2 > 30 || (1ull << new_log2) < c->hm.slots || (!rm && (1ull << new_log2) == c->hm.slots))
+        return hipErrorInvalidValue;
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
     const u64 nslots = 1ull << new_log2;
@@ -2121,10 +2290,11 @@ static hipError_t hm_grow(nrg_ctx* c, u32 new_log2) {
     if (e == hipSuccess) {
         const unsigned grid = (unsigned)((c->hm.slots + RH_RUN - 1) / RH_RUN);
         NRG_LAUNCH(c, "hm_rehash", hm_rehash_kernel, grid, RH_TPB, 0, c->stream, c->hm.d_table, c->hm.slots, nt,
-                   64 - new_log2, nslots - 1, c->d_ctl);
+                   64 - new_log2, nslots - 1, c->d_ctl, rm, c->hm.tombstone);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemsetAsync(c->hm.d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream);
+    if (e == hipSuccess && rm) e = hipMemsetAsync(c->hm.d_dead, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream);
     for (int i = 0; i < 2 && c->hm.d_put_slot[i] && e == hipSuccess; i++)
         e = hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_alloc * sizeof(u32), c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
@@ -2169,6 +2339,28 @@ hipError_t hm_room(nrg_ctx* c, u64 n, bool* due) {
     if (e != hipSuccess) return e;
     u64 exact = 0;
     if ((e = hipMemcpyAsync(&exact, &c->d_ctl->nkeys_total, sizeof(u64), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+    if (c->hm.removal) {
+        // Removal enabled: keys_ub bounds the OCCUPANCY (live and dead slots: what the load limit and
+        // a full table see), and a record still claims at most one slot. Over the limit, the target is
+        // the size that holds the live keys and the n records, never a smaller table: a larger one is
+        // a grow, the same one with dead slots a purge (a rehash into a table of the same size);
+        // either leaves no dead slot behind. The decision depends on the log prefix and the
+        // configuration alone, as above.
+        u64 occ = 0;
+        if ((e = hipMemcpyAsync(&occ, &c->d_ctl->occ_total, sizeof(u64), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+        if (occ + n > limit) {
+            u32 want = hm_slots_for(exact + n);
+            if (want > c->hm.grow_max_log2) want = c->hm.grow_max_log2;
+            if (want < log2_slots) want = log2_slots;
+            if (want > log2_slots || occ > exact) {
+                if ((e = hm_grow(c, want)) != hipSuccess) return e;
+                occ = exact;
+            }
+        }
+        c->hm.keys_ub = occ + n;
+        return hipSuccess;
+    }
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
     if (exact + n > limit) {
         u32 want = hm_slots_for(exact + n);
@@ -2184,7 +2376,8 @@ static hipError_t next_epoch(nrg_ctx* c, u32* e) {
     if (c->hm.epoch >= c->hm.epoch_limit) {
         hipError_t r = hm_flush(c);
         if (r != hipSuccess) return r;
-        hm_renorm_kernel<<<grid_for(c->hm.slots, 16384), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl);
+        hm_renorm_kernel<<<grid_for(c->hm.slots, 16384), TPB, 0, c->stream>>>(c->hm.d_table, c->hm.slots, c->d_ctl,
+                                                                              c->hm.removal, c->hm.tombstone);
         if ((r = hipGetLastError()) != hipSuccess) return r;
         for (int i = 0; i < 2 && c->hm.d_put_slot[i]; i++)  // win / over epoch tags of the old epochs
             if ((r = hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_alloc * sizeof(u32), c->stream)) != hipSuccess)
@@ -2204,10 +2397,16 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
     if (n == 0) return R ? hm_reads(c, d_get_keys, R, d_get_vals, d_get_found) : hm_flush(c);
     if (n > HM_MAX_BATCH) return hipErrorInvalidValue;
     const nrg_put* src = (const nrg_put*)src_recs;
-    const bool want_prev = d_prev && resp_lo < lo + n && resp_hi > lo;
+    // Removal enabled: ONE schedule. Every write round is a previous-value partition round (IX_PART_ALL,
+    // then the apply kernel's removal arm), with or without responses (then the window is empty):
+    // no small round, no stamp round, no dedup, whatever the knobs say.
+    const bool rm = c->hm.removal;
+    const bool have_resp = d_prev && resp_lo < lo + n && resp_hi > lo;
+    const bool want_prev = have_resp || rm;
+    if (!have_resp) resp_lo = resp_hi = 0;
     hipError_t eg = hm_room(c, n);  // every round kind below: the table grows first if it has to
     if (eg != hipSuccess) return eg;
-    if (c->hm.small_max && n <= c->hm.small_max && n <= SM_W && R <= SM_R) {  // one launch, nothing deferred
+    if (!rm && c->hm.small_max && n <= c->hm.small_max && n <= SM_W && R <= SM_R) {  // one launch, nothing deferred
         hipError_t e = small_round(c, src, lo, n, write_ring, d_get_keys, R, d_get_vals, d_get_found, resp_lo, resp_hi,
                                    want_prev ? d_prev : nullptr, d_prev_found);
         c->rounds++;
@@ -2289,8 +2488,11 @@ hipError_t hm_replay_chunk(nrg_ctx* c, const void* src_recs, u64 lo, u64 n, bool
         aj.prevf = d_prev_found;
         aj.stall = c->stall;
         aj.dbg = (c->exp & 2) ? c->d_dbg : nullptr;
+        aj.tomb = c->hm.tombstone;
+        aj.dead_acc = c->hm.d_dead;
         const unsigned dyn = ((ij.nblocks + 1) * 4 + ij.nblocks * 2 + 3) & ~3u;
-        if (want_prev) NRG_LAUNCH(c, "hm_papply", (hm_papply_kernel<true, 256>), 1u << nb_log, 256, dyn, c->stream, aj);
+        if (rm) NRG_LAUNCH(c, "hm_papply", (hm_papply_kernel<true, 256, false, true>), 1u << nb_log, 256, dyn, c->stream, aj);
+        else if (want_prev) NRG_LAUNCH(c, "hm_papply", (hm_papply_kernel<true, 256>), 1u << nb_log, 256, dyn, c->stream, aj);
         else if (pa_t == 1024) NRG_LAUNCH(c, "hm_papply", (hm_papply_kernel<false, 1024>), 1u << nb_log, 1024, dyn, c->stream, aj);
         else if (pa_t == 512 && n <= PA_NT_MAX)
             NRG_LAUNCH(c, "hm_papply", (hm_papply_kernel<false, 512, true>), 1u << nb_log, 512, dyn, c->stream, aj);
@@ -2395,6 +2597,20 @@ static int hm_items(nrg_ctx* c, u64* n);
 static hipError_t hm_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx);
 static int hm_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_only);
 
+// *hits = how many of n {key, value} pairs, `stride` words apart, hold the tombstone as their value
+// (table: the slots of the table and the side slot; empty slots are no pairs). Synchronous.
+static int hm_find_val(nrg_ctx* c, const u64* pairs, u64 n, u32 stride, bool table, u64* hits) {
+    HIPCHK(hipMemsetAsync(&c->d_ctl->counter, 0, sizeof(u64), c->stream));
+    NRG_LAUNCH(c, "hm_find_val", hm_find_val_kernel, grid_for(n, 8192), TPB, 0, c->stream, pairs, n, stride, table,
+               c->hm.tombstone, c->d_ctl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hits, &c->d_ctl->counter, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return NRG_OK;
+}
+
+bool hm_removal(const nrg_ctx* c) { return c->cfg.ds_kind == NRG_DS_HASHMAP && c->hm.removal; }
+
 const DsOps* hm_ops() {
     static const DsOps ops = {sizeof(nrg_put), sizeof(u64), hm_open, hm_close, hm_flush, hm_replay,
                               hm_floor, hm_set_knob, hm_dbg_words, nullptr, hm_digest,
@@ -2413,14 +2629,16 @@ hipError_t hm_prefill_range(nrg_ctx* c, u64 n, u64 off, u32 part, u32 parts) {
     }
     if ((e = hm_room(c, mine)) != hipSuccess) return e;
     hm_prefill_range_kernel<<<grid_for(n, 8192), TPB, 0, c->stream>>>(c->hm.d_table, n, off, c->hm.slot_shift,
-                                                                      c->hm.slots - 1, c->d_ctl, part, parts);
+                                                                      c->hm.slots - 1, c->d_ctl, part, parts,
+                                                                      c->hm.tombstone, c->hm.removal ? c->hm.d_dead : nullptr);
     return hipGetLastError();
 }
 
 static hipError_t hm_count(nrg_ctx* c) {
     hipError_t e = hm_flush(c);
     if (e != hipSuccess) return e;
-    hm_count_kernel<<<1, TPB, 0, c->stream>>>(c->hm.d_created, HM_CREATED_SLOTS, c->d_ctl);
+    hm_count_kernel<<<1, TPB, 0, c->stream>>>(c->hm.d_created, HM_CREATED_SLOTS, c->d_ctl,
+                                              c->hm.removal ? c->hm.d_dead : nullptr);
     return hipGetLastError();
 }
 
@@ -2430,7 +2648,7 @@ static hipError_t hm_dump(nrg_ctx* c, u64* d_keys, u64* d_vals) {
     e = hipMemsetAsync(&c->d_ctl->counter, 0, sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
     NRG_LAUNCH(c, "hm_dump", hm_dump_kernel, grid_for(c->hm.slots, 8192), TPB, 0, c->stream, (const Slot*)c->hm.d_table,
-               (u64)c->hm.slots, c->d_ctl, d_keys, d_vals);
+               (u64)c->hm.slots, c->d_ctl, d_keys, d_vals, c->hm.removal, c->hm.tombstone);
     return hipGetLastError();
 }
 
@@ -2440,7 +2658,8 @@ static hipError_t hm_digest(nrg_ctx* c, u64* d_out3) {
     e = hipMemsetAsync(d_out3, 0, 3 * sizeof(u64), c->stream);
     if (e != hipSuccess) return e;
     NRG_LAUNCH(c, "hm_digest", hm_digest_kernel, grid_for(c->hm.slots, 8192), TPB, 0, c->stream,
-               (const Slot*)c->hm.d_table, (u64)c->hm.slots, (const DevCtl*)c->d_ctl, d_out3);
+               (const Slot*)c->hm.d_table, (u64)c->hm.slots, (const DevCtl*)c->d_ctl, d_out3, c->hm.removal,
+               c->hm.tombstone);
     return hipGetLastError();
 }
 
@@ -2461,9 +2680,11 @@ static hipError_t hm_snapshot(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx) {
     const u64 cap_items = cap >= SNAP_HDR ? (cap - SNAP_HDR) / 16 : 0;
     const u64 tiles = (c->hm.slots + SN_TILE - 1) / SN_TILE;
     NRG_LAUNCH(c, "hm_snapshot", hm_snapshot_kernel, (unsigned)(tiles < 8192 ? tiles : 8192), TPB, 0, c->stream,
-               (const Slot*)c->hm.d_table, (u64)c->hm.slots, c->d_ctl, (u64x2*)((char*)d_buf + SNAP_HDR), cap_items);
+               (const Slot*)c->hm.d_table, (u64)c->hm.slots, c->d_ctl, (u64x2*)((char*)d_buf + SNAP_HDR), cap_items,
+               c->hm.removal, c->hm.tombstone);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hm_snapshot_head_kernel<<<1, 64, 0, c->stream>>>(c->d_ctl, (u64*)d_buf, cap, log_idx);
+    hm_snapshot_head_kernel<<<1, 64, 0, c->stream>>>(c->d_ctl, (u64*)d_buf, cap, log_idx, c->hm.removal,
+                                                     c->hm.tombstone);
     return hipGetLastError();
 }
 
@@ -2476,7 +2697,15 @@ static int hm_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_o
     const bool grows = c->hm.grow_max_log2 > cur;
     if (check_only) {
         const u64 limit = grows ? (1ull << c->hm.grow_max_log2) / HM_GROW_SLOTS_PER_KEY : c->hm.slots;
-        return items > limit ? NRG_E_TABLE_FULL : NRG_OK;
+        if (items > limit) return NRG_E_TABLE_FULL;
+        // removal enabled: an image that holds the tombstone as a value is not a state of this context
+        if (c->hm.removal && d_payload && items) {
+            u64 hits = 0;
+            int r = hm_find_val(c, (const u64*)d_payload, items, 2, false, &hits);
+            if (r) return r;
+            if (hits) return NRG_E_INVAL;
+        }
+        return NRG_OK;
     }
     if (!d_payload) items = 0;
     if (grows) {
@@ -2500,6 +2729,7 @@ static int hm_restore(nrg_ctx* c, const void* d_payload, u64 items, bool check_o
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(c->d_ctl, 0, sizeof(DevCtl), c->stream));
     HIPCHK(hipMemsetAsync(c->hm.d_created, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
+    if (c->hm.d_dead) HIPCHK(hipMemsetAsync(c->hm.d_dead, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream));
     for (int i = 0; i < 2 && c->hm.d_put_slot[i]; i++)
         HIPCHK(hipMemsetAsync(c->hm.d_put_slot[i], 0, 3 * c->hm.stamp_alloc * sizeof(u32), c->stream));
     HIPCHK(hipMemsetAsync(c->hm.d_dup, 0, 2 * HM_DUP_SLOTS * sizeof(u64), c->stream));
@@ -2539,6 +2769,7 @@ hipError_t copy_segments(nrg_ctx* c, const void* d_base, u32 nseg, u64 seg_strid
 int hm_small_job(nrg_ctx* c, const nrg_put* recs, u64 W, u32 origin, const u64* keys, u64 R, u64* vals,
                  uint8_t* found, u64* prev, uint8_t* prevf, u32* e_out, SmallJobBlob* blob, u64* lo_out) {
     if (!c || c->cfg.ds_kind != NRG_DS_HASHMAP || W > c->cfg.max_batch || c->ltail != c->tail) return NRG_E_INVAL;
+    if (c->hm.removal) return NRG_E_INVAL;  // (no small round there, and no combiner to ask for one)
     if ((W && !recs) || (R && (!keys || !vals || !found))) return NRG_E_INVAL;
     int r = reserve(c, W);  // (caught up and nothing deferred: only moves head, launches nothing)
     if (r) return r == NRG_E_RING_FULL ? NRG_E_INVAL : r;  // more than the log ever holds: not a small round
@@ -2655,6 +2886,9 @@ int nrg_hashmap_round_segments_async(nrg_ctx* c, const nrg_put* d_base, uint32_t
 int nrg_hashmap_prefill(nrg_ctx* c, const uint64_t* keys, const uint64_t* vals, uint64_t n) {
     int r = need(c, NRG_DS_HASHMAP);
     if (r) return r;
+    if (c->hm.removal)  // a prefilled value is a value: never the tombstone
+        for (uint64_t i = 0; i < n; i++)
+            if (vals[i] == c->hm.tombstone) return NRG_E_INVAL;
     Staging* s = c->stg;
     uint64_t done = 0;
     const uint64_t chunk = c->cfg.max_batch;
@@ -2680,6 +2914,7 @@ int nrg_hashmap_prefill(nrg_ctx* c, const uint64_t* keys, const uint64_t* vals, 
 int nrg_hashmap_prefill_range(nrg_ctx* c, uint64_t n, uint64_t off) {
     int r = need(c, NRG_DS_HASHMAP);
     if (r) return r;
+    if (c->hm.removal && c->hm.tombstone - off < n) return NRG_E_INVAL;  // some k + off is the tombstone
     HIPCHK(hm_prefill_range(c, n, off));
     HIPCHK(sync_all(c));
     return check_err(c);
@@ -2694,6 +2929,66 @@ int nrg_hashmap_reserve(nrg_ctx* c, uint64_t n_keys) {
     const uint32_t want = hm_slots_for(n_keys);
     if ((1ull << want) <= c->hm.slots) return NRG_OK;
     HIPCHK(hm_grow(c, want));
+    return NRG_OK;
+}
+
+// ---- removal (HashMap::remove; include/nrgpu.h, DESIGN.md "NrHashMap", Removal) --------------------
+int nrg_hashmap_enable_removal(nrg_ctx* c, uint64_t tombstone) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (c->hm.removal) return tombstone == c->hm.tombstone ? NRG_OK : NRG_E_INVAL;
+    if (c->comb.open) return NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    HIPCHK(sync_all(c));  // (flushes the deferred half)
+    // one scan before anything changes: no present value may be the tombstone
+    c->hm.tombstone = tombstone;
+    u64 hits = 0;
+    r = hm_find_val(c, (const u64*)c->hm.d_table, c->hm.slots, (u32)(sizeof(Slot) / 8), true, &hits);
+    if (r == NRG_OK && hits) r = NRG_E_INVAL;
+    if (r == NRG_OK && !c->hm.d_dead) {
+        hipError_t e = hipMalloc(&c->hm.d_dead, HM_CREATED_SLOTS * sizeof(u64));
+        if (e == hipSuccess) e = hipMemsetAsync(c->hm.d_dead, 0, HM_CREATED_SLOTS * sizeof(u64), c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) (void)hipGetLastError();
+        r = hip_fail(e);
+    }
+    if (r != NRG_OK) {
+        c->hm.tombstone = 0;
+        return r;
+    }
+    c->hm.removal = true;
+    return NRG_OK;
+}
+
+int nrg_hashmap_removal(nrg_ctx* c, uint64_t* tombstone, int* enabled) {  // no device is touched
+    if (!c || c->cfg.ds_kind != NRG_DS_HASHMAP) return NRG_E_INVAL;
+    if (tombstone) *tombstone = c->hm.removal ? c->hm.tombstone : 0;
+    if (enabled) *enabled = c->hm.removal ? 1 : 0;
+    return NRG_OK;
+}
+
+int nrg_hashmap_occupancy(nrg_ctx* c, uint64_t* slots_taken) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (!slots_taken) return NRG_E_INVAL;
+    HIPCHK(hm_count(c));
+    HIPCHK(hipMemcpyAsync(slots_taken, &c->d_ctl->occ_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    return check_err(c);
+}
+
+int nrg_hashmap_purge(nrg_ctx* c) {
+    int r = need(c, NRG_DS_HASHMAP);
+    if (r) return r;
+    if (!c->hm.removal) return NRG_OK;
+    u64 cnt[2] = {0, 0};  // live, taken
+    HIPCHK(hm_count(c));
+    HIPCHK(hipMemcpyAsync(&cnt[0], &c->d_ctl->nkeys_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&cnt[1], &c->d_ctl->occ_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (cnt[1] == cnt[0]) return NRG_OK;  // nothing dead
+    HIPCHK(hm_grow(c, 64 - c->hm.slot_shift));
+    if (c->hm.keys_ub > cnt[0]) c->hm.keys_ub = cnt[0];
     return NRG_OK;
 }
 

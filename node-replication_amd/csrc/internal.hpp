@@ -165,6 +165,10 @@ struct HmHost {  // NrHashMap (hashmap.hip)
     uint32_t* err_out = nullptr;  // the next hm_round launch copies (and clears) the error latch here
     uint32_t dup_rounds = 0, dup_every = 16;
     bool skewed = false;
+    // Removal (nrg_hashmap_enable_removal; off: none of the below exists and no round looks at it)
+    bool removal = false;
+    uint64_t tombstone = 0;      // a record whose val equals it is Remove(key); a slot whose val equals it is dead
+    uint64_t* d_dead = nullptr;  // [HM_CREATED_SLOTS] slots that died minus slots revived (a wrapping sum)
 };
 
 struct StHost {  // stack (stack.hip)
@@ -277,6 +281,7 @@ struct CombKnobs {  // read by nrg_combiner_open (combiner.cpp); NRG_KNOB_COMB_*
     uint32_t depth = 0;   // 0 = default
     int32_t gather = -1;  // us; -1 = default
     int32_t serve = -1;   // -1 = default: on
+    uint32_t open = 0;    // combiners open on the context (nrg_hashmap_enable_removal refuses while one is)
 };
 
 struct PtHost {  // key partitioning (partition.hip): tile counts / offsets, grown on demand
@@ -328,7 +333,7 @@ struct DsOps {
     // magic = 0 and latches ERR_CAPACITY. Deferred work has been launched.
     hipError_t (*snapshot)(nrg_ctx* c, void* d_buf, u64 cap, u64 log_idx);
     // nrg_restore. check_only: may a payload of `items` items go into this context? An NRG_* code,
-    // nothing touched. Else: replace the structure's contents and rebuild its bookkeeping from the
+    // nothing of the structure touched (the hashmap may read the payload on the stream and wait for it). Else: replace the structure's contents and rebuild its bookkeeping from the
     // payload (the stream has been drained, nothing is deferred). d_payload == nullptr: the empty
     // structure of a fresh context instead (after a restore whose digest did not match).
     int (*restore)(nrg_ctx* c, const void* d_payload, u64 items, bool check_only);
@@ -557,6 +562,7 @@ hipError_t sl_seek_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u64* d
 hipError_t sl_count_launch(nrg_ctx* c, const u64* d_los, const u64* d_his, u64 n, u64* d_counts);
 hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 limit, u64* d_okeys, u64* d_ovals,
                           u32* d_counts);
+bool hm_removal(const nrg_ctx* c);  // hashmap.hip: nrg_hashmap_enable_removal was called (nrg_combiner_open refuses)
 bool sl_removal(const nrg_ctx* c);  // nrg_skiplist_enable_removal was called (group_partitioned.cpp refuses such a member)
 // queue.hip
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads (the combiner)

@@ -716,6 +716,7 @@ int nrg_hashmap_prefill_partition(nrg_ctx* c, uint64_t n, uint64_t off, uint32_t
     int r = need(c, NRG_DS_HASHMAP);
     if (r) return r;
     if (parts == 0 || parts > NRG_MAX_PARTS || part >= parts) return NRG_E_INVAL;
+    if (c->hm.removal && c->hm.tombstone - off < n) return NRG_E_INVAL;  // some k + off is the tombstone
     HIPCHK(hm_prefill_range(c, n, off, part, parts));
     HIPCHK(sync_all(c));
     return check_err(c);

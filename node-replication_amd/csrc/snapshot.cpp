@@ -98,7 +98,9 @@ int nrg_restore(nrg_ctx* c, const void* d_buf, uint64_t bytes) {
     if (!c || !d_buf || ((uintptr_t)d_buf & 15)) return NRG_E_INVAL;
     int r = ctx_use_device(c);
     if (r) return r;
-    // 1, 2: the header against the format, then against this context; nothing is touched yet
+    // 1, 2: the header against the format, then against this context; nothing of the replica's state is
+    // touched yet (a hashmap with removal enabled scans the payload for its tombstone here: one launch,
+    // a stream synchronise, and DevCtl::counter, which is scratch of the dump and the snapshot)
     nrg_snapshot_info info;
     if ((r = read_header(c, d_buf, bytes, &info))) return r;
     if (info.ds_kind != c->cfg.ds_kind) return NRG_E_INVAL;

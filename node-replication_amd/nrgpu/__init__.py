@@ -43,6 +43,7 @@ from .replica import (
     Queue,
     ReadOnly,
     ReadWrite,
+    Remove,
     Replica,
     ReplicaToken,
     Scan,
@@ -62,7 +63,7 @@ from .replica import (
 __all__ = [
     "_lib", "digest", "snapshot", "NrgError", "load", "Combiner", "PUT_DTYPE", "QUEUE_OP_DTYPE", "STACK_OP_DTYPE", "SYNTH_OP_DTYPE", "SYNTH_RD_DTYPE",
     "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
-    "ReadOnly", "ReadWrite", "Replica", "ReplicaToken", "Stack", "WriteOnly",
+    "ReadOnly", "ReadWrite", "Remove", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
     "Scan", "Seek", "SkipList", "SlPush", "SlRemove",
     "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfSetAttr", "MfWrite",

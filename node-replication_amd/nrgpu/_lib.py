@@ -246,6 +246,10 @@ SIGNATURES = {
     "nrg_hashmap_size": (C.c_int, [vp, u64p]),
     "nrg_hashmap_reserve": (C.c_int, [vp, u64]),
     "nrg_hashmap_capacity": (C.c_int, [vp, C.POINTER(u32)]),
+    "nrg_hashmap_enable_removal": (C.c_int, [vp, u64]),
+    "nrg_hashmap_removal": (C.c_int, [vp, u64p, C.POINTER(C.c_int)]),
+    "nrg_hashmap_occupancy": (C.c_int, [vp, u64p]),
+    "nrg_hashmap_purge": (C.c_int, [vp]),
     "nrg_hashmap_dump": (C.c_int, [vp, vp, vp, u64, u64p]),
     "nrg_hashmap_digest": (C.c_int, [vp, vp]),
     "nrg_stack_init": (C.c_int, [vp, vp, u64]),

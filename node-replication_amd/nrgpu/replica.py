@@ -523,6 +523,42 @@ class DeviceReplica:
         L.check(self._lib.nrg_hashmap_capacity(self._h, C.byref(n)), "capacity")
         return n.value
 
+    def hm_enable_removal(self, tombstone: int = 2**64 - 1):
+        """From here on a record whose val == tombstone is Remove(key) (nrg_hashmap_enable_removal).
+        Idempotent for one tombstone; there is no way back. Every replica of a log enables it at the
+        same log index. Refused while any present value equals the tombstone."""
+        L.check(self._lib.nrg_hashmap_enable_removal(self._h, tombstone), "hashmap_enable_removal")
+
+    def hm_removal(self):
+        """The tombstone, or None while removal is off (nrg_hashmap_removal)."""
+        t, on = C.c_uint64(), C.c_int()
+        L.check(self._lib.nrg_hashmap_removal(self._h, C.byref(t), C.byref(on)), "hashmap_removal")
+        return t.value if on.value else None
+
+    def hm_remove(self, keys, origin: int = 1):
+        """HashMap::remove for a batch, in order: Remove(key) records appended to the log and replayed.
+        Returns (prev u64[n], found u8[n]): the value each key had at its log position, found = 0 (and
+        prev = 0) where it was absent."""
+        tomb = self.hm_removal()
+        if tomb is None:
+            raise L.NrgError(L.NRG_E_INVAL, "hm_remove: removal is not enabled (hm_enable_removal)")
+        recs = np.zeros(len(keys), PUT_DTYPE)
+        recs["key"], recs["val"] = np.asarray(keys, np.uint64), tomb
+        if len(recs) == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint8)
+        first = self.log_append(recs, origin)
+        return self.log_exec(first, first + len(recs))
+
+    def hm_occupancy(self) -> int:
+        """Slots taken, live and dead (nrg_hashmap_occupancy); hm_size() is the live keys."""
+        n = C.c_uint64()
+        L.check(self._lib.nrg_hashmap_occupancy(self._h, C.byref(n)), "hashmap_occupancy")
+        return n.value
+
+    def hm_purge(self):
+        """Drop the dead slots: a rehash into a table of the same size (nrg_hashmap_purge). Synchronous."""
+        L.check(self._lib.nrg_hashmap_purge(self._h), "hashmap_purge")
+
     def hm_dump(self):
         """(keys, vals) sorted by key"""
         n = self.hm_size()
@@ -1124,6 +1160,16 @@ class Put:  # benches/hashmap.rs:52-56
 
 
 @dataclass(frozen=True)
+class Remove:  # HashMap::remove(key): a record {key, tombstone}, the tombstone the replicas enabled removal with
+    key: int
+    tombstone: int = 2**64 - 1  # checked against the replica's (NrHashMap.check_ops): a mismatch is an error
+
+    @property
+    def val(self) -> int:
+        return self.tombstone
+
+
+@dataclass(frozen=True)
 class Get:  # benches/hashmap.rs:59-63
     key: int
 
@@ -1265,10 +1311,34 @@ class ReadOnly:  # benches/synthetic.rs:28-31
 
 
 class NrHashMap:
-    """NrHashMap: HashMap<u64,u64>; Put -> previous value (nr/examples/hashmap.rs:46-50)."""
+    """NrHashMap: HashMap<u64,u64>; Put -> previous value (nr/examples/hashmap.rs:46-50). Remove -> the
+    previous value or None, once every replica of the log has called its DeviceReplica.hm_enable_removal()
+    with Remove's tombstone."""
 
     kind = L.NRG_DS_HASHMAP
     rec_dtype = PUT_DTYPE
+
+    @staticmethod
+    def clone_prepare(dev: DeviceReplica, peer: DeviceReplica):
+        """Before `dev` is restored from `peer`'s image: an image does not carry the removal setting."""
+        tomb = peer.hm_removal()
+        if tomb is not None:
+            dev.hm_enable_removal(tomb)
+
+    @staticmethod
+    def check_ops(dev: DeviceReplica, ops):
+        """Before a batch is enqueued: what a record means depends on the replica's tombstone alone, so a
+        Remove built for another tombstone (or for a replica without removal) would silently be a Put of
+        that value, and a Put of the replica's tombstone silently a Remove. Both are refused here."""
+        tomb = dev.hm_removal()  # (touches no device)
+        for o in ops:
+            if isinstance(o, Remove):
+                if tomb is None:
+                    raise L.NrgError(L.NRG_E_INVAL, "Remove: removal is not enabled on this replica (hm_enable_removal)")
+                if o.tombstone != tomb:
+                    raise ValueError(f"Remove(tombstone={o.tombstone:#x}) on a replica whose tombstone is {tomb:#x}")
+            elif tomb is not None and o.val == tomb:
+                raise ValueError(f"Put of the value {tomb:#x}, which is this replica's tombstone (it would be a Remove)")
 
     @staticmethod
     def encode(ops: Sequence[Put]) -> np.ndarray:
@@ -1949,6 +2019,9 @@ class Replica:
         """Host batcher: enqueue many of this thread's writes, combine once."""
         tid = tok.id()
         ops = list(ops)
+        check_ops = getattr(self.ds, "check_ops", None)
+        if check_ops is not None:  # (NrHashMap) an op that would not mean on this replica what it says
+            check_ops(self.dev, ops)
         records_for = getattr(self.ds, "records_for", None)
         if records_for is not None:  # (MemFs) an op that no single append can carry is refused here
             lim = self.log.size - GC_FROM_HEAD
