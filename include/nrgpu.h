@@ -765,9 +765,10 @@ int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_
  * :73-97): that is nrg_group_partitioned_round on a group of skip-list replicas, with
  * nrg_skiplist_prefill_partition and the group-wide ordered reads nrg_group_skiplist_seek /
  * nrg_group_skiplist_range_count / nrg_group_skiplist_scan (the cnr section below). Out of scope: there is no combiner
- * (nrg_combiner_open returns NRG_E_INVAL, as for the page table), no removal of keys in partitioned
- * rounds (nrg_skiplist_enable_removal below: replicated groups and single replicas only) and no
- * pop_front / pop_back. Every call below returns NRG_E_INVAL on a context of another kind. */
+ * (nrg_combiner_open returns NRG_E_INVAL, as for the page table), and neither removal of keys nor
+ * pop_front / pop_back in partitioned rounds (nrg_skiplist_enable_removal and nrg_skiplist_enable_pops
+ * below: replicated groups and single replicas only). Every call below returns NRG_E_INVAL on a context
+ * of another kind. */
 /* Replica::combine for one batch of Push(k, v) records (nr/src/replica.rs:544-595): Log::append of the
  * n records in d_ops (device) with `origin`, then Log::exec, with the log copy written by the
  * replay's first pass. Responses (d_resp[i] = the key, d_some[i] = 1; nullable) as nrg_log_exec_async
@@ -878,6 +879,56 @@ int nrg_skiplist_enable_removal(nrg_ctx* ctx, uint64_t tombstone);
 /* Query, no device touched: *enabled = 1 and *tombstone once removal is on, else 0 and 0 (either
  * pointer may be NULL). */
 int nrg_skiplist_removal(nrg_ctx* ctx, uint64_t* tombstone, int* enabled);
+/* SkipMap::pop_front / pop_back through the log, one or many at a time: what makes the ordered map a
+ * priority queue or a work list. (seek + Remove is two records with a host round trip between them, and
+ * another replica's record can land in between; a pop is one record, ordered by the log.) The context
+ * opts in, under nrg_skiplist_enable_removal's rules: skip-list contexts only; synchronous, no way
+ * back; NRG_E_NOT_SYNCED while ltail < tail; replicas of one log, and every member of a group, enable at
+ * the same log index with the same marks; again with the same marks is NRG_OK, with others NRG_E_INVAL.
+ * The two marks must differ from each other and from the tombstone, whichever of removal and pops is
+ * enabled first: NRG_E_INVAL otherwise.
+ *   From here on a record {key = n, val = front_mark} is PopFront x n and {key = n, val = back_mark} is
+ * PopBack x n: pop_front() (pop_back()) called n times, n = 1 being the reference's call. It removes the
+ * n smallest (largest) entries the map has at that log position, or all of them if it has fewer; n = 0
+ * does nothing. Its response in the ordinary resp / some arrays is resp = m, the entries popped
+ * (0 .. n), and some = (m >= 1): for n = 1 that is pop_front()'s Some / None. Only records are
+ * interpreted: values already stored that equal a mark stay ordinary values, nothing is scanned when
+ * pops are enabled, and the nrg_skiplist_prefill* calls, which take pairs and not records, insert a
+ * mark as the value it is. A context that never enables runs exactly the kernels and launches of
+ * before; its {k, mark} records are Pushes.
+ *   A pop is an ordinary 16-byte record: nrg_log_append* / nrg_log_exec*, nrg_skiplist_round_async,
+ * replicated group rounds and nrg_group_resync carry it and answer the counts; the popped entries
+ * themselves are delivered only by the two calls below. Partitioned rounds return NRG_E_INVAL for a
+ * member with pops enabled (the front of a key-partitioned map is a group-wide question), dropped like
+ * a round with any other bad argument; nrg_combiner_open stays NRG_E_INVAL. Snapshot, restore, digest,
+ * dump and every read are unchanged (the two runs stay dense), and an image does not record the setting.
+ *   Cost: a pop depends on every record before it, so a chunk is cut at its pop records: each maximal
+ * run of consecutive pop records is one pop step (one small launch and one 64-byte readback, whatever
+ * the counts and the mix of ends), and the ordinary records between two runs replay as a chunk of
+ * their own. A batch that alternates Push and Pop record by record therefore replays as one segment per
+ * record: correct and slow. Group pops into runs where the order allows it, and prefer one PopFront x n
+ * to n PopFront x 1 in different places (DESIGN.md "Skip list replay", Pops). An enabled context also
+ * pays one small launch and a readback per chunk to find the pop records. */
+int nrg_skiplist_enable_pops(nrg_ctx* ctx, uint64_t front_mark, uint64_t back_mark);
+/* Query, no device touched: *enabled = 1 and the marks once pops are on, else 0, 0 and 0 (any pointer
+ * may be NULL). */
+int nrg_skiplist_pops(nrg_ctx* ctx, uint64_t* front_mark, uint64_t* back_mark, int* enabled);
+/* nrg_skiplist_round_async on a context with pops enabled (NRG_E_INVAL otherwise, or with d_pop_n NULL,
+ * or with pop_cap > 0 and an array NULL), which also hands out the entries the batch's pop records
+ * popped (not those of records the round replays ahead of the batch): packed in record order, each
+ * record's entries in the order popped (front: ascending keys, back: descending), so the offsets are the
+ * exclusive scan of resp over the batch's pop records, the layout nrg_memfs_pread uses for bytes.
+ * *d_pop_n = the total popped; only the first pop_cap entries are stored in d_pop_keys / d_pop_vals and
+ * nothing is written past them: a caller whose pop_cap covers the sum of its records' counts loses
+ * nothing. All pointers are device pointers; the arrays are written on the context's stream. */
+int nrg_skiplist_round_pops_async(nrg_ctx* ctx, const nrg_put* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                                  uint8_t* d_some, uint64_t* d_pop_keys, uint64_t* d_pop_vals, uint64_t pop_cap,
+                                  uint64_t* d_pop_n);
+/* One PopFront x n (back = 0) or PopBack x n record, synchronously, into host arrays: what the log
+ * holds is replayed first, then the record is appended with `origin` and replayed; *m = the entries
+ * popped, keys[0 .. m) / vals[0 .. m) the entries in the order popped. The arrays hold min(n,
+ * nrg_skiplist_len) entries or more. NRG_E_INVAL before nrg_skiplist_enable_pops. */
+int nrg_skiplist_pop(nrg_ctx* ctx, int back, uint64_t n, uint32_t origin, uint64_t* keys, uint64_t* vals, uint64_t* m);
 
 /* ---- file store (kind NRG_DS_MEMFS; benches/memfs.rs) ---------------------------------------
  * NrMemFilesystem (benches/memfs.rs:106-192) behind Dispatch (:194-292) with ReadOperation = (): every

@@ -84,8 +84,10 @@ int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
         nrg_ctx* c = m.ctx;
         int err = NRG_OK;
         const uint32_t kind = c->cfg.ds_kind;
-        // (a skip list with removal: a Remove's response is not the asker's to write, see grp_push_resp_kernel)
-        if ((kind != NRG_DS_HASHMAP && kind != NRG_DS_SKIPLIST) || nrg::sl_removal(c) || (x.n && !x.recs) ||
+        // (a skip list with removal: a Remove's response is not the asker's to write, see grp_push_resp_kernel;
+        // with pops: the front of a key-partitioned map is no member's own)
+        if ((kind != NRG_DS_HASHMAP && kind != NRG_DS_SKIPLIST) || nrg::sl_removal(c) || nrg::sl_pops(c) ||
+            (x.n && !x.recs) ||
             (x.n_gets && (!x.get_keys || !x.get_vals || !x.get_found)))
             err = NRG_E_INVAL;
         else if (x.n >= (1ull << 32) || x.n_gets >= (1ull << 32) || (uint64_t)G * x.n >= (1ull << 32) ||

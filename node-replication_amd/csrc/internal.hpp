@@ -108,7 +108,8 @@ struct VsState {
 // The skip list's device state (skiplist.hip): keys in the base and in the delta run, and the delta
 // count before the chunk being replayed with that chunk's new keys (what its merge reads). With removal
 // enabled (nrg_skiplist_enable_removal) a chunk's scan also leaves the keys the chunk removes from each
-// run: nb and nd_in are then already the counts after the drop passes the host launches next.
+// run: nb and nd_in are then already the counts after the drop passes the host launches next. A pop step
+// (nrg_skiplist_enable_pops) leaves the counts after it the same way, ahead of the host's shifts.
 struct SlState {
     u64 nb, nd;
     u64 nd_in, nnew;
@@ -232,6 +233,19 @@ struct SlHost {  // skip list / ordered map (skiplist.hip): two sorted runs with
     uint32_t* d_kidx = nullptr;   // [max_batch] where a surviving Remove found its key
     uint32_t* d_kcnt = nullptr;   // [2 * tiles] removed base / delta keys per tile, then their offsets
     uint32_t *d_deadb = nullptr, *d_deadd = nullptr;  // [max_batch] the chunk's dead indices of each run, ascending
+    // Pops (nrg_skiplist_enable_pops; off: none of the below exists and no chunk looks at it)
+    bool pops = false;
+    uint64_t front_mark = 0, back_mark = 0;  // a record whose val equals one is PopFront x key / PopBack x key
+    uint32_t* d_pfcnt = nullptr;  // [find tiles] the edges of pop runs in each tile of a chunk's positions
+    uint32_t* d_pfev = nullptr;   // [find tiles * tile] their positions, compacted per tile
+    uint64_t* d_poff = nullptr;   // [max_batch + 1] a pop step's output offsets per record
+    uint64_t* d_prank = nullptr;  // [max_batch] a pop step's first rank per record, from the record's end
+    uint64_t* d_pplan = nullptr;  // a pop step's plan (skiplist.hip SlPop::plan)
+    std::vector<uint32_t> h_pf;   // the host's copy of d_pfcnt, then of the edges read
+    // where the popped entries go, for the duration of one nrg_skiplist_round_pops_async (po_n == nullptr:
+    // nowhere): the entries of pop records at log positions >= po_from, po_total of them so far
+    uint64_t *po_keys = nullptr, *po_vals = nullptr, *po_n = nullptr;
+    uint64_t po_cap = 0, po_from = 0, po_total = 0;
 };
 
 struct MfHost {  // file store (memfs.hip): F files of B = 2^log2_b bytes, contiguous in inode order
@@ -564,6 +578,7 @@ hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 li
                           u32* d_counts);
 bool hm_removal(const nrg_ctx* c);  // hashmap.hip: nrg_hashmap_enable_removal was called (nrg_combiner_open refuses)
 bool sl_removal(const nrg_ctx* c);  // nrg_skiplist_enable_removal was called (group_partitioned.cpp refuses such a member)
+bool sl_pops(const nrg_ctx* c);     // nrg_skiplist_enable_pops was called (refused there too: the front is group-wide)
 // queue.hip
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads (the combiner)
 }  // namespace nrg

@@ -53,12 +53,31 @@
 //   sl_drop_base      only when kb > 0: the base run without its dead indices into the other buffer
 //   sl_drop_delta     only when kd > 0: the same for the delta run, before the merge of the new keys
 //   sl_merge, sl_compact   as before, on exact counts
+//
+// Pops (nrg_skiplist_enable_pops; DESIGN.md "Skip list replay", Pops). On an enabled context a record
+// {n, front_mark} is PopFront x n and {n, back_mark} PopBack x n (SkipMap::pop_front / pop_back n times),
+// answered (m, m >= 1), m the entries popped. The smallest m entries are a prefix of each run and the
+// largest a suffix, split by one merge-path co-rank, so a run of pop records is one step whatever its
+// counts. A pop depends on everything before it, so a chunk there is cut at its pop records:
+//   sl_pop_find       once per chunk, ahead of sl_stream: the edges of the maximal runs of pop records,
+//                     compacted per tile of SL_FIND_PART positions; the host reads the tiles' counts and,
+//                     where one is not zero, the edges. None: the chunk as it is, through the pipeline above.
+//   (else the chunk is replayed as alternating segments: an ordinary stretch is a chunk of its own through
+//   the pipeline above, with or without removal; a run of pop records is one pop step)
+//   sl_pop_plan       one workgroup: the grants of skiplist_pop_plan.hpp, the responses, per record its
+//                     output offset and first rank, the totals and their co-ranks, the counts after the step
+//   (the host reads the plan back: it cannot know otherwise whether a buffer flips)
+//   sl_pop_take       only for nrg_skiplist_round_pops_async: the popped entries, packed in record order,
+//                     the work spread over output positions
+//   sl_pop_shift      only for a run that lost a prefix: the rest of it to the start of its other buffer.
+//                     Back pops alone lower the counts.
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "internal.hpp"
+#include "skiplist_pop_plan.hpp"
 #include "../../include/nrgpu_testing.h"
 
 namespace nrg {
@@ -73,6 +92,9 @@ constexpr int SL_SCAN_TPB = 1024;
 constexpr u32 SL_MAX_GRID = 4096;    // merge workgroups launched at most; the rest by stride
 constexpr u32 SL_DROP_ITEMS = 8;     // inputs per lane of a drop pass
 constexpr u32 SL_DROP_PART = 2048;   // inputs per drop workgroup and turn: SL_TPB * SL_DROP_ITEMS
+constexpr u32 SL_FIND_ITEMS = 8;     // positions per lane of the pop-run search
+constexpr u32 SL_FIND_PART = 2048;   // positions per sl_pop_find workgroup: SL_TPB * SL_FIND_ITEMS
+constexpr u32 SL_TAKE_PART = 2048;   // outputs per sl_pop_take workgroup and turn
 constexpr u32 SL_LOG2_MIN = 4, SL_LOG2_MAX = 28, SL_LOG2_DEFAULT = 24;
 // delta_max unless NRG_KNOB_SL_DELTA_MAX sets it (microbench/skiplist_round.py, DESIGN.md "Skip list replay")
 constexpr u64 SL_DELTA_DEFAULT = 1ull << 22;
@@ -80,6 +102,7 @@ static_assert(SL_MERGE_PART == SL_TPB * SL_MERGE_ITEMS, "a merge workgroup's lan
 static_assert(SL_SORT_TILE == SORT_TILE, "the radix sort's tile, mirrored for the tests' chunk sizes");
 static_assert(SL_RES_TILE == SL_TPB, "resolve and scatter take one record per lane");
 static_assert(SL_DROP_PART == SL_TPB * SL_DROP_ITEMS, "a drop workgroup's lanes cover its partition");
+static_assert(SL_FIND_PART == SL_TPB * SL_FIND_ITEMS, "a find workgroup's lanes cover its partition");
 
 struct SlJob {
     const nrg_put* src;  // the batch of a fused round or a prefill, or nullptr: read from the ring
@@ -501,6 +524,160 @@ __global__ __launch_bounds__(SL_TPB) void sl_merge_kernel(SlMerge m) {
 
 __global__ void sl_set_state_kernel(SlState* st, u64 nb, u64 nd) { *st = SlState{nb, nd, nd, 0}; }
 
+// ---- pops (nrg_skiplist_enable_pops) ---------------------------------------------------------------
+struct SlPop {
+    u64 fm, bm;        // val of a PopFront / PopBack record
+    u64* off;          // [n + 1] entries granted to the records before record i of the run (the output offsets)
+    u64* rank;         // [n] entries granted to the earlier records of record i's own end (F_i or B_i)
+    u64* plan;         // [SL_PLAN_WORDS] {f, b, fb, fd, bb, bd, nb, nd}: totals, co-ranks, the counts before the step
+    u64* pop_n;        // delivery (nrg_skiplist_round_pops_async): *pop_n = pop_base + f + b; or nullptr
+    u64 pop_base;
+};
+constexpr u32 SL_PLAN_WORDS = 8;
+
+// The edges of a chunk's pop runs: the positions x in [0, n] where "record x - 1 is a pop record"
+// and "record x is one" differ (neither holds outside the chunk). In ascending order they alternate
+// between the start of a maximal run and its end, so the host pairs them up. A workgroup takes
+// SL_FIND_PART positions, SL_TPB consecutive ones at a time, and compacts its edges into its own
+// stretch of ev[] by ballot ranks (as sl_drop); cnt[] gets the tile's number. No workgroup needs
+// another's count, nothing is scanned: the host reads cnt[], and ev[] only where it is not all zero.
+__global__ __launch_bounds__(SL_TPB) void sl_pop_find_kernel(SlJob j, u64 fm, u64 bm, u32* __restrict__ cnt,
+                                                             u32* __restrict__ ev) {
+    __shared__ u32 s_cnt[SL_TPB / 64];
+    const u32 t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const u64 x0 = (u64)blockIdx.x * SL_FIND_PART;
+    u32 out = 0;
+    for (u32 it = 0; it < SL_FIND_ITEMS; it++) {
+        const u64 x = x0 + it * SL_TPB + t;
+        bool edge = false;
+        if (x <= j.n) {
+            const u64 va = x > 0 ? sl_load(j, x - 1).val : 0, vb = x < j.n ? sl_load(j, x).val : 0;
+            const bool a = x > 0 && (va == fm || va == bm), b = x < j.n && (vb == fm || vb == bm);
+            edge = a != b;
+        }
+        const u64 bal = __ballot(edge);
+        if (lane == 0) s_cnt[w] = (u32)__popcll(bal);
+        __syncthreads();
+        u32 pos = (u32)__popcll(bal & ((1ull << lane) - 1)), tot = 0;
+        for (u32 q = 0; q < SL_TPB / 64; q++) {
+            const u32 c = s_cnt[q];
+            if (q < w) pos += c;
+            tot += c;
+        }
+        if (edge) ev[x0 + out + pos] = (u32)x;
+        out += tot;
+        __syncthreads();  // the counts are written again
+    }
+    if (t == 0) cnt[blockIdx.x] = out;
+}
+
+// the workgroup's exclusive prefix sums of one value per lane; *total gets their sum
+__device__ __forceinline__ u64 sl_scan_lanes(u64 mine, u64* s_scan, u64* total) {
+    const u32 t = threadIdx.x;
+    s_scan[t] = mine;
+    __syncthreads();
+    for (u32 s = 1; s < SL_SCAN_TPB; s <<= 1) {
+        const u64 o = t >= s ? s_scan[t - s] : 0;
+        __syncthreads();
+        s_scan[t] += o;
+        __syncthreads();
+    }
+    const u64 ex = s_scan[t] - mine;
+    *total = s_scan[SL_SCAN_TPB - 1];
+    __syncthreads();  // s_scan may be filled again
+    return ex;
+}
+
+// One pop step: the chunk j is a run of consecutive pop records (key = the count n_i, val = the end's
+// mark), replayed against the len = nb + nd entries of the state. One workgroup, a contiguous stretch
+// of the run per lane, three walks over it with the grants of skiplist_pop_plan.hpp:
+//   the sum of the clipped counts, scanned: S_i, so off[i] = min(len, S_i) and the grant m_i
+//   the grants to front records, scanned: F_i (and B_i = off[i] - F_i)
+//   off[], rank[], the responses (m_i, m_i >= 1) inside the window, the log copy of a fused round
+// Lane 0 then splits the totals f and b between the runs (sl_split: index bounds, no padding key: the
+// f smallest entries are base[0, fb) and delta[0, fd), the b largest base[nb - bb, nb) and
+// delta[nd - bd, nd)), leaves the plan for sl_pop_take and the host, and stores the counts after the
+// step. The runs themselves are untouched here: the host launches the shifts from the plan.
+__global__ __launch_bounds__(SL_SCAN_TPB) void sl_pop_plan_kernel(SlJob j, SlPop p) {
+    __shared__ u64 s_scan[SL_SCAN_TPB];
+    const u32 t = threadIdx.x;
+    const u64 nb = j.st->nb, nd = j.st->nd, len = nb + nd;
+    const u64 per = (j.n + SL_SCAN_TPB - 1) / SL_SCAN_TPB;
+    const u64 i0 = t * per < j.n ? t * per : j.n, i1 = i0 + per < j.n ? i0 + per : j.n;
+    u64 mine = 0;
+    for (u64 i = i0; i < i1; i++) mine += slp::clip(sl_load(j, i).key, len);  // (< 2^24 * 2^28: no wrap)
+    u64 stot, f;
+    const u64 S = sl_scan_lanes(mine, s_scan, &stot);
+    u64 s = S, fmine = 0;
+    for (u64 i = i0; i < i1; i++) {
+        const nrg_put r = sl_load(j, i);
+        const u64 n = slp::clip(r.key, len);
+        if (r.val == p.fm) fmine += slp::grant(n, len, s);
+        s += n;
+    }
+    u64 F = sl_scan_lanes(fmine, s_scan, &f);
+    s = S;
+    for (u64 i = i0; i < i1; i++) {
+        const nrg_put r = sl_load(j, i);
+        const u64 n = slp::clip(r.key, len), m = slp::grant(n, len, s), o = slp::taken(len, s);
+        const bool front = r.val == p.fm;
+        p.off[i] = o;
+        p.rank[i] = front ? F : o - F;
+        if (front) F += m;
+        s += n;
+        const u64 g = j.lo + i;
+        if (j.wring) j.ring[g & j.ring_mask] = r;  // Log::append of a fused round
+        if (j.resp && g >= j.rlo && g < j.rhi) {
+            j.resp[g - j.rlo] = m;  // entries popped: pop_front() n times, Some while the map had one
+            j.some[g - j.rlo] = m ? 1 : 0;
+        }
+    }
+    if (t == 0) {
+        const u64 all = slp::taken(len, stot), b = all - f;
+        p.off[j.n] = all;
+        const u64 fb = sl_split(j.bk, nb, j.dk, nd, f), fd = f - fb;
+        const u64 bb = nb - sl_split(j.bk, nb, j.dk, nd, len - b), bd = b - bb;
+        p.plan[0] = f, p.plan[1] = b, p.plan[2] = fb, p.plan[3] = fd, p.plan[4] = bb, p.plan[5] = bd;
+        p.plan[6] = nb, p.plan[7] = nd;
+        *j.st = SlState{nb - fb - bb, nd - fd - bd, nd - fd - bd, 0, 0, 0};
+        if (p.pop_n) *p.pop_n = p.pop_base + all;
+    }
+}
+
+// The popped entries of a step, packed: output x in [0, cnt) is entry x - off[i] of the record i with
+// off[i] <= x < off[i + 1], the entry of ascending rank slp::rank_of in the merge of the two runs as they
+// were before the step (the plan's nb, nd; the shifts come later on the stream). The work is spread over
+// output positions, SL_TAKE_PART per workgroup and turn, whatever the records' counts: a tile's records
+// are found once by two searches of off[] (every lane the same: the loads broadcast), a lane's record
+// inside that stretch, its entry by the merge-path split of its rank. Consecutive lanes store
+// consecutive slots. cnt is the host's: the step's total, clipped to the room the caller's arrays have.
+__global__ __launch_bounds__(SL_TPB) void sl_pop_take_kernel(SlJob j, SlPop p, u64* __restrict__ okeys,
+                                                             u64* __restrict__ ovals, u64 cnt) {
+    const u64 nb = p.plan[6], nd = p.plan[7], len = nb + nd;
+    for (u64 part = blockIdx.x; part * SL_TAKE_PART < cnt; part += gridDim.x) {
+        const u64 x0 = part * SL_TAKE_PART, x1 = x0 + SL_TAKE_PART < cnt ? x0 + SL_TAKE_PART : cnt;
+        const u64 r0 = sl_upper(p.off, j.n, x0) - 1, r1 = sl_upper(p.off, j.n, x1 - 1) - 1;  // (off[0] = 0 <= x)
+        for (u64 x = x0 + threadIdx.x; x < x1; x += SL_TPB) {
+            const u64 i = r0 + sl_upper(p.off + r0, r1 - r0 + 1, x) - 1;
+            const bool back = sl_load(j, i).val == p.bm;
+            const u64 q = slp::rank_of(back, len, p.rank[i], x - p.off[i]);
+            const u64 ia = sl_split(j.bk, nb, j.dk, nd, q), id = q - ia;  // (ia < nb or id < nd: q < len)
+            const bool ta = id >= nd || (ia < nb && j.bk[ia] < j.dk[id]);
+            okeys[x] = ta ? j.bk[ia] : j.dk[id];
+            ovals[x] = ta ? j.bv[ia] : j.dv[id];
+        }
+    }
+}
+
+// what a front pop leaves of a run, in[from, from + n), to the start of the run's other buffer
+__global__ __launch_bounds__(SL_TPB) void sl_pop_shift_kernel(const u64* __restrict__ ik, const u64* __restrict__ iv,
+                                                              u64 from, u64 n, u64* __restrict__ ok, u64* __restrict__ ov) {
+    for (u64 i = (u64)blockIdx.x * SL_TPB + threadIdx.x; i < n; i += (u64)gridDim.x * SL_TPB) {
+        ok[i] = ik[from + i];
+        ov[i] = iv[from + i];
+    }
+}
+
 // ---- reads: one lane per query, a binary search per run --------------------------------------------
 __global__ __launch_bounds__(SL_TPB) void sl_get_kernel(const u64* bk, const u64* bv, const u64* dk, const u64* dv,
                                                         const SlState* st, const u64* keys, u64 n, u64* vals,
@@ -816,9 +993,149 @@ static hipError_t sl_chunk(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u
     return hipSuccess;
 }
 
+// ---- pops: a chunk cut at its pop runs ---------------------------------------------------------------
+// what the pop kernels read of a job: the records, the window, the state and the current runs
+static SlJob sl_pop_job(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
+                        uint8_t* d_some) {
+    SlHost& s = c->sl;
+    SlJob j{};
+    j.src = src;
+    j.ring = (nrg_put*)c->d_ring;
+    j.ring_mask = c->log_size - 1;
+    j.wring = wring ? 1 : 0;
+    j.lo = lo;
+    j.n = n;
+    const bool want = d_resp != nullptr && d_some != nullptr && resp_lo < resp_hi && resp_lo < lo + n && resp_hi > lo;
+    j.rlo = want ? resp_lo : 0;
+    j.rhi = want ? resp_hi : 0;
+    j.resp = want ? (u64*)d_resp : nullptr;
+    j.some = want ? d_some : nullptr;
+    j.st = s.d_state;
+    j.ctl = c->d_ctl;
+    j.bk = s.d_bk[s.bcur], j.bv = s.d_bv[s.bcur];
+    j.dk = s.d_dk[s.dcur], j.dv = s.d_dv[s.dcur];
+    j.cap = s.cap;
+    j.dcap = s.dcap;
+    return j;
+}
+
+// The chunk's pop runs into s.h_pf as ascending edges (start, end, start, end, ...), *ne their number.
+// The records live on the device: one launch, and a readback of the tiles' counts (4 bytes per
+// SL_FIND_PART records); the edges themselves are read only where a count is not zero.
+static hipError_t sl_pop_find(nrg_ctx* c, const nrg_put* src, u64 lo, u64 n, size_t* ne) {
+    SlHost& s = c->sl;
+    hipError_t e;
+    const SlJob j = sl_pop_job(c, src, false, lo, n, 0, 0, nullptr, nullptr);
+    const u32 tiles = (u32)((n + 1 + SL_FIND_PART - 1) / SL_FIND_PART);
+    NRG_LAUNCH(c, "sl_pop_find", sl_pop_find_kernel, tiles, SL_TPB, 0, c->stream, j, s.front_mark, s.back_mark, s.d_pfcnt,
+               s.d_pfev);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    std::vector<u32>& h = s.h_pf;
+    h.resize(tiles);
+    if ((e = hipMemcpyAsync(h.data(), s.d_pfcnt, tiles * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+    u64 total = 0;
+    u32 t0 = tiles, t1 = 0;
+    for (u32 t = 0; t < tiles; t++) {
+        if (h[t] > SL_FIND_PART) return hipErrorUnknown;  // (never)
+        if (h[t]) t0 = t < t0 ? t : t0, t1 = t + 1;
+        total += h[t];
+    }
+    *ne = (size_t)total;
+    if (total == 0) return hipSuccess;
+    if (total & 1) return hipErrorUnknown;  // (never: the flag is 0 at both ends)
+    // the tiles [t0, t1) in one copy behind the counts, then compacted to the front
+    h.resize(tiles + (size_t)(t1 - t0) * SL_FIND_PART);
+    if ((e = hipMemcpyAsync(h.data() + tiles, s.d_pfev + (size_t)t0 * SL_FIND_PART, (size_t)(t1 - t0) * SL_FIND_PART * 4,
+                            hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+        return e;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+    std::vector<u32> edges;
+    edges.reserve(total);
+    for (u32 t = t0; t < t1; t++) {
+        const u32* ev = h.data() + tiles + (size_t)(t - t0) * SL_FIND_PART;
+        edges.insert(edges.end(), ev, ev + h[t]);
+    }
+    for (size_t i = 0; i < edges.size(); i++)
+        if (edges[i] > n || (i && edges[i] <= edges[i - 1])) return hipErrorUnknown;  // (never)
+    h.swap(edges);
+    return hipSuccess;
+}
+
+static unsigned sl_part_grid(u64 n, u64 part) {
+    const u64 g = (n + part - 1) / part;
+    return g < 1 ? 1u : (g > SL_MAX_GRID ? SL_MAX_GRID : (unsigned)g);
+}
+
+// One pop step: the n records at [lo, lo + n) are a run of pop records. The plan, its readback (64 bytes
+// and a synchronise: whether a buffer flips is known only from it), the entries if a caller asked for
+// them, and a shift per run that lost a prefix. Back pops alone copy nothing. After it the host knows nb
+// and nd exactly and its bounds are the counts.
+static hipError_t sl_pop_step(nrg_ctx* c, const nrg_put* src, bool wring, u64 lo, u64 n, u64 resp_lo, u64 resp_hi,
+                              void* d_resp, uint8_t* d_some) {
+    SlHost& s = c->sl;
+    hipError_t e;
+    const SlJob j = sl_pop_job(c, src, wring, lo, n, resp_lo, resp_hi, d_resp, d_some);
+    SlPop p{s.front_mark, s.back_mark, s.d_poff, s.d_prank, s.d_pplan, nullptr, 0};
+    const bool deliver = s.po_n != nullptr && lo >= s.po_from;
+    if (deliver) p.pop_n = s.po_n, p.pop_base = s.po_total;
+    NRG_LAUNCH(c, "sl_pop_plan", sl_pop_plan_kernel, 1, SL_SCAN_TPB, 0, c->stream, j, p);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    u64 pl[SL_PLAN_WORDS];
+    if ((e = hipMemcpyAsync(pl, s.d_pplan, sizeof pl, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+    const u64 f = pl[0], b = pl[1], fb = pl[2], fd = pl[3], bb = pl[4], bd = pl[5], nb = pl[6], nd = pl[7];
+    if (nb > s.cap || nd > s.dcap || fb + bb > nb || fd + bd > nd || fb + fd != f || bb + bd != b) return hipErrorUnknown;  // (never)
+    if (deliver) {
+        const u64 room = s.po_total < s.po_cap ? s.po_cap - s.po_total : 0, cnt = f + b < room ? f + b : room;
+        if (cnt)
+            NRG_LAUNCH(c, "sl_pop_take", sl_pop_take_kernel, sl_part_grid(cnt, SL_TAKE_PART), SL_TPB, 0, c->stream, j, p,
+                       s.po_keys + s.po_total, s.po_vals + s.po_total, cnt);
+        s.po_total += f + b;
+    }
+    if (fb) {
+        NRG_LAUNCH(c, "sl_pop_shift", sl_pop_shift_kernel, sl_part_grid(nb - fb - bb, SL_MERGE_PART), SL_TPB, 0, c->stream,
+                   (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], fb, nb - fb - bb, s.d_bk[s.bcur ^ 1],
+                   s.d_bv[s.bcur ^ 1]);
+        s.bcur ^= 1;
+    }
+    if (fd) {
+        NRG_LAUNCH(c, "sl_pop_shift", sl_pop_shift_kernel, sl_part_grid(nd - fd - bd, SL_MERGE_PART), SL_TPB, 0, c->stream,
+                   (const u64*)s.d_dk[s.dcur], (const u64*)s.d_dv[s.dcur], fd, nd - fd - bd, s.d_dk[s.dcur ^ 1],
+                   s.d_dv[s.dcur ^ 1]);
+        s.dcur ^= 1;
+    }
+    s.nd_ub = nd - fd - bd;
+    if (c->growth.max_items) c->growth.len_ub = nb + nd - f - b;
+    return hipGetLastError();
+}
+
+// DsOps::replay. A context without pops: the chunk as it is. With pops the chunk is cut at its pop runs,
+// which depend on everything before them: the ordinary stretches between them go through the pipeline
+// as chunks of their own (their window, their ring copy), each run is one pop step. A chunk that
+// alternates Push and Pop record by record is one segment per record: correct and slow.
 static hipError_t sl_replay_chunk(nrg_ctx* c, const void* src, u64 lo, u64 n, u64 resp_lo, u64 resp_hi, void* d_resp,
                                   uint8_t* d_some) {
-    return sl_chunk(c, (const nrg_put*)src, src != nullptr, lo, n, resp_lo, resp_hi, d_resp, d_some);
+    const nrg_put* recs = (const nrg_put*)src;
+    const bool wring = src != nullptr;
+    if (!c->sl.pops || n == 0) return sl_chunk(c, recs, wring, lo, n, resp_lo, resp_hi, d_resp, d_some);
+    hipError_t e;
+    size_t ne = 0;
+    if ((e = sl_pop_find(c, recs, lo, n, &ne)) != hipSuccess) return e;
+    if (ne == 0) return sl_chunk(c, recs, wring, lo, n, resp_lo, resp_hi, d_resp, d_some);
+    const std::vector<u32> edges(c->sl.h_pf.begin(), c->sl.h_pf.begin() + ne);
+    u64 at = 0;
+    for (size_t k = 0; k < ne; k += 2) {
+        const u64 a = edges[k], b = edges[k + 1];
+        if (a > at && (e = sl_chunk(c, recs ? recs + at : nullptr, wring, lo + at, a - at, resp_lo, resp_hi, d_resp,
+                                    d_some)) != hipSuccess)
+            return e;
+        if ((e = sl_pop_step(c, recs ? recs + a : nullptr, wring, lo + a, b - a, resp_lo, resp_hi, d_resp, d_some)) != hipSuccess)
+            return e;
+        at = b;
+    }
+    if (at < n) return sl_chunk(c, recs ? recs + at : nullptr, wring, lo + at, n - at, resp_lo, resp_hi, d_resp, d_some);
+    return hipSuccess;
 }
 
 static void sl_free_delta(SlHost& s) {
@@ -859,7 +1176,8 @@ static void sl_close(nrg_ctx* c) {
     sl_free_pair(s.d_bv);
     sl_free_delta(s);
     void* ptrs[] = {s.d_state, s.d_sk,   s.d_nk,   s.d_nv,   s.d_sp,    s.d_k32,  s.d_pv,
-                    s.d_miss,  s.d_tcnt, s.d_kidx, s.d_kcnt, s.d_deadb, s.d_deadd};
+                    s.d_miss,  s.d_tcnt, s.d_kidx, s.d_kcnt, s.d_deadb, s.d_deadd,
+                    s.d_pfcnt, s.d_pfev, s.d_poff, s.d_prank, s.d_pplan};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
 }
@@ -976,6 +1294,30 @@ static int sl_enable_removal(nrg_ctx* c, u64 tombstone) {
     if (!s.d_kcnt) HIPCHK(hipMalloc(&s.d_kcnt, 2 * tiles * 4));
     s.tombstone = tombstone;
     s.removal = true;
+    return NRG_OK;
+}
+
+bool sl_pops(const nrg_ctx* c) { return c->cfg.ds_kind == NRG_DS_SKIPLIST && c->sl.pops; }
+
+// nrg_skiplist_enable_pops on a drained stream: the scratch of the pop-run search and of a pop step
+// (sl_close frees it, also after a failure half way: the flag is set last)
+static int sl_enable_pops(nrg_ctx* c, u64 front_mark, u64 back_mark) {
+    SlHost& s = c->sl;
+    const u64 mb = c->cfg.max_batch ? c->cfg.max_batch : 1;
+    const u64 tiles = (mb + 1 + SL_FIND_PART - 1) / SL_FIND_PART;
+    if (!s.d_pfcnt) HIPCHK(hipMalloc(&s.d_pfcnt, tiles * 4));
+    if (!s.d_pfev) HIPCHK(hipMalloc(&s.d_pfev, tiles * SL_FIND_PART * 4));
+    if (!s.d_poff) HIPCHK(hipMalloc(&s.d_poff, (mb + 1) * 8));
+    if (!s.d_prank) HIPCHK(hipMalloc(&s.d_prank, mb * 8));
+    if (!s.d_pplan) HIPCHK(hipMalloc(&s.d_pplan, SL_PLAN_WORDS * 8));
+    try {
+        s.h_pf.reserve(tiles);
+    } catch (const std::bad_alloc&) {
+        return NRG_E_NOMEM;
+    }
+    s.front_mark = front_mark;
+    s.back_mark = back_mark;
+    s.pops = true;
     return NRG_OK;
 }
 
@@ -1335,6 +1677,7 @@ int nrg_skiplist_enable_removal(nrg_ctx* c, uint64_t tombstone) {
     int r = need(c, NRG_DS_SKIPLIST);
     if (r) return r;
     if (c->sl.removal) return tombstone == c->sl.tombstone ? NRG_OK : NRG_E_INVAL;
+    if (c->sl.pops && (tombstone == c->sl.front_mark || tombstone == c->sl.back_mark)) return NRG_E_INVAL;
     if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
     HIPCHK(sync_all(c));
     return sl_enable_removal(c, tombstone);
@@ -1345,6 +1688,76 @@ int nrg_skiplist_removal(nrg_ctx* c, uint64_t* tombstone, int* enabled) {  // no
     if (tombstone) *tombstone = c->sl.removal ? c->sl.tombstone : 0;
     if (enabled) *enabled = c->sl.removal ? 1 : 0;
     return NRG_OK;
+}
+
+int nrg_skiplist_enable_pops(nrg_ctx* c, uint64_t front_mark, uint64_t back_mark) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    SlHost& s = c->sl;
+    if (s.pops) return front_mark == s.front_mark && back_mark == s.back_mark ? NRG_OK : NRG_E_INVAL;
+    if (front_mark == back_mark || (s.removal && (front_mark == s.tombstone || back_mark == s.tombstone))) return NRG_E_INVAL;
+    if (c->ltail != c->tail) return NRG_E_NOT_SYNCED;
+    HIPCHK(sync_all(c));
+    return sl_enable_pops(c, front_mark, back_mark);
+}
+
+int nrg_skiplist_pops(nrg_ctx* c, uint64_t* front_mark, uint64_t* back_mark, int* enabled) {  // no device is touched
+    if (!c || c->cfg.ds_kind != NRG_DS_SKIPLIST) return NRG_E_INVAL;
+    if (front_mark) *front_mark = c->sl.pops ? c->sl.front_mark : 0;
+    if (back_mark) *back_mark = c->sl.pops ? c->sl.back_mark : 0;
+    if (enabled) *enabled = c->sl.pops ? 1 : 0;
+    return NRG_OK;
+}
+
+int nrg_skiplist_round_pops_async(nrg_ctx* c, const nrg_put* d_ops, uint64_t n, uint32_t origin, uint64_t* d_resp,
+                                  uint8_t* d_some, uint64_t* d_pop_keys, uint64_t* d_pop_vals, uint64_t pop_cap,
+                                  uint64_t* d_pop_n) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    SlHost& s = c->sl;
+    if (!s.pops || !d_pop_n || (pop_cap && (!d_pop_keys || !d_pop_vals))) return NRG_E_INVAL;
+    if (n > c->cfg.max_batch) return NRG_E_CAPACITY;  // (before anything is queued)
+    HIPCHK(hipMemsetAsync(d_pop_n, 0, sizeof(uint64_t), c->stream));
+    // the batch goes to the log's tail: what the round replays ahead of it (others' records) delivers nothing
+    s.po_keys = d_pop_keys, s.po_vals = d_pop_vals, s.po_n = d_pop_n;
+    s.po_cap = pop_cap, s.po_from = c->tail, s.po_total = 0;
+    r = round_common(c, NRG_DS_SKIPLIST, d_ops, n, origin, d_resp, d_some);
+    s.po_keys = s.po_vals = s.po_n = nullptr;
+    return r;
+}
+
+int nrg_skiplist_pop(nrg_ctx* c, int back, uint64_t n, uint32_t origin, uint64_t* keys, uint64_t* vals, uint64_t* m) {
+    int r = need(c, NRG_DS_SKIPLIST);
+    if (r) return r;
+    SlHost& s = c->sl;
+    if (!s.pops || !m) return NRG_E_INVAL;
+    // what the log holds is replayed first: the record can pop no more than the map then has
+    if ((r = exec_range(c, 0, 0, nullptr, nullptr))) return r;
+    SlState st{};
+    HIPCHK(sl_read_state(c, &st));
+    const uint64_t cap = n < st.nb + st.nd ? n : st.nb + st.nd;
+    if (cap && (!keys || !vals)) return NRG_E_INVAL;
+    Staging* g = c->stg;
+    if ((r = staging(g[0], 64)) || (r = staging(g[1], cap * 8)) || (r = staging(g[2], cap * 8))) return r;
+    // the record, its response and some byte, and the entries' number in one slot
+    char* d = (char*)g[0].p;
+    const nrg_put rec{n, back ? s.back_mark : s.front_mark};
+    HIPCHK(hipMemcpyAsync(d, &rec, sizeof rec, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // (rec leaves the stack)
+    if ((r = nrg_skiplist_round_pops_async(c, (const nrg_put*)d, 1, origin, (u64*)(d + 16), (uint8_t*)(d + 24), (u64*)g[1].p,
+                                           (u64*)g[2].p, cap, (u64*)(d + 32))))
+        return r;
+    uint64_t got = 0;
+    HIPCHK(hipMemcpyAsync(&got, d + 32, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(sync_all(c));
+    if (got > cap) return NRG_E_HIP;  // (never: a record pops at most min(n, len))
+    if (got) {
+        HIPCHK(hipMemcpyAsync(keys, g[1].p, got * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(vals, g[2].p, got * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(sync_all(c));
+    }
+    *m = got;
+    return check_err(c);
 }
 
 int nrg_skiplist_reserve(nrg_ctx* c, uint64_t n_keys) { return reserve_common(c, NRG_DS_SKIPLIST, n_keys); }

@@ -51,6 +51,8 @@ from .replica import (
     SkipList,
     SlPush,
     SlRemove,
+    SlPopFront,
+    SlPopBack,
     Stack,
     VSpace,
     WriteOnly,
@@ -65,7 +67,7 @@ __all__ = [
     "AbstractDataStructure", "DeviceReplica", "Get", "Len", "Log", "NrHashMap", "Peek", "Pop", "Push", "Put", "Queue",
     "ReadOnly", "ReadWrite", "Remove", "Replica", "ReplicaToken", "Stack", "WriteOnly",
     "VSPACE_LEAF_DTYPE", "VSPACE_OP_DTYPE", "VSPACE_RESP_DTYPE", "Identify", "Map", "MapDevice", "VSpace",
-    "Scan", "Seek", "SkipList", "SlPush", "SlRemove",
+    "Scan", "Seek", "SkipList", "SlPush", "SlRemove", "SlPopFront", "SlPopBack",
     "MEMFS_OP_DTYPE", "MEMFS_RD_DTYPE", "MEMFS_RESP_DTYPE", "MemFs", "MfGetAttr", "MfPread", "MfRead", "MfSetAttr", "MfWrite",
     "MEMFS_WR_DTYPE", "MfPwrite", "memfs_pwrite_plan", "memfs_wr",
     "MfPreadLogged", "memfs_pread_logged_plan", "memfs_rd",

@@ -291,6 +291,10 @@ SIGNATURES = {
     "nrg_skiplist_capacity": (C.c_int, [vp, u64p]),
     "nrg_skiplist_enable_removal": (C.c_int, [vp, u64]),
     "nrg_skiplist_removal": (C.c_int, [vp, u64p, C.POINTER(C.c_int)]),
+    "nrg_skiplist_enable_pops": (C.c_int, [vp, u64, u64]),
+    "nrg_skiplist_pops": (C.c_int, [vp, u64p, u64p, C.POINTER(C.c_int)]),
+    "nrg_skiplist_round_pops_async": (C.c_int, [vp, vp, u64, u32, vp, vp, vp, vp, u64, vp]),
+    "nrg_skiplist_pop": (C.c_int, [vp, C.c_int, u64, u32, vp, vp, u64p]),
     "nrg_memfs_round_async": (C.c_int, [vp, vp, u64, u32, vp, vp]),
     "nrg_memfs_init": (C.c_int, [vp, u64, vp, u64]),
     "nrg_memfs_read": (C.c_int, [vp, u64, u64, u64, vp, u64p]),

@@ -26,6 +26,8 @@ from . import _lib as L
 from . import snapshot as _snapshot
 
 PUT_DTYPE = np.dtype([("key", "<u8"), ("val", "<u8")])
+# DeviceReplica.sl_enable_pops' default marks (the default tombstone is 2^64 - 1)
+SL_FRONT_MARK, SL_BACK_MARK = 2**64 - 2, 2**64 - 3
 STACK_OP_DTYPE = np.dtype([("val", "<u4"), ("op", "<u4")])
 QUEUE_OP_DTYPE = np.dtype([("val", "<u8"), ("op", "<u8")])
 SYNTH_OP_DTYPE = np.dtype([("tid", "<u8"), ("r1", "<u8"), ("r2", "<u8"), ("op", "<u8")])
@@ -840,6 +842,47 @@ class DeviceReplica:
         first = self.log_append(recs, origin)
         return self.log_exec(first, first + len(recs))
 
+    def sl_enable_pops(self, front_mark: int = SL_FRONT_MARK, back_mark: int = SL_BACK_MARK):
+        """From here on a record {n, front_mark} is PopFront x n and {n, back_mark} is PopBack x n
+        (nrg_skiplist_enable_pops). Idempotent for one pair of marks; there is no way back. Every replica
+        of a log enables it at the same log index."""
+        L.check(self._lib.nrg_skiplist_enable_pops(self._h, front_mark, back_mark), "skiplist_enable_pops")
+
+    def sl_pops(self):
+        """(front_mark, back_mark), or None while pops are off (nrg_skiplist_pops)."""
+        f, b, on = C.c_uint64(), C.c_uint64(), C.c_int()
+        L.check(self._lib.nrg_skiplist_pops(self._h, C.byref(f), C.byref(b), C.byref(on)), "skiplist_pops")
+        return (f.value, b.value) if on.value else None
+
+    def _sl_pop(self, back: int, n: int, origin: int):
+        if self.sl_pops() is None:
+            raise L.NrgError(L.NRG_E_INVAL, "sl_pop: pops are not enabled (sl_enable_pops)")
+        self.log_exec()  # the length the record will see
+        room = min(n, self.sl_len())
+        k, v = np.zeros(max(room, 1), np.uint64), np.zeros(max(room, 1), np.uint64)
+        m = C.c_uint64()
+        L.check(self._lib.nrg_skiplist_pop(self._h, back, n, origin, _ptr(k), _ptr(v), C.byref(m)), "skiplist_pop")
+        return k[: m.value], v[: m.value]
+
+    def sl_pop_front(self, n: int = 1, origin: int = 1):
+        """SkipMap::pop_front n times as one log record: (keys, vals) of the entries popped, ascending;
+        fewer than n where the map is shorter (nrg_skiplist_pop)."""
+        return self._sl_pop(0, n, origin)
+
+    def sl_pop_back(self, n: int = 1, origin: int = 1):
+        """SkipMap::pop_back n times as one log record: (keys, vals) of the entries popped, descending."""
+        return self._sl_pop(1, n, origin)
+
+    @_stream_ordered
+    def sl_round_pops_device(self, d_ops, n: int, origin: int, d_resp, d_some, d_pop_keys, d_pop_vals, pop_cap: int,
+                             d_pop_n):
+        """sl_round_device on a replica with pops enabled, which also packs the entries its pop records
+        popped into d_pop_keys / d_pop_vals (the first pop_cap) and their number into d_pop_n
+        (nrg_skiplist_round_pops_async)."""
+        L.check(self._lib.nrg_skiplist_round_pops_async(self._h, _dptr(d_ops), n, origin, _dptr(d_resp), _dptr(d_some),
+                                                        _dptr(d_pop_keys), _dptr(d_pop_vals), pop_cap, _dptr(d_pop_n)),
+                "skiplist_round_pops")
+
     # -- file store ----------------------------------------------------------------
     def mf_geometry(self):
         """(F, B): the number of files and a file's bytes (nrg_memfs_geometry)."""
@@ -1231,6 +1274,34 @@ class SlRemove:  # SkipMap::remove(key): a record {key, tombstone}; the replicas
 
 
 @dataclass(frozen=True)
+class SlPopFront:  # SkipMap::pop_front n times: a record {n, front_mark}; the replicas called sl_enable_pops
+    n: int = 1
+    mark: int = SL_FRONT_MARK  # checked against the replica's (SkipList.check_ops): a mismatch is an error
+
+    @property
+    def key(self) -> int:
+        return self.n
+
+    @property
+    def val(self) -> int:
+        return self.mark
+
+
+@dataclass(frozen=True)
+class SlPopBack:  # SkipMap::pop_back n times: a record {n, back_mark}
+    n: int = 1
+    mark: int = SL_BACK_MARK
+
+    @property
+    def key(self) -> int:
+        return self.n
+
+    @property
+    def val(self) -> int:
+        return self.mark
+
+
+@dataclass(frozen=True)
 class Seek:  # SkipMap::lower_bound / upper_bound; mode: L.NRG_SEEK_GE / GT / LE / LT
     key: int
     mode: int
@@ -1454,17 +1525,40 @@ class SkipList:
     """SkipListWrapper (benches/lockfree_partitioned.rs:86-118): an ordered map u64 -> u64. SlPush ->
     the key (Ok(Some(key))); Get -> the value or None; Seek -> (key, value) or None; Scan -> a list of
     (key, value) in the scan's order. SlRemove -> the previous value or None, once every replica of the
-    log has called its DeviceReplica.sl_enable_removal(); before, its record is a Push of the tombstone."""
+    log has called its DeviceReplica.sl_enable_removal(); before, its record is a Push of the tombstone.
+    SlPopFront(n) / SlPopBack(n) -> the number of entries popped, or None where the map was empty, once
+    every replica of the log has called its DeviceReplica.sl_enable_pops() (the entries themselves:
+    DeviceReplica.sl_pop_front / sl_pop_back)."""
 
     kind = L.NRG_DS_SKIPLIST
     rec_dtype = PUT_DTYPE
 
     @staticmethod
     def clone_prepare(dev: DeviceReplica, peer: DeviceReplica):
-        """Before `dev` is restored from `peer`'s image: an image does not carry the removal setting."""
+        """Before `dev` is restored from `peer`'s image: an image carries neither the removal nor the
+        pops setting."""
         tomb = peer.sl_removal()
         if tomb is not None:
             dev.sl_enable_removal(tomb)
+        marks = peer.sl_pops()
+        if marks is not None:
+            dev.sl_enable_pops(*marks)
+
+    @staticmethod
+    def check_ops(dev: DeviceReplica, ops):
+        """Before a batch is enqueued: what a record means depends on the replica's marks alone, so a pop
+        built for other marks (or for a replica without pops) would silently be a Push, and a Push of a
+        mark silently a pop. Both are refused here."""
+        marks = dev.sl_pops()  # (touches no device)
+        for o in ops:
+            if isinstance(o, (SlPopFront, SlPopBack)):
+                if marks is None:
+                    raise L.NrgError(L.NRG_E_INVAL, "pop: pops are not enabled on this replica (sl_enable_pops)")
+                mine = marks[1] if isinstance(o, SlPopBack) else marks[0]
+                if o.mark != mine:
+                    raise ValueError(f"{type(o).__name__}(mark={o.mark:#x}) on a replica whose mark is {mine:#x}")
+            elif marks is not None and isinstance(o, SlPush) and o.val in marks:
+                raise ValueError(f"Push of the value {o.val:#x}, which is a pop mark of this replica (it would be a pop)")
 
     @staticmethod
     def encode(ops) -> np.ndarray:
