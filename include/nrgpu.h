@@ -766,8 +766,10 @@ int nrg_vspace_dump(nrg_ctx* ctx, nrg_vspace_leaf* leaves, uint64_t cap, uint64_
  * nrg_skiplist_prefill_partition and the group-wide ordered reads nrg_group_skiplist_seek /
  * nrg_group_skiplist_range_count / nrg_group_skiplist_scan (the cnr section below). Out of scope: there is no combiner
  * (nrg_combiner_open returns NRG_E_INVAL, as for the page table), and neither removal of keys nor
- * pop_front / pop_back in partitioned rounds (nrg_skiplist_enable_removal and nrg_skiplist_enable_pops
- * below: replicated groups and single replicas only). Every call below returns NRG_E_INVAL on a context
+ * pop_front / pop_back in partitioned rounds unless the group agreed on it (nrg_skiplist_enable_removal
+ * and nrg_skiplist_enable_pops below serve replicated groups and single replicas; a partitioned group
+ * opts in as a whole with nrg_group_skiplist_enable_removal / nrg_group_skiplist_enable_pops and pops
+ * with nrg_group_skiplist_pop, the cnr section below). Every call below returns NRG_E_INVAL on a context
  * of another kind. */
 /* Replica::combine for one batch of Push(k, v) records (nr/src/replica.rs:544-595): Log::append of the
  * n records in d_ops (device) with `origin`, then Log::exec, with the log copy written by the
@@ -865,9 +867,11 @@ int nrg_skiplist_capacity(nrg_ctx* ctx, uint64_t* n_keys);
  * the ring's wrap and GC, nrg_group_round_async and nrg_group_resync carry it unchanged. The
  * nrg_skiplist_prefill* calls run the same pipeline: on an enabled context a prefilled record whose
  * value is the tombstone is a Remove too. Partitioned rounds (nrg_group_partitioned_round*) return
- * NRG_E_INVAL when a member has removal enabled (a partitioned Push response is written by the asker
- * from its own records, which is wrong for a Remove): the round is dropped like one with any other
- * bad argument, nothing of it is written and no log moves; nrg_combiner_open stays NRG_E_INVAL.
+ * NRG_E_INVAL when a member has removal enabled, unless the group agreed on it
+ * (nrg_group_skiplist_enable_removal: a partitioned Push response is written by the asker from its own
+ * records, which is wrong for a Remove; on such a group the owners answer): the round is dropped like
+ * one with any other bad argument, nothing of it is written and no log moves; nrg_combiner_open stays
+ * NRG_E_INVAL.
  *   Capacity: a chunk's new keys are admitted against the key count BEFORE the chunk's own removals
  * (a full map replaying Remove(a), Push(new b) in one chunk latches NRG_E_CAPACITY); the room a chunk
  * frees is there for the next chunk. The host's bounds (growth, compaction) stay upper bounds: on an
@@ -899,7 +903,8 @@ int nrg_skiplist_removal(nrg_ctx* ctx, uint64_t* tombstone, int* enabled);
  *   A pop is an ordinary 16-byte record: nrg_log_append* / nrg_log_exec*, nrg_skiplist_round_async,
  * replicated group rounds and nrg_group_resync carry it and answer the counts; the popped entries
  * themselves are delivered only by the two calls below. Partitioned rounds return NRG_E_INVAL for a
- * member with pops enabled (the front of a key-partitioned map is a group-wide question), dropped like
+ * member with pops enabled, unless the group agreed on it (nrg_group_skiplist_enable_pops; the front of
+ * a key-partitioned map is a group-wide question: nrg_group_skiplist_pop), dropped like
  * a round with any other bad argument; nrg_combiner_open stays NRG_E_INVAL. Snapshot, restore, digest,
  * dump and every read are unchanged (the two runs stay dense), and an image does not record the setting.
  *   Cost: a pop depends on every record before it, so a chunk is cut at its pop records: each maximal
@@ -1532,6 +1537,100 @@ typedef struct {
     uint32_t* counts;
 } nrg_scan;
 int nrg_group_skiplist_scan(nrg_group* g, const nrg_scan* scans, uint32_t mode, uint32_t limit);
+
+/* Removal and pops in a partitioned skip-list group. A member that enabled either on its own context
+ * makes a partitioned round return NRG_E_INVAL (above); a GROUP opts in as a whole, through a collective
+ * in which every rank passes the same values, so that no round can find two owners reading {k, v}
+ * differently. Both calls are collectives shaped like nrg_group_verify: every rank calls them; they
+ * first complete queued group work as nrg_group_sync does (a posted partitioned round included; an
+ * error of that work counts as the rank's local error below); every rank's values and local status are
+ * exchanged (8-byte words, read back under the group's deadline) and every rank derives the same code
+ * BEFORE anything is enabled anywhere: the first local error in rank order, else NRG_E_INVAL where the
+ * ranks' values differ. Local errors: NRG_E_INVAL for a member that is no skip list, a member already
+ * enabled with other values, values other than the group's earlier agreement, marks equal to each other
+ * or to the tombstone (the member's or the group's); NRG_E_NOT_SYNCED for a member with ltail < tail. On
+ * NRG_OK every local member is enabled (nrg_skiplist_enable_removal / nrg_skiplist_enable_pops; one
+ * already enabled with the same values is fine) and the group records the agreement. Again with the same
+ * values: NRG_OK; with others: NRG_E_INVAL. There is no way back. A group that never calls them behaves
+ * as before in every respect and launches the same kernels, the refusals above included.
+ *   Removal: from here on a record whose val == tombstone is Remove(key) in partitioned rounds (both
+ * forms, the one-rank identity included). It is routed by its key like a Push, so it reaches the key's
+ * owner; the owner replays the slices it received in rank order and, where some rank passed resp / some,
+ * answers EVERY received record (Push: (key, 1); Remove: (previous value, 1) or (0, 0), as
+ * nrg_skiplist_round_async answers); the responses travel back to the askers as a hashmap group's
+ * previous values do and arrive in issue order. They are bit for bit what one replica holding the whole
+ * map answers when it replays the round's records in rank order, then issue order; the round's Gets are
+ * answered against the post-round state. The asker-side Push response launch is not used on such a
+ * group. Costs beyond a plain skip-list round: the response traffic, and what removal costs a replay
+ * (nrg_skiplist_enable_removal: a count readback per chunk).
+ *   Pops: a record whose val is a mark would be routed by the hash of its count and pop one partition's
+ * front, so on a group that agreed on pops a partitioned round that holds a mark record on ANY rank is
+ * refused on EVERY rank with NRG_E_INVAL, like a round with any other bad argument: before any payload
+ * moves, no response written, no log moved, the group usable. The marks are found on the device in the
+ * post step (one small pass over the member's records, launched only on such a group) and folded into
+ * the round's exchanged error word. A pops group pays for it: the one-rank identity form, which
+ * otherwise never waits for its post step, reads that flag on the host before it replays. Rounds without
+ * mark records run as before, so Push rounds and nrg_group_skiplist_pop alternate freely. */
+int nrg_group_skiplist_enable_removal(nrg_group* g, uint64_t tombstone);
+int nrg_group_skiplist_enable_pops(nrg_group* g, uint64_t front_mark, uint64_t back_mark);
+/* The group-wide pop: "the n smallest entries" is a question about the union of G partitions with
+ * disjoint key sets, which no member answers alone. A collective shaped like nrg_group_skiplist_seek, on
+ * a group that agreed on pops; pops[i] is local member i's part (reqs a HOST array, every other pointer a
+ * device pointer on the member's GPU). The ranks' requests, concatenated in rank order (rank 0's in issue
+ * order, then rank 1's, ...), are ONE run of consecutive pop records replayed against the whole
+ * partitioned map: the grants, front ranks and back ranks of nrg_skiplist_enable_pops' pop step with
+ * len = the sum of the members' lengths (counts up to 2^64 - 1, clipped to len). Every rank gets what
+ * nrg_skiplist_round_pops_async would give it for its own records of that run on a single replica
+ * holding the union: resp[j] = entries popped by request j, some[j] = (resp[j] >= 1), the popped entries
+ * packed in request order, each request's in the order popped (front ascending, back descending), and
+ * *pop_n = the total this member popped. Only the first pop_cap entries are stored and nothing is
+ * written past them. Afterwards the union of the members is the map minus the popped entries and every
+ * member still holds only keys it owns. On the replica's stream, host waits under the group's deadline:
+ *   1  queued group work completes; every rank's {n, flags, exact length} (one all-gather of three words
+ *      per rank, read back), then, unless every n is 0, the requests themselves, padded to the longest n
+ *      (a second all-gather, read back). Every rank now derives the whole plan as host arithmetic:
+ *      the front and back totals F and Bk, every record's grant, first rank and offset in its asker's
+ *      packed output.
+ *   2  Member o peeks its min(F, len_o) smallest and min(Bk, len_o) largest entries without popping (a
+ *      merge-path prefix and suffix of its two runs, one launch; NRG_SCAN_MAX_LIMIT does not apply); the
+ *      candidate blocks (keys and values) are all-gathered, padded to the longest.
+ *   3  One launch per member selects: a candidate's rank in the union is its index in its own list plus
+ *      the candidates of every other list below (back: above) its key; rank < F (Bk) is popped; where the
+ *      rank falls in one of this member's own records the entry is stored at its place under pop_cap.
+ *      The same launch writes resp, some and *pop_n, counts the member's own popped candidates c_f and
+ *      c_b and writes the records {c_f, front_mark}, {c_b, back_mark} into a device buffer.
+ *   4  Every member replays those two device records with nrg_skiplist_round_async (origin rank + 1):
+ *      its log moves by two records per call. Fronts and backs cannot meet inside a member because they
+ *      do not meet in the union.
+ * A one-rank group whose n <= max_batch skips 2 to 4: its own pop step (nrg_skiplist_round_pops_async
+ * over the n records) answers straight into the caller's buffers (NRG_KNOB_EXP bit 16, measurement, makes
+ * it take every step). The call returns when the answers are in the callers' buffers. Errors are agreed
+ * on by every rank from step 1 before any data moves, the first in rank order wins, and the group stays
+ * usable:
+ *   NRG_E_INVAL       the group has not agreed on pops; members that are no skip lists; n > 0 with a NULL
+ *                     reqs; resp without some or the reverse; pop_cap > 0 with a NULL array; a NULL pop_n
+ *                     with n > 0; back > 1
+ *   NRG_E_NOT_SYNCED  a member with ltail < tail
+ *   NRG_E_CAPACITY    n >= 2^32; or G * (the longest n of the ranks) > 2^24 requests (their staging, on
+ *                     every rank: 256 MiB); or G * (the longest candidate block, front and back candidates
+ *                     together) > 2^27 entries (the scan's scratch bound)
+ * NRG_E_COMM / NRG_E_TIMEOUT as nrg_group_verify. n = 0 on every rank returns NRG_OK after the exchange. */
+typedef struct {
+    uint64_t n;        /* PopFront x n (back = 0) or PopBack x n (back = 1) */
+    uint32_t back;
+    uint32_t reserved;
+} nrg_pop_req;
+typedef struct {
+    const nrg_pop_req* reqs; /* host, this member's pop requests in issue order */
+    uint64_t n;
+    uint64_t* resp;          /* device, n: entries popped per request (nullable with some) */
+    uint8_t* some;           /* device, n: resp >= 1 */
+    uint64_t* pop_keys;      /* device: the popped entries, packed in request order, each */
+    uint64_t* pop_vals;      /* request's in the order popped (front ascending, back descending) */
+    uint64_t pop_cap;
+    uint64_t* pop_n;         /* device: the total this member popped */
+} nrg_pops;
+int nrg_group_skiplist_pop(nrg_group* g, const nrg_pops* pops);
 
 /* ---- device memory helpers (for callers without their own allocator) ----------------- */
 int nrg_dev_alloc(nrg_ctx* ctx, uint64_t bytes, void** d_ptr);

@@ -107,6 +107,12 @@ int nrg_test_combiner_times(nrg_combiner* m, uint64_t out[4]);
  * blocks until all ranks joined, and each collective blocks its thread until its peers posted
  * theirs. Tests check both shapes against the oracle. 0 switches back to RCCL for later groups. */
 int nrg_test_loopback_collectives(int on);
+/* What a group's partitioned rounds have launched of the group's own kernels since it was created
+ * (the replays' launches are the members': nrg_kernel_time): out = {fused partitions (one per member
+ * and posted round that moves data), route-back launches, asker-side Push response launches (a
+ * skip-list group that has not agreed on removal), mark passes (a group that agreed on pops)}. A
+ * one-rank group in the identity form counts none of the first three. */
+int nrg_test_group_launches(const nrg_group* g, uint64_t out[4]);
 // Hashmap: 1 when the sampled key skew sends rounds to partition rounds (hashmap.hip
 // skew_sample), 0 when the round size decides.
 int nrg_test_hm_skewed(nrg_ctx* ctx, int* out);

@@ -119,6 +119,7 @@ void member_free(Member& m, const Rccl* R) {
     m.sk.free();
     m.fp.free();
     m.pr.free();
+    m.po.free();
     if (m.ord_ev) (void)hipEventDestroy(m.ord_ev);
     if (m.pstream) (void)hipStreamSynchronize(m.pstream);
     if (m.pstream) (void)hipStreamDestroy(m.pstream);

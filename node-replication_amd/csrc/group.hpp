@@ -1,9 +1,10 @@
-// group.hpp — what the replica group's five files share (private to the library):
+// group.hpp — what the replica group's six files share (private to the library):
 //   group.cpp              the backend, join / open / close, the replicated round, sync, verify, resync
 //   group_partitioned.cpp  key-partitioned rounds (PtMember, PtGroup)
 //   group_reads.cpp        group-wide ordered reads of a partitioned skip-list group (SkMember)
 //   group_files.cpp        file-partitioned rounds of a file-store group (FpMember)
 //   group_file_reads.cpp   the group-wide pread of such a group (PrMember)
+//   group_pops.cpp         what a partitioned skip-list group opts into as a whole, and its group-wide pop (PoMember)
 // A member's state of a protocol is a struct of that protocol's file, embedded in Member: only the
 // owner's file touches its struct (the rule internal.hpp states for HmHost ... MfHost), and
 // member_init / member_free call its init / free. The decisions taken from exchanged words are
@@ -82,6 +83,16 @@ enum SkBuf { SK_SEND, SK_QALL, SK_CK, SK_CV, SK_CF, SK_BK, SK_BV, SK_BF, SK_N };
 struct SkMember {
     DBuf b[SK_N];
     void free();  // (group_reads.cpp; nothing to set up at join: the buffers grow with the first read)
+};
+
+// The group-wide pop of a partitioned skip-list group (nrg_group_skiplist_pop): the padded send copy of
+// this member's requests and every rank's, its candidates (keys, values: cfmax front slots, then cbmax
+// back slots), every member's, its part of the plan, and the two records it replays.
+enum PoBuf { PO_SEND, PO_ALLREQ, PO_CK, PO_CV, PO_ALLK, PO_ALLV, PO_PLAN, PO_REC, PO_N };
+
+struct PoMember {
+    DBuf b[PO_N];
+    void free();  // (group_pops.cpp; nothing to set up at join: the buffers grow with the first pop)
 };
 
 // File-partitioned rounds of a file-store group (nrg_group_file_round): the state of one member. A
@@ -174,6 +185,7 @@ struct Member {
     SkMember sk;
     FpMember fp;
     PrMember pr;
+    PoMember po;
 };
 
 }  // namespace grp
@@ -189,6 +201,17 @@ struct nrg_group {
     uint32_t timeout_ms = NRG_GROUP_DEFAULT_TIMEOUT_MS;  // deadline of every wait on the peers
     int broken = NRG_OK;  // sticky: a timed-out collective or disagreeing ranks end the group
     nrg::grp::PtGroup pt;
+    // what every rank agreed on (nrg_group_skiplist_enable_removal): each member removes with this
+    // tombstone, and a partitioned round's Push / Remove responses come from the keys' owners
+    bool sl_rm = false;
+    uint64_t sl_tomb = 0;
+    // ... and nrg_group_skiplist_enable_pops: a round that holds a mark record is refused everywhere,
+    // and nrg_group_skiplist_pop pops the union
+    bool sl_pops = false;
+    uint64_t sl_front = 0, sl_back = 0;
+    // the partitioned rounds' own launches (nrg_test_group_launches)
+    enum { L_FUSED, L_ROUTE, L_PUSH_RESP, L_MARKS, L_N };
+    uint64_t launches[L_N] = {};
     char diag[256] = {};  // what broke it (nrg_group_last_error)
 };
 

@@ -20,7 +20,10 @@
 // A group of skip-list replicas (the reference's skiplist-mlnr, benches/lockfree.rs:228-317) takes
 // the same rounds: the records are Push(k, v), the owner's replay is nrg_skiplist_round_async per
 // slice and nrg_skiplist_get_async for the Gets, nothing is deferred, and the Push responses
-// Ok(Some(key)) are written on the asker's side in stage B (they never travel: XW_PREV = 0).
+// Ok(Some(key)) are written on the asker's side in stage B (they never travel: XW_PREV = 0). A group
+// that agreed on removal (group_pops.cpp) also carries Remove(k): there the owners' replay answers
+// every received record and the responses come back as a hashmap's previous values do; one that
+// agreed on pops looks for mark records in the post step and refuses a round that holds one.
 // A one-rank group owns every key, so its partition is the identity and so is the route-back
 // (pt_ident): the owner's replay reads the caller's records and Get keys and answers straight into
 // the caller's buffers -- no data moves, as a cnr replica with one log appends and replays in place
@@ -28,6 +31,7 @@
 // its data like a multi-rank one: partition copy on the side stream, route-back launch.
 #include <algorithm>
 
+#include "../../include/nrgpu_testing.h"
 #include "group.hpp"
 
 using namespace nrg::grp;
@@ -71,6 +75,20 @@ __global__ __launch_bounds__(GRP_TPB) void grp_push_resp_kernel(const nrg_put* _
     }
 }
 
+// A group that agreed on pops (nrg_group_skiplist_enable_pops): a record whose val is a mark would be
+// routed by the hash of its count and pop one partition's front, so a round that holds one is refused.
+// One pass over the member's records; a mark makes *err_word -NRG_E_INVAL (the member's XW_ERR, zero
+// before: the lanes that find one all store the same word).
+__global__ __launch_bounds__(GRP_TPB) void grp_find_marks_kernel(const nrg_put* __restrict__ recs, uint64_t n, uint64_t fm,
+                                                                 uint64_t bm, uint64_t* err_word) {
+    bool hit = false;
+    for (uint64_t i = blockIdx.x * (uint64_t)GRP_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * GRP_TPB) {
+        const uint64_t v = recs[i].val;
+        hit |= v == fm || v == bm;
+    }
+    if (hit) *err_word = (uint64_t)(-NRG_E_INVAL);
+}
+
 int grow(Member& m, PtBuf k, uint64_t bytes) { return grow_buf(m, m.pt.pt[k], bytes); }
 
 int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
@@ -84,9 +102,11 @@ int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
         nrg_ctx* c = m.ctx;
         int err = NRG_OK;
         const uint32_t kind = c->cfg.ds_kind;
-        // (a skip list with removal: a Remove's response is not the asker's to write, see grp_push_resp_kernel;
-        // with pops: the front of a key-partitioned map is no member's own)
-        if ((kind != NRG_DS_HASHMAP && kind != NRG_DS_SKIPLIST) || nrg::sl_removal(c) || nrg::sl_pops(c) ||
+        // (a skip list with removal: a Remove's response is not the asker's to write, see grp_push_resp_kernel,
+        // unless the group agreed on it and the owners answer; with pops: the front of a key-partitioned
+        // map is no member's own, and a group that agreed on them refuses the mark records below)
+        if ((kind != NRG_DS_HASHMAP && kind != NRG_DS_SKIPLIST) || (nrg::sl_removal(c) && !g->sl_rm) ||
+            (nrg::sl_pops(c) && !g->sl_pops) ||
             (x.n && !x.recs) ||
             (x.n_gets && (!x.get_keys || !x.get_vals || !x.get_found)))
             err = NRG_E_INVAL;
@@ -110,8 +130,9 @@ int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
             }
         }
         uint64_t* w = t.xwords;
-        // (a skip list's Push responses are its own keys: they never travel, see pt_stage_b)
-        w[XW_PREV] = (kind == NRG_DS_HASHMAP && x.resp && x.some) ? 1 : 0;
+        // (a skip list's Push responses are its own keys: they never travel, see pt_stage_b; on a group
+        // that agreed on removal they are the owners' and travel as the hashmap's previous values do)
+        w[XW_PREV] = ((kind == NRG_DS_HASHMAP || g->sl_rm) && x.resp && x.some) ? 1 : 0;
         w[XW_KIND] = kind;
         // receive capacities of the round's parity (one rank replays straight from its partition
         // output: no RPUT / RKEY)
@@ -131,6 +152,17 @@ int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
             t.pr[sl] = x;
             t.cap_p[sl] = err ? 0 : n;
             t.cap_k[sl] = err ? 0 : k;
+            if (g->sl_pops) {  // the mark pass writes the slot's mapped error word: stage A waits for it
+                uint64_t* ew = &t.h_cnt[sl][2 * G + XW_ERR];
+                *ew = 0;  // (the slot's previous round is through stage A: nothing on the device writes it now)
+                if (n) {
+                    grp_find_marks_kernel<<<grp_grid(n), GRP_TPB, 0, c->stream>>>((const nrg_put*)x.recs, n, g->sl_front,
+                                                                                 g->sl_back, ew);
+                    GCHK(hipGetLastError());
+                    g->launches[nrg_group::L_MARKS]++;
+                }
+                GCHK(hipEventRecord(t.cnt_ev[sl], c->stream));
+            }
             continue;
         }
         hipStream_t ps = c->stream;
@@ -151,6 +183,14 @@ int pt_post(nrg_group* g, const nrg_round* rounds, uint64_t e) {
                                             t.epoch, G == 1 ? t.h_cnt[sl] : (uint64_t*)t.pp[sl][PP_CNT].p, w,
                                             XW_N);
         if (he != hipSuccess) return hip_rc(he);
+        g->launches[nrg_group::L_FUSED]++;
+        if (g->sl_pops && ok && n) {  // after the partition wrote the words: a mark record makes XW_ERR -NRG_E_INVAL
+            uint64_t* cnt = G == 1 ? t.h_cnt[sl] : (uint64_t*)t.pp[sl][PP_CNT].p;
+            grp_find_marks_kernel<<<grp_grid(n), GRP_TPB, 0, ps>>>((const nrg_put*)x.recs, n, g->sl_front, g->sl_back,
+                                                                  cnt + 2 * G + XW_ERR);
+            GCHK(hipGetLastError());
+            g->launches[nrg_group::L_MARKS]++;
+        }
         t.pr[sl] = x;
         t.cap_p[sl] = n;
         t.cap_k[sl] = k;
@@ -184,6 +224,12 @@ int pt_counts(nrg_group* g, int sl, uint64_t* H1, const uint64_t** H) {
             H1[0] = m.pt.cap_p[sl];
             H1[1] = m.pt.cap_k[sl];
             for (int q = 0; q < (int)XW_N; q++) H1[2 + q] = m.pt.xw1[sl][q];
+            // a group that agreed on pops pays a host wait here: the mark pass of the post step has the
+            // last word on the round's error (a mark record: the round is dropped before any replay)
+            if (g->sl_pops) {
+                RCHK(wait_event(g, m.pt.cnt_ev[sl], "partitioned round: mark records"));
+                if (!H1[2 + XW_ERR]) H1[2 + XW_ERR] = m.pt.h_cnt[sl][2 + XW_ERR];
+            }
         } else {
             RCHK(wait_event(g, m.pt.cnt_ev[sl], "partitioned count exchange"));
         }
@@ -326,14 +372,20 @@ int owner_replay_hashmap(const nrg_group* g, Member& m, int sl, int par, bool an
 // compaction policy and growth), which every send and recv it waits for allows: they were all
 // enqueued before any member's replay.
 // Identity form: the responses Ok(Some(key)) come from the replay itself.
-int owner_replay_skiplist(const nrg_group* g, Member& m, int sl, int par) {
+// A group that agreed on removal: where some rank asked for responses, the replay answers every
+// received record (Push: the key; Remove: the previous value or None) into the receive-side
+// previous-value buffers, chunk by chunk at the chunk's offset, and stage B takes them back to the
+// askers as it takes a hashmap's previous values.
+int owner_replay_skiplist(const nrg_group* g, Member& m, int sl, int par, bool any_prev) {
     const PtPlan& P = m.pt.plan[sl];
     nrg_ctx* c = m.ctx;
     const uint64_t chunk = replay_chunk(c->log_size, c->cfg.max_batch);
     const OwnerIo io = owner_io(g, m, sl, par);
     const nrg_round& x = m.pt.pr[sl];
-    uint64_t* presp = pt_ident(g, m) && x.resp && x.some ? (uint64_t*)x.resp : nullptr;
-    uint8_t* psome = presp ? x.some : nullptr;
+    const bool owners = g->sl_rm && any_prev && !pt_ident(g, m);
+    uint64_t* presp = owners ? (uint64_t*)m.pt.rv[par][PR_RPREV].p
+                             : pt_ident(g, m) && x.resp && x.some ? (uint64_t*)x.resp : nullptr;
+    uint8_t* psome = owners ? (uint8_t*)m.pt.rv[par][PR_RPREVF].p : presp ? x.some : nullptr;
     for (uint64_t off = 0; off < P.rp; off += chunk) {
         const uint64_t n = std::min(chunk, P.rp - off);
         RCHK(nrg_skiplist_round_async(c, io.rput + off, n, (uint32_t)m.rank + 1, presp ? presp + off : nullptr,
@@ -356,7 +408,7 @@ int pt_stage_a(nrg_group* g, uint64_t e) {
     if (g->nranks > 1) RCHK(pt_move(g, sl, par));
     for (Member& m : g->m) {
         RCHK(nrg::ctx_use_device(m.ctx));
-        RCHK(A.kind == NRG_DS_SKIPLIST ? owner_replay_skiplist(g, m, sl, par)
+        RCHK(A.kind == NRG_DS_SKIPLIST ? owner_replay_skiplist(g, m, sl, par, A.any_prev)
                                        : owner_replay_hashmap(g, m, sl, par, A.any_prev));
     }
     return NRG_OK;
@@ -369,13 +421,15 @@ int pt_stage_b(nrg_group* g, uint64_t e) {
     const int G = g->nranks;
     const int sl = (int)(e % PT_DEPTH), par = (int)(e & 1);
     if (g->pt.drop[sl]) return NRG_OK;  // dropped in stage A (its error was returned there)
-    // (the kind every rank agreed on in stage A: a skip list's Push responses never travel)
+    // (the kind every rank agreed on in stage A: a skip list's Push responses never travel, unless
+    // the group agreed on removal: then the owners answered and the responses come back)
     const bool skiplist = g->m[0].ctx->cfg.ds_kind == NRG_DS_SKIPLIST;
+    const bool travel = !skiplist || g->sl_rm;
     const uint64_t* H = g->m[0].pt.h_cnt[sl];
     if (G > 1)  // answers back to the ranks that asked, into their owner regions
         RCHK(collective(g, "partitioned answers back", [&](Member& m, int) {
             const PtPlan& P = m.pt.plan[sl];
-            const bool mine = !skiplist && m.pt.pr[sl].resp && m.pt.pr[sl].some;
+            const bool mine = travel && m.pt.pr[sl].resp && m.pt.pr[sl].some;
             const uint64_t cp = m.pt.cap_p[sl], ck = m.pt.cap_k[sl];
             const DBuf *rv = m.pt.rv[par], *pt = m.pt.pt;
             hipStream_t s = m.ctx->stream;
@@ -413,7 +467,7 @@ int pt_stage_b(nrg_group* g, uint64_t e) {
         const int r = m.rank;
         if (pt_ident(g, m)) continue;  // the replay answered into the caller's buffers
         RCHK(nrg::ctx_use_device(c));
-        const bool mine = !skiplist && x.resp && x.some;
+        const bool mine = travel && x.resp && x.some;
         const uint64_t cp = t.cap_p[sl], ck = t.cap_k[sl];
         const DBuf* rv = t.rv[par];
         void *aval = t.pt[PB_AVAL].p, *afound = t.pt[PB_AFOUND].p, *aprev = t.pt[PB_APREV].p, *aprevf = t.pt[PB_APREVF].p;
@@ -439,10 +493,12 @@ int pt_stage_b(nrg_group* g, uint64_t e) {
             x.get_vals, x.get_found, (const uint64_t*)aprev, (const uint8_t*)aprevf,
             (const uint32_t*)t.pp[sl][PP_PPOS].p, mine ? x.n : 0, mine ? (uint64_t*)x.resp : nullptr, mine ? x.some : nullptr);
         if (he != hipSuccess) return hip_rc(he);
-        if (skiplist && x.n && x.resp && x.some) {  // Ok(Some(key)) from the asker's own records
+        g->launches[nrg_group::L_ROUTE]++;
+        if (skiplist && !travel && x.n && x.resp && x.some) {  // Ok(Some(key)) from the asker's own records
             grp_push_resp_kernel<<<grp_grid(x.n), GRP_TPB, 0, c->stream>>>((const nrg_put*)x.recs, x.n,
                                                                           (uint64_t*)x.resp, x.some);
             GCHK(hipGetLastError());
+            g->launches[nrg_group::L_PUSH_RESP]++;
         }
     }
     g->round++;
@@ -495,6 +551,12 @@ int nrg::grp::pt_check(nrg_group* g) {
 }
 
 extern "C" {
+
+int nrg_test_group_launches(const nrg_group* g, uint64_t out[4]) {
+    if (!g || !out) return NRG_E_INVAL;
+    for (int k = 0; k < nrg_group::L_N; k++) out[k] = g->launches[k];
+    return NRG_OK;
+}
 
 int nrg_group_partitioned_round_async(nrg_group* g, const nrg_round* rounds) {
     int r = pt_check(g);

@@ -121,6 +121,17 @@ inline void plan_for(const uint64_t* H, int G, int r, PtPlan& P) {
     P.rk = d;
 }
 
+// What a group opts into as a whole (nrg_group_skiplist_enable_removal): H holds {value, -NRG_E_* of
+// the rank's local check, or 0} of every rank. The first local error in rank order wins; ranks that
+// passed different values are NRG_E_INVAL. Nothing is enabled anywhere unless this is NRG_OK.
+inline int optin_agree(const uint64_t* H, int G) {
+    for (int r = 0; r < G; r++)
+        if (H[2 * r + 1]) return -(int)H[2 * r + 1];
+    for (int r = 1; r < G; r++)
+        if (H[2 * r] != H[0]) return NRG_E_INVAL;
+    return NRG_OK;
+}
+
 constexpr uint64_t GC_FROM_HEAD = 32 * 256;  // nr/src/log.rs:36 (the ring keeps this much free)
 
 // The most Puts an owner replays in one call: its max_batch, within what the log's ring takes.

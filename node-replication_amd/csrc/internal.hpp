@@ -576,9 +576,13 @@ hipError_t sl_seek_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u64* d
 hipError_t sl_count_launch(nrg_ctx* c, const u64* d_los, const u64* d_his, u64 n, u64* d_counts);
 hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 limit, u64* d_okeys, u64* d_ovals,
                           u32* d_counts);
+// ... and a member's candidates of a group-wide pop (group_pops.cpp): its nf smallest entries ascending,
+// its nk largest descending, nothing popped
+hipError_t sl_peek_launch(nrg_ctx* c, u64 nf, u64 nk, u64* d_fk, u64* d_fv, u64* d_kk, u64* d_kv);
 bool hm_removal(const nrg_ctx* c);  // hashmap.hip: nrg_hashmap_enable_removal was called (nrg_combiner_open refuses)
-bool sl_removal(const nrg_ctx* c);  // nrg_skiplist_enable_removal was called (group_partitioned.cpp refuses such a member)
-bool sl_pops(const nrg_ctx* c);     // nrg_skiplist_enable_pops was called (refused there too: the front is group-wide)
+bool sl_removal(const nrg_ctx* c);  // nrg_skiplist_enable_removal was called (group_partitioned.cpp refuses such a member,
+                                    // unless its group agreed on removal)
+bool sl_pops(const nrg_ctx* c);     // nrg_skiplist_enable_pops was called (likewise: the front is group-wide, group_pops.cpp)
 // queue.hip
 hipError_t qu_len_answers(nrg_ctx* c, u32 n, u64* d_out, uint8_t* d_some);  // n Len reads (the combiner)
 }  // namespace nrg

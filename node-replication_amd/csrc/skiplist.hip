@@ -71,6 +71,8 @@
 //                     the work spread over output positions
 //   sl_pop_shift      only for a run that lost a prefix: the rest of it to the start of its other buffer.
 //                     Back pops alone lower the counts.
+//   sl_peek           for the group-wide pop of a partitioned group (group_pops.cpp): a member's smallest and
+//                     largest entries by the same merge-path split, nothing popped
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -666,6 +668,29 @@ __global__ __launch_bounds__(SL_TPB) void sl_pop_take_kernel(SlJob j, SlPop p, u
             okeys[x] = ta ? j.bk[ia] : j.dk[id];
             ovals[x] = ta ? j.bv[ia] : j.dv[id];
         }
+    }
+}
+
+// The nf smallest entries of the map in ascending order and its nk largest in descending order, nothing
+// popped: a member's candidates of a group-wide pop (group_pops.cpp). A lane per output, its entry by
+// the merge-path split of its rank as in sl_pop_take; consecutive lanes store consecutive slots. The
+// host's nf and nk are at most the state's length (it read the counts back); a rank the state does not
+// have is skipped all the same.
+__global__ __launch_bounds__(SL_TPB) void sl_peek_kernel(const u64* __restrict__ bk, const u64* __restrict__ bv,
+                                                         const u64* __restrict__ dk, const u64* __restrict__ dv,
+                                                         const SlState* __restrict__ st, u64 nf, u64 nk,
+                                                         u64* __restrict__ fk, u64* __restrict__ fv,
+                                                         u64* __restrict__ kk, u64* __restrict__ kv) {
+    const u64 nb = st->nb, nd = st->nd, len = nb + nd;
+    for (u64 x = (u64)blockIdx.x * SL_TPB + threadIdx.x; x < nf + nk; x += (u64)gridDim.x * SL_TPB) {
+        const bool back = x >= nf;
+        const u64 r = back ? x - nf : x;
+        if (r >= len) continue;
+        const u64 q = slp::rank_of(back, len, 0, r);
+        const u64 ia = sl_split(bk, nb, dk, nd, q), id = q - ia;  // (ia < nb or id < nd: q < len)
+        const bool ta = id >= nd || (ia < nb && bk[ia] < dk[id]);
+        (back ? kk : fk)[r] = ta ? bk[ia] : dk[id];
+        (back ? kv : fv)[r] = ta ? bv[ia] : dv[id];
     }
 }
 
@@ -1402,6 +1427,20 @@ hipError_t sl_walk_launch(nrg_ctx* c, const u64* d_keys, u64 n, u32 mode, u32 li
                (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur],
                (const u64*)s.d_dv[s.dcur], (const SlState*)s.d_state, d_keys, n, mode, limit, lw, d_okeys, d_ovals,
                d_counts);
+    return hipGetLastError();
+}
+
+// A member's candidates of a group-wide pop: its nf smallest entries into fk / fv (ascending) and its nk
+// largest into kk / kv (descending), in the group's scratch; nothing is popped and nothing is bounded
+// by NRG_SCAN_MAX_LIMIT or max_reads.
+hipError_t sl_peek_launch(nrg_ctx* c, u64 nf, u64 nk, u64* d_fk, u64* d_fv, u64* d_kk, u64* d_kv) {
+    if (nf + nk == 0) return hipSuccess;
+    if (c->cfg.ds_kind != NRG_DS_SKIPLIST || nf > c->sl.cap || nk > c->sl.cap) return hipErrorInvalidValue;
+    SlHost& s = c->sl;
+    const u64 blocks = (nf + nk + SL_TPB - 1) / SL_TPB;
+    NRG_LAUNCH(c, "sl_peek", sl_peek_kernel, (unsigned)(blocks < 4096 ? blocks : 4096), SL_TPB, 0, c->stream,
+               (const u64*)s.d_bk[s.bcur], (const u64*)s.d_bv[s.bcur], (const u64*)s.d_dk[s.dcur],
+               (const u64*)s.d_dv[s.dcur], (const SlState*)s.d_state, nf, nk, d_fk, d_fv, d_kk, d_kv);
     return hipGetLastError();
 }
 

@@ -187,6 +187,28 @@ class Count(C.Structure):
     ]
 
 
+class PopReq(C.Structure):
+    """nrg_pop_req: one request of nrg_group_skiplist_pop: PopFront x n (back = 0) or PopBack x n (back = 1)."""
+
+    _fields_ = [("n", C.c_uint64), ("back", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Pops(C.Structure):
+    """nrg_pops: one group member's part of nrg_group_skiplist_pop (reqs a host array, the rest device
+    pointers on its GPU)."""
+
+    _fields_ = [
+        ("reqs", C.POINTER(PopReq)),
+        ("n", C.c_uint64),
+        ("resp", C.c_void_p),
+        ("some", C.c_void_p),
+        ("pop_keys", C.c_void_p),
+        ("pop_vals", C.c_void_p),
+        ("pop_cap", C.c_uint64),
+        ("pop_n", C.c_void_p),
+    ]
+
+
 class Pread(C.Structure):
     """nrg_pread: one group member's requests of nrg_group_memfs_pread (device pointers on its GPU)."""
 
@@ -367,6 +389,9 @@ SIGNATURES = {
     "nrg_group_skiplist_seek": (C.c_int, [vp, C.POINTER(Seek), C.c_uint32]),
     "nrg_group_skiplist_range_count": (C.c_int, [vp, C.POINTER(Count)]),
     "nrg_group_skiplist_scan": (C.c_int, [vp, C.POINTER(Scan), C.c_uint32, C.c_uint32]),
+    "nrg_group_skiplist_enable_removal": (C.c_int, [vp, u64]),
+    "nrg_group_skiplist_enable_pops": (C.c_int, [vp, u64, u64]),
+    "nrg_group_skiplist_pop": (C.c_int, [vp, C.POINTER(Pops)]),
 }
 
 # include/nrgpu_testing.h (kernel unit-test hooks)
@@ -382,6 +407,7 @@ TEST_SIGNATURES = {
     "nrg_test_hm_skewed": (C.c_int, [vp, vp]),
     "nrg_test_set_knob": (C.c_int, [vp, C.c_int, u64]),
     "nrg_test_loopback_collectives": (C.c_int, [C.c_int]),
+    "nrg_test_group_launches": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 # nrg_test_set_knob knobs (include/nrgpu_testing.h): tuning and diagnostics of an open context

@@ -26,6 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from .replica import SL_BACK_MARK, SL_FRONT_MARK
 
 
 def _ptr(t) -> int:
@@ -276,7 +277,65 @@ def key_owner(keys, parts: int):
 class PartitionedGroup(ReplicaGroup):
     """This rank's replica (a hashmap or a skip list; every rank the same kind) as partition `rank`
     of a key-partitioned group (libnrgpu.so, RCCL send/recv): nrg_group_partitioned_round. For a
-    skip list prev / prev_found receive the Push responses (the key, 1)."""
+    skip list prev / prev_found receive the Push responses (the key, 1); on a group that agreed on
+    removal (enable_removal) they are the Push / Remove responses, written by the keys' owners: Push
+    (the key, 1), Remove (the previous value, 1) or (0, 0), in issue order."""
+
+    def enable_removal(self, tombstone: int = 2**64 - 1):
+        """nrg_group_skiplist_enable_removal (a collective: every rank calls it with the same
+        tombstone): from here on a record whose val == tombstone is Remove(key) in this group's
+        partitioned rounds, answered by the key's owner. Nothing is enabled anywhere unless every rank
+        agrees; idempotent for one tombstone; there is no way back."""
+        rc = self._lib.nrg_group_skiplist_enable_removal(self._h, int(tombstone))
+        if rc:
+            self._check(rc, "nrg_group_skiplist_enable_removal")
+
+    def enable_pops(self, front_mark: int = SL_FRONT_MARK, back_mark: int = SL_BACK_MARK):
+        """nrg_group_skiplist_enable_pops (a collective: every rank calls it with the same marks): from
+        here on pop / pop_front / pop_back pop the whole partitioned map, and a partitioned round that
+        holds a mark record on any rank is refused on every rank. Idempotent for one pair of marks;
+        there is no way back."""
+        rc = self._lib.nrg_group_skiplist_enable_pops(self._h, int(front_mark), int(back_mark))
+        if rc:
+            self._check(rc, "nrg_group_skiplist_enable_pops")
+
+    def pop(self, reqs):
+        """nrg_group_skiplist_pop (a collective: every rank calls it, with its own requests and any
+        number of them). reqs: a list of (n, back), back = 0 for PopFront x n and 1 for PopBack x n. The
+        ranks' requests in rank order are one run of pop records against the whole partitioned map.
+        Returns (counts, keys, vals): counts[j] entries popped by request j (a numpy uint64 array), and
+        this rank's popped entries packed in request order, each request's in the order popped (numpy
+        uint64 arrays). The buffers are sized from the requests, each clipped to world x this replica's
+        capacity (no map of a group whose ranks opened alike holds more); synchronous."""
+        import numpy as np
+
+        reqs = [(int(n), int(back)) for n, back in reqs]
+        n = len(reqs)
+        dev = torch.device("cuda", self.replica.device)
+        room = self.world * self.replica.sl_capacity()  # no map of this group holds more
+        cap = sum(min(c, room) for c, _ in reqs)
+        arr = (L.PopReq * max(n, 1))(*[L.PopReq(c, b, 0) for c, b in reqs])
+        resp = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        some = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        keys = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+        vals = torch.zeros_like(keys)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)  # the buffers exist before the replica's stream writes them
+        q = L.Pops(arr, n, _ptr(resp), _ptr(some), _ptr(keys), _ptr(vals), cap, _ptr(total))
+        rc = self._lib.nrg_group_skiplist_pop(self._h, C.byref(q))
+        if rc:
+            self._check(rc, "nrg_group_skiplist_pop")
+        m = int(total.item())
+        return (resp[:n].cpu().numpy().view(np.uint64), keys[:m].cpu().numpy().view(np.uint64),
+                vals[:m].cpu().numpy().view(np.uint64))
+
+    def pop_front(self, n: int = 1):
+        """SkipMap::pop_front n times over the whole partitioned map (a collective: pop([(n, 0)]))."""
+        return self.pop([(n, 0)])
+
+    def pop_back(self, n: int = 1):
+        """SkipMap::pop_back n times over the whole partitioned map (a collective: pop([(n, 1)]))."""
+        return self.pop([(n, 1)])
 
     def round(self, puts, n: int, get_keys, n_gets: int, get_vals, get_found, prev=None, prev_found=None):
         """One round, queued once its counts are exchanged (nrg_group_partitioned_round)."""
